@@ -11,6 +11,13 @@ BASELINE config 3).  Rank 0 prints one JSON line.
     python bench.py [--gpus N] [--steps K] [--warmup W] [--worlds WPG]
     torchrun --nproc-per-node N bench.py --gpus N ...
 
+A plain run sets up, warms up, times the K steps and prints the line (metric,
+value, ms_per_step, the headline's HBM roofline from the timed region's own
+events).  `--dump-outputs DIR` also writes what the last timed step left in the
+manager's exported columns -- a fixed, seeded sample of rows, the same rows for
+the same arguments -- as DIR/<name>.npy, so two builds can be compared output
+for output.  Everything below runs only with `--full`.
+
 With several ranks (or --gather) a second timed loop measures BASELINE config
 5: after every step each rank's learner records (what the reference training
 loop reads, 272 B/agent) are gathered to rank 0 over RCCL and unpacked there,
@@ -18,7 +25,7 @@ rank 0 picks actions and memory, and they are scattered back to the ranks that
 own the rows (madrona-bots_amd/harness/gather.py); reported as "config5".
 `python bench.py --gpus N` without a launcher starts the N ranks itself.
 
-After the main line (unless --no-secondary): "steady_state", the same loop
+After the main line (with --full, unless --no-secondary): "steady_state", the same loop
 from step 250 on, once the worlds' food has reached its cap (the per-step cost
 rises with the food count over the first ~250 steps, so the early window of a
 short run is not the long-run rate: profiles/r05_drivergap.json); "config2",
@@ -30,7 +37,9 @@ current and previous rows, PrevHiddenState, shift, the learner's one-hot
 actions and memory written back) at 4096 worlds/GPU -- BASELINE config 2,
 "random-action rollout, obs/reward tensors on-device", reported as
 "secondary" -- and at the main line's size ("reference_loop"), each with its
-own HBM roofline.
+own HBM roofline.  With --full the line also carries the per-kernel event times
+of an untimed pass (unless --no-kernel-timing) and the CPU baseline (unless
+--no-cpu-baseline).
 """
 import argparse
 import datetime
@@ -467,12 +476,65 @@ def config5_loop(main_mgr, args, rank, world_size, dev, distributed):
             "roundtrip_roofline": rt}
 
 
+DUMP_ROWS = 32768            # rows of every column --dump-outputs keeps
+DUMP_SEED = 20240              # of the row sample
+DUMP_MAX_BYTES = 64 << 20
+DUMP_COLUMNS = ("species", "position", "health", "surrounding", "reward", "action", "stats",
+                "hidden_state", "semantic")
+
+
+def dump_outputs(mgr, out_dir):
+    """--dump-outputs: the manager's exported columns as the last timed step
+    (step + shift + action write) left them -- what a caller of that loop reads
+    next: species_count and every current / previous column -- as
+    <out_dir>/<name>.npy.  Columns of more than DUMP_ROWS rows are cut to a
+    seeded sample of rows (sorted, the same rows for every column and every run
+    with the same row count; "rows.npy" names them).  float32 and 8-bit columns
+    are written as float32, int32 columns as float64 (both exact)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = mgr.num_agents()
+    rows = None
+    if n > DUMP_ROWS:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_ROWS, replace=False))
+    idx = None if rows is None else torch.from_numpy(rows).to(mgr.device)
+
+    def host(t, sample):
+        if sample and idx is not None:
+            t = t.index_select(0, idx)
+        a = t.cpu().numpy()
+        return a.astype(np.float32 if a.dtype.itemsize < 4 or a.dtype == np.float32 else np.float64)
+
+    arrays = {"num_agents": np.array([n], np.float64),
+              "rows": (np.arange(n) if rows is None else rows).astype(np.float64),
+              "species_count": host(mgr.species_count_tensor().to_torch(), False)}
+    for name in DUMP_COLUMNS:
+        for is_prev in (False, True):
+            t = getattr(mgr, name + "_tensor")(is_prev).to_torch()
+            if name == "health":   # an int32 behind the reference's float32 export
+                t = t.view(torch.int32)
+            arrays[("prev_" if is_prev else "") + name] = host(t, True)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        sys.exit(f"bench.py: --dump-outputs would write {total} bytes (limit {DUMP_MAX_BYTES}): fewer --worlds")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--worlds", type=int, default=65536, help="worlds per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures: the "
+                         "per-kernel event pass, the steady-state line, config 5 (several ranks or --gather), "
+                         "the secondary lines and the CPU baseline (each with its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the manager's exported columns after the last timed step (a seeded sample of "
+                         "rows) as DIR/<name>.npy")
     ap.add_argument("--cpu-worlds", type=int, default=4096)
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -481,7 +543,7 @@ def main():
     ap.add_argument("--full-records", action="store_true",
                     help="config 5: ship the full 272-B learner records every step (no provenance rebuild)")
     ap.add_argument("--gather", action="store_true",
-                    help="config 5 also at one rank (always run with several ranks): learner records "
+                    help="with --full: config 5 also at one rank (--full always runs it with several ranks): learner records "
                          "gathered to rank 0, actions / memory scattered back")
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend for the bench's barrier/max/sum (nccl = RCCL); "
@@ -496,6 +558,10 @@ def main():
                          "stream is always high): both chains at high priority run the step 1.6 %% "
                          "faster than the caller's chain at normal (DESIGN.md 'Schedule')")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline's setup, warm-up, timed steps and line only
+        args.no_kernel_timing = args.no_secondary = args.no_cpu_baseline = True
+        args.gather = False
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # `python bench.py --gpus N` without a launcher: start the N ranks
@@ -573,6 +639,10 @@ def main():
     elapsed = t1 - t0
     span_ms = max(ev[0].elapsed_time(ev[1]), ev[0].elapsed_time(ev[2])) / args.steps
     agent_steps = mgr.agent_steps() - steps_before
+    if args.dump_outputs:
+        # (before any later pass steps the manager on; each rank its own folder)
+        dump_outputs(mgr, args.dump_outputs if not distributed else
+                     os.path.join(args.dump_outputs, f"rank{rank}"))
 
     # per-kernel event spans: a separate pass after the timed region (the
     # events between kernels would idle the GPU inside the timed steps)
@@ -628,7 +698,7 @@ def main():
     # tensors): its own timed loop after the main line, by default whenever the
     # bench runs several ranks (so the driver's 1..8-GPU run covers it)
     cfg5 = None
-    if distributed or args.gather:
+    if args.full and (distributed or args.gather):
         try:
             cfg5 = config5_loop(mgr, args, rank, world_size, dev, distributed)
         except Exception as e:   # reported in the line; the main measurement stands

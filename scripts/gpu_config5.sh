@@ -9,9 +9,9 @@ timeout -k 10 600 python -u -m pytest tests/test_learner_roundtrip.py tests/test
     --timeout-method thread -p no:warnings > gpurun_out/c5_tests.log 2>&1
 rc=$?; tail -2 gpurun_out/c5_tests.log
 if [ $rc -ne 0 ]; then grep -E "^E |FAILED|Error" gpurun_out/c5_tests.log | head -20; exit $rc; fi
-timeout -k 10 300 python -u bench.py --gather --steps 20 --warmup 5 --no-cpu-baseline --no-secondary \
+timeout -k 10 300 python -u bench.py --full --gather --steps 20 --warmup 5 --no-cpu-baseline --no-secondary \
     --no-kernel-timing > gpurun_out/c5_slim.json 2> gpurun_out/c5_slim.err || { tail -5 gpurun_out/c5_slim.err; exit 1; }
-timeout -k 10 300 python -u bench.py --gather --full-records --steps 20 --warmup 5 --no-cpu-baseline --no-secondary \
+timeout -k 10 300 python -u bench.py --full --gather --full-records --steps 20 --warmup 5 --no-cpu-baseline --no-secondary \
     --no-kernel-timing > gpurun_out/c5_full.json 2> gpurun_out/c5_full.err || { tail -5 gpurun_out/c5_full.err; exit 1; }
 python - <<'PY'
 import json

@@ -21,11 +21,11 @@ print(sys.argv[2], "ms/step", round(d["ms_per_step"], 4), "span", round(d["roofl
       "config2", round(d["config2"]["ms_per_step"], 4) if "config2" in d else "-")
 PY
 }
-run driver1 --gpus 1 --steps 20 --warmup 5
+run driver1 --full --gpus 1 --steps 20 --warmup 5
 timeout -k 10 120 python3 -u scripts/steptrace.py --steps 300 > $O/trace.json 2> $O/trace.err || { tail -5 $O/trace.err; exit 1; }
-run s20w5 --steps 20 --warmup 5 --no-secondary --no-cpu-baseline
-run s100w20 --steps 100 --warmup 20 --no-secondary --no-cpu-baseline
-run s20w100 --steps 20 --warmup 100 --no-secondary --no-cpu-baseline
-run s20w5_nospan --steps 20 --warmup 5 --no-secondary --no-cpu-baseline
-run s100w5 --steps 100 --warmup 5 --no-secondary --no-cpu-baseline
-run driver2 --gpus 1 --steps 20 --warmup 5
+run s20w5 --full --steps 20 --warmup 5 --no-secondary --no-cpu-baseline
+run s100w20 --full --steps 100 --warmup 20 --no-secondary --no-cpu-baseline
+run s20w100 --full --steps 20 --warmup 100 --no-secondary --no-cpu-baseline
+run s20w5_nospan --full --steps 20 --warmup 5 --no-secondary --no-cpu-baseline
+run s100w5 --full --steps 100 --warmup 5 --no-secondary --no-cpu-baseline
+run driver2 --full --gpus 1 --steps 20 --warmup 5

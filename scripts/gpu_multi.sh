@@ -3,7 +3,7 @@
 # `python bench.py --gpus N` with no launcher starts N ranks itself; on a
 # one-GPU box they share cuda:0 over gloo (--same-device).  Config 5 (the
 # learner round trip: records gathered to rank 0, actions scattered back) runs
-# by default with several ranks.  Then the real `--gpus 2` path on one GPU,
+# with --full and several ranks.  Then the real `--gpus 2` path on one GPU,
 # which must end with the ranks' own error (the parent makes no GPU call).
 set -o pipefail
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
@@ -11,7 +11,7 @@ export TMPDIR=/tmp
 mkdir -p gpurun_out
 TAG=${TAG:-r04}
 for n in ${RANKS:-2 4}; do
-  timeout -k 10 300 python -u bench.py --gpus $n --backend gloo --same-device --steps 40 --warmup 10 \
+  timeout -k 10 300 python -u bench.py --full --gpus $n --backend gloo --same-device --steps 40 --warmup 10 \
       --worlds ${WORLDS:-16384} $([ -z "${SECONDARY:-}" ] && echo --no-secondary) --no-cpu-baseline > gpurun_out/${TAG}_multi$n.log 2>&1 \
       || { tail -5 gpurun_out/${TAG}_multi$n.log; exit 1; }
   grep '^{' gpurun_out/${TAG}_multi$n.log | tail -1 > gpurun_out/${TAG}_rehearsal_${n}rank_same_device.json

@@ -6,7 +6,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export TMPDIR=/tmp
 TAG=${TAG:-r04}
 mkdir -p gpurun_out
-B="bench.py --steps 30 --warmup 100 --no-cpu-baseline --no-secondary"
+B="bench.py --full --steps 30 --warmup 100 --no-cpu-baseline --no-secondary"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_$TAG -o run \
     -- python $B > gpurun_out/prof_$TAG.log 2>&1 || { echo "stats pass failed"; tail gpurun_out/prof_$TAG.log; exit 1; }
 for c in FETCH_SIZE WRITE_SIZE; do

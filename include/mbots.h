@@ -312,6 +312,27 @@ int mbots_load_checkpoint(mbots_handle *h, const void *host_src, uint64_t bytes)
  * fractions; may be NULL) and the live agent count. */
 int mbots_world_state(mbots_handle *h, uint32_t world, float *xy_rwrz, int32_t *sp_hp_finder,
                       uint64_t *food, uint32_t *food_rot, int32_t *n_out);
+/* The inverse of mbots_world_state for geometry (a debug / test entry point:
+ * it puts a chosen scene in front of the sensor): writes the live agents'
+ * (x, y, rot.w, rot.z) -- xy_rwrz holds n_agents rows of 4 f32 -- and replaces
+ * the world's food by n_food packages, food[k] = (chunk, x, y, 22-bit
+ * rotation) with x, y in arena cells as the Python world_state reports them.
+ * Each chunk's packages take its slots 0, 1, ... in the order given, and the
+ * world's food count follows them.  Population, species, health, finder
+ * slots, RNG and the export table stay as they are: the table shows the
+ * scene after the next step, and a shoot or breed of that step still acts on
+ * the finder slots of the old geometry (in the K1 finder mode on the new
+ * one's), so a comparison takes one step without either first.
+ * MBOTS_E_INVALID, with the manager untouched, when n_agents differs from the
+ * world's population; a coordinate is not finite or outside [0, 127] x
+ * [0, 95] (what actionSystem's clamp leaves, sim.cpp:485-486); (rot.w, rot.z)
+ * is not finite or |w^2 + z^2 - 1| > 1e-3; a chunk is out of range or holds
+ * more than 5 packages, the world more than 30; a package lies outside its
+ * chunk's 16 x 16 cells or its rotation is >= 2^22; or the manager's stream
+ * is being captured.  HIP mode goes through the checkpoint path (save, patch
+ * the blob, load), so the call costs a checkpoint round trip. */
+int mbots_set_world_state(mbots_handle *h, uint32_t world, const float *xy_rwrz, uint32_t n_agents,
+                          const int32_t *food, uint32_t n_food);
 
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event

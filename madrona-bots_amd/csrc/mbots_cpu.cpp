@@ -702,6 +702,21 @@ void Sim::world_state(uint32_t w, float *xy_rwrz, int32_t *sp_hp_finder, uint64_
     *n_out = n_[w];
 }
 
+void Sim::set_world_state(uint32_t w, const float *xy_rwrz, const uint64_t *food, const uint32_t *food_rot,
+                          int32_t n_food)
+{
+    const size_t base = (size_t)w * cap_;
+    for (int32_t i = 0; i < n_[w]; ++i) {
+        x_[base + i] = xy_rwrz[i * 4 + 0];
+        y_[base + i] = xy_rwrz[i * 4 + 1];
+        rw_[base + i] = xy_rwrz[i * 4 + 2];
+        rz_[base + i] = xy_rwrz[i * 4 + 3];
+    }
+    memcpy(&food_[(size_t)w * kNumChunks], food, kNumChunks * sizeof(uint64_t));
+    memcpy(&food_rot_[(size_t)w * kNumPkg], food_rot, kNumPkg * sizeof(uint32_t));
+    cur_food_[w] = n_food;
+}
+
 // ---- checkpoint: the config, every state array and the live table half ----
 namespace {
 constexpr char kMagic[8] = {'M', 'B', 'O', 'T', 'S', 'C', 'P', 'U'};

@@ -56,6 +56,11 @@ public:
     const int32_t *src_of() const { return src_of_.data(); }
     void world_state(uint32_t w, float *xy_rwrz, int32_t *sp_hp_finder, uint64_t *food,
                      uint32_t *food_rot, int32_t *n_out) const;
+    uint32_t population(uint32_t w) const { return (uint32_t)n_[w]; }
+    // mbots_set_world_state (arguments already checked): the live agents'
+    // (x, y, rw, rz), the world's packed food records, rotations and count
+    void set_world_state(uint32_t w, const float *xy_rwrz, const uint64_t *food, const uint32_t *food_rot,
+                         int32_t n_food);
     uint64_t checkpoint_bytes() const;
     int save(void *dst, uint64_t bytes, std::string &err) const;
     int load(const void *src, uint64_t bytes, std::string &err);

@@ -22,6 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1948,6 +1949,111 @@ int mbots_world_state(mbots_handle *h, uint32_t world, float *xy_rwrz, int32_t *
         HIP_TRY(hipMemcpy(food_rot, S.food_rot + (size_t)world * kNumPkg, kNumPkg * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(n_out, S.n + world, 4, hipMemcpyDeviceToHost));
     return MBOTS_OK;
+}
+
+namespace {
+// mbots_set_world_state's argument checks (everything but the population):
+// the states actionSystem's clamp, the rotation steps and addFoodToChunk can
+// leave, so a written scene is one the simulator could have reached
+const char *scene_invalid(const float *a, uint32_t n_agents, const int32_t *food, uint32_t n_food)
+{
+    for (uint32_t i = 0; i < n_agents; ++i) {
+        const float x = a[4 * i], y = a[4 * i + 1], rw = a[4 * i + 2], rz = a[4 * i + 3];
+        if (!std::isfinite(x) || !std::isfinite(y) || x < 0.0f || x > mbots::kLx - 1.0f || y < 0.0f ||
+            y > mbots::kLy - 1.0f)
+            return "an agent position is not finite or outside [0, 127] x [0, 95]";
+        const double d = (double)rw * rw + (double)rz * rz - 1.0;
+        if (!std::isfinite(rw) || !std::isfinite(rz) || d > 1e-3 || d < -1e-3)
+            return "an agent rotation is not finite or not a unit quaternion (|w^2 + z^2 - 1| > 1e-3)";
+    }
+    if (n_food > (uint32_t)mbots::kFoodCap) return "more than 30 food packages";
+    int per_chunk[mbots::kNumChunks] = {};
+    for (uint32_t k = 0; k < n_food; ++k) {
+        const int32_t c = food[4 * k], x = food[4 * k + 1], y = food[4 * k + 2], rot = food[4 * k + 3];
+        if (c < 0 || c >= mbots::kNumChunks) return "a food package's chunk is out of range";
+        const int32_t lx = x - (c % mbots::kChunksX) * mbots::kChunkW, ly = y - (c / mbots::kChunksX) * mbots::kChunkW;
+        if (lx < 0 || lx >= mbots::kChunkW || ly < 0 || ly >= mbots::kChunkW)
+            return "a food package lies outside its chunk";
+        if (rot < 0 || rot >= (1 << 22)) return "a food package's rotation is not a 22-bit quarter-turn fraction";
+        if (++per_chunk[c] > mbots::kMaxPkg) return "more than 5 food packages in one chunk";
+    }
+    return nullptr;
+}
+
+// the packed records ([48] of 5 x (x | y << 4), live mask << 40) and rotations
+// ([5][48]) of a package list: each chunk's slots fill from 0 in list order
+void pack_food(const int32_t *food, uint32_t n_food, uint64_t *rec, uint32_t *rot)
+{
+    using namespace mbots;
+    memset(rec, 0, kNumChunks * sizeof(uint64_t));
+    memset(rot, 0, kNumPkg * sizeof(uint32_t));
+    int used[kNumChunks] = {};
+    for (uint32_t k = 0; k < n_food; ++k) {
+        const int c = food[4 * k], q = used[c]++;
+        const uint64_t lx = (uint64_t)(food[4 * k + 1] - (c % kChunksX) * kChunkW);
+        const uint64_t ly = (uint64_t)(food[4 * k + 2] - (c / kChunksX) * kChunkW);
+        rec[c] |= ((lx | (ly << 4)) << (8 * q)) | (1ull << (40 + q));
+        rot[q * kNumChunks + c] = (uint32_t)food[4 * k + 3];
+    }
+}
+}  // namespace
+
+int mbots_set_world_state(mbots_handle *h, uint32_t world, const float *xy_rwrz, uint32_t n_agents,
+                          const int32_t *food, uint32_t n_food)
+{
+    using namespace mbots;
+    if (!h || (!xy_rwrz && n_agents) || (!food && n_food)) return fail(MBOTS_E_INVALID, "null argument");
+    if (world >= h->cfg.num_worlds) return fail(MBOTS_E_INVALID, "world out of range");
+    if (const char *why = scene_invalid(xy_rwrz, n_agents, food, n_food)) return fail(MBOTS_E_INVALID, why);
+    uint64_t rec[kNumChunks];
+    uint32_t rot[kNumPkg];
+    pack_food(food, n_food, rec, rot);
+    static const char *kPop = "the agent count differs from the world's population";
+    if (h->cpu) {
+        if (n_agents != h->cpu->population(world)) return fail(MBOTS_E_INVALID, kPop);
+        h->cpu->set_world_state(world, xy_rwrz, rec, rot, (int32_t)n_food);
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = capture_guard(h, h->last_stream)) return rc;
+    if (capturing_now(h))
+        return fail(MBOTS_E_INVALID, "set_world_state is a host-side write and cannot be captured into a graph");
+    // the checkpoint path: save, patch the blob's segments (found by pointer
+    // identity, as mbots_load_checkpoint finds S.n and S.totals), load -- the
+    // load resets the lazy / pending / alias bookkeeping
+    uint64_t bytes = 0;
+    if (int rc = mbots_checkpoint_size(h, &bytes)) return rc;
+    std::vector<char> blob(bytes);
+    if (int rc = mbots_save_checkpoint(h, blob.data(), bytes)) return rc;
+    CkptHeader hd;
+    memcpy(&hd, blob.data(), sizeof(hd));
+    const SimState &S = h->S;
+    const size_t cap = h->cfg.agent_capacity, base = (size_t)world * cap;
+    const auto segs = ckpt_segments(h, h->T[h->tb], hd.n_rows);
+    char *q = blob.data() + sizeof(hd);
+    for (const Seg &s : segs) {   // the population first: nothing is patched on a mismatch
+        if (s.p == S.n) {
+            int32_t n;
+            memcpy(&n, q + 4 * (size_t)world, 4);
+            if (n < 0 || (uint32_t)n != n_agents) return fail(MBOTS_E_INVALID, kPop);
+        }
+        q += s.bytes;
+    }
+    q = blob.data() + sizeof(hd);
+    for (const Seg &s : segs) {
+        const float *const col[4] = {S.x, S.y, S.rw, S.rz};
+        for (int c = 0; c < 4; ++c)
+            if (s.p == col[c])
+                for (uint32_t i = 0; i < n_agents; ++i) memcpy(q + 4 * (base + i), &xy_rwrz[4 * i + c], 4);
+        if (s.p == S.food) memcpy(q + (size_t)world * kNumChunks * 8, rec, sizeof(rec));
+        if (s.p == S.food_rot) memcpy(q + (size_t)world * kNumPkg * 4, rot, sizeof(rot));
+        if (s.p == S.cur_food) {
+            const int32_t nf = (int32_t)n_food;
+            memcpy(q + 4 * (size_t)world, &nf, 4);
+        }
+        q += s.bytes;
+    }
+    return mbots_load_checkpoint(h, blob.data(), bytes);
 }
 
 int mbots_enable_kernel_timing(mbots_handle *h, int32_t enable)

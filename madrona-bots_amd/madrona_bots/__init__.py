@@ -71,6 +71,7 @@ def _load():
         "mbots_save_checkpoint": [vp, vp, ctypes.c_uint64],
         "mbots_load_checkpoint": [vp, vp, ctypes.c_uint64],
         "mbots_world_state": [vp, u32, vp, vp, vp, vp, P(i32)],
+        "mbots_set_world_state": [vp, u32, vp, u32, vp, u32],
         "mbots_export": [vp, i32, P(_CTensor)],
         "mbots_export_on": [vp, i32, vp, P(_CTensor)],
         "mbots_set_action": [vp, u32, P(i32)],
@@ -728,6 +729,22 @@ class SimManager:
                 "finder": shf[:k, 2].copy(),
                 "food": np.array(pk, np.int32).reshape(-1, 4)}
 
+    def set_world_state(self, world_idx, position, rotation_wz, food):
+        """Debug / test entry point, the inverse of world_state() for geometry
+        (mbots_set_world_state): write the live agents' position [n, 2] and
+        rotation (w, z) [n, 2] and replace the world's food by the packages
+        [k, 4] of (chunk, x, y, rotation).  Population, species, health, finder
+        slots, RNG and the exported table stay; a scene the simulator could
+        not reach by its own steps raises RuntimeError and changes nothing.
+        In HIP mode the call is a checkpoint round trip."""
+        import numpy as np
+        xyr = np.ascontiguousarray(np.concatenate(
+            [np.asarray(position, np.float32).reshape(-1, 2),
+             np.asarray(rotation_wz, np.float32).reshape(-1, 2)], axis=1))
+        fd = np.ascontiguousarray(np.asarray(food, np.int32).reshape(-1, 4))
+        _check(_lib.mbots_set_world_state(self._h, int(world_idx), ctypes.c_void_p(xyr.ctypes.data),
+                                          len(xyr), ctypes.c_void_p(fd.ctypes.data), len(fd)))
+
     def dump_worlds(self, path, worlds):
         """Write world_state() of each world in `worlds` to one .npz
         (keys "w<idx>/<field>") for offline inspection -- the build's
@@ -739,6 +756,13 @@ class SimManager:
                 arrays[f"w{int(w)}/{k}"] = v
         np.savez(path, **arrays)
         return sorted(arrays)
+
+    def load_worlds(self, path):
+        """Write the worlds of a dump_worlds() file back (set_world_state)."""
+        import numpy as np
+        z = np.load(path)
+        for w in sorted({int(k.split("/")[0][1:]) for k in z.files}):
+            self.set_world_state(w, z[f"w{w}/position"], z[f"w{w}/rotation_wz"], z[f"w{w}/food"])
 
     def join(self):
         """Make torch's current stream wait for the manager's outstanding

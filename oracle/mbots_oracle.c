@@ -1074,6 +1074,51 @@ int32_t orc_world_food(const orc_sim *s, uint32_t wi, int32_t *out)
     return k;
 }
 
+int orc_set_world_state(orc_sim *s, uint32_t wi, const float *xy_rwrz, uint32_t n_agents,
+                        const int32_t *food, uint32_t n_food)
+{
+    if (!s || wi >= s->cfg.num_worlds) return -1;
+    orc_world *w = &s->w[wi];
+    if (w->n < 0 || (uint32_t)w->n != n_agents) return -1;
+    for (uint32_t i = 0; i < n_agents; ++i) {
+        float x = xy_rwrz[4 * i], y = xy_rwrz[4 * i + 1], rw = xy_rwrz[4 * i + 2], rz = xy_rwrz[4 * i + 3];
+        if (!isfinite(x) || !isfinite(y) || x < 0.0f || x > kLx - 1.0f || y < 0.0f || y > kLy - 1.0f) return -1;
+        double d = (double)rw * rw + (double)rz * rz - 1.0;
+        if (!isfinite(rw) || !isfinite(rz) || d > 1e-3 || d < -1e-3) return -1;
+    }
+    if (n_food > ORC_FOOD_CAP) return -1;
+    int used[ORC_NUM_CHUNKS] = {0};
+    for (uint32_t k = 0; k < n_food; ++k) {
+        int32_t c = food[4 * k], x = food[4 * k + 1], y = food[4 * k + 2], rot = food[4 * k + 3];
+        if (c < 0 || c >= ORC_NUM_CHUNKS) return -1;
+        int32_t lx = x - (c % ORC_CHUNKS_X) * ORC_CHUNK_W, ly = y - (c / ORC_CHUNKS_X) * ORC_CHUNK_W;
+        if (lx < 0 || lx >= ORC_CHUNK_W || ly < 0 || ly >= ORC_CHUNK_W) return -1;
+        if (rot < 0 || rot >= (1 << 22)) return -1;
+        if (++used[c] > ORC_MAX_PKG) return -1;
+    }
+    for (uint32_t i = 0; i < n_agents; ++i) {
+        orc_agent *a = &w->ag[i];
+        a->x = xy_rwrz[4 * i];
+        a->y = xy_rwrz[4 * i + 1];
+        a->rw = xy_rwrz[4 * i + 2];
+        a->rz = xy_rwrz[4 * i + 3];
+    }
+    memset(w->pkg_x, 0, sizeof(w->pkg_x));
+    memset(w->pkg_y, 0, sizeof(w->pkg_y));
+    memset(w->pkg_n, 0, sizeof(w->pkg_n));
+    memset(w->pkg_rot, 0, sizeof(w->pkg_rot));
+    memset(used, 0, sizeof(used));
+    for (uint32_t k = 0; k < n_food; ++k) {
+        int c = food[4 * k], q = used[c]++;
+        w->pkg_x[c][q] = (uint8_t)(food[4 * k + 1] - (c % ORC_CHUNKS_X) * ORC_CHUNK_W);
+        w->pkg_y[c][q] = (uint8_t)(food[4 * k + 2] - (c / ORC_CHUNKS_X) * ORC_CHUNK_W);
+        w->pkg_n[c][q] = 1;
+        w->pkg_rot[c][q] = (uint32_t)food[4 * k + 3];
+    }
+    w->cur_food = (int32_t)n_food;
+    return 0;
+}
+
 void orc_probe_agent(float ax, float ay, float hx, float hy, float cx, float cy, uint8_t *hit, float *z)
 {
     orc_hit hits[ORC_SENSOR + 1];

@@ -86,6 +86,19 @@ void     orc_world_state(const orc_sim *s, uint32_t w, float *xy, float *rot,
 /* live food packages of world w in (chunk, package) order: out[k] = (chunk,
  * x, y, 22-bit rotation); returns their count (<= 240 entries of 4) */
 int32_t  orc_world_food(const orc_sim *s, uint32_t w, int32_t *out);
+/* the inverse for geometry (tests place a chosen scene in front of the
+ * sensor): writes ag[i].x / y / rw / rz for the world's n_agents live agents
+ * (rows of 4 f32) and replaces its food by n_food packages (chunk, x, y,
+ * rotation) as orc_world_food reports them, each chunk's slots filled from 0
+ * in the order given; cur_food follows.  Population, species, health, finder
+ * slots, RNG and the export table are untouched.  Returns 0, or -1 with
+ * nothing written under the conditions of mbots_set_world_state
+ * (include/mbots.h): another population, a position outside [0, 127] x
+ * [0, 95], a rotation off the unit circle by more than 1e-3, more than 5
+ * packages in a chunk or 30 in the world, a package outside its chunk, a
+ * rotation >= 2^22 */
+int      orc_set_world_state(orc_sim *s, uint32_t w, const float *xy_rwrz, uint32_t n_agents,
+                             const int32_t *food, uint32_t n_food);
 
 /* exposed primitives for known-answer tests */
 /* one food box (centre (cx, cy), 22-bit rotation) seen from an agent at

@@ -75,6 +75,8 @@ def lib():
         L.orc_world_state.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp]
         L.orc_world_food.restype = i32
         L.orc_world_food.argtypes = [vp, u32, vp]
+        L.orc_set_world_state.restype = ctypes.c_int
+        L.orc_set_world_state.argtypes = [vp, u32, vp, u32, vp, u32]
         L.orc_threefry2x32.argtypes = [vp, vp, vp]
         L.orc_sample_uniform.restype = ctypes.c_float
         L.orc_sample_uniform.argtypes = [u32]
@@ -200,6 +202,18 @@ class OracleSim:
         nf = int(lib().orc_world_food(self._h, w, food.ctypes.data))
         return dict(xy=xy[:k], rot=rot[:k], species=sp[:k], health=hp[:k], finder=fd[:k],
                     food=food[:nf].copy())
+
+    def set_world_state(self, w, position, rotation_wz, food):
+        """Write a scene into world w (orc_set_world_state): the live agents'
+        position [n, 2] and rotation (w, z) [n, 2], and the food packages
+        [k, 4] of (chunk, x, y, rotation) as world_state() reports them."""
+        xyr = np.ascontiguousarray(np.concatenate(
+            [np.asarray(position, np.float32).reshape(-1, 2),
+             np.asarray(rotation_wz, np.float32).reshape(-1, 2)], axis=1))
+        fd = np.ascontiguousarray(np.asarray(food, np.int32).reshape(-1, 4))
+        if lib().orc_set_world_state(self._h, int(w), xyr.ctypes.data, len(xyr), fd.ctypes.data, len(fd)):
+            raise ValueError("orc_set_world_state: the scene is not a state the simulator can reach "
+                             "(see mbots_oracle.h)")
 
     def snapshot(self, include_prev=True):
         """Copy of every exported column (dict name -> array)."""

@@ -273,57 +273,8 @@ def test_food_box_containing_the_agent_near_sphere():
 
 
 # ---- the near sphere and the agent disc -------------------
-R_AGENT, NEAR = 0.92, 1.1
-
-
-def _dirs(heading):
-    """World directions of the 33 rays (float64): 24 forward, 8 backward, finder."""
-    hx, hy = heading
-    out = []
-    for k in range(33):
-        u = (2 * k - 23) / 24 if k < 24 else ((2 * (k - 24) - 7) / 8 if k < 32 else 0.0)
-        sg = -1.0 if 24 <= k < 32 else 1.0
-        out.append((sg * (hx + u * hy), sg * (hy - u * hx)))
-    return np.array(out)
-
-
-def _ref_disc(agent, heading, centre, R=R_AGENT):
-    """Independent float64 restatement: ray k sees the disc iff it leaves it at
-    distance >= 1.1; returns (hit[33], margin[33]) -- margin: how far the ray
-    is from either decision boundary (tangency, t_exit = 1.1)."""
-    d = _dirs(heading)
-    d /= np.linalg.norm(d, axis=1)[:, None]
-    v = np.array(centre, np.float64) - np.array(agent, np.float64)
-    tm = d @ v
-    dist2 = v @ v - tm * tm
-    half = np.sqrt(np.maximum(R * R - dist2, 0.0))
-    hit = (dist2 <= R * R) & (tm + half >= NEAR)
-    margin = np.minimum(np.abs(R * R - dist2), np.where(dist2 <= R * R, np.abs(tm + half - NEAR), 1.0))
-    return hit, margin
-
-
-def _ref_box(agent, heading, centre, rot22):
-    """float64 slab restatement for a food square (rotation = quarter-turn
-    fraction * pi/2): hit iff the ray's parameter interval in the square is
-    non-empty and it exits at distance >= 1.1."""
-    w = rot22 * (np.pi / 2) / 4194304.0
-    a1 = np.array([np.cos(w), np.sin(w)])
-    a2 = np.array([-np.sin(w), np.cos(w)])
-    d = _dirs(heading)
-    d /= np.linalg.norm(d, axis=1)[:, None]
-    o = np.array(agent, np.float64) - np.array(centre, np.float64)
-    lo = np.full(33, -np.inf)
-    hi = np.full(33, np.inf)
-    for ax in (a1, a2):
-        b = d @ ax
-        m = o @ ax
-        with np.errstate(divide="ignore", invalid="ignore"):
-            t1, t2 = (-1.0 - m) / b, (1.0 - m) / b
-        lo = np.maximum(lo, np.where(b != 0, np.minimum(t1, t2), np.where(abs(m) <= 1, -np.inf, np.inf)))
-        hi = np.minimum(hi, np.where(b != 0, np.maximum(t1, t2), np.where(abs(m) <= 1, np.inf, -np.inf)))
-    hit = (lo <= hi) & (hi >= NEAR)
-    margin = np.minimum(np.abs(hi - lo), np.abs(hi - NEAR))
-    return hit, margin
+# (the float64 geometry lives in scene_ref.py, shared with the scene renderer)
+from scene_ref import NEAR, R_AGENT, dirs as _dirs, ref_box as _ref_box, ref_disc as _ref_disc  # noqa: E402,F401
 
 
 def test_disc_at_1_5_ahead():

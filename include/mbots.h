@@ -291,8 +291,8 @@ int mbots_write_actions(mbots_handle *h, const int32_t *action, const float *hid
 int mbots_num_rows(mbots_handle *h, uint32_t *out);
 /* the largest world population after the last step (the shard ghost
  * included): waits for that step's row counts only (K2), not for its sensor
- * or the caller's chain -- what SimManager(agent_capacity="auto") checks
- * before each step (a step adds at most n births and A respawns) */
+ * or the caller's chain -- what mbots_set_auto_capacity checks before each
+ * step (a step adds at most n births and A respawns) */
 int mbots_max_population(mbots_handle *h, uint32_t *out);
 
 /* Checkpoint / restore (the reference has none): the live state
@@ -301,11 +301,60 @@ int mbots_max_population(mbots_handle *h, uint32_t *out);
  * configuration continues bit-exactly after mbots_load_checkpoint -- also
  * one of another agent_capacity, when every world of the blob fits it (the
  * per-slot columns are re-laid out; a world that does not fit is refused
- * before anything is overwritten).  The Python SimManager's
- * agent_capacity="auto" grows a run through the capacity classes this way. */
+ * before anything is overwritten).  The Python SimManager's CPU mode grows a
+ * run through the capacity classes this way; HIP mode and C callers grow in
+ * place (mbots_grow_capacity below). */
 int mbots_checkpoint_size(mbots_handle *h, uint64_t *bytes);
 int mbots_save_checkpoint(mbots_handle *h, void *host_dst, uint64_t bytes);
 int mbots_load_checkpoint(mbots_handle *h, const void *host_src, uint64_t bytes);
+
+/* Capacity growth in place (the reference's worlds have no population cap,
+ * sim.cpp:561-564, :830-834; a manager's have agent_capacity).
+ *
+ * mbots_capacity: the current slots per world (host state, no
+ * synchronisation).
+ *
+ * mbots_grow_capacity moves the manager into new_capacity slots per world
+ * inside the same handle.  Afterwards the manager is indistinguishable from a
+ * fresh manager of new_capacity that loaded this manager's checkpoint -- bitwise,
+ * on every export and every later step, shift, pack and checkpoint -- except
+ * that each row's provenance is carried too, so mbots_pack_learner_slim between
+ * the growth and the next step gives the records it gave before the growth.
+ * Kernel-timing totals, the agent-step and dropped-agent counters and the
+ * MBOTS_W_CAPACITY reporting carry on.  In HIP mode the state moves device to
+ * device (one kernel re-lays the per-slot columns, the per-world arrays and
+ * the table's live rows are copied; nothing goes through the host), after the
+ * device has drained.  new_capacity equal to the current one: MBOTS_OK,
+ * nothing done; smaller, or above MBOTS_MAX_CAPACITY, or with
+ * (num_worlds + ghost) * new_capacity >= 2^31: MBOTS_E_INVALID (shrinking
+ * stays with checkpoints).  MBOTS_E_INVALID also while the manager's stream
+ * is being captured, and once any step of this manager has been captured into
+ * a graph: captured graphs pin the capacity (a replay writes through the
+ * pointers it recorded).  MBOTS_E_NOMEM when the new storage cannot be
+ * allocated: the manager is untouched and keeps running at its capacity.
+ *
+ * Retired storage: a growth does not free the storage it leaves, so a view
+ * (mbots_export) taken before it still reads what it read -- but no longer
+ * follows the manager; take views again after a growth (their pointers and
+ * the column allocations behind them change).  The handle keeps the retired
+ * storage until mbots_destroy or mbots_release_retired, after which such
+ * views dangle.  Capacity classes double, so everything retired together is
+ * smaller than the live storage.
+ *
+ * mbots_set_auto_capacity(h, 1): mbots_step first reads the largest world
+ * population n as mbots_max_population does (a wait for the last step's K2
+ * only) and, when 2 n + init_num_agents_per_world exceeds the capacity --
+ * the step could overflow -- grows to the smallest class (128, 256, ... 4096)
+ * that holds it; at 4096 it stops growing and MBOTS_W_CAPACITY reporting
+ * takes over.  A failed growth is returned by mbots_step, which then has not
+ * stepped.  mbots_step under stream capture returns MBOTS_E_INVALID while
+ * this is enabled: automatic capacity cannot be captured into a graph.  A
+ * runtime switch, not a configuration flag: checkpoints of automatic and
+ * fixed managers are interchangeable. */
+int mbots_capacity(mbots_handle *h, uint32_t *out);
+int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity);
+int mbots_set_auto_capacity(mbots_handle *h, int32_t enable);
+int mbots_release_retired(mbots_handle *h);
 /* Debug dump of one world (viewer replacement): host arrays of agent_capacity
  * rows -- (x, y, rot.w, rot.z) f32, (species, health, finder) i32 -- the 48
  * packed food records, the food boxes' rotations ([5][48] 22-bit quarter-turn

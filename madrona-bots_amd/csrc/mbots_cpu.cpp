@@ -12,6 +12,8 @@
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
+#include <new>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -840,6 +842,59 @@ int Sim::load(const void *src, uint64_t bytes, std::string &err)
 #define X(c) col(t.c);
     MB_CPU_TABLE(X)
 #undef X
+    return MBOTS_OK;
+}
+
+int Sim::grow(uint32_t new_cap, std::string &err)
+{
+    const size_t rows_old = (size_t)W_ * cap_, rows = (size_t)W_ * new_cap;
+    try {
+        // everything new first: a failed allocation leaves the Sim as it was
+        auto slots = [&](const auto &v) {   // [world][cap_] -> [world][new_cap], the new slots zero
+            std::remove_const_t<std::remove_reference_t<decltype(v)>> o(rows);
+            for (size_t w = 0; w < W_; ++w) std::copy_n(v.begin() + w * cap_, cap_, o.begin() + w * new_cap);
+            return o;
+        };
+#define X(v) auto n##v = slots(v);
+        MB_CPU_SLOT_ARRAYS(X)
+#undef X
+        Table t0, t1;
+        t0.resize(rows);
+        t1.resize(rows);
+        const Table &cur = T_[tb_];
+#define X(c) std::copy_n(cur.c.begin(), cur.c.size(), t0.c.begin());
+        MB_CPU_TABLE(X)
+#undef X
+        std::vector<int32_t> zr(rows), si(rows), so(rows);
+        std::copy_n(src_of_.begin(), rows_old, so.begin());
+        struct Retired {
+            Table t[2];
+            std::vector<int32_t> zeros_rows, sensor_index;
+        };
+        auto old = std::make_shared<Retired>();
+        retired_.reserve(retired_.size() + 1);
+        // from here on only moves: nothing throws (the buffers, and views of
+        // them, stay where they are)
+        old->t[0] = std::move(T_[0]);
+        old->t[1] = std::move(T_[1]);
+        old->zeros_rows = std::move(zeros_rows_);
+        old->sensor_index = std::move(sensor_index_);
+        retired_.push_back(std::move(old));
+#define X(v) v = std::move(n##v);
+        MB_CPU_SLOT_ARRAYS(X)
+#undef X
+        T_[0] = std::move(t0);
+        T_[1] = std::move(t1);
+        zeros_rows_ = std::move(zr);
+        sensor_index_ = std::move(si);
+        src_of_ = std::move(so);
+    } catch (const std::bad_alloc &) {
+        err = "host allocation for agent_capacity " + std::to_string(new_cap) + " failed";
+        return MBOTS_E_NOMEM;
+    }
+    tb_ = 0;
+    cap_ = new_cap;
+    cfg_.agent_capacity = new_cap;
     return MBOTS_OK;
 }
 

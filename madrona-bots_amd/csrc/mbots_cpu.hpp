@@ -13,6 +13,7 @@
 #include "mbots_device.hpp"
 
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -64,6 +65,16 @@ public:
     uint64_t checkpoint_bytes() const;
     int save(void *dst, uint64_t bytes, std::string &err) const;
     int load(const void *src, uint64_t bytes, std::string &err);
+    // mbots_grow_capacity (new_cap > the current capacity, already checked):
+    // the per-slot arrays re-laid out to [W][new_cap] with the new slots zero,
+    // the live table half as half 0 of new_cap rows per world, the rest kept --
+    // what a fresh Sim of new_cap holds after load() of this one's save(), and
+    // src_of() besides.  The vectors a host view may point into (the table
+    // columns, the Done zeros, the sensor index) are not freed but retired, so
+    // a view taken before still reads what it read, until release_retired().
+    // MBOTS_E_NOMEM (nothing changed) when the new arrays cannot be allocated.
+    int grow(uint32_t new_cap, std::string &err);
+    void release_retired() { retired_.clear(); }
     const mbots_config &config() const { return cfg_; }
 
 private:
@@ -95,6 +106,7 @@ private:
     uint32_t totals_[5] = {};
     uint64_t agent_steps_ = 0;
     std::vector<int32_t> zeros_rows_, zeros_worlds_, sensor_index_, src_of_;
+    std::vector<std::shared_ptr<void>> retired_;   // vectors earlier growths left (grow())
 };
 
 }  // namespace cpu

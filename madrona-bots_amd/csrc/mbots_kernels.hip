@@ -3185,4 +3185,60 @@ hipError_t launch_sensor_index(const SimState &S, int32_t *out, hipStream_t st)
     return hipGetLastError();
 }
 
+// ---------------------------------------------------------------------------
+// Capacity growth (mbots_grow_capacity): the per-slot columns from
+// [world][cap_old] to [world][cap_new], every column in one launch.
+// blockIdx.y is the column, blockIdx.x a tile of kGrowPerBlock destination
+// units in row-major order (a world tile: kGrowPerBlock / units-per-row
+// worlds), so consecutive lanes write consecutive addresses and read
+// consecutive ones within a row.  A unit is 16 bytes (kVec: both capacities
+// multiples of 4 -- every class -- and the arena's 256-byte column alignment
+// make every row start 16-byte aligned) or one 4-byte slot.
+// The tail [cap_old, cap_new) of each row is written with zero in the same
+// pass: that is what a fresh manager that loaded the checkpoint holds there
+// (mbots_create clears the arena, init_kernel above writes only slots < A,
+// and mbots_load_checkpoint copies min(cap, cap_src) slots per row).
+// ---------------------------------------------------------------------------
+constexpr uint32_t kGrowThreads = 256, kGrowPerThread = 4;
+constexpr uint32_t kGrowPerBlock = kGrowThreads * kGrowPerThread;
+
+template <bool kVec>
+__global__ __launch_bounds__(kGrowThreads) void grow_slots_kernel(GrowCols c, uint32_t W, uint32_t row_old,
+                                                                  uint32_t row_new)
+{
+    using U = std::conditional_t<kVec, uint4, uint32_t>;
+    const U *__restrict__ src = static_cast<const U *>(c.src[blockIdx.y]);
+    U *__restrict__ dst = static_cast<U *>(c.dst[blockIdx.y]);
+    const uint32_t total = W * row_new;   // (< 2^31 slots: checked by the caller)
+    const uint32_t g0 = blockIdx.x * kGrowPerBlock + threadIdx.x;
+    U v[kGrowPerThread];
+#pragma unroll
+    for (uint32_t k = 0; k < kGrowPerThread; ++k) {   // every load in flight before the first store
+        const uint32_t g = g0 + k * kGrowThreads;
+        const uint32_t w = g / row_new, j = g - w * row_new;
+        v[k] = U{};
+        if (g < total && j < row_old) v[k] = src[(size_t)w * row_old + j];
+    }
+#pragma unroll
+    for (uint32_t k = 0; k < kGrowPerThread; ++k) {
+        const uint32_t g = g0 + k * kGrowThreads;
+        if (g < total) dst[g] = v[k];
+    }
+}
+
+hipError_t launch_grow_slots(const GrowCols &c, uint32_t W, uint32_t cap_old, uint32_t cap_new, hipStream_t st)
+{
+    if (cap_new < cap_old || (uint64_t)W * cap_new >= (1ull << 31)) return hipErrorInvalidValue;
+    const bool vec = cap_old % 4 == 0 && cap_new % 4 == 0;
+    for (int k = 0; vec && k < kGrowCols; ++k)
+        if ((reinterpret_cast<uintptr_t>(c.src[k]) | reinterpret_cast<uintptr_t>(c.dst[k])) & 15u)
+            return hipErrorInvalidValue;
+    const uint32_t row_old = vec ? cap_old / 4 : cap_old, row_new = vec ? cap_new / 4 : cap_new;
+    const uint32_t total = W * row_new;
+    const dim3 grid((total + kGrowPerBlock - 1) / kGrowPerBlock, kGrowCols), blk(kGrowThreads);
+    if (vec) hipLaunchKernelGGL(grow_slots_kernel<true>, grid, blk, 0, st, c, W, row_old, row_new);
+    else hipLaunchKernelGGL(grow_slots_kernel<false>, grid, blk, 0, st, c, W, row_old, row_new);
+    return hipGetLastError();
+}
+
 }  // namespace mbots

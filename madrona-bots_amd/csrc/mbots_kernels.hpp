@@ -202,6 +202,15 @@ __host__ __device__ inline int32_t rebuild_row(const RebuildPlan &p, int32_t r, 
     while (t > 0 && o < p.last_l[k][t]) --t;
     return p.last_g[k][t] + (o - p.last_l[k][t]);
 }
+// capacity growth (mbots_grow_capacity): the per-slot columns ([world][cap],
+// 4-byte slots) re-laid from cap_old to cap_new slots per world in one launch,
+// the new slots [cap_old, cap_new) of every world zeroed
+constexpr int kGrowCols = 11;
+struct GrowCols {
+    const void *src[kGrowCols];
+    void *dst[kGrowCols];
+};
+hipError_t launch_grow_slots(const GrowCols &c, uint32_t W, uint32_t cap_old, uint32_t cap_new, hipStream_t st);
 hipError_t launch_rebuild_learner(const RebuildPlan &p, const int32_t *src, uint32_t rows, uint32_t last_rows,
                                   const int32_t *last_action, const float *last_memory, const float *last_hidden,
                                   int32_t *action, float *hidden, float *prev_hidden, hipStream_t st);

@@ -150,6 +150,9 @@ struct mbots_handle {
     std::vector<hipEvent_t> pool;
     double acc_ms[MBOTS_TK_COUNT] = {};
     uint64_t acc_n[MBOTS_TK_COUNT] = {};
+    bool auto_cap = false;            // mbots_set_auto_capacity: mbots_step grows before it could overflow
+    std::vector<char *> retired;      // arenas earlier growths left (views taken then still read
+                                      // them): freed by mbots_release_retired / mbots_destroy
 };
 
 namespace {
@@ -219,6 +222,12 @@ bool fork_by_value(uint32_t W) { return W <= MB_VALUE_FORK_MAX && W > MB_K1_FIND
 bool join_by_value(uint32_t W)
 {
     return MB_VALUE_JOIN && W <= MB_VALUE_JOIN_MAX && W > MB_K1_FINDER_MAX && value_waits_safe();
+}
+
+bool mixed_wanted()
+{
+    const char *e = std::getenv("MBOTS_MIXED");
+    return !(e && *e == '0');
 }
 
 hipEvent_t get_event(mbots_handle *h)
@@ -834,9 +843,7 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
         // and sensor take every world that fits them and the class kernels
         // only the worlds K2 lists (DESIGN.md "Capacity"); MBOTS_MIXED=0 runs
         // every world in the class kernels
-        const char *e = std::getenv("MBOTS_MIXED");
-        const bool want = !(e && *e == '0');
-        S.mixed = (want && S.cap > (uint32_t)mbots::kSmallCap && !h->k1_finder) ? 1u : 0u;
+        S.mixed = (mixed_wanted() && S.cap > (uint32_t)mbots::kSmallCap && !h->k1_finder) ? 1u : 0u;
     }
 
     int rc = MBOTS_OK;
@@ -946,11 +953,34 @@ int mbots_destroy(mbots_handle *h)
     if (h->aux) (void)hipStreamDestroy(h->aux);
     if (h->h_totals) (void)hipHostFree(h->h_totals);
     if (h->arena.base) (void)hipFree(h->arena.base);
+    for (char *p : h->retired) (void)hipFree(p);
     delete h;
     return MBOTS_OK;
 }
 
 // MBOTS_W_CAPACITY / MBOTS_E_CAPACITY once per rise of the dropped-agent total
+// the smallest kernel capacity class holding `need` agents (the largest when
+// none does)
+static uint32_t capacity_class(uint64_t need)
+{
+    uint32_t c = (uint32_t)mbots::kSmallCap;
+    while (c < MBOTS_MAX_CAPACITY && c < need) c *= 2;
+    return c;
+}
+
+// mbots_set_auto_capacity: before a step that could overflow -- it adds at most
+// n births (one per agent, sim.cpp:561-564) and A respawns (:830-834) to the
+// largest world's n agents -- the smallest class that holds 2 n + A
+static int auto_grow(mbots_handle *h)
+{
+    if (h->cfg.agent_capacity >= MBOTS_MAX_CAPACITY) return MBOTS_OK;   // (MBOTS_W_CAPACITY from here on)
+    uint32_t n = 0;
+    if (int rc = mbots_max_population(h, &n)) return rc;
+    const uint64_t need = 2ull * n + h->cfg.init_num_agents_per_world;
+    if (need <= h->cfg.agent_capacity) return MBOTS_OK;
+    return mbots_grow_capacity(h, capacity_class(need));
+}
+
 static int capacity_report(mbots_handle *h, uint32_t dropped)
 {
     if (dropped <= h->ovf_reported) return MBOTS_OK;
@@ -970,6 +1000,8 @@ int mbots_step(mbots_handle *h, void *stream)
 {
     if (!h) return fail(MBOTS_E_INVALID, "null handle");
     if (h->cpu) {
+        if (h->auto_cap)
+            if (int rc = auto_grow(h)) return rc;
         h->cpu->step();
         ++h->steps;
         return capacity_report(h, (uint32_t)std::min<uint64_t>(h->cpu->overflow(), 0xFFFFFFFFu));
@@ -981,6 +1013,15 @@ int mbots_step(mbots_handle *h, void *stream)
     unsigned long long cap_id = 0;
     HIP_TRY(hipStreamGetCaptureInfo(st, &cap_status, &cap_id));
     const bool capturing = cap_status == hipStreamCaptureStatusActive;
+    if (h->auto_cap) {
+        // (the check reads the host-side population and a growth moves the
+        // arena: neither can be part of a graph)
+        if (capturing)
+            return fail(MBOTS_E_INVALID, "automatic capacity cannot be captured into a graph: a step with "
+                                         "mbots_set_auto_capacity enabled reads the largest population on the "
+                                         "host and may move the manager's storage; disable it before capturing");
+        if ((rc = auto_grow(h))) return rc;
+    }
     if (capturing && cap_id != h->cap_seen) {
         // a new capture: the previous one must have held an even number of steps
         if ((rc = capture_guard(h, nullptr))) return rc;
@@ -1818,6 +1859,44 @@ int mbots_save_checkpoint(mbots_handle *h, void *dst, uint64_t bytes)
     return MBOTS_OK;
 }
 
+// the state a restore ends with (mbots_load_checkpoint, mbots_grow_capacity):
+// the restored table is half 0, the scan tiles are clear, nothing is deferred,
+// no sensor is outstanding and the device is idle
+static int restored_reset(mbots_handle *h, bool sensed)
+{
+    HIP_TRY(hipMemset(h->S.tiles, 0, (size_t)2 * h->S.ntiles * mbots::kTileBuckets * 5 * sizeof(int32_t)));
+    if (h->S.mixed) {
+        // the first K1 after the load (parity 0) reads the class list of slot 1
+        HIP_TRY(hipMemset(h->S.big_cnt, 0, 4 * sizeof(uint32_t)));
+        HIP_TRY(mbots::launch_build_lists(h->S, 1, nullptr));
+    }
+    h->tb = 0;
+    h->parity = 0;
+    h->last_join = -1;
+    h->prev_join = -1;
+    h->waited_serial = h->sensor_serial;   // (the device is idle)
+    h->join_epoch = 0;
+    h->prev_lazy[0] = h->prev_lazy[1] = false;
+    h->ah_pending[0] = h->ah_pending[1] = false;
+    h->six_pending[0] = h->six_pending[1] = false;
+    h->cur_ah_pending[0] = h->cur_ah_pending[1] = false;
+    h->psem_pending[0] = h->psem_pending[1] = false;
+    h->a_alias[0] = h->a_alias[1] = h->h_alias[0] = h->h_alias[1] = false;
+    h->forced = 0;
+    h->prefetched = 0;
+    h->steps = 1;
+    h->sensed = sensed;
+    hipStream_t st = nullptr;
+    h->last_stream = st;
+    h->totals_ok = false;
+    int rc = record_totals(h, st);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    h->ovf_reported = h->h_totals[mbots::kTotOverflow];   // drops before the checkpoint were reported then
+    h->maxpop_stale = true;
+    return MBOTS_OK;
+}
+
 int mbots_load_checkpoint(mbots_handle *h, const void *src, uint64_t bytes)
 {
     if (!h || !src) return fail(MBOTS_E_INVALID, "null argument");
@@ -1885,36 +1964,182 @@ int mbots_load_checkpoint(mbots_handle *h, const void *src, uint64_t bytes)
         }
         p += segs_src[i].bytes;
     }
-    HIP_TRY(hipMemset(h->S.tiles, 0, (size_t)2 * h->S.ntiles * mbots::kTileBuckets * 5 * sizeof(int32_t)));
-    if (h->S.mixed) {
-        // the first K1 after the load (parity 0) reads the class list of slot 1
-        HIP_TRY(hipMemset(h->S.big_cnt, 0, 4 * sizeof(uint32_t)));
-        HIP_TRY(mbots::launch_build_lists(h->S, 1, nullptr));
+    return restored_reset(h, hd.sensed != 0);
+}
+
+// ---- capacity growth in place (absent in the reference, whose worlds have no
+// cap: sim.cpp:561-564, :830-834) ----
+int mbots_capacity(mbots_handle *h, uint32_t *out)
+{
+    if (!h || !out) return fail(MBOTS_E_INVALID, "null argument");
+    *out = h->cfg.agent_capacity;
+    return MBOTS_OK;
+}
+
+namespace {
+// everything layout() sets
+struct LayoutPtrs {
+    mbots::SimState S;
+    mbots::ObsTable T[2];
+    int32_t *row_base2[2], *sorder2[2], *obsrow_out2[2], *done_zeros, *reset_zeros, *sensor_index;
+};
+LayoutPtrs layout_ptrs(const mbots_handle *h)
+{
+    return {h->S, {h->T[0], h->T[1]}, {h->row_base2[0], h->row_base2[1]}, {h->sorder2[0], h->sorder2[1]},
+            {h->obsrow_out2[0], h->obsrow_out2[1]}, h->done_zeros, h->reset_zeros, h->sensor_index};
+}
+void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
+{
+    h->S = p.S;
+    for (int k = 0; k < 2; ++k) {
+        h->T[k] = p.T[k];
+        h->row_base2[k] = p.row_base2[k];
+        h->sorder2[k] = p.sorder2[k];
+        h->obsrow_out2[k] = p.obsrow_out2[k];
     }
-    h->tb = 0;
-    h->parity = 0;
-    h->last_join = -1;
-    h->prev_join = -1;
-    h->waited_serial = h->sensor_serial;   // (the device is idle)
-    h->join_epoch = 0;
-    h->prev_lazy[0] = h->prev_lazy[1] = false;
-    h->ah_pending[0] = h->ah_pending[1] = false;
-    h->six_pending[0] = h->six_pending[1] = false;
-    h->cur_ah_pending[0] = h->cur_ah_pending[1] = false;
-    h->psem_pending[0] = h->psem_pending[1] = false;
-    h->a_alias[0] = h->a_alias[1] = h->h_alias[0] = h->h_alias[1] = false;
-    h->forced = 0;
-    h->prefetched = 0;
-    h->steps = 1;
-    h->sensed = hd.sensed != 0;
-    hipStream_t st = nullptr;
-    h->last_stream = st;
-    h->totals_ok = false;
-    int rc = record_totals(h, st);
+    h->done_zeros = p.done_zeros;
+    h->reset_zeros = p.reset_zeros;
+    h->sensor_index = p.sensor_index;
+}
+}  // namespace
+
+int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    const uint32_t cap_old = h->cfg.agent_capacity;
+    if (new_capacity > (uint32_t)mbots::kMaxCap)
+        return fail(MBOTS_E_INVALID, "agent_capacity must be in [4, " + std::to_string(mbots::kMaxCap) + "]");
+    if (new_capacity < cap_old)
+        return fail(MBOTS_E_INVALID, "mbots_grow_capacity cannot shrink (" + std::to_string(cap_old) + " -> " +
+                                         std::to_string(new_capacity) +
+                                         " slots): load a checkpoint into a smaller manager instead");
+    if (h->cpu) {
+        if (new_capacity == cap_old) return MBOTS_OK;
+        std::string err;
+        const int r = h->cpu->grow(new_capacity, err);
+        if (r) return fail(r, err);
+        h->cfg.agent_capacity = new_capacity;
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (capturing_now(h))
+        return fail(MBOTS_E_INVALID, "grow_capacity moves the manager's storage and cannot be captured into a graph");
+    if (int rc = capture_guard(h, h->last_stream)) return rc;
+    if (new_capacity == cap_old) return MBOTS_OK;
+    if (h->cap_seen != 0)
+        return fail(MBOTS_E_INVALID, "captured graphs pin the capacity: a step of this manager was captured into a "
+                                     "graph, whose replays write through the current storage's pointers; create "
+                                     "a new manager (or load a checkpoint into one) to change agent_capacity");
+    if ((uint64_t)h->S.W * new_capacity >= (1ull << 31))
+        return fail(MBOTS_E_INVALID, "num_worlds * agent_capacity >= 2^31");
+    int rc = materialize_prev(h, h->last_stream);
+    if (!rc) rc = materialize_prev_ah(h, h->last_stream);
+    if (!rc) rc = materialize_cur_ah(h, h->last_stream, 3);
+    if (!rc) rc = materialize_psem(h, h->last_stream);
     if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    h->ovf_reported = h->h_totals[mbots::kTotOverflow];   // drops before the checkpoint were reported then
-    h->maxpop_stale = true;
+    HIP_TRY(hipDeviceSynchronize());   // the sensor's finder / semantic rows included
+    if ((rc = sync_totals(h))) return rc;
+    const uint32_t n_rows = h->h_totals[mbots::kTotRows];   // the shard ghost's rows included
+    // the old storage: what a checkpoint would save, and the row provenance
+    const std::vector<Seg> from = ckpt_segments(h, h->T[h->tb], n_rows);
+    const int32_t *src_of_old = h->S.src_of;
+    const LayoutPtrs old = layout_ptrs(h);
+    const Arena old_arena = h->arena;
+    h->cfg.agent_capacity = new_capacity;   // (layout() sizes by it)
+    Arena fresh;
+    const size_t bytes = layout(h, fresh);
+    auto undo = [&] {
+        set_layout_ptrs(h, old);
+        h->cfg.agent_capacity = cap_old;
+        h->arena = old_arena;
+    };
+    h->retired.reserve(h->retired.size() + 1);   // (so retiring the old arena below cannot throw)
+    if (hipMalloc(&fresh.base, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        undo();
+        return fail(MBOTS_E_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes for agent_capacity " +
+                                       std::to_string(new_capacity) + " failed; the manager keeps running at " +
+                                       std::to_string(cap_old));
+    }
+    fresh.size = bytes;
+    fresh.used = 0;
+    h->arena = fresh;
+    layout(h, h->arena);
+    h->S.cap = new_capacity;
+    const std::vector<Seg> to = ckpt_segments(h, h->T[0], n_rows);
+    hipStream_t st = nullptr;
+    auto move = [&]() -> hipError_t {
+        // the per-slot columns lead the arena (layout()'s first takes) and the
+        // kernel writes every slot of them: everything behind them is cleared,
+        // as mbots_create clears it
+        char *rest = reinterpret_cast<char *>(h->S.n);
+        for (size_t i = 0; i < kSlotSegs; ++i)
+            if (static_cast<char *>(to[i].p) + to[i].bytes > rest) rest = h->arena.base;
+        hipError_t e = hipMemsetAsync(rest, 0, (size_t)(h->arena.base + bytes - rest), st);
+        if (e != hipSuccess) return e;
+        mbots::GrowCols c{};
+        static_assert(kSlotSegs == (size_t)mbots::kGrowCols, "ckpt_segments");
+        for (size_t i = 0; i < kSlotSegs; ++i) {
+            c.src[i] = from[i].p;
+            c.dst[i] = to[i].p;
+        }
+        if ((e = mbots::launch_grow_slots(c, (uint32_t)h->S.W, cap_old, new_capacity, st)) != hipSuccess) return e;
+        for (size_t i = kSlotSegs; i < to.size(); ++i)
+            if (to[i].bytes &&
+                (e = hipMemcpyAsync(to[i].p, from[i].p, to[i].bytes, hipMemcpyDeviceToDevice, st)) != hipSuccess)
+                return e;
+        // (a checkpoint does not carry it: slim learner records packed before the
+        // next step keep their provenance)
+        if (n_rows && (e = hipMemcpyAsync(h->S.src_of, src_of_old, (size_t)n_rows * sizeof(int32_t),
+                                          hipMemcpyDeviceToDevice, st)) != hipSuccess)
+            return e;
+        if ((e = mbots::upload_ray_table(h->S, st)) != hipSuccess) return e;
+        return hipStreamSynchronize(st);
+    };
+    if (const hipError_t e = move(); e != hipSuccess) {
+        (void)hipDeviceSynchronize();
+        (void)hipFree(fresh.base);
+        undo();
+        return fail(MBOTS_E_HIP, std::string("mbots_grow_capacity: ") + hipGetErrorString(e));
+    }
+    // what mbots_create derives from the capacity
+    h->k1_finder = h->S.W <= MB_K1_FINDER_MAX && h->S.cap <= 256;
+    h->S.k1_finder = h->k1_finder ? 1u : 0u;
+    h->S.mixed = (mixed_wanted() && h->S.cap > (uint32_t)mbots::kSmallCap && !h->k1_finder) ? 1u : 0u;
+    h->retired.push_back(old_arena.base);
+    const uint32_t reported = h->ovf_reported;
+    const bool sensed = h->sensed;
+    rc = restored_reset(h, sensed);
+    h->ovf_reported = reported;   // (drops not yet reported stay owed: nothing was restored)
+    return rc;
+}
+
+int mbots_set_auto_capacity(mbots_handle *h, int32_t enable)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    h->auto_cap = enable != 0;
+    if (h->auto_cap && !h->cpu && !h->S.track_maxpop) {
+        // K2 publishes the tile maxima from the next step on (not from the
+        // first check on, a step later)
+        h->S.track_maxpop = 1u;
+        h->maxpop_stale = true;
+    }
+    return MBOTS_OK;
+}
+
+int mbots_release_retired(mbots_handle *h)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    if (h->cpu) {
+        h->cpu->release_retired();
+        return MBOTS_OK;
+    }
+    if (h->retired.empty()) return MBOTS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    if (capturing_now(h)) return fail(MBOTS_E_INVALID, "release_retired cannot be captured into a graph");
+    HIP_TRY(hipDeviceSynchronize());   // (a caller's kernel may still read a retired view)
+    for (char *p : h->retired) (void)hipFree(p);
+    h->retired.clear();
     return MBOTS_OK;
 }
 

@@ -97,6 +97,10 @@ def _load():
         "mbots_kernel_times": [vp, P(ctypes.c_double), P(ctypes.c_uint64)],
         "mbots_schedule_info": [vp, P(u32)],
         "mbots_max_population": [vp, P(u32)],
+        "mbots_capacity": [vp, P(u32)],
+        "mbots_grow_capacity": [vp, u32],
+        "mbots_set_auto_capacity": [vp, i32],
+        "mbots_release_retired": [vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -214,6 +218,7 @@ class Tensor:
         self._keep = keep            # the manager's _Handle: keeps its memory alive
         self._mgr = mgr              # the manager (its view cache), for table columns
         self._column = column        # a table column: W x cap row slots behind it
+        self._gen = mgr._gen if mgr is not None else 0   # the manager's storage it points into
         self._ptr = int(ct.data or 0)
         self._torch_dtype, self._typestr = _DTYPES[ct.dtype]
         self._device = int(ct.device)
@@ -242,10 +247,11 @@ class Tensor:
         # the learner reads ~10 views per step and is host-bound at small world
         # counts (scripts/refhost.py); building a view from the array interface
         # every time is most of an accessor's host cost
-        # (a view taken before an agent_capacity="auto" growth belongs to the
-        # manager's previous storage: no cached view of the current one)
+        # (a view taken before a capacity growth belongs to the manager's
+        # previous storage: no cached view of the current one)
         base = self._mgr._view_cache(self) if (self._column and self._mgr is not None
-                                                and self._keep is self._mgr._hd) else None
+                                                and self._keep is self._mgr._hd
+                                                and self._gen == self._mgr._gen) else None
         if base is not None:
             return base[:self.shape[0]]
         t = torch.as_tensor(self, device=dev)
@@ -391,29 +397,35 @@ class SimManager:
     birth or respawn makes step() raise CapacityError instead of warning with
     CapacityWarning: the reference has no cap).
 
-    agent_capacity="auto" grows the worlds' capacity instead of dropping
-    agents: before each step() the manager reads the largest world population
-    n (mbots_max_population: a wait for the last step's row counts, not for
-    its sensor) and, when the step could overflow -- a step adds at
-    most n births (one per agent, sim.cpp:561-564) and A respawns
-    (:830-834) -- moves its state into the next capacity class (128, 256, 512,
-    1024) through a checkpoint, so the run stays the reference's (bitwise equal
-    to a manager that never drops) up to 1024 agents per world.  Views fetched
-    before a growth keep the old storage alive but no longer follow the
-    manager: take them after step(), as learn/training_loop.py:43-50 does."""
+    auto_grow=True grows the worlds' capacity instead of dropping agents:
+    before each step() the manager reads the largest world population n
+    (mbots_max_population: a wait for the last step's row counts, not for its
+    sensor) and, when the step could overflow -- a step adds at most n births
+    (one per agent, sim.cpp:561-564) and A respawns (:830-834) -- moves its
+    state into the smallest capacity class (128, 256, 512, 1024, 2048, 4096)
+    that holds 2 n + A, so the run stays the reference's (bitwise equal to a
+    manager that never drops) up to 4096 agents per world.  The run starts at
+    agent_capacity; agent_capacity="auto" is the class of 3 A with growth on.
+    In HIP mode the growth is the library's (mbots_set_auto_capacity: a
+    device-side move inside the same handle), in CPU mode a hand-over to a
+    new native manager through a checkpoint.  A sharded run grows each
+    rank on its own worlds (shard_ghost counted): results do not depend on
+    the class a world runs in.  grow_capacity(cap) grows by hand.  Views
+    fetched before a growth keep reading the storage they were taken from
+    (kept until release_retired() or the manager's end) but no longer follow
+    the manager: take them after step(), as learn/training_loop.py:43-50 does.
+    A step captured into a HIP graph pins the capacity."""
 
     def __init__(self, gpu_id, num_worlds, rand_seed, init_num_agents_per_world, *,
                  exec_mode="hip", agent_capacity=128, world_offset=0, reward_fixed=False,
-                 fix_depth_alias=False, shard_ghost=False, strict_capacity=False):
+                 fix_depth_alias=False, shard_ghost=False, strict_capacity=False, auto_grow=False):
         self.exec_mode = _exec_mode(exec_mode)
         self.gpu_id = int(gpu_id)
         self.num_worlds = int(num_worlds)
-        self._auto_cap = isinstance(agent_capacity, str)
-        if self._auto_cap:
+        self._auto_cap = isinstance(agent_capacity, str) or bool(auto_grow)
+        if isinstance(agent_capacity, str):
             if agent_capacity != "auto":
                 raise ValueError('agent_capacity must be an int or "auto"')
-            if shard_ghost:
-                raise ValueError('agent_capacity="auto" does not combine with shard_ghost')
             agent_capacity = _capacity_class(3 * int(init_num_agents_per_world))
         self.agent_capacity = int(agent_capacity)
         flags = (FLAG_REWARD_FIXED if reward_fixed else 0) | \
@@ -425,6 +437,7 @@ class SimManager:
         self._ghost = bool(shard_ghost)
         self._fix_depth = bool(fix_depth_alias)
         self._ktiming = False
+        self._gen = 0                # bumped when the columns' storage moves (a growth)
         self._open(self.agent_capacity)
 
     def _open(self, cap):
@@ -436,14 +449,42 @@ class SimManager:
         _check(_lib.mbots_create(ctypes.byref(cfg), ctypes.byref(h)))
         self._hd = _Handle(h)        # destroyed when the manager and all its views are gone
         self._h = h
+        if self._auto_cap and self.exec_mode == ExecMode.HIP:
+            _check(_lib.mbots_set_auto_capacity(h, 1))   # mbots_step grows in place
+        self._set_capacity(cap)
+
+    def _set_capacity(self, cap):
         self.agent_capacity = int(cap)
         # row slots of every table column (the shard ghost is one more world)
         self._cap_rows = (self.num_worlds + (1 if self._ghost else 0)) * self.agent_capacity
         self._views = {}
+        self._gen += 1
+
+    def _refresh_capacity(self):
+        """Follow a growth the library did (mbots_capacity: host state, no
+        synchronisation)."""
+        v = ctypes.c_uint32()
+        _check(_lib.mbots_capacity(self._h, ctypes.byref(v)))
+        if v.value != self.agent_capacity:
+            self._set_capacity(v.value)
+
+    def grow_capacity(self, cap):
+        """Move the manager into `cap` slots per world in place
+        (mbots_grow_capacity: same handle, device-side in HIP mode); `cap`
+        equal to agent_capacity does nothing, a smaller one or one above
+        MAX_CAPACITY raises.  Views taken before read the retired storage."""
+        _check(_lib.mbots_grow_capacity(self._h, int(cap)))
+        self._refresh_capacity()
+
+    def release_retired(self):
+        """Free the storage earlier growths retired (mbots_release_retired);
+        views taken before those growths must not be used afterwards."""
+        _check(_lib.mbots_release_retired(self._h))
 
     def _grow_if_needed(self):
-        """agent_capacity="auto": the next capacity class before a step that
-        could overflow this one (at most 2 n + A agents after it)."""
+        """CPU mode with growth on: the next capacity class before a step that
+        could overflow this one (at most 2 n + A agents after it), handed
+        over to a new native manager through a checkpoint."""
         if self.agent_capacity >= MAX_CAPACITY:
             return
         # (waits for the last step's row counts only, not for its sensor or the
@@ -454,13 +495,13 @@ class SimManager:
         if need <= self.agent_capacity:
             return
         blob = self.save_checkpoint()
-        old = (self._hd, self._h, self.agent_capacity, self._cap_rows, self._views)
+        old = (self._hd, self._h, self.agent_capacity, self._cap_rows, self._views, self._gen)
         self._open(_capacity_class(need))   # (raises with the manager unchanged)
         try:
             _check(_lib.mbots_load_checkpoint(self._h, ctypes.c_void_p(blob.ctypes.data), blob.size))
         except BaseException:
             # keep running in the old class rather than on a fresh world
-            self._hd, self._h, self.agent_capacity, self._cap_rows, self._views = old
+            self._hd, self._h, self.agent_capacity, self._cap_rows, self._views, self._gen = old
             raise
         if self._ktiming:
             self.enable_kernel_timing(True)
@@ -500,9 +541,12 @@ class SimManager:
 
     # -- graphs -------------------------------------------------------------
     def step(self):
-        if self._auto_cap:
+        native = self._auto_cap and self.exec_mode == ExecMode.HIP
+        if self._auto_cap and not native:
             self._grow_if_needed()
         rc = _lib.mbots_step(self._h, self._stream())
+        if native:
+            self._refresh_capacity()
         if rc == _W_CAPACITY:   # the step ran; agents were dropped at the cap (reported late by a few steps)
             warnings.warn(f"madrona_bots: {_lib.mbots_last_error().decode(errors='replace')}",
                           CapacityWarning, stacklevel=2)

@@ -114,7 +114,10 @@ enum mbots_export_id {
     MBOTS_EXPORT_NUM_REFERENCE = 22,
     /* build extensions (not exported by the reference) */
     MBOTS_EXPORT_SPECIES = 32,           /* SpeciesObservation column     */
-    MBOTS_EXPORT_PREV_SPECIES = 33       /* PrevSpeciesObservation column */
+    MBOTS_EXPORT_PREV_SPECIES = 33,      /* PrevSpeciesObservation column */
+    MBOTS_EXPORT_EPISODE = 34,           /* int32 [num_worlds, 1]: the world's episode   */
+    MBOTS_EXPORT_EPISODE_STEP = 35       /* int32 [num_worlds, 1]: steps since its last
+                                            reset or creation                            */
 };
 
 /* element types (madrona::py::TensorElementType subset) */
@@ -383,6 +386,58 @@ int mbots_world_state(mbots_handle *h, uint32_t world, float *xy_rwrz, int32_t *
 int mbots_set_world_state(mbots_handle *h, uint32_t world, const float *xy_rwrz, uint32_t n_agents,
                           const int32_t *food, uint32_t n_food);
 
+/* Episodes and resets.  The reference registers WorldReset, exports it as
+ * ExportID::Reset (sim.cpp:64-75) and seeds a world with
+ * split_i(initRandKey, curWorldEpisode++, worldID) (sim.cpp:1236-1240), but its
+ * resetSystem is a stub (sim.cpp:302-305); this finishes it with that key
+ * schedule: episode e of global world gw is keyed threefry2x32(seed, 0, e, gw),
+ * episode 0 being the world mbots_create builds.
+ *
+ * Reset, then step: a world flagged for reset is re-initialised at the start
+ * of the next mbots_step -- exactly as mbots_create initialises it, from its
+ * episode's key -- and is then stepped like every other world.  All its agents
+ * are new: their rows have no predecessor (Action, HiddenState, every Prev*
+ * column and the prev sensor zero, provenance -1, as for a newborn).  The
+ * dropped-agent and agent-step counters stay cumulative, the capacity stays,
+ * Done stays zeros (derive it from MBOTS_EXPORT_EPISODE_STEP).
+ *
+ * MBOTS_EXPORT_RESET is the live, writable flag array, one int32 per world:
+ * 0 none; 1 reset to the world's next episode (what a learner writes); v >= 2
+ * reset to episode v - 2.  The step that consumes a flag clears it.
+ * MBOTS_EXPORT_EPISODE is each world's current episode (from 0),
+ * MBOTS_EXPORT_EPISODE_STEP the steps since its last reset or creation (1
+ * after the step that reset it; counted from 0 again by a checkpoint load that
+ * brings no episodes).  All three arrays hold one entry per
+ * simulated world: the views show the num_worlds exported worlds, a shard
+ * ghost's entry follows at index num_worlds.
+ *
+ * mbots_reset_worlds flags `n` worlds by global index (episodes NULL: each
+ * world's next episode; else episodes[k], < 2^31 - 2, for global_worlds[k]),
+ * stream-ordered on `stream`.  Entries outside this manager's worlds are
+ * ignored, so every rank of a sharded run can be handed the same list; a rank
+ * whose shard ghost is world world_offset + num_worlds resets its ghost from
+ * it.  n == 0 does nothing.  MBOTS_E_INVALID while `stream` is being captured
+ * (the list is uploaded from the host): under capture, write the flag array.
+ *
+ * mbots_set_episode_length(h, steps): a world whose MBOTS_EXPORT_EPISODE_STEP
+ * has reached `steps` at the start of a step is reset to its next episode, as
+ * if its flag were 1 (0: off, the default).  The shard ghost follows the same
+ * rule, so shards stay equal to one device with no communication.  Refused
+ * once a step of the manager has been captured into a graph.
+ *
+ * Arming: a manager is unarmed until the first mbots_reset_worlds with n > 0,
+ * the first export of MBOTS_EXPORT_RESET or a non-zero episode length; until
+ * then mbots_step enqueues exactly what it always did.  An armed manager's
+ * steps run the reset pass (one small kernel) before the world step; they stay
+ * capturable, and the flag array is read at replay time.  Checkpoints of an
+ * armed manager carry the episodes, the ages, the pending flags and the
+ * episode length, and arm the manager that loads them; an unarmed manager's
+ * checkpoints are unchanged, and loading one into an armed manager starts every
+ * world at episode 0, age 0. */
+int mbots_reset_worlds(mbots_handle *h, const uint32_t *global_worlds, uint32_t n,
+                       const uint32_t *episodes /* NULL: next */, void *stream);
+int mbots_set_episode_length(mbots_handle *h, uint32_t steps);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That
@@ -423,9 +478,9 @@ int mbots_kernel_times(mbots_handle *h, double ms[MBOTS_TK_COUNT],
 /* The step schedule the manager chose (diagnostics, no device call):
  * out[0] flags -- 1 K1-finder mode (the next K1 does not wait for the last
  * sensor), 2 fork by value, 4 join by value, 8 MBOTS_SWAP, 16 mixed capacity
- * classes (MBOTS_MIXED); out[1] the last
+ * classes (MBOTS_MIXED), 32 armed for episodes (both modes); out[1] the last
  * value-wait epoch raised; out[2] how often the epochs restarted from 0;
- * out[3] steps run.  CPU mode: all 0 but out[3]. */
+ * out[3] steps run.  CPU mode: all 0 but the 32 of out[0] and out[3]. */
 int mbots_schedule_info(mbots_handle *h, uint32_t out[4]);
 
 const char *mbots_last_error(void);

@@ -102,7 +102,9 @@ Sim::Sim(const mbots_config &cfg)
     T_[0].resize(rows);
     T_[1].resize(rows);
     put(zeros_rows_, rows);
-    put(zeros_worlds_, W_);
+    put(reset_flags_, W_);
+    put(episode_, W_);
+    put(age_, W_);
     put(sensor_index_, rows);
     put(src_of_, rows);
     // Sim::Sim + initWorld (sim.cpp:1232-1256, :233-275), then the first export
@@ -113,10 +115,24 @@ Sim::Sim(const mbots_config &cfg)
     tb_ = 0;
 }
 
-void Sim::init_world(uint32_t w)
+// episode e of global world gw is keyed threefry2x32(seed, 0, e, gw):
+// split_i(initKey, episode, world), sim.cpp:1236-1240.  reset: a world's
+// re-initialisation between steps (reset_pass) also clears what a fresh Sim
+// holds as zeros
+void Sim::init_world(uint32_t w, uint32_t episode, bool reset)
 {
     const size_t base = (size_t)w * cap_;
-    const uint2 key = threefry2x32(cfg_.rand_seed, 0u, 0u, cfg_.world_offset + w);
+    const uint2 key = threefry2x32(cfg_.rand_seed, 0u, episode, cfg_.world_offset + w);
+    if (reset) {
+        for (uint32_t i = 0; i < A_; ++i) {
+            sur0_[base + i] = sur1_[base + i] = 0.0f;
+            stats_[base + i] = 0u;
+        }
+        std::fill_n(food_.begin() + (size_t)w * kNumChunks, kNumChunks, 0ull);
+        std::fill_n(food_rot_.begin() + (size_t)w * kNumPkg, kNumPkg, 0u);
+        std::fill_n(sreward_.begin() + (size_t)w * kNumSpecies, kNumSpecies, 0.0f);
+        cur_food_[w] = 0;
+    }
     for (uint32_t i = 0; i < A_; ++i) {
         x_[base + i] = u01(rng_draw(key, 2u * i)) * kLx;
         y_[base + i] = u01(rng_draw(key, 2u * i + 1u)) * kLy;
@@ -522,8 +538,51 @@ void Sim::sensor_world(uint32_t w, Table &nxt, int lo, int hi)
     }
 }
 
+void Sim::arm()
+{
+    if (armed_) return;
+    armed_ = true;
+    std::fill(age_.begin(), age_.end(), (int32_t)std::min<uint64_t>(age0_, 0x7FFFFFFFu));
+}
+
+void Sim::reset_worlds(const uint32_t *global_worlds, uint32_t n, const uint32_t *episodes)
+{
+    arm();
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t gw = global_worlds[k];
+        if (gw < cfg_.world_offset || gw - cfg_.world_offset >= W_) continue;   // another rank's
+        reset_flags_[gw - cfg_.world_offset] = episodes ? (int32_t)(episodes[k] + 2u) : 1;
+    }
+}
+
+void Sim::set_episode_length(uint32_t steps)
+{
+    if (steps) arm();
+    ep_len_ = steps;
+}
+
+// the reset pass of an armed Sim, before the world step (reset_worlds_kernel):
+// a flagged or expired world starts over and is then stepped like the others
+void Sim::reset_pass()
+{
+    for_worlds([&](uint32_t w) {
+        const int32_t flag = reset_flags_[w], age = age_[w];
+        if (flag == 0 && (ep_len_ == 0 || (uint32_t)age < ep_len_)) {
+            age_[w] = age + 1;
+            return;
+        }
+        const int32_t e = flag >= 2 ? flag - 2 : episode_[w] + 1;
+        init_world(w, (uint32_t)e, true);
+        episode_[w] = e;
+        age_[w] = 1;   // the world is stepped right after
+        reset_flags_[w] = 0;
+    });
+}
+
 void Sim::step()
 {
+    if (armed_) reset_pass();
+    else ++age0_;
     const Table &cur = T_[tb_];
     Table &nxt = T_[tb_ ^ 1];
     for_worlds([&](uint32_t w) { world_step(w, cur); });
@@ -627,7 +686,11 @@ int Sim::export_tensor(int32_t id, mbots_tensor *out)
     int dt = MBOTS_DTYPE_INT32;
     int64_t rows = N_, cols = 1;
     switch (id) {
-    case MBOTS_EXPORT_RESET: p = zeros_worlds_.data(); rows = Wx_; break;
+    case MBOTS_EXPORT_RESET: arm(); p = reset_flags_.data(); rows = Wx_; break;   // live: whoever holds it may write
+    case MBOTS_EXPORT_EPISODE: p = episode_.data(); rows = Wx_; break;
+    case MBOTS_EXPORT_EPISODE_STEP:
+        if (!armed_) std::fill(age_.begin(), age_.end(), (int32_t)std::min<uint64_t>(age0_, 0x7FFFFFFFu));
+        p = age_.data(); rows = Wx_; break;
     case MBOTS_EXPORT_ACTION: p = t.action.data(); cols = 6; break;
     case MBOTS_EXPORT_PREV_ACTION: p = t.paction.data(); cols = 6; break;
     case MBOTS_EXPORT_HIDDEN_STATE: p = t.hidden.data(); dt = MBOTS_DTYPE_FLOAT32; cols = kHidden; break;
@@ -736,9 +799,17 @@ constexpr char kMagic[8] = {'M', 'B', 'O', 'T', 'S', 'C', 'P', 'U'};
     X(sur) X(reward) X(hidden) X(ppos) X(psur) X(preward) X(phidden) X(sem) X(psem) X(depth)      \
     X(pdepth)
 
+// an armed Sim's blob ends with a trailer (an unarmed one's is what it always
+// was): magic, the episode length, then episode, age and the pending flags per
+// simulated world
+namespace {
+constexpr char kEpMagic[8] = {'M', 'B', 'O', 'T', 'S', 'E', 'P', '5'};
+}  // namespace
+
 uint64_t Sim::checkpoint_bytes() const
 {
-    uint64_t b = sizeof(kMagic) + sizeof(mbots_config) + sizeof(N_) + sizeof(totals_) + sizeof(agent_steps_);
+    uint64_t b = armed_ ? sizeof(kEpMagic) + 4 + (uint64_t)W_ * 12 : 0;
+    b += sizeof(kMagic) + sizeof(mbots_config) + sizeof(N_) + sizeof(totals_) + sizeof(agent_steps_);
 #define X(v) b += v.size() * sizeof(v[0]);
     MB_CPU_ARRAYS(X)
 #undef X
@@ -766,6 +837,13 @@ int Sim::save(void *dst, uint64_t bytes, std::string &err) const
 #define X(c) w(t.c.data(), t.c.size() * sizeof(t.c[0]));
     MB_CPU_TABLE(X)
 #undef X
+    if (armed_) {
+        w(kEpMagic, sizeof(kEpMagic));
+        w(&ep_len_, 4);
+        w(episode_.data(), (size_t)W_ * 4);
+        w(age_.data(), (size_t)W_ * 4);
+        w(reset_flags_.data(), (size_t)W_ * 4);
+    }
     return MBOTS_OK;
 }
 
@@ -804,7 +882,9 @@ int Sim::load(const void *src, uint64_t bytes, std::string &err)
 #define X(c) need += src_bytes(t0.c.size(), sizeof(t0.c[0]), true);
     MB_CPU_TABLE(X)
 #undef X
-    if (bytes != need) { err = "checkpoint size mismatch"; return MBOTS_E_INVALID; }
+    const size_t trailer = sizeof(kEpMagic) + 4 + (size_t)W_ * 12;
+    const bool episodes = bytes == need + trailer && memcmp(p + need, kEpMagic, sizeof(kEpMagic)) == 0;
+    if (bytes != need && !episodes) { err = "checkpoint size mismatch"; return MBOTS_E_INVALID; }
     for (uint32_t w = 0; w < W_; ++w) {   // n_ leads the per-world arrays
         int32_t n;
         memcpy(&n, p + n_off + 4 * (size_t)w, 4);
@@ -842,6 +922,22 @@ int Sim::load(const void *src, uint64_t bytes, std::string &err)
 #define X(c) col(t.c);
     MB_CPU_TABLE(X)
 #undef X
+    // episodes: an armed Sim's blob brings its armed state along; an unarmed
+    // one's knows no episodes -- an armed Sim stays armed, keeps its episode
+    // length and starts every world at episode 0, age 0, no flag pending
+    if (episodes) {
+        p += sizeof(kEpMagic);
+        armed_ = true;
+        r(&ep_len_, 4);
+        r(episode_.data(), (size_t)W_ * 4);
+        r(age_.data(), (size_t)W_ * 4);
+        r(reset_flags_.data(), (size_t)W_ * 4);
+    } else {
+        std::fill(episode_.begin(), episode_.end(), 0);
+        std::fill(age_.begin(), age_.end(), 0);
+        std::fill(reset_flags_.begin(), reset_flags_.end(), 0);
+        age0_ = 0;
+    }
     return MBOTS_OK;
 }
 

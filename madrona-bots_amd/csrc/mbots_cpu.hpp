@@ -75,11 +75,20 @@ public:
     // MBOTS_E_NOMEM (nothing changed) when the new arrays cannot be allocated.
     int grow(uint32_t new_cap, std::string &err);
     void release_retired() { retired_.clear(); }
+    // episodes (include/mbots.h "Episodes and resets"): the same operations as
+    // the HIP path's on the host vectors.  reset_worlds: global indices, entries
+    // outside this Sim's worlds (the shard ghost is one of them) ignored;
+    // episodes null: each world's next one (arguments already checked, n > 0)
+    void reset_worlds(const uint32_t *global_worlds, uint32_t n, const uint32_t *episodes);
+    void set_episode_length(uint32_t steps);
+    bool armed() const { return armed_; }
     const mbots_config &config() const { return cfg_; }
 
 private:
     template <typename F> void for_worlds(F &&fn) const;
-    void init_world(uint32_t w);
+    void init_world(uint32_t w, uint32_t episode = 0, bool reset = false);
+    void arm();
+    void reset_pass();
     void world_step(uint32_t w, const Table &cur);
     void scan();
     void export_world(uint32_t w, const Table &cur, Table &nxt, bool init);
@@ -105,7 +114,14 @@ private:
     uint32_t N_ = 0;
     uint32_t totals_[5] = {};
     uint64_t agent_steps_ = 0;
-    std::vector<int32_t> zeros_rows_, zeros_worlds_, sensor_index_, src_of_;
+    std::vector<int32_t> zeros_rows_, sensor_index_, src_of_;
+    // episodes, per simulated world: the live reset flags (MBOTS_EXPORT_RESET),
+    // the current episode, the steps since the last reset or creation (kept by
+    // the reset pass once armed; age0_ for every world before)
+    std::vector<int32_t> reset_flags_, episode_, age_;
+    bool armed_ = false;
+    uint32_t ep_len_ = 0;
+    uint64_t age0_ = 0;
     std::vector<std::shared_ptr<void>> retired_;   // vectors earlier growths left (grow())
 };
 

@@ -2584,43 +2584,110 @@ __global__ __launch_bounds__(256) void shift_kernel(const uint32_t *totals, ObsT
 // World init: Sim::Sim + initWorld (sim.cpp:233-275, :1232-1256) and the Init
 // graph's initializeChunks (sim.cpp:277-300).
 // ---------------------------------------------------------------------------
+// one world's init, a wave per world: episode `episode` of global world gw is
+// keyed threefry2x32(seed, 0, episode, gw) -- split_i(initKey, episode, world),
+// sim.cpp:1236-1240 -- and agent i takes the key's draws 2 i, 2 i + 1.  The
+// 2 A draws are spread over the lanes (lane l of a round computes draw
+// 64 r + l; the even lanes own an agent and fetch its y from their neighbour).
+// kReset: a world's re-initialisation between steps (reset_worlds_kernel): the
+// cumulative drop counter and K1's old-row column stay, the food rotations of
+// the cleared packages are zeroed as a fresh arena's are
+template <bool kReset>
+__device__ __forceinline__ void init_world_body(const SimState &S, uint32_t w, uint32_t lane, uint32_t episode)
+{
+    const size_t base = (size_t)w * S.cap;
+    const uint32_t gw = S.world_offset + w;
+    const uint2 key = threefry2x32(S.seed, 0u, episode, gw);
+    const uint32_t A = S.A, nd = 2u * A;
+    for (uint32_t u0 = 0; u0 < nd; u0 += 64) {   // wave-uniform trips (the shuffle)
+        const uint32_t u = u0 + lane;
+        const float v = u01(rng_draw(key, u));
+        const float vy = __shfl_down(v, 1);
+        const uint32_t i = u >> 1;
+        if (!(u & 1u) && i < A) {
+            S.x[base + i] = v * kLx;
+            S.y[base + i] = vy * kLy;
+            S.rw[base + i] = 1.0f;
+            S.rz[base + i] = 0.0f;
+            S.species[base + i] = (int32_t)(i % kNumSpecies) + 1;
+            S.health[base + i] = 100;
+            S.finder[base + i] = -1;
+            S.obsrow[base + i] = -1;
+            if (!kReset) S.obsrow_out[base + i] = -1;   // the initial export's old rows: none
+            S.sur0[base + i] = 0.0f;
+            S.sur1[base + i] = 0.0f;
+            S.stats[base + i] = 0u;
+        }
+    }
+    if (lane < kNumChunks) S.food[(size_t)w * kNumChunks + lane] = 0ull;
+    if (kReset)
+        for (uint32_t k = lane; k < (uint32_t)kNumPkg; k += 64) S.food_rot[(size_t)w * kNumPkg + k] = 0u;
+    if (lane < kNumSpecies) {
+        S.scount[(size_t)w * kNumSpecies + lane] = (int32_t)(A / kNumSpecies + (lane < A % kNumSpecies ? 1u : 0u));
+        S.sreward[(size_t)w * kNumSpecies + lane] = 0.0f;
+    }
+    if (lane == 0) {
+        S.key[w] = key;
+        S.ctr[w] = nd;
+        S.n[w] = (int32_t)A;
+        S.cur_food[w] = 0;
+        if (!kReset) S.overflow[w] = 0u;
+    }
+}
+
 __global__ __launch_bounds__(256) void init_kernel(SimState S)
 {
     const uint32_t wv = threadIdx.x >> 6;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t w = uniform(blockIdx.x * kWorldsPerBlock + wv);
     if (w >= S.W) return;
-    const size_t base = (size_t)w * S.cap;
-    const uint32_t gw = S.world_offset + w;
-    const uint2 key = threefry2x32(S.seed, 0u, 0u, gw);   // split_i(initKey(seed), 0, world)
-    const int A = (int)S.A;
-    for (int i = lane; i < A; i += 64) {
-        const float x = u01(rng_draw(key, 2u * (uint32_t)i)) * kLx;
-        const float y = u01(rng_draw(key, 2u * (uint32_t)i + 1u)) * kLy;
-        S.x[base + i] = x;
-        S.y[base + i] = y;
-        S.rw[base + i] = 1.0f;
-        S.rz[base + i] = 0.0f;
-        S.species[base + i] = (i % kNumSpecies) + 1;
-        S.health[base + i] = 100;
-        S.finder[base + i] = -1;
-        S.obsrow[base + i] = -1;
-        S.obsrow_out[base + i] = -1;   // the initial export's old rows: none
-        S.sur0[base + i] = 0.0f;
-        S.sur1[base + i] = 0.0f;
-        S.stats[base + i] = 0u;
+    init_world_body<false>(S, w, lane, 0u);   // split_i(initKey(seed), 0, world)
+}
+
+// ---------------------------------------------------------------------------
+// Episodes: the reset pass of an armed manager, before K1 on K1's stream (the
+// reference's resetSystem is a stub, sim.cpp:302-305; its key schedule is
+// Sim::Sim's, :1236-1240).  A wave per world.  A world whose flag is set, or
+// whose age has reached the episode length, is re-initialised in the state half
+// K1 reads, exactly as init_kernel initialises it, and is then stepped like
+// every other world; its agents' old rows are "none", so the export treats
+// them as newborns.  Every other world only counts the step (two loads, one
+// store: the wave-uniform early exit).  The K1-finder variants need no word for
+// a reset world: they compute its finder slots from the re-initialised state,
+// and no agent of it reads one this step -- its rows are new, so its actions
+// are zero, and only a shoot or a breed reads the slot.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void reset_worlds_kernel(SimState S, ResetArgs R, int parity)
+{
+    const uint32_t wv = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
+    // mixed classes: the K1 class list this step's K1 reads is rebuilt after
+    // this pass (build_lists_kernel appends to it): its count restarts here
+    if (S.mixed && blockIdx.x == 0 && threadIdx.x == 0) S.big_cnt[((uint32_t)parity ^ 1u) * 2u] = 0u;
+    const uint32_t w = uniform(blockIdx.x * kWorldsPerBlock + wv);
+    if (w >= S.W) return;
+    const int32_t flag = uniform(R.flag[w]);
+    const int32_t age = uniform(R.age[w]);
+    if (flag == 0 && (R.len == 0u || (uint32_t)age < R.len)) {
+        if (lane == 0) R.age[w] = age + 1;
+        return;
     }
-    if (lane < kNumChunks) S.food[(size_t)w * kNumChunks + lane] = 0ull;
-    if (lane < kNumSpecies) {
-        S.scount[(size_t)w * kNumSpecies + lane] = A / kNumSpecies + ((int)lane < A % kNumSpecies ? 1 : 0);
-        S.sreward[(size_t)w * kNumSpecies + lane] = 0.0f;
-    }
+    // 1: the next episode (what a learner writes); v >= 2: episode v - 2
+    const int32_t e = flag >= 2 ? flag - 2 : uniform(R.episode[w]) + 1;
+    init_world_body<true>(S, w, lane, (uint32_t)e);
     if (lane == 0) {
-        S.key[w] = key;
-        S.ctr[w] = 2u * (uint32_t)A;
-        S.n[w] = A;
-        S.cur_food[w] = 0;
-        S.overflow[w] = 0u;
+        R.episode[w] = e;
+        R.age[w] = 1;   // the world is stepped right after
+        R.flag[w] = 0;
+    }
+}
+
+__global__ __launch_bounds__(256) void set_flags_kernel(int32_t *flag, const int32_t *v, uint32_t W)
+{
+    const uint32_t w = blockIdx.x * blockDim.x + threadIdx.x;
+    if (w < W) {
+        const int32_t x = v[w];
+        if (x != 0) flag[w] = x;
     }
 }
 
@@ -2726,6 +2793,17 @@ hipError_t upload_ray_table(const SimState &S, hipStream_t st)
 hipError_t launch_init(const SimState &S, hipStream_t st)
 {
     hipLaunchKernelGGL(init_kernel, dim3(world_blocks(S.W)), dim3(256), 0, st, S);
+    return hipGetLastError();
+}
+hipError_t launch_reset_worlds(const SimState &S, const ResetArgs &R, int parity, hipStream_t st)
+{
+    hipLaunchKernelGGL(reset_worlds_kernel, dim3(world_blocks(S.W)), dim3(256), 0, st, S, R, parity);
+    if (S.mixed) hipLaunchKernelGGL(build_lists_kernel, dim3((S.W + 255) / 256), dim3(256), 0, st, S, parity ^ 1);
+    return hipGetLastError();
+}
+hipError_t launch_set_flags(int32_t *flag, const int32_t *v, uint32_t W, hipStream_t st)
+{
+    hipLaunchKernelGGL(set_flags_kernel, dim3((W + 255) / 256), dim3(256), 0, st, flag, v, W);
     return hipGetLastError();
 }
 // the join as a value wait (small world counts, mbots_step): one wave after the

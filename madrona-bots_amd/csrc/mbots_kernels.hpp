@@ -83,6 +83,14 @@ struct SimState {
     uint32_t *big_cnt;
 };
 
+// per-world episode state of an armed manager (reset_worlds_kernel)
+struct ResetArgs {
+    int32_t *flag;      // [W] MBOTS_EXPORT_RESET: 0 none, 1 next episode, v >= 2 episode v - 2
+    int32_t *episode;   // [W] the world's current episode
+    int32_t *age;       // [W] steps since the world's last reset or creation
+    uint32_t len;       // episode length in steps (0: off)
+};
+
 // the small kernel class of mixed-class dispatch
 constexpr int kSmallCap = 128;
 // a world whose next K1 needs the class kernel: it may end with 2 n + A agents
@@ -118,6 +126,13 @@ bool sensor_order_used(uint32_t W);
 // counters (block index mod 8): fewer same-address atomics at K1's end
 constexpr int kTileBuckets = 8;
 hipError_t launch_init(const SimState &S, hipStream_t st);
+// the reset pass of an armed manager, before K1 on K1's stream: flagged or
+// expired worlds re-initialised in the state half K1 reads (parity: this
+// step's; mixed classes: the K1 class list K1 reads is rebuilt from the new
+// populations)
+hipError_t launch_reset_worlds(const SimState &S, const ResetArgs &R, int parity, hipStream_t st);
+// flag[w] = v[w] wherever v[w] != 0 (mbots_reset_worlds)
+hipError_t launch_set_flags(int32_t *flag, const int32_t *v, uint32_t W, hipStream_t st);
 // the sensor's ray table (host-computed with the kernels' own u_of / near_pt)
 hipError_t upload_ray_table(const SimState &S, hipStream_t st);
 hipError_t launch_tile_sum(const SimState &S, int parity, hipStream_t st);

@@ -78,7 +78,19 @@ struct mbots_handle {
     int parity = 0;                   // K1 -> K2 tile-count buffer of this step
     Arena arena;
     int32_t *done_zeros = nullptr;    // Done column (never written, sim.cpp:74-75, B.7)
-    int32_t *reset_zeros = nullptr;   // WorldReset singleton per world
+    int32_t *reset_flags = nullptr;   // WorldReset singleton per world: the live flag array
+                                      // (MBOTS_EXPORT_RESET; zeros until someone writes)
+    // episodes (include/mbots.h "Episodes and resets"): per simulated world, the
+    // shard ghost included
+    int32_t *episode = nullptr;       // the world's current episode
+    int32_t *age = nullptr;           // steps since its last reset or creation (kept by the
+                                      // reset pass: current once armed, or filled on export)
+    bool armed = false;               // every step runs the reset pass before K1
+    uint32_t ep_len = 0;              // episode length in steps (0: off)
+    uint64_t age0 = 0;                // steps since creation (every world's age while unarmed)
+    int32_t *flag_stage = nullptr;    // mbots_reset_worlds: pinned host / device staging of
+    int32_t *flag_stage_dev = nullptr;   // one value per world, and the event after its last
+    hipEvent_t ev_stage = nullptr;    // upload
     int32_t *sensor_index = nullptr;  // scratch for sensorIndexTensor
     uint32_t *h_totals = nullptr;     // pinned mirror of S.totals
     hipEvent_t ev_totals = nullptr;
@@ -342,7 +354,9 @@ size_t layout(mbots_handle *h, Arena &a)
     fill_table(h->T[0], a, rows);
     fill_table(h->T[1], a, rows);
     h->done_zeros = a.take<int32_t>(rows);
-    h->reset_zeros = a.take<int32_t>(W);
+    h->reset_flags = a.take<int32_t>(W);
+    h->episode = a.take<int32_t>(W);
+    h->age = a.take<int32_t>(W);
     h->sensor_index = a.take<int32_t>(rows);
     return a.used;
 }
@@ -590,6 +604,28 @@ int sync_totals(mbots_handle *h)
     return MBOTS_OK;
 }
 
+// episodes: every world's age is the manager's while no reset pass runs
+int fill_ages(mbots_handle *h, hipStream_t st)
+{
+    if (capturing(st))
+        return fail(MBOTS_E_INVALID, "the episode-step export of an unarmed manager cannot be captured into a graph");
+    HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->age, (int)std::min<uint64_t>(h->age0, 0x7FFFFFFFu), h->S.W, st));
+    return MBOTS_OK;
+}
+// arm the manager (on `st`, which the manager's calls are ordered on): from
+// the next step on every step runs the reset pass
+int arm(mbots_handle *h, hipStream_t st)
+{
+    if (h->armed) return MBOTS_OK;
+    if (capturing(st))
+        return fail(MBOTS_E_INVALID, "a manager cannot be armed for episodes while its stream is being captured: "
+                                     "export MBOTS_EXPORT_RESET, call mbots_reset_worlds or set an episode length "
+                                     "before the capture begins");
+    if (int rc = fill_ages(h, st)) return rc;
+    h->armed = true;
+    return MBOTS_OK;
+}
+
 int record_totals(mbots_handle *h, hipStream_t st)
 {
     HIP_TRY(hipMemcpyAsync(h->h_totals, h->S.totals, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost,
@@ -609,8 +645,12 @@ struct CkptHeader {
     uint32_t sensed, pad;   // 4: whether a sensor had run (the finder slots are its)
 };
 // 3: totals[kTotRows] (every table row, the shard ghost's included) is part
-// of the state and must equal the header's n_rows; 4: `sensed`
+// of the state and must equal the header's n_rows; 4: `sensed`;
+// 5 (armed managers only; the others keep writing 4): the per-world episode,
+// age and pending reset flags as three trailing segments, the episode length
+// in `pad`
 constexpr uint32_t kCkptVersion = 4;
+constexpr uint32_t kCkptVersionEpisodes = 5;
 
 struct Seg {
     void *p;
@@ -642,6 +682,13 @@ std::vector<Seg> ckpt_segments(mbots_handle *h, mbots::ObsTable &t, uint32_t n_r
         {t.psem, N * kSensor}, {t.pdepth, N * kSensor},
     };
     return v;
+}
+
+// version 5's trailing segments
+std::vector<Seg> ckpt_episode_segments(mbots_handle *h)
+{
+    const size_t W = h->S.W;
+    return {{h->episode, W * 4}, {h->age, W * 4}, {h->reset_flags, W * 4}};
 }
 
 size_t ckpt_bytes(const std::vector<Seg> &v)
@@ -952,6 +999,9 @@ int mbots_destroy(mbots_handle *h)
     for (auto e : h->ev_join) if (e) (void)hipEventDestroy(e);
     if (h->aux) (void)hipStreamDestroy(h->aux);
     if (h->h_totals) (void)hipHostFree(h->h_totals);
+    if (h->flag_stage) (void)hipHostFree(h->flag_stage);
+    if (h->flag_stage_dev) (void)hipFree(h->flag_stage_dev);
+    if (h->ev_stage) (void)hipEventDestroy(h->ev_stage);
     if (h->arena.base) (void)hipFree(h->arena.base);
     for (char *p : h->retired) (void)hipFree(p);
     delete h;
@@ -1092,6 +1142,21 @@ int mbots_step(mbots_handle *h, void *stream)
         if (!capturing) h->waited_serial = std::max(h->waited_serial, h->join_serial[h->last_join]);
     }
     h->S.finder_from_state = h->sensed ? 0u : 1u;
+    if (h->armed) {
+        // the reset pass (episodes), before K1 on K1's stream and after K1's
+        // waits: it writes the state half K1 reads, whose finder slots the last
+        // sensor wrote, and reads the flags the caller's stream wrote.  In
+        // K1-finder mode K1 does not wait for that sensor, which still reads
+        // this half: the pass does
+        if (h->k1_finder && h->last_join >= 0 && (!capturing || h->join_capture == cap_id)) {
+            HIP_TRY(hipStreamWaitEvent(kst, h->ev_join[h->last_join], 0));
+            if (!capturing) h->waited_serial = std::max(h->waited_serial, h->join_serial[h->last_join]);
+        }
+        const mbots::ResetArgs R{h->reset_flags, h->episode, h->age, h->ep_len};
+        HIP_TRY(mbots::launch_reset_worlds(h->S, R, par, kst));
+    } else {
+        ++h->age0;
+    }
     // K1 writes this step's old rows into the half the step before last used:
     // the sensor that read it (K1-finder mode: the sensor before the last one)
     // has been waited for above
@@ -1311,7 +1376,14 @@ int mbots_export_on(mbots_handle *h, int32_t id, void *stream, mbots_tensor *out
     int dt = MBOTS_DTYPE_INT32;
     int64_t rows = N, cols = 1;
     switch (id) {
-    case MBOTS_EXPORT_RESET: p = h->reset_zeros; rows = h->cfg.num_worlds; break;
+    case MBOTS_EXPORT_RESET:   // the live flag array: whoever holds it may write it
+        if ((rc = arm(h, st))) return rc;
+        p = h->reset_flags; rows = h->cfg.num_worlds; break;
+    case MBOTS_EXPORT_EPISODE: p = h->episode; rows = h->cfg.num_worlds; break;
+    case MBOTS_EXPORT_EPISODE_STEP:
+        // (unarmed: no pass keeps the ages; every world's is the manager's)
+        if (!h->armed && (rc = fill_ages(h, st))) return rc;
+        p = h->age; rows = h->cfg.num_worlds; break;
     case MBOTS_EXPORT_ACTION: p = t.action; cols = 6; break;
     case MBOTS_EXPORT_PREV_ACTION: p = t.paction; cols = 6; break;
     case MBOTS_EXPORT_HIDDEN_STATE: p = t.hidden; dt = MBOTS_DTYPE_FLOAT32; cols = kHidden; break;
@@ -1811,7 +1883,8 @@ int mbots_checkpoint_size(mbots_handle *h, uint64_t *out)
     }
     int rc = sync_totals(h);
     if (rc) return rc;
-    *out = ckpt_bytes(ckpt_segments(h, h->T[h->tb], h->h_totals[mbots::kTotRows]));
+    *out = ckpt_bytes(ckpt_segments(h, h->T[h->tb], h->h_totals[mbots::kTotRows])) +
+           (h->armed ? ckpt_bytes(ckpt_episode_segments(h)) - sizeof(CkptHeader) : 0);
     return MBOTS_OK;
 }
 
@@ -1834,12 +1907,15 @@ int mbots_save_checkpoint(mbots_handle *h, void *dst, uint64_t bytes)
     int rc = sync_totals(h);
     if (rc) return rc;
     const uint32_t n_rows = h->h_totals[mbots::kTotRows];   // the shard ghost's rows included
-    const auto segs = ckpt_segments(h, h->T[h->tb], n_rows);
+    auto segs = ckpt_segments(h, h->T[h->tb], n_rows);
+    if (h->armed)
+        for (const Seg &s : ckpt_episode_segments(h)) segs.push_back(s);
     const size_t need = ckpt_bytes(segs);
     if (bytes < need) return fail(MBOTS_E_INVALID, "checkpoint buffer too small");
     CkptHeader hd{};
     memcpy(hd.magic, "MBOTSCK", 8);
-    hd.version = kCkptVersion;
+    hd.version = h->armed ? kCkptVersionEpisodes : kCkptVersion;
+    hd.pad = h->armed ? h->ep_len : 0u;
     hd.num_worlds = h->cfg.num_worlds;
     hd.cap = h->cfg.agent_capacity;
     hd.A = h->cfg.init_num_agents_per_world;
@@ -1910,8 +1986,9 @@ int mbots_load_checkpoint(mbots_handle *h, const void *src, uint64_t bytes)
     if (bytes < sizeof(CkptHeader)) return fail(MBOTS_E_INVALID, "checkpoint truncated");
     CkptHeader hd;
     memcpy(&hd, src, sizeof(hd));
-    if (memcmp(hd.magic, "MBOTSCK", 8) != 0 || hd.version != kCkptVersion)
+    if (memcmp(hd.magic, "MBOTSCK", 8) != 0 || (hd.version != kCkptVersion && hd.version != kCkptVersionEpisodes))
         return fail(MBOTS_E_INVALID, "not a checkpoint of this version");
+    const bool episodes = hd.version == kCkptVersionEpisodes;
     // (another agent_capacity is fine when every world of the blob fits this
     // manager's: its per-slot columns are re-laid out, world by world -- a
     // learner growing its worlds' capacity, SimManager(agent_capacity="auto"))
@@ -1923,8 +2000,13 @@ int mbots_load_checkpoint(mbots_handle *h, const void *src, uint64_t bytes)
     if (hd.n_rows > (uint64_t)h->S.W * cap)
         return fail(MBOTS_E_INVALID, "checkpoint row count out of range");
     if (int rc = capture_guard(h, h->last_stream)) return rc;
-    const auto segs = ckpt_segments(h, h->T[0], hd.n_rows);
-    const auto segs_src = ckpt_segments(h, h->T[0], hd.n_rows, cap_src);
+    auto segs = ckpt_segments(h, h->T[0], hd.n_rows);
+    auto segs_src = ckpt_segments(h, h->T[0], hd.n_rows, cap_src);
+    if (episodes)
+        for (const Seg &s : ckpt_episode_segments(h)) {
+            segs.push_back(s);
+            segs_src.push_back(s);
+        }
     if (bytes < ckpt_bytes(segs_src) || hd.bytes != ckpt_bytes(segs_src))
         return fail(MBOTS_E_INVALID, "checkpoint size mismatch");
     {
@@ -1964,6 +2046,16 @@ int mbots_load_checkpoint(mbots_handle *h, const void *src, uint64_t bytes)
         }
         p += segs_src[i].bytes;
     }
+    // episodes: a version-5 blob brings its manager's armed state along; a
+    // version-4 one knows no episodes -- an armed manager stays armed, keeps its
+    // episode length and starts every world at episode 0, age 0, no flag pending
+    if (episodes) {
+        h->armed = true;
+        h->ep_len = hd.pad;
+    } else {
+        for (const Seg &s : ckpt_episode_segments(h)) HIP_TRY(hipMemset(s.p, 0, s.bytes));
+        h->age0 = 0;
+    }
     return restored_reset(h, hd.sensed != 0);
 }
 
@@ -1981,12 +2073,14 @@ namespace {
 struct LayoutPtrs {
     mbots::SimState S;
     mbots::ObsTable T[2];
-    int32_t *row_base2[2], *sorder2[2], *obsrow_out2[2], *done_zeros, *reset_zeros, *sensor_index;
+    int32_t *row_base2[2], *sorder2[2], *obsrow_out2[2], *done_zeros, *reset_flags, *sensor_index;
+    int32_t *episode, *age;
 };
 LayoutPtrs layout_ptrs(const mbots_handle *h)
 {
     return {h->S, {h->T[0], h->T[1]}, {h->row_base2[0], h->row_base2[1]}, {h->sorder2[0], h->sorder2[1]},
-            {h->obsrow_out2[0], h->obsrow_out2[1]}, h->done_zeros, h->reset_zeros, h->sensor_index};
+            {h->obsrow_out2[0], h->obsrow_out2[1]}, h->done_zeros, h->reset_flags, h->sensor_index,
+            h->episode, h->age};
 }
 void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
 {
@@ -1998,8 +2092,10 @@ void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
         h->obsrow_out2[k] = p.obsrow_out2[k];
     }
     h->done_zeros = p.done_zeros;
-    h->reset_zeros = p.reset_zeros;
+    h->reset_flags = p.reset_flags;
     h->sensor_index = p.sensor_index;
+    h->episode = p.episode;
+    h->age = p.age;
 }
 }  // namespace
 
@@ -2043,6 +2139,7 @@ int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
     // the old storage: what a checkpoint would save, and the row provenance
     const std::vector<Seg> from = ckpt_segments(h, h->T[h->tb], n_rows);
     const int32_t *src_of_old = h->S.src_of;
+    const std::vector<Seg> ep_from = ckpt_episode_segments(h);
     const LayoutPtrs old = layout_ptrs(h);
     const Arena old_arena = h->arena;
     h->cfg.agent_capacity = new_capacity;   // (layout() sizes by it)
@@ -2067,6 +2164,7 @@ int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
     layout(h, h->arena);
     h->S.cap = new_capacity;
     const std::vector<Seg> to = ckpt_segments(h, h->T[0], n_rows);
+    const std::vector<Seg> ep_to = ckpt_episode_segments(h);
     hipStream_t st = nullptr;
     auto move = [&]() -> hipError_t {
         // the per-slot columns lead the arena (layout()'s first takes) and the
@@ -2093,6 +2191,10 @@ int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
         if (n_rows && (e = hipMemcpyAsync(h->S.src_of, src_of_old, (size_t)n_rows * sizeof(int32_t),
                                           hipMemcpyDeviceToDevice, st)) != hipSuccess)
             return e;
+        for (size_t i = 0; i < ep_to.size(); ++i)   // episodes, ages and pending flags carry on
+            if ((e = hipMemcpyAsync(ep_to[i].p, ep_from[i].p, ep_to[i].bytes, hipMemcpyDeviceToDevice, st)) !=
+                hipSuccess)
+                return e;
         if ((e = mbots::upload_ray_table(h->S, st)) != hipSuccess) return e;
         return hipStreamSynchronize(st);
     };
@@ -2281,6 +2383,74 @@ int mbots_set_world_state(mbots_handle *h, uint32_t world, const float *xy_rwrz,
     return mbots_load_checkpoint(h, blob.data(), bytes);
 }
 
+// ---- episodes and resets (the reference registers WorldReset and keeps
+// curWorldEpisode, sim.cpp:64-75, :1236-1240; its resetSystem is a stub,
+// :302-305) ----
+int mbots_reset_worlds(mbots_handle *h, const uint32_t *global_worlds, uint32_t n, const uint32_t *episodes,
+                       void *stream)
+{
+    if (!h || (!global_worlds && n)) return fail(MBOTS_E_INVALID, "null argument");
+    if (episodes)
+        for (uint32_t k = 0; k < n; ++k)
+            if (episodes[k] >= 0x7FFFFFFEu)
+                return fail(MBOTS_E_INVALID, "episode " + std::to_string(episodes[k]) + " is out of range (< 2^31 - 2)");
+    if (n == 0) return MBOTS_OK;
+    if (h->cpu) {
+        h->cpu->reset_worlds(global_worlds, n, episodes);
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = as_stream(stream);
+    if (capturing(st))
+        return fail(MBOTS_E_INVALID, "mbots_reset_worlds uploads its list from the host and cannot be captured into "
+                                     "a graph: write the flags of MBOTS_EXPORT_RESET on the captured stream or "
+                                     "between replays instead");
+    int rc = use_stream(h, st);
+    if (rc) return rc;
+    if ((rc = arm(h, st))) return rc;
+    const uint32_t W = h->S.W;   // (the shard ghost is world W - 1: global index world_offset + num_worlds)
+    if (!h->flag_stage) {
+        HIP_TRY(hipHostMalloc((void **)&h->flag_stage, (size_t)W * sizeof(int32_t), hipHostMallocDefault));
+        HIP_TRY(hipMalloc((void **)&h->flag_stage_dev, (size_t)W * sizeof(int32_t)));
+        HIP_TRY(hipEventCreateWithFlags(&h->ev_stage, hipEventDisableTiming));
+    } else {
+        HIP_TRY(hipEventSynchronize(h->ev_stage));   // the last call's upload has left the staging buffer
+    }
+    memset(h->flag_stage, 0, (size_t)W * sizeof(int32_t));
+    bool any = false;
+    for (uint32_t k = 0; k < n; ++k) {
+        const uint32_t gw = global_worlds[k];
+        if (gw < h->cfg.world_offset || gw - h->cfg.world_offset >= W) continue;   // another rank's
+        h->flag_stage[gw - h->cfg.world_offset] = episodes ? (int32_t)(episodes[k] + 2u) : 1;
+        any = true;
+    }
+    if (!any) return MBOTS_OK;
+    HIP_TRY(hipMemcpyAsync(h->flag_stage_dev, h->flag_stage, (size_t)W * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(h->ev_stage, st));
+    HIP_TRY(mbots::launch_set_flags(h->reset_flags, h->flag_stage_dev, W, st));
+    return MBOTS_OK;
+}
+
+int mbots_set_episode_length(mbots_handle *h, uint32_t steps)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    if (h->cpu) {
+        h->cpu->set_episode_length(steps);
+        return MBOTS_OK;
+    }
+    if (steps == h->ep_len) return MBOTS_OK;
+    if (h->cap_seen != 0)
+        return fail(MBOTS_E_INVALID, "captured graphs pin the episode length: a step of this manager was captured "
+                                     "into a graph, whose replays carry the length they recorded");
+    if (steps != 0 && !h->armed) {
+        HIP_TRY(hipSetDevice(h->device));
+        if (int rc = capture_guard(h, h->last_stream)) return rc;
+        if (int rc = arm(h, h->last_stream)) return rc;
+    }
+    h->ep_len = steps;
+    return MBOTS_OK;
+}
+
 int mbots_enable_kernel_timing(mbots_handle *h, int32_t enable)
 {
     if (!h) return fail(MBOTS_E_INVALID, "null handle");
@@ -2298,12 +2468,13 @@ int mbots_schedule_info(mbots_handle *h, uint32_t out[4])
 {
     if (!h || !out) return fail(MBOTS_E_INVALID, "null argument");
     if (h->cpu) {
-        out[0] = out[1] = out[2] = 0;
+        out[0] = h->cpu->armed() ? 32u : 0u;
+        out[1] = out[2] = 0;
         out[3] = (uint32_t)h->steps;
         return MBOTS_OK;
     }
     out[0] = (h->k1_finder ? 1u : 0u) | (h->sig_fork ? 2u : 0u) | (h->sig_join ? 4u : 0u) | (h->swap ? 8u : 0u) |
-             (h->S.mixed ? 16u : 0u);
+             (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u);
     out[1] = h->epoch;
     out[2] = h->epoch_wraps;
     out[3] = (uint32_t)h->steps;

@@ -101,6 +101,8 @@ def _load():
         "mbots_grow_capacity": [vp, u32],
         "mbots_set_auto_capacity": [vp, i32],
         "mbots_release_retired": [vp],
+        "mbots_reset_worlds": [vp, vp, u32, vp, vp],
+        "mbots_set_episode_length": [vp, u32],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -150,7 +152,7 @@ class ExportID:
         Position, PrevPosition, Health, PrevHealth, Surrounding, PrevSurrounding, \
         SensorSemantic, SensorDepth, PrevSensorSemantic, PrevSensorDepth, Stats, PrevStats, \
         SensorIndex, SpeciesCount = range(22)
-    Species, PrevSpecies = 32, 33
+    Species, PrevSpecies, Episode, EpisodeStep = 32, 33, 34, 35
 
 
 _DTYPES = {0: (torch.uint8, "|u1"), 1: (torch.int8, "|i1"), 2: (torch.int32, "<i4"),
@@ -189,6 +191,10 @@ def _exec_mode(v):
 OBS_DIM = 69   # learn/env.py:19
 # TK_* indices of mbots_kernel_times
 KERNELS = ("world_step", "scan", "export", "sensor", "shift", "actions", "move", "obs")
+
+
+# per-world exports (not table columns)
+_WORLD_EXPORTS = (ExportID.SpeciesCount, ExportID.Reset, ExportID.Episode, ExportID.EpisodeStep)
 
 
 class _Handle:
@@ -414,11 +420,25 @@ class SimManager:
     fetched before a growth keep reading the storage they were taken from
     (kept until release_retired() or the manager's end) but no longer follow
     the manager: take them after step(), as learn/training_loop.py:43-50 does.
-    A step captured into a HIP graph pins the capacity."""
+    A step captured into a HIP graph pins the capacity.
+
+    Episodes: reset_worlds(worlds, episodes=None) flags worlds (global
+    indices) to start over at the next step() -- reset, then step: the world is
+    re-initialised from its episode's key (episode e of global world gw:
+    threefry2x32(seed, 0, e, gw), the reference's split_i(initKey, episode,
+    world); episode 0 is the world the constructor builds) and then stepped
+    like the others, its agents' rows new (Action, HiddenState and every Prev
+    column zero).  reset_tensor() is the live flag array (0 none, 1 next
+    episode, v >= 2 episode v - 2; the step clears what it consumes),
+    episode_tensor() / episode_step_tensor() each world's episode and its
+    steps since the last reset or creation.  episode_length=k (or
+    set_episode_length(k)) resets every world whose episode_step has reached k.
+    A manager that uses none of these steps exactly as before."""
 
     def __init__(self, gpu_id, num_worlds, rand_seed, init_num_agents_per_world, *,
                  exec_mode="hip", agent_capacity=128, world_offset=0, reward_fixed=False,
-                 fix_depth_alias=False, shard_ghost=False, strict_capacity=False, auto_grow=False):
+                 fix_depth_alias=False, shard_ghost=False, strict_capacity=False, auto_grow=False,
+                 episode_length=0):
         self.exec_mode = _exec_mode(exec_mode)
         self.gpu_id = int(gpu_id)
         self.num_worlds = int(num_worlds)
@@ -438,7 +458,12 @@ class SimManager:
         self._fix_depth = bool(fix_depth_alias)
         self._ktiming = False
         self._gen = 0                # bumped when the columns' storage moves (a growth)
+        self._episode_length = int(episode_length)
+        if not 0 <= self._episode_length < 2 ** 32:
+            raise ValueError("episode_length must be in [0, 2^32)")
         self._open(self.agent_capacity)
+        if self._episode_length:
+            _check(_lib.mbots_set_episode_length(self._h, self._episode_length))
 
     def _open(self, cap):
         """Create the native manager at capacity `cap` (and reset the caches
@@ -563,7 +588,7 @@ class SimManager:
         # on whatever stream its previous call used (mbots_export_on)
         ct = _CTensor()
         _check(_lib.mbots_export_on(self._h, eid, self._stream(), ctypes.byref(ct)))
-        return Tensor(self._hd, ct, column=eid not in (ExportID.SpeciesCount, ExportID.Reset), mgr=self)
+        return Tensor(self._hd, ct, column=eid not in _WORLD_EXPORTS, mgr=self)
 
     def depth_tensor(self, is_prev=False):
         return self._export(ExportID.PrevSensorDepth if is_prev else ExportID.SensorDepth)
@@ -604,6 +629,53 @@ class SimManager:
 
     def species_tensor(self, is_prev=False):
         return self._export(ExportID.PrevSpecies if is_prev else ExportID.Species)
+
+    # -- episodes -----------------------------------------------------------
+    def reset_tensor(self):
+        """The live reset flags, int32 [num_worlds, 1] (MBOTS_EXPORT_RESET):
+        write 1 to start a world's next episode at the next step(), e + 2 for
+        episode e.  Taking it arms the manager."""
+        return self._export(ExportID.Reset)
+
+    def episode_tensor(self):
+        """Each world's current episode, int32 [num_worlds, 1]."""
+        return self._export(ExportID.Episode)
+
+    def episode_step_tensor(self):
+        """Steps since each world's last reset or creation, int32
+        [num_worlds, 1] (1 after the step that reset it)."""
+        return self._export(ExportID.EpisodeStep)
+
+    def reset_worlds(self, worlds, episodes=None):
+        """Flag `worlds` (a sequence or tensor of global world indices) to
+        start over at the next step(): each at its next episode, or at
+        episodes[k].  Indices outside this manager's worlds are ignored (every
+        rank of a sharded run takes the same list)."""
+        import numpy as np
+
+        def arr(v, what):
+            if isinstance(v, torch.Tensor):
+                v = v.detach().cpu().numpy()
+            v = np.asarray(list(v) if not isinstance(v, np.ndarray) else v).reshape(-1)
+            if v.size and (v.min() < 0 or v.max() >= 2 ** 32):
+                raise ValueError(f"madrona_bots: {what} out of range")
+            return np.ascontiguousarray(v, dtype=np.uint32)
+
+        w = arr(worlds, "world index")
+        e = None
+        if episodes is not None:
+            e = arr(episodes, "episode")
+            if e.size != w.size:
+                raise ValueError(f"madrona_bots: {w.size} worlds but {e.size} episodes")
+        _check(_lib.mbots_reset_worlds(self._h, ctypes.c_void_p(w.ctypes.data if w.size else None), int(w.size),
+                                       ctypes.c_void_p(e.ctypes.data if e is not None and e.size else None),
+                                       self._stream()))
+
+    def set_episode_length(self, steps):
+        """Reset every world whose episode_step has reached `steps` at the
+        start of a step (0: off)."""
+        _check(_lib.mbots_set_episode_length(self._h, int(steps)))
+        self._episode_length = int(steps)
 
     def set_action(self, agent_idx, forward, backward, rotate_left, rotate_right, shoot, breed):
         a = (ctypes.c_int32 * 6)(forward, backward, rotate_left, rotate_right, shoot, breed)
@@ -843,13 +915,14 @@ class SimManager:
 
     def schedule_info(self):
         """The step schedule in use (mbots_schedule_info): {"k1_finder",
-        "fork_by_value", "join_by_value", "swap", "mixed_classes": bool,
+        "fork_by_value", "join_by_value", "swap", "mixed_classes", "episodes_armed": bool,
         "epoch", "epoch_wraps", "steps": int}."""
         v = (ctypes.c_uint32 * 4)()
         _check(_lib.mbots_schedule_info(self._h, v))
         f = v[0]
         return {"k1_finder": bool(f & 1), "fork_by_value": bool(f & 2), "join_by_value": bool(f & 4),
-                "swap": bool(f & 8), "mixed_classes": bool(f & 16), "epoch": int(v[1]),
+                "swap": bool(f & 8), "mixed_classes": bool(f & 16), "episodes_armed": bool(f & 32),
+                "epoch": int(v[1]),
                 "epoch_wraps": int(v[2]), "steps": int(v[3])}
 
     def kernel_times(self):

@@ -86,6 +86,7 @@ typedef struct {
     uint32_t num_agents[ORC_NUM_CHUNKS];    /* ChunkInfo::numAgents           */
     uint32_t total_speed[ORC_NUM_CHUNKS];   /* ChunkInfo::totalSpeed          */
     int32_t n;
+    int32_t hi;                             /* most slots ever written (world_clear) */
     orc_agent *ag;                          /* [cap]                          */
     orc_agent *tmp;                         /* [cap]                          */
     float species_reward[ORC_NUM_SPECIES];  /* SpeciesReward                  */
@@ -115,6 +116,11 @@ struct orc_sim {
     int32_t *world_off;          /* [W] world-major offsets                  */
     int32_t *row_base;           /* [W][4] first export row per (world,sp)   */
     uint32_t total;
+    /* episodes (INTEGRATION.md "Episodes and resets") */
+    int32_t *reset_flag;         /* [W] 0 none, 1 next episode, v >= 2: v - 2 */
+    int32_t *episode;            /* [W] current episode                      */
+    int32_t *age;                /* [W] steps since the last reset / creation */
+    uint32_t episode_length;     /* 0: off                                   */
 };
 
 static const float kLx = 128.0f, kLy = 96.0f;   /* sim.cpp:161-166 */
@@ -372,8 +378,76 @@ static void surrounding(orc_world *w, orc_agent *a)
     a->sur[1] = yi * sx1 + (1.0f - yi) * sx0;
 }
 
+/* The per-world part of construction, for one episode.  Sim::Sim
+ * (sim.cpp:1232-1256) seeds a world with split_i(initKey(seed),
+ * curWorldEpisode++, worldID) (sim.cpp:64-75, :1236-1240) and runs initWorld
+ * (sim.cpp:233-275).  The world's simulation state must be what calloc gave it
+ * (world_clear), so episode e of global world gw is, by construction, the world
+ * a one-world oracle at world_offset = gw starts from when e = 0. */
+static void world_begin_episode(orc_sim *s, uint32_t wi, uint32_t episode)
+{
+    orc_world *w = &s->w[wi];
+    const orc_config *cfg = &s->cfg;
+    uint32_t k0[2] = {cfg->rand_seed, 0u}, c[2] = {episode, cfg->world_offset + wi};
+    orc_threefry2x32(k0, c, w->key);
+    w->ctr = 0;
+    for (uint32_t i = 0; i < cfg->init_agents && i < cfg->cap; ++i) {
+        int32_t sp = (int32_t)(i % ORC_NUM_SPECIES) + 1;
+        float x = sample_uniform(w) * kLx;
+        float y = sample_uniform(w) * kLy;
+        agent_init(&w->ag[i], x, y, sp, 100);
+        w->n += 1;
+    }
+    if (w->n > w->hi) w->hi = w->n;
+    for (int i = 0; i < ORC_NUM_SPECIES; ++i) w->species_count[i] = 0;
+    for (int32_t i = 0; i < w->n; ++i) w->species_count[w->ag[i].species - 1] += 1;
+}
+
+/* Back to the zeros of a world not yet constructed: food, chunk info, species
+ * rewards, the population and every slot of both arrays that was ever written.  The slot storage stays
+ * allocated and the dropped-agent counter stays cumulative. */
+static void world_clear(orc_sim *s, uint32_t wi)
+{
+    orc_world *w = &s->w[wi];
+    orc_agent *ag = w->ag, *tmp = w->tmp;
+    uint32_t overflow = w->overflow;
+    int32_t hi = w->hi;
+    (void)s;
+    /* (slots from hi on were never written: they are calloc's zeros still) */
+    memset(ag, 0, (size_t)hi * sizeof(orc_agent));
+    memset(tmp, 0, (size_t)hi * sizeof(orc_agent));
+    memset(w, 0, sizeof(*w));
+    w->ag = ag;
+    w->tmp = tmp;
+    w->overflow = overflow;
+    w->hi = hi;
+}
+
+/* Reset, then step (INTEGRATION.md "Episodes and resets"): at the start of a
+ * step a world without a flag whose episode has not run out grows one step
+ * older; any other world starts the flagged episode (v >= 2: episode v - 2) or
+ * its next one, from that episode's key, with age 1 and its flag cleared, and
+ * is then stepped like every other.  Its agents carry obs_row = -1, so
+ * world_phase_c gives them a newborn's rows. */
+static void episode_pass(orc_sim *s, uint32_t wi)
+{
+    int32_t flag = s->reset_flag[wi];
+    uint32_t len = s->episode_length;
+    if (flag == 0 && (len == 0 || (uint32_t)s->age[wi] < len)) {
+        s->age[wi] += 1;
+        return;
+    }
+    int32_t e = flag >= 2 ? flag - 2 : s->episode[wi] + 1;
+    world_clear(s, wi);
+    world_begin_episode(s, wi, (uint32_t)e);
+    s->episode[wi] = e;
+    s->age[wi] = 1;
+    s->reset_flag[wi] = 0;
+}
+
 static void world_phase_a(orc_sim *s, uint32_t wi)
 {
+    episode_pass(s, wi);
     orc_world *w = &s->w[wi];
     const uint32_t A = s->cfg.init_agents, cap = s->cfg.cap;
 
@@ -415,6 +489,7 @@ static void world_phase_a(orc_sim *s, uint32_t wi)
             }
         }
     }
+    if (w->n > w->hi) w->hi = w->n;
     /* SortArchetypeNode<Agent, WorldID> (:1129): drop dead rows, keep order */
     int32_t m = 0;
     for (int32_t i = 0; i < w->n; ++i) {
@@ -894,7 +969,11 @@ orc_sim *orc_create(const orc_config *cfg)
     s->species_count = calloc((size_t)W * 4, 4);
     s->world_off = calloc(W, 4);
     s->row_base = calloc((size_t)W * 4, 4);
-    int ok = s->w && s->species_count && s->world_off && s->row_base;
+    s->reset_flag = calloc(W, 4);
+    s->episode = calloc(W, 4);
+    s->age = calloc(W, 4);
+    int ok = s->w && s->species_count && s->world_off && s->row_base && s->reset_flag && s->episode &&
+             s->age;
     for (int b = 0; b < 2 && ok; ++b) ok = cols_alloc(&s->cur[b], rows) && cols_alloc(&s->prev[b], rows);
     if (!ok) { orc_destroy(s); return NULL; }
     for (uint32_t wi = 0; wi < W; ++wi) {
@@ -902,20 +981,7 @@ orc_sim *orc_create(const orc_config *cfg)
         w->ag = calloc(cap, sizeof(orc_agent));
         w->tmp = calloc(cap, sizeof(orc_agent));
         if (!w->ag || !w->tmp) { orc_destroy(s); return NULL; }
-        /* Sim::Sim (sim.cpp:1232-1256): rng = split_i(initKey(seed), 0, world) */
-        uint32_t k0[2] = {cfg->rand_seed, 0u}, c[2] = {0u, cfg->world_offset + wi};
-        orc_threefry2x32(k0, c, w->key);
-        w->ctr = 0;
-        /* initWorld (sim.cpp:233-275) */
-        for (uint32_t i = 0; i < cfg->init_agents && i < cap; ++i) {
-            int32_t sp = (int32_t)(i % ORC_NUM_SPECIES) + 1;
-            float x = sample_uniform(w) * kLx;
-            float y = sample_uniform(w) * kLy;
-            agent_init(&w->ag[i], x, y, sp, 100);
-            w->n += 1;
-        }
-        for (int i = 0; i < ORC_NUM_SPECIES; ++i) w->species_count[i] = 0;
-        for (int32_t i = 0; i < w->n; ++i) w->species_count[w->ag[i].species - 1] += 1;
+        world_begin_episode(s, wi, 0u);
     }
     /* Initial export: rows in species-major order; Prev and sensor columns zero. */
     compute_rows(s);
@@ -947,8 +1013,24 @@ void orc_destroy(orc_sim *s)
     }
     for (int b = 0; b < 2; ++b) { cols_free(&s->cur[b]); cols_free(&s->prev[b]); }
     free(s->species_count); free(s->world_off); free(s->row_base);
+    free(s->reset_flag); free(s->episode); free(s->age);
     free(s);
 }
+
+void orc_reset_worlds(orc_sim *s, const uint32_t *global_worlds, uint32_t n, const uint32_t *episodes)
+{
+    const uint32_t lo = s->cfg.world_offset, W = s->cfg.num_worlds;
+    for (uint32_t k = 0; k < n; ++k) {
+        uint32_t gw = global_worlds[k];
+        if (gw < lo || gw - lo >= W) continue;   /* another rank's world */
+        s->reset_flag[gw - lo] = episodes ? (int32_t)(episodes[k] + 2u) : 1;
+    }
+}
+
+void orc_set_episode_length(orc_sim *s, uint32_t steps) { s->episode_length = steps; }
+int32_t *orc_reset_flags(orc_sim *s) { return s->reset_flag; }
+const int32_t *orc_episode(const orc_sim *s) { return s->episode; }
+const int32_t *orc_episode_step(const orc_sim *s) { return s->age; }
 
 void orc_step(orc_sim *s)
 {

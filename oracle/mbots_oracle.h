@@ -14,6 +14,18 @@
  * pieces follow the build's written spec.  Everything
  * else restates the cited reference lines; boundary shapes are pinned by the
  * reference checkpoints (obs width 69, action width 6: tests/golden/).
+ *
+ * RESETS AND EPISODES: the oracle restates them too, written from
+ * INTEGRATION.md "Episodes and resets" and the reference's key schedule
+ * (sim.cpp:64-75, :1236-1240: split_i(initKey, episode, world)) and not from
+ * the product's reset pass: a reset clears the world and runs the same
+ * per-world constructor orc_create runs, with the episode in the key.  Pinned
+ * by known answers of its own in tests/test_oracle_kat.py (positions from
+ * Threefry, all-reset == fresh, one reset world == a one-world oracle, the
+ * episode length, the two flag forms, the faithful reward over a reset
+ * neighbour); tests/test_reset_oracle.py and the episode call sequences of
+ * tests/test_parity_gpu.py / tests/test_reset_sequences_cpu.py hold both
+ * execution modes of the product against it.
  */
 #ifndef MBOTS_ORACLE_H
 #define MBOTS_ORACLE_H
@@ -99,6 +111,24 @@ int32_t  orc_world_food(const orc_sim *s, uint32_t w, int32_t *out);
  * rotation >= 2^22 */
 int      orc_set_world_state(orc_sim *s, uint32_t w, const float *xy_rwrz, uint32_t n_agents,
                              const int32_t *food, uint32_t n_food);
+
+/* Episodes and resets (see the header comment).  At the start of orc_step,
+ * per world: with flag 0 and (length 0 or episode_step < length) the world's
+ * episode_step grows by one; otherwise its episode becomes flag - 2 (flag >= 2)
+ * or episode + 1, the world is cleared to a not yet constructed one and
+ * constructed again from threefry2x32((seed, 0), (episode, global world)),
+ * episode_step = 1, flag = 0 -- and then it steps like every other world, its
+ * agents' rows new (Action, HiddenState and every Prev column zero).  The
+ * dropped-agent counter (orc_overflow) stays cumulative.  An oracle on which
+ * none of these is called does what it did before they existed. */
+/* flag the listed global worlds: 1 (episodes == NULL) or episodes[k] + 2;
+ * indices outside [world_offset, world_offset + num_worlds) are ignored */
+void     orc_reset_worlds(orc_sim *s, const uint32_t *global_worlds, uint32_t n,
+                          const uint32_t *episodes);
+void     orc_set_episode_length(orc_sim *s, uint32_t steps);       /* 0: off */
+int32_t *orc_reset_flags(orc_sim *s);         /* [W] live: a test may write */
+const int32_t *orc_episode(const orc_sim *s);                      /* [W]   */
+const int32_t *orc_episode_step(const orc_sim *s);                 /* [W]   */
 
 /* exposed primitives for known-answer tests */
 /* one food box (centre (cx, cy), 22-bit rotation) seen from an agent at

@@ -77,6 +77,11 @@ def lib():
         L.orc_world_food.argtypes = [vp, u32, vp]
         L.orc_set_world_state.restype = ctypes.c_int
         L.orc_set_world_state.argtypes = [vp, u32, vp, u32, vp, u32]
+        L.orc_reset_worlds.argtypes = [vp, vp, u32, vp]
+        L.orc_set_episode_length.argtypes = [vp, u32]
+        for fn in (L.orc_reset_flags, L.orc_episode, L.orc_episode_step):
+            fn.restype = vp
+            fn.argtypes = [vp]
         L.orc_threefry2x32.argtypes = [vp, vp, vp]
         L.orc_sample_uniform.restype = ctypes.c_float
         L.orc_sample_uniform.argtypes = [u32]
@@ -214,6 +219,37 @@ class OracleSim:
         if lib().orc_set_world_state(self._h, int(w), xyr.ctypes.data, len(xyr), fd.ctypes.data, len(fd)):
             raise ValueError("orc_set_world_state: the scene is not a state the simulator can reach "
                              "(see mbots_oracle.h)")
+
+    # -- episodes (mbots_oracle.h "Episodes and resets") ----------------------
+    def reset_worlds(self, worlds, episodes=None):
+        """Flag global worlds to start over at the next step(): their next
+        episode, or episodes[k].  Indices outside this oracle's worlds are
+        ignored."""
+        w = np.ascontiguousarray(np.asarray(list(worlds), np.int64).reshape(-1).astype(np.uint32))
+        e = None
+        if episodes is not None:
+            e = np.ascontiguousarray(np.asarray(list(episodes), np.int64).reshape(-1).astype(np.uint32))
+            if e.size != w.size:
+                raise ValueError(f"{w.size} worlds but {e.size} episodes")
+        lib().orc_reset_worlds(self._h, w.ctypes.data if w.size else None, int(w.size),
+                               e.ctypes.data if e is not None and e.size else None)
+
+    def set_episode_length(self, steps):
+        lib().orc_set_episode_length(self._h, int(steps))
+
+    def _world_i32(self, fn):
+        buf = (ctypes.c_int32 * self.num_worlds).from_address(fn(self._h))
+        return np.frombuffer(buf, dtype=np.int32)
+
+    def reset_flags(self):
+        """The live flag array, int32 [W]: writable, as a learner writes it."""
+        return self._world_i32(lib().orc_reset_flags)
+
+    def episode(self):
+        return self._world_i32(lib().orc_episode)
+
+    def episode_step(self):
+        return self._world_i32(lib().orc_episode_step)
 
     def snapshot(self, include_prev=True):
         """Copy of every exported column (dict name -> array)."""

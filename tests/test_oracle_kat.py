@@ -360,3 +360,215 @@ def test_food_box_rotation_follows_heading_frame():
     # heading +y: a box 10 ahead along +y behaves like the +x case
     hit, z = po.probe_box((20.0, 20.0), (0.0, 1.0), (20.0, 30.0), 0)
     assert _hit_pixels(hit) == [11, 12, 32] and z[11] == 9.0
+
+
+# ---------------------------------------------------------------------------
+# Resets and episodes (INTEGRATION.md "Episodes and resets"; the key schedule
+# split_i(initKey, episode, world) of sim.cpp:64-75, :1236-1240).  These pin the
+# oracle's own restatement: no manager is involved.
+# ---------------------------------------------------------------------------
+from reset_util import initial_positions  # noqa: E402
+
+_NAMES = ["species", "pos", "health", "surround", "reward", "action", "stats", "hidden", "semantic",
+          "depth"]
+
+
+def _drive_o(sims, t):
+    for s in sims:
+        s.step()
+        s.shift_observations()
+        s.write_synthetic_actions(1234, t, True)
+
+
+def _bytes_equal(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and np.array_equal(a.view(np.uint8), b.view(np.uint8))
+
+
+def _tables_equal(a, b, where):
+    """Two oracles: every column, current and Prev, bitwise."""
+    sa, sb = a.snapshot(), b.snapshot()
+    for k in sa:
+        assert _bytes_equal(sa[k], sb[k]), (where, k)
+
+
+def _world_slots(sim, w, prev=False):
+    """World w's rows of every column in slot order."""
+    cnt, off = sim.world_counts()
+    rows = sim.sensor_index()[off[w]:off[w] + cnt[w]]
+    return {nm: sim.column(i, prev)[rows] for i, nm in enumerate(_NAMES)}
+
+
+def _worlds_equal(a, wa, b, wb, where, prev=False):
+    """World wa of oracle a against world wb of oracle b: the slot state and
+    every column in slot order."""
+    sa, sb = a.world_state(wa), b.world_state(wb)
+    for k in sa:
+        assert _bytes_equal(sa[k], sb[k]), (where, "state", k)
+    ca, cb = _world_slots(a, wa, prev), _world_slots(b, wb, prev)
+    for k in ca:
+        assert _bytes_equal(ca[k], cb[k]), (where, k, prev)
+
+
+@pytest.mark.parametrize("A", [4, 32])
+@pytest.mark.parametrize("e", [0, 1, 7])
+@pytest.mark.parametrize("off", [0, 7])
+def test_reset_positions_from_threefry(A, e, off):
+    W, w = 3, 2
+    sim = po.OracleSim(W, 69, A, cap=128, world_offset=off)
+    for t in range(3):
+        _drive_o((sim,), t)
+    sim.column(po.COL_ACTION)[:] = 0
+    sim.reset_worlds([off + w], [e])
+    assert list(sim.reset_flags()) == [0, 0, e + 2]
+    sim.step()
+    assert list(sim.episode()) == [0, 0, e] and list(sim.episode_step()) == [4, 4, 1]
+    assert list(sim.reset_flags()) == [0, 0, 0]
+    st = sim.world_state(w)
+    assert list(st["species"]) == [i % 4 + 1 for i in range(A)]
+    assert (st["health"][:A] >= 100).all()
+    want = initial_positions(69, A, e, off + w)
+    # the step's only motion on all-zero actions: the clamp of sim.cpp:485-486
+    want[:, 0] = np.minimum(f32(127), np.maximum(f32(0), want[:, 0]))
+    want[:, 1] = np.minimum(f32(95), np.maximum(f32(0), want[:, 1]))
+    assert _bytes_equal(st["xy"], want)
+    assert _bytes_equal(st["rot"], np.tile(np.array([1, 0], np.float32), (A, 1)))
+    # a reset world's rows are new: Action, HiddenState and every Prev column zero
+    for prev in (False, True):
+        c = _world_slots(sim, w, prev)
+        for nm in (("action", "hidden") if not prev else _NAMES):
+            assert not c[nm].view(np.uint8).any(), (nm, prev)
+    # an index outside the oracle's worlds is another rank's
+    sim.reset_worlds([off + W, (off - 1) & 0xFFFFFFFF])
+    assert list(sim.reset_flags()) == [0, 0, 0]
+
+
+def test_reset_everything_equals_fresh_oracle():
+    W = 5
+    sim = po.OracleSim(W, 69, 32)
+    for t in range(6):
+        _drive_o((sim,), t)
+    sim.reset_worlds(range(W), [0] * W)
+    fresh = po.OracleSim(W, 69, 32)
+    for t in range(6, 12):
+        for s in (sim, fresh):
+            s.step()
+        _tables_equal(sim, fresh, f"step {t}")
+        for s in (sim, fresh):
+            s.shift_observations()
+        _tables_equal(sim, fresh, f"shift {t}")
+        for s in (sim, fresh):
+            s.write_synthetic_actions(1234, t, True)
+    assert list(sim.episode()) == [0] * W and list(sim.episode_step()) == [6] * W
+    assert list(fresh.episode_step()) == [6] * W
+
+
+def test_partial_reset_equals_one_world_oracles():
+    W = 5
+    sim, never = po.OracleSim(W, 69, 32, reward_fixed=True), po.OracleSim(W, 69, 32, reward_fixed=True)
+    for t in range(6):
+        _drive_o((sim, never), t)
+    sim.reset_worlds([1, 3], [0, 0])
+    ones = {w: po.OracleSim(1, 69, 32, world_offset=w, reward_fixed=True) for w in (1, 3)}
+    for t in range(6, 14):
+        for s in [sim, never] + list(ones.values()):
+            s.step()
+        for prev in (False, True):
+            for w in (1, 3):
+                _worlds_equal(sim, w, ones[w], 0, f"step {t} world {w}", prev)
+            for w in (0, 2, 4):
+                _worlds_equal(sim, w, never, w, f"step {t} world {w}", prev)
+        for s in [sim, never] + list(ones.values()):
+            s.shift_observations()
+            s.write_synthetic_actions(1234, t, True)
+    assert list(sim.episode_step()) == [14, 8, 14, 8, 14]
+    assert list(sim.episode()) == [0] * W
+
+
+def test_episode_length_and_flag_forms():
+    W = 3
+    sim, twin = po.OracleSim(W, 69, 32), po.OracleSim(W, 69, 32)
+    sim.set_episode_length(4)
+    for t in range(11):
+        if t and t % 4 == 0:
+            twin.reset_worlds(range(W))
+        _drive_o((sim, twin), t)
+        assert list(sim.episode_step()) == [t % 4 + 1] * W, t
+        assert list(sim.episode()) == [t // 4] * W, t
+        assert list(twin.episode()) == [t // 4] * W, t
+        _tables_equal(sim, twin, f"step {t}")
+    # a flag written as 1 is reset_worlds([w]); as e + 2, reset_worlds([w], [e])
+    a, b = po.OracleSim(W, 69, 32, world_offset=5), po.OracleSim(W, 69, 32, world_offset=5)
+    flags = a.reset_flags()        # (taken early: the array is live)
+    for t in range(4):
+        _drive_o((a, b), t)
+    flags[2] = 1
+    b.reset_worlds([5 + 2])
+    assert list(b.reset_flags()) == [0, 0, 1]
+    for t in range(4, 7):
+        _drive_o((a, b), t)
+        _tables_equal(a, b, f"flag 1, step {t}")
+    assert list(a.episode()) == list(b.episode()) == [0, 0, 1]
+    flags[0] = 5 + 2
+    b.reset_worlds([5], [5])
+    assert list(b.reset_flags()) == [7, 0, 0]
+    for t in range(7, 10):
+        _drive_o((a, b), t)
+        _tables_equal(a, b, f"flag e + 2, step {t}")
+    assert list(a.episode()) == list(b.episode()) == [5, 0, 1]
+    assert list(a.episode_step()) == list(b.episode_step()) == [3, 10, 6]
+    assert list(a.reset_flags()) == [0] * W
+
+
+def test_faithful_reward_reads_the_reset_neighbour():
+    """B.3: species 4 of world w reads species_reward[0] of world w + 1, which
+    is final after phase A of every world -- so in the step that resets world
+    1, world 0's species-4 rows read the reward of world 1's fresh population."""
+    W, A = 3, 32
+    sim, never = po.OracleSim(W, 69, A), po.OracleSim(W, 69, A)
+    # (action stream 1246: under it world 1's species 1 has bred and been shot
+    # by step 5 -- 9 agents, healths 60 and 50 among them -- so its old
+    # population's reward differs from a fresh one's; under 1234 it does not)
+    for t in range(5):
+        for s in (sim, never):
+            s.step()
+            s.shift_observations()
+            s.write_synthetic_actions(1246, t, True)
+    sim.reset_worlds([1])
+    sim.step()
+    never.step()
+    assert list(sim.episode()) == [0, 1, 0] and list(sim.episode_step()) == [6, 1, 6]
+
+    def sr0_of_world_1(s):
+        # speciesInfoSync (sim.cpp:791-838) over world 1's species-1 agents;
+        # nobody of a fresh population dies or is born in its first step
+        c = _world_slots(s, 1)
+        h = c["health"][c["species"].ravel() == 1].ravel()
+        count = len(h)
+        avg = f32(np.uint32(h.sum())) / f32(count)
+        return f32(f32(f32(count) / f32(A)) + f32(avg / f32(100.0))) - f32(2.0)
+
+    c1 = _world_slots(sim, 1)
+    assert len(c1["species"]) == A and (c1["species"].ravel() == 1).sum() == A // 4
+    sr = sr0_of_world_1(sim)
+    c0 = _world_slots(sim, 0)
+    sp4 = c0["species"].ravel() == 4
+    assert sp4.any()
+    want = []
+    for hp, st in zip(c0["health"][sp4].ravel(), c0["stats"][sp4]):
+        rew = f32(f32(sr + f32(f32(hp) / f32(100.0))) - f32(0.5))    # rewardSystem :942-956
+        if st[2]:
+            rew = f32(rew + f32(10.0))
+        if st[3]:
+            rew = f32(rew + f32(10.0))
+        if st[1]:
+            rew = f32(rew + f32(15.0))
+        want.append(rew)
+    assert _bytes_equal(c0["reward"][sp4].ravel(), np.array(want, np.float32))
+    # (the check bites: world 1's old population would have given another reward)
+    n0 = _world_slots(never, 0)
+    assert _bytes_equal(n0["health"], c0["health"]) and _bytes_equal(n0["stats"], c0["stats"])
+    assert not _bytes_equal(n0["reward"][sp4], c0["reward"][sp4])
+    # species 1..3 of world 0 and all of world 2 (the table's last: 0) are untouched
+    assert _bytes_equal(n0["reward"][~sp4], c0["reward"][~sp4])
+    assert _bytes_equal(_world_slots(never, 2)["reward"], _world_slots(sim, 2)["reward"])

@@ -378,6 +378,164 @@ def test_random_call_sequences_swapped_schedule(seed):
     test_random_call_sequences(seed, W=16400)
 
 
+EPISODE_SEEDS = list(range(1, 13))
+
+
+def run_episode_sequence(seed, W=None, exec_mode="hip"):
+    """The random call sequences with episodes: the operations above plus
+    reset_worlds, torch writes into a reset_tensor() view, set_episode_length,
+    grow_capacity in place and set_world_state (with and without a pending
+    flag), against an oracle taking the same calls.  They cross the reset pass
+    with the lazy shift, the deferred Prev columns, the K1-finder wait, the
+    value waits (4100 worlds), the armed version-5 checkpoint and the blob
+    set_world_state patches.  The manager starts at 128 slots and takes its
+    flag view first, so it is armed throughout and every hand-over loads a
+    version-5 blob; the oracle holds 1024 slots, the largest class a sequence
+    grows into.  No world may drop an agent on either side (asserted: with
+    different capacities a drop would void the comparison); on the oracle alone
+    no world of these seeds, 101 and 102 included, exceeds 46 agents.
+
+    After set_world_state the world's shoot and breed actions are held at zero
+    until its next step: that step acts on the finder slots of the old geometry,
+    in the K1-finder mode on the new one's (include/mbots.h), which the oracle
+    does not model.  Returns what the sequence did (scripts/fuzz_calls.py)."""
+    from reset_util import episode_errors
+    from simpair import COLUMNS, bits, gpu_column
+    import madrona_bots as mb
+    rng = np.random.default_rng(seed)
+    caps = np.random.default_rng(seed + 1000)
+    W = W or (4100 if seed % 4 == 0 else 20 + seed)
+    fixd = bool(seed % 2)
+    classes = [c for c in mb.CAPACITY_CLASSES if c <= 1024]
+    mgr = mb.SimManager(0, W, 69, 32, fix_depth_alias=fixd, exec_mode=exec_mode)
+    orc = pyoracle.OracleSim(W, 69, 32, cap=1024, num_threads=8)
+    flags = mgr.reset_tensor().to_torch()   # (arms the manager)
+    oflags = orc.reset_flags()
+    special = [w for w in (0, W - 1, 1023, 1024) if 0 <= w < W]
+    quiet = set()       # worlds whose scene was set since their last step
+    grown = n_scenes = peak = 0
+    t = 0
+
+    def check(where):
+        errs = compare(mgr, orc, where, depth_fixed=fixd) + episode_errors(mgr, orc, where)
+        assert not errs, errs[:5]
+
+    def hush():
+        """No shoot, no breed in the quiet worlds' current actions."""
+        if not quiet:
+            return
+        cnt, off = orc.world_counts()
+        rows = np.concatenate([orc.sensor_index()[off[w]:off[w] + cnt[w]] for w in sorted(quiet)])
+        orc.column(pyoracle.COL_ACTION)[rows, 4:6] = 0
+        mgr.action_tensor().to_torch()[torch.as_tensor(rows, dtype=torch.int64, device=mgr.device), 4:6] = 0
+
+    for it in range(48):
+        op = int(rng.integers(0, 16))   # (a quarter steps, as above)
+        if op < 4:
+            wh = bool(rng.integers(0, 2))
+            mgr.write_synthetic_actions(1234, t, wh)
+            orc.write_synthetic_actions(1234, t, wh)
+            hush()
+            mgr.step()
+            orc.step()
+            quiet.clear()
+            peak = max(peak, int(orc.world_counts()[0].max()))
+            t += 1
+        elif op in (4, 5):
+            mgr.shift_observations()
+            orc.shift_observations()
+        elif op == 6:
+            wh = bool(rng.integers(0, 2))
+            mgr.write_synthetic_actions(4321, t, wh)
+            orc.write_synthetic_actions(4321, t, wh)
+            hush()
+        elif op == 7:
+            name, cid = COLUMNS[int(rng.integers(len(COLUMNS)))]
+            prev = bool(rng.integers(0, 2))
+            g, o = gpu_column(mgr, name, prev), orc.column(cid, prev)
+            assert g.shape == o.shape and np.array_equal(bits(g), bits(o)), (it, name, prev)
+        elif op == 8:
+            prev = bool(rng.integers(0, 2))
+            g = mgr.construct_obs(prev).cpu().numpy()
+            o = _obs_rows_oracle(orc, prev, fixd)
+            assert g.shape == o.shape and np.array_equal(bits(g), bits(o)), (it, "construct_obs", prev)
+        elif op == 9:
+            if rng.integers(0, 2):   # (half the draws: a checkpoint is a rare call)
+                blob = mgr.save_checkpoint()
+                if exec_mode == "hip":   # (the CPU mode's armed blob carries a trailer instead)
+                    assert int(np.frombuffer(blob.tobytes()[8:12], np.uint32)[0]) == 5
+                mgr = mb.SimManager(0, W, 69, 32, fix_depth_alias=fixd, exec_mode=exec_mode,
+                                    agent_capacity=int(caps.choice(classes)))
+                mgr.load_checkpoint(blob)
+                assert mgr.schedule_info()["episodes_armed"]   # (by the blob, not by the view below)
+                flags = mgr.reset_tensor().to_torch()
+        elif op in (10, 11):
+            k = int(rng.integers(1, 6))
+            worlds = rng.choice(W, size=k, replace=False).tolist()
+            if rng.integers(0, 2):
+                s = int(rng.choice(special))
+                if s not in worlds:
+                    worlds[0] = s
+            eps = None if rng.integers(0, 2) else rng.integers(0, 8, size=k).tolist()
+            mgr.reset_worlds(worlds, eps)
+            orc.reset_worlds(worlds, eps)
+        elif op == 12:
+            w = int(rng.integers(W))
+            v = 1 if rng.integers(0, 2) else int(rng.integers(0, 8)) + 2
+            if rng.integers(0, 4) == 0:   # (sometimes a fresh view)
+                flags = mgr.reset_tensor().to_torch()
+            flags[w] = v
+            oflags[w] = v
+        elif op == 13:
+            n = int(rng.choice([0, 3, 5]))
+            mgr.set_episode_length(n)
+            orc.set_episode_length(n)
+        elif op == 14:
+            if grown < 2 and mgr.agent_capacity < 1024:
+                mgr.grow_capacity(2 * mgr.agent_capacity)
+                grown += 1
+                flags = mgr.reset_tensor().to_torch()   # (views do not follow a growth)
+        elif op == 15:
+            w = int(rng.integers(W))
+            if rng.integers(0, 3) == 0:   # (a pending flag: the blob patched is an armed one)
+                mgr.reset_worlds([w])
+                orc.reset_worlds([w])
+            st = mgr.world_state(w)
+            pos, rot = st["position"].copy(), st["rotation_wz"].copy()
+            pos[[0, 1]] = pos[[1, 0]]
+            rot[[0, 1]] = rot[[1, 0]]
+            # (a world that has not stepped since its creation, or one holding a
+            # respawn of the last step, has agents where the draw put them, up
+            # to 128 x 96: not a scene set_world_state takes before the next
+            # step's clamp, sim.cpp:485-486)
+            if (pos[:, 0] <= 127).all() and (pos[:, 1] <= 95).all():
+                mgr.set_world_state(w, pos, rot, st["food"])
+                orc.set_world_state(w, pos, rot, st["food"])
+                quiet.add(w)
+                hush()
+                n_scenes += 1
+        if it % 4 == 3:
+            check(f"op {it}")
+    check("end")
+    assert mgr.overflow() == 0 and orc.overflow() == 0
+    return {"steps": t, "grown": grown, "scenes": n_scenes, "peak_population": peak}
+
+
+@pytest.mark.parametrize("seed", EPISODE_SEEDS)
+def test_random_call_sequences_episodes(seed, W=None, exec_mode="hip"):
+    """run_episode_sequence: 48 random operations, resets and episodes among
+    them, against the oracle (seeds % 4 == 0 at 4100 worlds, the others at 21+
+    worlds in K1-finder mode)."""
+    run_episode_sequence(seed, W, exec_mode)
+
+
+@pytest.mark.parametrize("seed", [101, 102])
+def test_random_call_sequences_episodes_swapped_schedule(seed):
+    """The episode call sequences at 16400 worlds, on the swapped schedule: the
+    flags are written on the caller's stream, the pass runs on the internal one."""
+    test_random_call_sequences_episodes(seed, W=16400)
+
+
 @pytest.mark.parametrize("ops", ["hss" + "wss" * 9, "hsswss" + "ss" * 4 + "wsw", "sss" + "hss" * 6,
                                  "hsS" + "wsS" * 5 + "ws"])
 def test_aliased_current_action_hidden(ops):

@@ -17,6 +17,7 @@ import pytest
 import torch
 
 import pyoracle
+from reset_util import initial_positions
 from simpair import COLUMNS, compare
 
 SEED, A = 69, 32
@@ -92,14 +93,9 @@ def _world_equals_world(m, b, w, where):
 
 
 def _initial_positions(episode, gw):
-    """The test's own computation of a world's initial positions: the episode
-    key threefry2x32((seed, 0), (episode, gw)), draw c = the first word of
-    threefry2x32(key, (c, 0)) (rng_draw), agent i at (u(draw 2i) * 128,
-    u(draw 2i + 1) * 96) in float32."""
-    key = pyoracle.threefry2x32((SEED, 0), (episode, gw))
-    u = lambda c: np.float32(pyoracle.lib().orc_sample_uniform(pyoracle.threefry2x32(key, (c, 0))[0]))
-    return np.array([[u(2 * i) * np.float32(128.0), u(2 * i + 1) * np.float32(96.0)] for i in range(A)],
-                    np.float32)
+    """The test's own computation of a world's initial positions
+    (reset_util.initial_positions, shared with the oracle's known answers)."""
+    return initial_positions(SEED, A, episode, gw)
 
 
 # ------------------------------------------------------------------ tests --

@@ -1,7 +1,10 @@
 """Per-world resets and episodes on the device (reset_worlds_kernel and its
 place in mbots_step).  Where the whole manager is reset the reference is the
 oracle; otherwise a CPU-mode twin taking the same calls, every current and Prev
-column bitwise.  tests/test_reset_cpu.py holds the semantics; here each case
+column bitwise -- and, in the value-fork, swapped-schedule and captured-graph
+cases, an oracle taking them too (it restates resets on its own: see
+tests/test_reset_oracle.py, which holds the directed cases against it).
+tests/test_reset_cpu.py holds the semantics; here each case
 is a schedule the reset pass has to fit: the K1-finder mode (whose K1 does not
 wait for the last sensor; the pass must), the value forks just past it, the
 swapped schedule, mixed capacity classes (the class list is rebuilt after the
@@ -11,6 +14,7 @@ import pytest
 import torch
 
 import pyoracle
+from reset_util import episode_errors
 from simpair import COLUMNS, compare
 from test_grow_capacity import _breed_heavy
 
@@ -56,6 +60,13 @@ def _check(mgr, orc, where):
     assert not errs, errs[:5]
 
 
+def _check_episodes(mgr, orc, where):
+    """_check and the three episode arrays: an oracle that took the same calls."""
+    _check(mgr, orc, where)
+    errs = episode_errors(mgr, orc, where)
+    assert not errs, errs
+
+
 def _ints(t):
     return t.to_torch().cpu().numpy().reshape(-1).tolist()
 
@@ -96,15 +107,17 @@ def test_value_forks_scan_tile_edges():
     the scan-tile edge and the last world."""
     W = 2052
     mgr, twin = _hip(W), _cpu(W)
+    orc = pyoracle.OracleSim(W, SEED, A, num_threads=8)
     assert not mgr.schedule_info()["k1_finder"]
     for t in range(6):
-        _drive((mgr, twin), t)
-    for m in (mgr, twin):
+        _drive((mgr, twin, orc), t)
+    for m in (mgr, twin, orc):
         m.reset_worlds([0, 1023, 1024, 2051])
     for t in range(6, 12):
-        _drive((mgr, twin), t)
+        _drive((mgr, twin, orc), t)
         if t in (6, 8, 11):
             _same(mgr, twin, f"step {t}")
+            _check_episodes(mgr, orc, f"step {t}")
     want = [0] * W
     for w in (0, 1023, 1024, 2051):
         want[w] = 1
@@ -116,15 +129,18 @@ def test_swapped_schedule_flags_written_by_torch():
     on the caller's stream."""
     W = 8200
     mgr, twin = _hip(W), _cpu(W)
+    orc = pyoracle.OracleSim(W, SEED, A, num_threads=8)
     for t in range(3):
-        _drive((mgr, twin), t)
+        _drive((mgr, twin, orc), t)
     idx = [0, 4100, 8199]
     mgr.reset_tensor().to_torch()[idx] = 1
     twin.reset_tensor().to_torch()[idx] = 1
+    orc.reset_flags()[idx] = 1
     for t in range(3, 7):
-        _drive((mgr, twin), t)
+        _drive((mgr, twin, orc), t)
         if t in (3, 6):
             _same(mgr, twin, f"step {t} (swap {mgr.schedule_info()['swap']})")
+            _check_episodes(mgr, orc, f"step {t}")
     assert _ints(mgr.reset_tensor()) == [0] * W
     assert [_ints(mgr.episode_tensor())[w] for w in idx] == [1, 1, 1]
 
@@ -161,6 +177,12 @@ def test_graph_capture():
     time, so a torch write between replays resets worlds."""
     W = 64
     mgr, twin = _hip(W), _cpu(W)
+    orc = pyoracle.OracleSim(W, SEED, A, num_threads=4)
+    for t in (0, 1, 2, 3):   # (the steps before the capture and the first replay)
+        _drive((orc,), t)
+    orc.reset_flags()[[5, 40]] = 1
+    for t in (2, 3):         # (the second replay)
+        _drive((orc,), t)
     s = torch.cuda.Stream()
     s.wait_stream(torch.cuda.current_stream())
     g = torch.cuda.CUDAGraph()
@@ -193,6 +215,7 @@ def test_graph_capture():
             _drive((twin,), t)
         torch.cuda.synchronize()
         _same(mgr, twin, "second replay")
+        _check_episodes(mgr, orc, "second replay")
         assert _ints(mgr.episode_tensor())[5] == _ints(mgr.episode_tensor())[40] == 1
         assert _ints(mgr.episode_step_tensor())[5] == 2
 

@@ -438,6 +438,98 @@ int mbots_reset_worlds(mbots_handle *h, const uint32_t *global_worlds, uint32_t 
                        const uint32_t *episodes /* NULL: next */, void *stream);
 int mbots_set_episode_length(mbots_handle *h, uint32_t steps);
 
+/* Trajectory window: agent lifelines, returns and GAE(lambda) over up to
+ * `horizon` consecutive tables.  Every step re-sorts the export table by
+ * species, so row r after one step is not row r after the next; the manager
+ * alone knows which row an agent came from.  A window records that, per pushed
+ * table t and row r < N_t (exported rows only, never the shard ghost's):
+ *   MBOTS_TRAJ_LINK    int32  the row of table t - 1 this agent came from (the
+ *                             step's own provenance); -1 for a newborn, a
+ *                             respawn, any agent of a world re-initialised by
+ *                             that step.  Table 0's is recorded, never followed.
+ *   MBOTS_TRAJ_REWARD  f32    the Reward column
+ *   MBOTS_TRAJ_VALUE   f32    the caller's critic estimate handed to the push
+ *   MBOTS_TRAJ_WORLD   int32  the row's global world index
+ * and, per world, whether the step that produced table t re-initialised it (an
+ * armed manager's reset pass leaves the mark; an unarmed manager has none).
+ * The window stores no observations: the learner keeps its own tensors in each
+ * step's row order and gathers them with these maps.
+ *
+ * A manager holds at most one window; it is off until mbots_traj_open, and a
+ * manager that never opens one enqueues in mbots_step exactly what it always
+ * did.  The window's storage is its own allocation of 32 bytes per row slot
+ * (horizon x max_rows), outside the manager's arena.
+ *
+ * mbots_traj_push(h, value, stream) records the current table (after
+ * mbots_create: the initial one; else the last step's).  value: N_t f32 of
+ * the manager's device (host memory in CPU mode) in the table's row order, or
+ * NULL for zeros; the launch reads its first min(N_t, max_rows) entries, so a
+ * buffer of max_rows entries is always large enough.  It does not synchronise the host: N_t is read from the
+ * device's totals inside the launch.  Stream-ordered like every call; it
+ * follows the step's export of the rows, not its sensor.  MBOTS_E_INVALID under
+ * stream capture and when the window already holds `horizon` tables.  A table
+ * of more than max_rows rows is recorded truncated with its true count: the
+ * next mbots_traj_compute returns MBOTS_E_RANGE, and keeps doing so until that
+ * table has left the window (mbots_traj_clear).
+ *
+ * mbots_traj_compute(h, gamma, lambda, death_reward, rows_out, n_out, stream)
+ * runs over the n pushed tables and fills, for row q of table t:
+ *   MBOTS_TRAJ_NEXT (t < n - 1)  the row of table t + 1 holding the same agent
+ *                                (the inverse of LINK[t + 1]), or -1
+ *   MBOTS_TRAJ_END  int32        0 has a successor; 1 died (no successor, its
+ *                                world not re-initialised by step t + 1); 2 cut
+ *                                off by a reset of its world; 3 window end
+ *                                (t == n - 1)
+ *   MBOTS_TRAJ_ADV, MBOTS_TRAJ_RET f32, with r = NEXT[t][q], gl = gamma * lambda
+ *   rounded once, and every product and every sum rounded to f32 on its own:
+ *     END 0: delta = (REWARD[t+1][r] + gamma * VALUE[t+1][r]) - VALUE[t][q];
+ *            ADV = delta + gl * ADV[t+1][r] if t + 1 <= n - 2, else delta
+ *     END 1: ADV = death_reward - VALUE[t][q]
+ *     END 2: ADV = 0 (neither a next state nor a reward: mask it by END)
+ *     RET = ADV + VALUE[t][q];  table n - 1: ADV = 0, RET = VALUE.
+ *   With value NULL and lambda 1, RET is the plain discounted return along the
+ *   lifeline.  rows_out[0 .. n) (space for `horizon`) receives N_0 .. N_{n-1},
+ *   *n_out the table count: the one host synchronisation of the window (on
+ *   `stream`, before the launches; the results are final in stream order).  It
+ *   may be repeated with other parameters without pushing again.  Both
+ *   execution modes give the same bits.  MBOTS_E_INVALID under stream capture
+ *   and on an empty window.
+ *
+ * mbots_traj_clear(h, keep_last) empties the window; keep_last != 0: its
+ * newest table becomes table 0 of the next window, so consecutive windows chain
+ * without losing a transition (host bookkeeping only: nothing is copied).
+ * mbots_load_checkpoint and mbots_set_world_state empty the window too (the
+ * rows' provenance is stale after a load); mbots_grow_capacity and automatic
+ * growth leave it intact.
+ *
+ * mbots_traj_view(h, what, t, out): a [N_t, 1] view of one column of table t,
+ * valid until the next mbots_traj_clear or mbots_traj_close (a push into a
+ * cleared window overwrites it).  The pushed columns can be viewed once the
+ * table's row count has reached the host (always in CPU mode, after
+ * mbots_traj_compute in HIP mode), the computed ones after a compute of the
+ * tables now in the window; else MBOTS_E_INVALID; t outside the window:
+ * MBOTS_E_RANGE.  mbots_traj_close frees the window (after the device has
+ * drained); every entry point but mbots_traj_open then returns
+ * MBOTS_E_INVALID. */
+enum mbots_traj_view_id {
+    MBOTS_TRAJ_LINK = 0, MBOTS_TRAJ_NEXT = 1, MBOTS_TRAJ_END = 2, MBOTS_TRAJ_WORLD = 3,
+    MBOTS_TRAJ_REWARD = 4, MBOTS_TRAJ_VALUE = 5, MBOTS_TRAJ_ADV = 6, MBOTS_TRAJ_RET = 7
+};
+#define MBOTS_TRAJ_END_NONE   0
+#define MBOTS_TRAJ_END_DIED   1
+#define MBOTS_TRAJ_END_RESET  2
+#define MBOTS_TRAJ_END_WINDOW 3
+int mbots_traj_open(mbots_handle *h, uint32_t horizon /* 2..65535 */, uint64_t max_rows);
+int mbots_traj_close(mbots_handle *h);
+int mbots_traj_push(mbots_handle *h, const float *value /* NULL: zeros */, void *stream);
+int mbots_traj_compute(mbots_handle *h, float gamma, float lambda, float death_reward,
+                       int64_t *rows_out /* [horizon], may be NULL */, uint32_t *n_out /* may be NULL */,
+                       void *stream);
+int mbots_traj_clear(mbots_handle *h, int32_t keep_last);
+/* tables pushed since the last clear (host state) */
+int mbots_traj_num_tables(mbots_handle *h, uint32_t *out);
+int mbots_traj_view(mbots_handle *h, int32_t what, uint32_t t, mbots_tensor *out);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That

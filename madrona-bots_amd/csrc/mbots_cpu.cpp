@@ -105,6 +105,7 @@ Sim::Sim(const mbots_config &cfg)
     put(reset_flags_, W_);
     put(episode_, W_);
     put(age_, W_);
+    put(reset_mark_, W_);
     put(sensor_index_, rows);
     put(src_of_, rows);
     // Sim::Sim + initWorld (sim.cpp:1232-1256, :233-275), then the first export
@@ -569,6 +570,7 @@ void Sim::reset_pass()
         const int32_t flag = reset_flags_[w], age = age_[w];
         if (flag == 0 && (ep_len_ == 0 || (uint32_t)age < ep_len_)) {
             age_[w] = age + 1;
+            reset_mark_[w] = 0;
             return;
         }
         const int32_t e = flag >= 2 ? flag - 2 : episode_[w] + 1;
@@ -576,7 +578,34 @@ void Sim::reset_pass()
         episode_[w] = e;
         age_[w] = 1;   // the world is stepped right after
         reset_flags_[w] = 0;
+        reset_mark_[w] = 1;
     });
+}
+
+// the trajectory window's launches (traj_push_kernel, launch_traj_compute) as
+// loops: the same element bodies in the same order of dependent passes
+void Sim::traj_push(const TrajWin &w, uint32_t slot, const float *value) const
+{
+    const uint32_t N = N_, lim = std::min(N, w.max_rows);
+    const Table &t = T_[tb_];
+    for (uint32_t r = 0; r < lim; ++r) traj_push_row(w, slot, r, src_of_.data(), t.reward.data(), value);
+    for (uint32_t k = 0; k < w.Wx * (uint32_t)kNumSpecies; ++k)
+        traj_push_world(w, slot, k, N, row_base_.data(), scount_.data(), reset_mark_.data());
+    w.count[slot] = N;
+}
+
+void Sim::traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n)
+{
+    auto rows = [&](uint32_t t) { return w.count[traj_slot(w, t)]; };
+    for (uint32_t t = 0; t + 1 < n; ++t)
+        for (uint32_t q = 0; q < rows(t); ++q) w.next[traj_at(w, t, q)] = -1;
+    for (uint32_t t = 1; t < n; ++t)
+        for (uint32_t r = 0; r < rows(t); ++r) {
+            const int32_t p = traj_link(w, t, r, rows(t - 1));
+            if (p >= 0) w.next[traj_at(w, t - 1, (uint32_t)p)] = (int32_t)r;
+        }
+    for (uint32_t t = 0; t < n; ++t)
+        for (uint32_t q = 0; q < rows(t); ++q) traj_sweep(w, P, n, t, q);
 }
 
 void Sim::step()

@@ -11,6 +11,7 @@
 
 #include "../../include/mbots.h"
 #include "mbots_device.hpp"
+#include "mbots_traj.hpp"
 
 #include <cstdint>
 #include <memory>
@@ -82,6 +83,11 @@ public:
     void reset_worlds(const uint32_t *global_worlds, uint32_t n, const uint32_t *episodes);
     void set_episode_length(uint32_t steps);
     bool armed() const { return armed_; }
+    // trajectory window (mbots_traj.hpp), the HIP path's launches as loops over
+    // host memory: the current table into ring slot `slot` (value: N f32 or
+    // null), and compute over the n pushed tables
+    void traj_push(const TrajWin &w, uint32_t slot, const float *value) const;
+    static void traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n);
     const mbots_config &config() const { return cfg_; }
 
 private:
@@ -119,6 +125,7 @@ private:
     // the current episode, the steps since the last reset or creation (kept by
     // the reset pass once armed; age0_ for every world before)
     std::vector<int32_t> reset_flags_, episode_, age_;
+    std::vector<int32_t> reset_mark_;   // 1: the last reset pass re-initialised the world
     bool armed_ = false;
     uint32_t ep_len_ = 0;
     uint64_t age0_ = 0;

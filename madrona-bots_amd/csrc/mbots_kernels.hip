@@ -2669,7 +2669,10 @@ __global__ __launch_bounds__(256) void reset_worlds_kernel(SimState S, ResetArgs
     const int32_t flag = uniform(R.flag[w]);
     const int32_t age = uniform(R.age[w]);
     if (flag == 0 && (R.len == 0u || (uint32_t)age < R.len)) {
-        if (lane == 0) R.age[w] = age + 1;
+        if (lane == 0) {
+            R.age[w] = age + 1;
+            R.mark[w] = 0;
+        }
         return;
     }
     // 1: the next episode (what a learner writes); v >= 2: episode v - 2
@@ -2679,6 +2682,7 @@ __global__ __launch_bounds__(256) void reset_worlds_kernel(SimState S, ResetArgs
         R.episode[w] = e;
         R.age[w] = 1;   // the world is stepped right after
         R.flag[w] = 0;
+        R.mark[w] = 1;
     }
 }
 
@@ -3316,6 +3320,75 @@ hipError_t launch_grow_slots(const GrowCols &c, uint32_t W, uint32_t cap_old, ui
     const dim3 grid((total + kGrowPerBlock - 1) / kGrowPerBlock, kGrowCols), blk(kGrowThreads);
     if (vec) hipLaunchKernelGGL(grow_slots_kernel<true>, grid, blk, 0, st, c, W, row_old, row_new);
     else hipLaunchKernelGGL(grow_slots_kernel<false>, grid, blk, 0, st, c, W, row_old, row_new);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Trajectory window (include/mbots.h "Trajectory window"; the element bodies
+// are mbots_traj.hpp's, shared with the CPU mode).  The push copies the step's
+// provenance, the Reward column and the caller's values for the rows [0, N) the
+// device's totals give, fills each row's world from K2's row bases and copies
+// the reset pass's per-world marks; a grid-stride launch sized by max_rows, so
+// the host needs no row count.  compute: `next` filled with -1 and scattered
+// from link (a survivor has one successor: unique targets), then the sweep, one
+// thread per (table, row) of which the lifeline ends walk their lifeline
+// backwards -- no launch per step, and no thread waits for another.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void traj_push_kernel(TrajWin w, uint32_t slot, const uint32_t *totals,
+                                                        const int32_t *src_of, const float *reward,
+                                                        const float *value, const int32_t *row_base,
+                                                        const int32_t *scount, const int32_t *reset_mark)
+{
+    const uint32_t N = totals[0];
+    const uint32_t lim = N < w.max_rows ? N : w.max_rows;
+    const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (uint32_t r = g; r < lim; r += stride) traj_push_row(w, slot, r, src_of, reward, value);
+    for (uint32_t k = g; k < w.Wx * (uint32_t)kNumSpecies; k += stride)
+        traj_push_world(w, slot, k, N, row_base, scount, reset_mark);
+    if (g == 0) w.count[slot] = N;
+}
+
+// grid (x: rows, y: tables 0 .. n - 2)
+__global__ __launch_bounds__(256) void traj_next_fill_kernel(TrajWin w)
+{
+    const uint32_t t = blockIdx.y, q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < w.count[traj_slot(w, t)]) w.next[traj_at(w, t, q)] = -1;
+}
+__global__ __launch_bounds__(256) void traj_next_scatter_kernel(TrajWin w)
+{
+    const uint32_t t = blockIdx.y + 1u, r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= w.count[traj_slot(w, t)]) return;
+    const int32_t p = traj_link(w, t, r, w.count[traj_slot(w, t - 1u)]);
+    if (p >= 0) w.next[traj_at(w, t - 1u, (uint32_t)p)] = (int32_t)r;
+}
+// grid (x: rows, y: tables 0 .. n - 1)
+__global__ __launch_bounds__(256) void traj_sweep_kernel(TrajWin w, TrajParams P, uint32_t n)
+{
+    const uint32_t t = blockIdx.y, q = blockIdx.x * blockDim.x + threadIdx.x;
+    if (q < w.count[traj_slot(w, t)]) traj_sweep(w, P, n, t, q);
+}
+
+hipError_t launch_traj_push(const SimState &S, const TrajWin &w, uint32_t slot, const float *reward,
+                            const float *value, const int32_t *reset_mark, hipStream_t st)
+{
+    if (slot >= w.horizon || w.Wx != S.Wx) return hipErrorInvalidValue;
+    const uint32_t items = std::max(w.max_rows, w.Wx * (uint32_t)kNumSpecies);
+    const uint32_t blocks = std::min<uint32_t>((items + 255u) / 256u, 2048u);
+    hipLaunchKernelGGL(traj_push_kernel, dim3(blocks), dim3(256), 0, st, w, slot, S.totals, S.src_of, reward, value,
+                       S.row_base, S.scount, reset_mark);
+    return hipGetLastError();
+}
+
+hipError_t launch_traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n, uint32_t max_count, hipStream_t st)
+{
+    if (n == 0 || n > w.horizon || max_count > w.max_rows) return hipErrorInvalidValue;
+    if (max_count == 0) return hipSuccess;
+    const uint32_t bx = (max_count + 255u) / 256u;
+    if (n > 1) {
+        hipLaunchKernelGGL(traj_next_fill_kernel, dim3(bx, n - 1), dim3(256), 0, st, w);
+        hipLaunchKernelGGL(traj_next_scatter_kernel, dim3(bx, n - 1), dim3(256), 0, st, w);
+    }
+    hipLaunchKernelGGL(traj_sweep_kernel, dim3(bx, n), dim3(256), 0, st, w, P, n);
     return hipGetLastError();
 }
 

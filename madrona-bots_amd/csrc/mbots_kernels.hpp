@@ -2,6 +2,7 @@
 #pragma once
 
 #include "mbots_device.hpp"
+#include "mbots_traj.hpp"
 #include "../../include/mbots.h"
 
 namespace mbots {
@@ -89,6 +90,8 @@ struct ResetArgs {
     int32_t *episode;   // [W] the world's current episode
     int32_t *age;       // [W] steps since the world's last reset or creation
     uint32_t len;       // episode length in steps (0: off)
+    int32_t *mark;      // [W] 1: this pass re-initialised the world, else 0 (the trajectory
+                        // window's push copies it)
 };
 
 // the small kernel class of mixed-class dispatch
@@ -229,5 +232,13 @@ hipError_t launch_grow_slots(const GrowCols &c, uint32_t W, uint32_t cap_old, ui
 hipError_t launch_rebuild_learner(const RebuildPlan &p, const int32_t *src, uint32_t rows, uint32_t last_rows,
                                   const int32_t *last_action, const float *last_memory, const float *last_hidden,
                                   int32_t *action, float *hidden, float *prev_hidden, hipStream_t st);
+
+// trajectory window (mbots_traj.hpp): the push of the current table (`reward`:
+// its Reward column; `value`: N f32 or null; reset_mark: the last reset pass's
+// marks or null) into ring slot `slot`, and compute's three launches over the
+// n pushed tables (max_count: the largest N_t, at most max_rows)
+hipError_t launch_traj_push(const SimState &S, const TrajWin &w, uint32_t slot, const float *reward,
+                            const float *value, const int32_t *reset_mark, hipStream_t st);
+hipError_t launch_traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n, uint32_t max_count, hipStream_t st);
 
 }  // namespace mbots

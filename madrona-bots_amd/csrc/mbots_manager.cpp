@@ -86,6 +86,9 @@ struct mbots_handle {
     int32_t *age = nullptr;           // steps since its last reset or creation (kept by the
                                       // reset pass: current once armed, or filled on export)
     bool armed = false;               // every step runs the reset pass before K1
+    int32_t *reset_mark = nullptr;    // [W] 1: the last reset pass re-initialised the world (its
+                                      // own allocation: a growth leaves it; the trajectory
+                                      // window's push copies it)
     uint32_t ep_len = 0;              // episode length in steps (0: off)
     uint64_t age0 = 0;                // steps since creation (every world's age while unarmed)
     int32_t *flag_stage = nullptr;    // mbots_reset_worlds: pinned host / device staging of
@@ -163,6 +166,18 @@ struct mbots_handle {
     double acc_ms[MBOTS_TK_COUNT] = {};
     uint64_t acc_n[MBOTS_TK_COUNT] = {};
     bool auto_cap = false;            // mbots_set_auto_capacity: mbots_step grows before it could overflow
+    // the trajectory window (include/mbots.h "Trajectory window"): storage of its
+    // own (one allocation, device or host), so growths leave it alone
+    struct Traj {
+        bool open = false;
+        mbots::TrajWin w{};
+        void *mem = nullptr;
+        uint32_t n = 0;               // tables pushed
+        uint32_t known = 0;           // tables whose row count the host holds (rows)
+        bool computed = false;        // next / end / adv / ret are those of the n tables
+        std::vector<int64_t> rows;    // N_t of table t < known
+        uint32_t *h_count = nullptr;  // pinned staging of w.count (HIP mode)
+    } traj;
     std::vector<char *> retired;      // arenas earlier growths left (views taken then still read
                                       // them): freed by mbots_release_retired / mbots_destroy
 };
@@ -634,6 +649,14 @@ int record_totals(mbots_handle *h, hipStream_t st)
     return MBOTS_OK;
 }
 
+// the trajectory window emptied (host bookkeeping only: its slots are a ring)
+void traj_empty(mbots_handle *h)
+{
+    h->traj.n = h->traj.known = 0;
+    h->traj.w.base = 0;
+    h->traj.computed = false;
+}
+
 }  // namespace
 
 // checkpoint segments (mbots_save_checkpoint / mbots_load_checkpoint)
@@ -911,6 +934,8 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
     constexpr unsigned kSyncEvent = hipEventDisableTiming | hipEventReleaseToDevice;
     check(hipEventCreateWithFlags(&h->ev_totals, kSyncEvent), "hipEventCreateWithFlags");
     check(hipEventCreateWithFlags(&h->ev_hop, kSyncEvent), "hipEventCreateWithFlags");
+    check(hipMalloc((void **)&h->reset_mark, (size_t)S.W * sizeof(int32_t)), "hipMalloc");
+    if (rc == MBOTS_OK) check(hipMemset(h->reset_mark, 0, (size_t)S.W * sizeof(int32_t)), "hipMemset");
     {
         // the words hipStreamWaitValue32 polls (the runtime's wait kernel reads
         // them); without signal memory the waits stay event waits
@@ -984,11 +1009,15 @@ int mbots_destroy(mbots_handle *h)
 {
     if (!h) return MBOTS_OK;
     if (h->cpu) {
+        std::free(h->traj.mem);
         delete h;
         return MBOTS_OK;
     }
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
+    if (h->traj.mem) (void)hipFree(h->traj.mem);
+    if (h->traj.h_count) (void)hipHostFree(h->traj.h_count);
+    if (h->reset_mark) (void)hipFree(h->reset_mark);
     for (auto &p : h->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : h->pool) (void)hipEventDestroy(e);
     if (h->ev_totals) (void)hipEventDestroy(h->ev_totals);
@@ -1152,7 +1181,7 @@ int mbots_step(mbots_handle *h, void *stream)
             HIP_TRY(hipStreamWaitEvent(kst, h->ev_join[h->last_join], 0));
             if (!capturing) h->waited_serial = std::max(h->waited_serial, h->join_serial[h->last_join]);
         }
-        const mbots::ResetArgs R{h->reset_flags, h->episode, h->age, h->ep_len};
+        const mbots::ResetArgs R{h->reset_flags, h->episode, h->age, h->ep_len, h->reset_mark};
         HIP_TRY(mbots::launch_reset_worlds(h->S, R, par, kst));
     } else {
         ++h->age0;
@@ -1981,6 +2010,7 @@ int mbots_load_checkpoint(mbots_handle *h, const void *src, uint64_t bytes)
         const int r = h->cpu->load(src, bytes, err);
         if (r) return fail(r, err);
         h->ovf_reported = (uint32_t)std::min<uint64_t>(h->cpu->overflow(), 0xFFFFFFFFu);
+        traj_empty(h);
         return MBOTS_OK;
     }
     if (bytes < sizeof(CkptHeader)) return fail(MBOTS_E_INVALID, "checkpoint truncated");
@@ -2035,6 +2065,7 @@ int mbots_load_checkpoint(mbots_handle *h, const void *src, uint64_t bytes)
     }
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipDeviceSynchronize());
+    traj_empty(h);   // (the rows' provenance is stale after a load: the window does not inherit it)
     const char *p = static_cast<const char *>(src) + sizeof(hd);
     for (size_t i = 0; i < segs.size(); ++i) {
         const Seg &s = segs[i];
@@ -2339,6 +2370,7 @@ int mbots_set_world_state(mbots_handle *h, uint32_t world, const float *xy_rwrz,
     if (h->cpu) {
         if (n_agents != h->cpu->population(world)) return fail(MBOTS_E_INVALID, kPop);
         h->cpu->set_world_state(world, xy_rwrz, rec, rot, (int32_t)n_food);
+        traj_empty(h);   // (as HIP mode's checkpoint round trip does)
         return MBOTS_OK;
     }
     HIP_TRY(hipSetDevice(h->device));
@@ -2506,6 +2538,211 @@ int mbots_kernel_times(mbots_handle *h, double ms[MBOTS_TK_COUNT], uint64_t laun
         if (ms) ms[k] = h->acc_ms[k];
         if (launches) launches[k] = h->acc_n[k];
     }
+    return MBOTS_OK;
+}
+
+// ---- the trajectory window (include/mbots.h "Trajectory window") ----
+int mbots_traj_open(mbots_handle *h, uint32_t horizon, uint64_t max_rows)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    auto &tj = h->traj;
+    if (tj.open) return fail(MBOTS_E_INVALID, "the manager already holds a trajectory window: close it first");
+    if (horizon < 2 || horizon > 65535u) return fail(MBOTS_E_INVALID, "horizon must be in [2, 65535]");
+    if (max_rows == 0 || max_rows >= (1ull << 31)) return fail(MBOTS_E_INVALID, "max_rows must be in [1, 2^31)");
+    const uint32_t Wx = h->cfg.num_worlds;
+    auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
+    const size_t col = pad((size_t)horizon * max_rows * 4), marks = pad((size_t)horizon * Wx * 4),
+                 counts = pad((size_t)horizon * 4);
+    const size_t bytes = 8 * col + marks + counts;
+    char *mem = nullptr;
+    if (h->cpu) {
+        mem = static_cast<char *>(std::calloc(bytes, 1));
+        if (!mem) return fail(MBOTS_E_NOMEM, "host allocation of the trajectory window failed");
+    } else {
+        HIP_TRY(hipSetDevice(h->device));
+        if (capturing_now(h)) return fail(MBOTS_E_INVALID, "a trajectory window cannot be opened under stream capture");
+        if (hipMalloc((void **)&mem, bytes) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MBOTS_E_NOMEM, "hipMalloc of " + std::to_string(bytes) + " bytes for the trajectory window failed");
+        }
+        hipError_t e = hipMemset(mem, 0, bytes);
+        if (e == hipSuccess && !tj.h_count)
+            e = hipHostMalloc((void **)&tj.h_count, 65535u * sizeof(uint32_t), hipHostMallocDefault);
+        if (e != hipSuccess) {
+            (void)hipFree(mem);
+            return fail(MBOTS_E_HIP, std::string("trajectory window: ") + hipGetErrorString(e));
+        }
+    }
+    mbots::TrajWin &w = tj.w;
+    char *p = mem;
+    auto take = [&](size_t b) { char *q = p; p += b; return q; };
+    w.link = (int32_t *)take(col);  w.world = (int32_t *)take(col);
+    w.next = (int32_t *)take(col);  w.end = (int32_t *)take(col);
+    w.reward = (float *)take(col);  w.value = (float *)take(col);
+    w.adv = (float *)take(col);     w.ret = (float *)take(col);
+    w.mark = (int32_t *)take(marks);
+    w.count = (uint32_t *)take(counts);
+    w.horizon = horizon;
+    w.max_rows = (uint32_t)max_rows;
+    w.Wx = Wx;
+    w.world_offset = h->cfg.world_offset;
+    tj.mem = mem;
+    tj.rows.assign(horizon, 0);
+    tj.open = true;
+    traj_empty(h);
+    return MBOTS_OK;
+}
+
+int mbots_traj_close(mbots_handle *h)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    auto &tj = h->traj;
+    if (!tj.open) return fail(MBOTS_E_INVALID, "no trajectory window is open");
+    if (h->cpu) {
+        std::free(tj.mem);
+    } else {
+        HIP_TRY(hipSetDevice(h->device));
+        if (capturing_now(h)) return fail(MBOTS_E_INVALID, "a trajectory window cannot be closed under stream capture");
+        HIP_TRY(hipDeviceSynchronize());   // its last push / compute, on whatever stream
+        HIP_TRY(hipFree(tj.mem));
+    }
+    tj.mem = nullptr;
+    tj.w = mbots::TrajWin{};
+    tj.open = false;
+    traj_empty(h);
+    return MBOTS_OK;
+}
+
+int mbots_traj_push(mbots_handle *h, const float *value, void *stream)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    auto &tj = h->traj;
+    if (!tj.open) return fail(MBOTS_E_INVALID, "no trajectory window is open");
+    if (tj.n >= tj.w.horizon)
+        return fail(MBOTS_E_INVALID, "the trajectory window is full (" + std::to_string(tj.n) +
+                                         " tables): compute and clear it first");
+    const uint32_t slot = mbots::traj_slot(tj.w, tj.n);
+    if (h->cpu) {
+        h->cpu->traj_push(tj.w, slot, value);
+        tj.rows[tj.n] = tj.w.count[slot];
+        tj.known = tj.n + 1;
+    } else {
+        HIP_TRY(hipSetDevice(h->device));
+        hipStream_t st = as_stream(stream);
+        if (capturing(st))
+            return fail(MBOTS_E_INVALID, "mbots_traj_push cannot be captured into a graph: the window's table count "
+                                         "is host state");
+        if (int rc = use_stream(h, st)) return rc;
+        // after the step's K3a (this stream's order), which wrote the
+        // provenance and the Reward column; not after its sensor
+        HIP_TRY(mbots::launch_traj_push(h->S, tj.w, slot, h->T[h->tb].reward, value, h->reset_mark, st));
+    }
+    ++tj.n;
+    tj.computed = false;
+    return MBOTS_OK;
+}
+
+int mbots_traj_compute(mbots_handle *h, float gamma, float lambda, float death_reward, int64_t *rows_out,
+                       uint32_t *n_out, void *stream)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    auto &tj = h->traj;
+    if (!tj.open) return fail(MBOTS_E_INVALID, "no trajectory window is open");
+    if (tj.n == 0) return fail(MBOTS_E_INVALID, "the trajectory window is empty");
+    hipStream_t st = as_stream(stream);
+    if (!h->cpu) {
+        HIP_TRY(hipSetDevice(h->device));
+        if (capturing(st))
+            return fail(MBOTS_E_INVALID, "mbots_traj_compute returns the row counts to the host and cannot be "
+                                         "captured into a graph");
+        if (int rc = use_stream(h, st)) return rc;
+        HIP_TRY(hipMemcpyAsync(tj.h_count, tj.w.count, (size_t)tj.w.horizon * sizeof(uint32_t), hipMemcpyDeviceToHost,
+                               st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    const uint32_t *cnt = h->cpu ? tj.w.count : tj.h_count;
+    uint32_t mx = 0;
+    for (uint32_t t = 0; t < tj.n; ++t) {
+        const uint32_t c = cnt[mbots::traj_slot(tj.w, t)];
+        tj.rows[t] = c;
+        if (rows_out) rows_out[t] = c;
+        mx = std::max(mx, c);
+    }
+    if (n_out) *n_out = tj.n;
+    if (mx > tj.w.max_rows) {
+        tj.known = 0;
+        tj.computed = false;
+        return fail(MBOTS_E_RANGE, "a pushed table held " + std::to_string(mx) + " rows, more than the window's max_rows " +
+                                       std::to_string(tj.w.max_rows) + ": clear the window (or reopen it larger)");
+    }
+    tj.known = tj.n;
+    volatile float gl = gamma * lambda;   // rounded once
+    const mbots::TrajParams P{gamma, gl, death_reward};
+    if (h->cpu) mbots::cpu::Sim::traj_compute(tj.w, P, tj.n);
+    else HIP_TRY(mbots::launch_traj_compute(tj.w, P, tj.n, mx, st));
+    tj.computed = true;
+    return MBOTS_OK;
+}
+
+int mbots_traj_clear(mbots_handle *h, int32_t keep_last)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    auto &tj = h->traj;
+    if (!tj.open) return fail(MBOTS_E_INVALID, "no trajectory window is open");
+    if (!keep_last || tj.n == 0) {
+        traj_empty(h);
+        return MBOTS_OK;
+    }
+    // the newest table's slot becomes slot of table 0: nothing moves
+    const bool known = tj.known == tj.n;
+    const int64_t rows_last = tj.rows[tj.n - 1];
+    tj.w.base = mbots::traj_slot(tj.w, tj.n - 1);
+    tj.n = 1;
+    tj.rows[0] = rows_last;
+    tj.known = known ? 1u : 0u;
+    tj.computed = false;
+    return MBOTS_OK;
+}
+
+int mbots_traj_num_tables(mbots_handle *h, uint32_t *out)
+{
+    if (!h || !out) return fail(MBOTS_E_INVALID, "null argument");
+    if (!h->traj.open) return fail(MBOTS_E_INVALID, "no trajectory window is open");
+    *out = h->traj.n;
+    return MBOTS_OK;
+}
+
+int mbots_traj_view(mbots_handle *h, int32_t what, uint32_t t, mbots_tensor *out)
+{
+    if (!h || !out) return fail(MBOTS_E_INVALID, "null argument");
+    auto &tj = h->traj;
+    if (!tj.open) return fail(MBOTS_E_INVALID, "no trajectory window is open");
+    const mbots::TrajWin &w = tj.w;
+    void *col = nullptr;
+    int32_t dtype = MBOTS_DTYPE_INT32;
+    bool derived = false;
+    switch (what) {
+    case MBOTS_TRAJ_LINK: col = w.link; break;
+    case MBOTS_TRAJ_WORLD: col = w.world; break;
+    case MBOTS_TRAJ_REWARD: col = w.reward; dtype = MBOTS_DTYPE_FLOAT32; break;
+    case MBOTS_TRAJ_VALUE: col = w.value; dtype = MBOTS_DTYPE_FLOAT32; break;
+    case MBOTS_TRAJ_NEXT: col = w.next; derived = true; break;
+    case MBOTS_TRAJ_END: col = w.end; derived = true; break;
+    case MBOTS_TRAJ_ADV: col = w.adv; dtype = MBOTS_DTYPE_FLOAT32; derived = true; break;
+    case MBOTS_TRAJ_RET: col = w.ret; dtype = MBOTS_DTYPE_FLOAT32; derived = true; break;
+    default: return fail(MBOTS_E_INVALID, "unknown trajectory view " + std::to_string(what));
+    }
+    if (t >= tj.n || (what == MBOTS_TRAJ_NEXT && t + 1 >= tj.n))
+        return fail(MBOTS_E_RANGE, "table " + std::to_string(t) + " is outside the window's " + std::to_string(tj.n));
+    if (derived && !tj.computed)
+        return fail(MBOTS_E_INVALID, "next / end / adv / ret exist after mbots_traj_compute of the pushed tables");
+    if (t >= tj.known)
+        return fail(MBOTS_E_INVALID, "the table's row count reaches the host with mbots_traj_compute");
+    out->data = static_cast<char *>(col) + mbots::traj_at(w, t, 0) * 4;
+    out->dtype = dtype;
+    out->device = h->cpu ? -1 : h->device;
+    out->dims[0] = tj.rows[t];
+    out->dims[1] = 1;
     return MBOTS_OK;
 }
 

@@ -22,12 +22,13 @@ import ctypes
 import os
 import types
 import warnings
+import weakref
 
 import torch  # loads the HIP runtime libmbots.so links against (same soname)
 
 __all__ = ["SimManager", "ScriptBotsViewer", "Tensor", "madrona", "ExportID", "ExecMode", "unpack_rollout",
            "unpack_learner", "rebuild_learner", "CapacityWarning", "CapacityError", "MAX_CAPACITY",
-           "CAPACITY_CLASSES"]
+           "CAPACITY_CLASSES", "TrajectoryWindow"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmbots.so")
@@ -103,6 +104,13 @@ def _load():
         "mbots_release_retired": [vp],
         "mbots_reset_worlds": [vp, vp, u32, vp, vp],
         "mbots_set_episode_length": [vp, u32],
+        "mbots_traj_open": [vp, u32, ctypes.c_uint64],
+        "mbots_traj_close": [vp],
+        "mbots_traj_push": [vp, vp, vp],
+        "mbots_traj_compute": [vp, ctypes.c_float, ctypes.c_float, ctypes.c_float, P(ctypes.c_int64), P(u32), vp],
+        "mbots_traj_clear": [vp, i32],
+        "mbots_traj_num_tables": [vp, P(u32)],
+        "mbots_traj_view": [vp, i32, u32, P(_CTensor)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -433,7 +441,15 @@ class SimManager:
     episode_tensor() / episode_step_tensor() each world's episode and its
     steps since the last reset or creation.  episode_length=k (or
     set_episode_length(k)) resets every world whose episode_step has reached k.
-    A manager that uses none of these steps exactly as before."""
+    A manager that uses none of these steps exactly as before.
+
+    Multi-step returns: trajectory_window(horizon, max_rows) opens the
+    manager's TrajectoryWindow, which follows every agent through the species
+    sort over up to `horizon` tables and computes lifelines, discounted returns
+    and GAE(lambda) advantages on the device (INTEGRATION.md "Multi-step
+    returns").  While one is open, a CPU-mode manager with growth on grows in
+    place (grow_capacity) rather than through a checkpoint hand-over, which
+    would leave the window behind."""
 
     def __init__(self, gpu_id, num_worlds, rand_seed, init_num_agents_per_world, *,
                  exec_mode="hip", agent_capacity=128, world_offset=0, reward_fixed=False,
@@ -458,6 +474,7 @@ class SimManager:
         self._fix_depth = bool(fix_depth_alias)
         self._ktiming = False
         self._gen = 0                # bumped when the columns' storage moves (a growth)
+        self._traj = None            # the open TrajectoryWindow, if any
         self._episode_length = int(episode_length)
         if not 0 <= self._episode_length < 2 ** 32:
             raise ValueError("episode_length must be in [0, 2^32)")
@@ -518,6 +535,11 @@ class SimManager:
         _check(_lib.mbots_max_population(self._h, ctypes.byref(v)))
         need = 2 * int(v.value) + self._cfg[3]
         if need <= self.agent_capacity:
+            return
+        if self._traj is not None:
+            # an open trajectory window lives in the native manager: grow that
+            # one in place (mbots_grow_capacity), which leaves the window intact
+            self.grow_capacity(_capacity_class(need))
             return
         blob = self.save_checkpoint()
         old = (self._hd, self._h, self.agent_capacity, self._cap_rows, self._views, self._gen)
@@ -676,6 +698,17 @@ class SimManager:
         start of a step (0: off)."""
         _check(_lib.mbots_set_episode_length(self._h, int(steps)))
         self._episode_length = int(steps)
+
+    # -- multi-step returns -------------------------------------------------
+    def trajectory_window(self, horizon, max_rows):
+        """Open the manager's trajectory window (mbots_traj_open): up to
+        `horizon` consecutive tables of up to `max_rows` rows each.  Returns a
+        TrajectoryWindow; one per manager, until its close()."""
+        if self._traj is not None:
+            raise RuntimeError("madrona_bots: the manager already holds a trajectory window")
+        _check(_lib.mbots_traj_open(self._h, int(horizon), int(max_rows)))
+        self._traj = TrajectoryWindow(self, int(horizon), int(max_rows))
+        return self._traj
 
     def set_action(self, agent_idx, forward, backward, rotate_left, rotate_right, shoot, breed):
         a = (ctypes.c_int32 * 6)(forward, backward, rotate_left, rotate_right, shoot, breed)
@@ -931,6 +964,124 @@ class SimManager:
         n = (ctypes.c_uint64 * len(KERNELS))()
         _check(_lib.mbots_kernel_times(self._h, ms, n))
         return {k: (ms[i], n[i]) for i, k in enumerate(KERNELS)}
+
+
+class TrajectoryWindow:
+    """Agent lifelines, returns and GAE(lambda) over up to `horizon`
+    consecutive tables (include/mbots.h "Trajectory window"), from
+    SimManager.trajectory_window().  push(value) after the constructor (the
+    initial table) or after a step() records the table's provenance, rewards,
+    world indices and the caller's value estimates; compute() returns, per
+    pushed table, the maps and sweeps as torch views of the window's storage.
+    The learner keeps its own per-step tensors (observations, log-probs) in each
+    step's row order and gathers them with "next" / lifelines()."""
+
+    LINK, NEXT, END, WORLD, REWARD, VALUE, ADV, RET = range(8)   # enum mbots_traj_view_id
+    END_NONE, END_DIED, END_RESET, END_WINDOW = range(4)
+    _KEYS = (("link", LINK), ("next", NEXT), ("end", END), ("world", WORLD), ("reward", REWARD),
+             ("value", VALUE), ("adv", ADV), ("ret", RET))
+
+    def __init__(self, mgr, horizon, max_rows):
+        self._mgr = weakref.ref(mgr)   # (the manager holds the window: no cycle)
+        self.horizon = horizon
+        self.max_rows = max_rows
+        self._last = None
+
+    def _live(self):
+        m = self._mgr() if self._mgr is not None else None
+        if m is None:
+            raise RuntimeError("madrona_bots: the trajectory window is closed")
+        return m
+
+    @property
+    def num_tables(self):
+        """Tables pushed since the last clear()."""
+        v = ctypes.c_uint32()
+        _check(_lib.mbots_traj_num_tables(self._live()._h, ctypes.byref(v)))
+        return v.value
+
+    def push(self, value=None):
+        """Record the current table (mbots_traj_push; no host synchronisation).
+        value: float32 [N] or [N, 1] on the manager's device in the table's row
+        order (the critic's estimate per row; a longer buffer's first N entries
+        are read), or None for zeros."""
+        m = self._live()
+        ptr = None
+        if value is not None:
+            if value.dtype != torch.float32 or value.device != m.device:
+                raise ValueError(f"value must be a float32 tensor on {m.device}")
+            value = value.reshape(-1).contiguous()
+            # the launch reads min(N, max_rows) values: a buffer of max_rows is
+            # always enough; a shorter one must hold the table's N (a host wait
+            # for the row count, which the learner's own reads already made)
+            if value.numel() < self.max_rows and value.numel() < m.num_agents():
+                raise ValueError(f"value holds {value.numel()} entries, the table {m.num_agents()} rows")
+            ptr = value.data_ptr()
+        _check(_lib.mbots_traj_push(m._h, ctypes.c_void_p(ptr), m._stream()))
+        self._last = None
+
+    def view(self, what, t):
+        """One column of table t as a [N_t, 1] torch view (mbots_traj_view)."""
+        m = self._live()
+        ct = _CTensor()
+        _check(_lib.mbots_traj_view(m._h, int(what), int(t), ctypes.byref(ct)))
+        return Tensor(m._hd, ct).to_torch()
+
+    def compute(self, gamma, lam=1.0, death_reward=0.0):
+        """mbots_traj_compute over the n pushed tables: {"rows": [N_0..N_{n-1}],
+        "link", "world", "reward", "value", "end", "adv", "ret": n tensors
+        [N_t, 1] each, "next": n - 1 tensors}, views of the window's storage
+        (valid until the next clear() / close(); a later compute() rewrites the
+        derived ones in place).  The one host synchronisation of the window."""
+        m = self._live()
+        rows = (ctypes.c_int64 * self.horizon)()
+        n = ctypes.c_uint32()
+        _check(_lib.mbots_traj_compute(m._h, float(gamma), float(lam), float(death_reward), rows,
+                                       ctypes.byref(n), m._stream()))
+        n = n.value
+        out = {"rows": [int(rows[t]) for t in range(n)]}
+        for key, what in self._KEYS:
+            out[key] = [self.view(what, t) for t in range(n - 1 if what == self.NEXT else n)]
+        self._last = out
+        return out
+
+    def lifelines(self, t0=0):
+        """int64 [n - t0, N_t0]: column j is agent j of table t0 followed
+        forward -- row k holds its row in table t0 + k, -1 from the step after
+        its end -- composed from the "next" maps of the last compute().  What a
+        recurrent learner gathers its own per-step tensors with."""
+        if self._last is None:
+            raise RuntimeError("madrona_bots: lifelines() follows a compute() of the pushed tables")
+        nxt, rows = self._last["next"], self._last["rows"]
+        n = len(rows)
+        if not 0 <= t0 < n:
+            raise ValueError(f"t0 must be in [0, {n})")
+        dev = self._live().device
+        cur = torch.arange(rows[t0], dtype=torch.int64, device=dev)
+        out = [cur]
+        for t in range(t0, n - 1):
+            alive = cur >= 0
+            step = torch.full_like(cur, -1)
+            if nxt[t].shape[0]:
+                step[alive] = nxt[t].reshape(-1).to(torch.int64)[cur[alive]]
+            cur = step
+            out.append(cur)
+        return torch.stack(out)
+
+    def clear(self, keep_last=False):
+        """Empty the window (mbots_traj_clear); keep_last: its newest table
+        becomes table 0 of the next window, so consecutive windows chain."""
+        _check(_lib.mbots_traj_clear(self._live()._h, 1 if keep_last else 0))
+        self._last = None
+
+    def close(self):
+        """Free the window (mbots_traj_close); its views must not be used
+        afterwards, and every later call on this object raises."""
+        m = self._live()
+        _check(_lib.mbots_traj_close(m._h))
+        m._traj = None
+        self._mgr = None
+        self._last = None
 
 
 class ScriptBotsViewer:

@@ -3,7 +3,8 @@
 # checkpoint save / load and mbots_max_population (tests/c_host/cap_asan.c) and
 # of the capacity growth in place with its retired lists
 # (tests/c_host/grow_asan.c, also under UndefinedBehaviorSanitizer) and of the
-# episode entry points (tests/c_host/reset_host.c, likewise) through the C ABI, against a libmbots built with -Xarch_host -fsanitize=address,undefined
+# episode entry points (tests/c_host/reset_host.c, likewise) and of the trajectory
+# window (tests/c_host/traj_host.c, likewise) through the C ABI, against a libmbots built with -Xarch_host -fsanitize=address,undefined
 # (the device code is not instrumented).
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
@@ -20,4 +21,7 @@ ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $d/
 /opt/rocm/llvm/bin/clang -g -fsanitize=address,undefined -std=c99 -I$ROOT/include $ROOT/tests/c_host/reset_host.c \
     -L$d -lmbots_asan -Wl,-rpath,$d -o $d/reset_host
 ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $d/reset_host
+/opt/rocm/llvm/bin/clang -g -fsanitize=address,undefined -std=c99 -I$ROOT/include $ROOT/tests/c_host/traj_host.c \
+    -L$d -lmbots_asan -Wl,-rpath,$d -o $d/traj_host
+ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $d/traj_host
 rm -rf $d

@@ -530,6 +530,64 @@ int mbots_traj_clear(mbots_handle *h, int32_t keep_last);
 int mbots_traj_num_tables(mbots_handle *h, uint32_t *out);
 int mbots_traj_view(mbots_handle *h, int32_t what, uint32_t t, mbots_tensor *out);
 
+/* Rasteriser: top-down images of chosen worlds, as they stand after the last
+ * step (or after create, load, reset-and-step, set_world_state or growth).  The
+ * reference's viewer (src/gfx) is out of scope; this is the picture without the
+ * window, and a per-world map tensor on the device with no host round trip.
+ *
+ * Image.  scale s in {1, 2, 4, 8} (else MBOTS_E_INVALID): H = 96 s rows by
+ * W = 128 s columns.  Pixel (row j, column i) is one point sample of the arena
+ * at px = (i + 0.5) / s, py = (j + 0.5) / s (exact in f32); row 0 is y ~ 0, no
+ * vertical flip.  Its class is the first rule that matches, every product and
+ * sum below one f32 rounding in the order written:
+ *   1. agent: the lowest live slot a (as mbots_world_state lists them) with
+ *      dx = px - x, dy = py - y, dx dx + dy dy <= 0.8464 (the sensor's disc of
+ *      radius 0.92).  With (hx, hy) the agent's heading, fa = dx hx + dy hy and
+ *      la = dy hx - dx hy, the pixel is a heading mark iff fa >= 0.3 and
+ *      |la| <= 0.25: class MBOTS_RENDER_MARK + species - 1, else
+ *      MBOTS_RENDER_BODY + species - 1.  The slot map holds a.
+ *   2. food: any live package, centre (X, Y) in cells and (c, s) the sensor's
+ *      cos / sin of its rotation, with |dx c + dy s| <= 1 and
+ *      |dy c - dx s| <= 1: MBOTS_RENDER_FOOD.
+ *   3. wall: the point lies in one of the four wall boxes (0.2 to either side
+ *      of the border): MBOTS_RENDER_WALL.  Sample points come within 0.2 of the
+ *      border only from scale 4 up (0.125 at scale 4, 0.25 at scale 2), so
+ *      scales 1 and 2 show no wall: point sampling, not a missing feature.
+ *   4. MBOTS_RENDER_FLOOR.
+ * The slot map is -1 wherever rule 1 did not match.  rgb is the 12 x 3 palette
+ * of mbots_render_palette indexed by class (entries 3 is unused and black),
+ * except that a body's channels are scaled by its health:
+ * k = 64 + 191 min(max(health, 0), 100) / 100, channel = base k / 255, both
+ * divisions truncating int32.  Both execution modes give the same bytes.
+ *
+ * mbots_render_worlds(h, worlds, k, scale, out, stream): image i is local
+ * world worlds[i] (host memory; any order, duplicates allowed; NULL: worlds
+ * 0 .. k-1, nothing is uploaded).  An index >= num_worlds -- the shard ghost's
+ * too, which is never rendered -- or k > num_worlds with a NULL list:
+ * MBOTS_E_RANGE, nothing written.  k == 0: MBOTS_OK.  out's arrays are memory
+ * of the manager's device (host memory in CPU mode), 4-byte aligned; any may
+ * be NULL, not all three (MBOTS_E_INVALID).  One kernel launch covers all k
+ * images; the call allocates nothing on the device except the list's staging
+ * buffer, which the handle keeps and grows on demand (a call with a list waits
+ * on the host only for the previous call's list upload, as mbots_reset_worlds
+ * does; never for a step).  Stream-ordered like every call: it follows the
+ * last step's world step, not its sensor, moves none of the step's deferred
+ * columns, and a later step cannot overwrite what a queued render reads.
+ * MBOTS_E_INVALID under stream capture (the list is uploaded from the host). */
+#define MBOTS_RENDER_FLOOR 0
+#define MBOTS_RENDER_WALL  1
+#define MBOTS_RENDER_FOOD  2
+#define MBOTS_RENDER_BODY  4   /* + species - 1: 4..7 */
+#define MBOTS_RENDER_MARK  8   /* + species - 1: 8..11 */
+typedef struct mbots_render_out {
+    uint8_t *cls;    /* [k][96 s][128 s]     class codes            */
+    int16_t *slot;   /* [k][96 s][128 s]     agent slot or -1       */
+    uint8_t *rgb;    /* [k][96 s][128 s][3]                         */
+} mbots_render_out;  /* any may be NULL, not all three; 4-byte aligned */
+int mbots_render_worlds(mbots_handle *h, const uint32_t *worlds /* NULL: worlds 0..k-1 */,
+                        uint32_t k, uint32_t scale, const mbots_render_out *out, void *stream);
+int mbots_render_palette(uint8_t rgb[36]);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That

@@ -608,6 +608,80 @@ void Sim::traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n)
         for (uint32_t q = 0; q < rows(t); ++q) traj_sweep(w, P, n, t, q);
 }
 
+// render_kernel's images on the host: the same predicates (mbots_render.hpp),
+// the agents of a row in ascending slots with the first hit final.  The image
+// rows of all k images are split over the threads.
+void Sim::render(const uint32_t *worlds, uint32_t k, uint32_t scale, const RenderOut &out) const
+{
+    const uint32_t Wp = (uint32_t)kRenderW * scale, Hp = (uint32_t)kRenderH * scale;
+    const float inv = 1.0f / (float)scale;
+    const uint64_t rows = (uint64_t)k * Hp;
+    auto work = [&](uint64_t lo, uint64_t hi) {
+        std::vector<RenderAgent> ag, hit;
+        float4 food[kMaxFood];
+        int nf = 0;
+        uint32_t cur = 0xFFFFFFFFu;
+        for (uint64_t g = lo; g < hi; ++g) {
+            const uint32_t img = (uint32_t)(g / Hp), j = (uint32_t)(g % Hp);
+            const uint32_t w = worlds ? worlds[img] : img;
+            if (img != cur) {   // stage the image's world: its agents and live food
+                cur = img;
+                const size_t base = (size_t)w * cap_;
+                const int n = std::min(n_[w], (int32_t)cap_);
+                ag.clear();
+                for (int a = 0; a < n; ++a)
+                    ag.push_back(render_agent((uint32_t)a, x_[base + a], y_[base + a], rw_[base + a], rz_[base + a],
+                                              species_[base + a], health_[base + a]));
+                nf = 0;
+                for (int c = 0; c < kNumChunks; ++c) {
+                    const uint64_t rec = food_[(size_t)w * kNumChunks + c];
+                    for (int q = 0; q < kMaxPkg; ++q) {
+                        if (!((rec >> (40 + q)) & 1u) || nf >= kMaxFood) continue;   // (<= 30 live: stage_food)
+                        const uint32_t xy = (uint32_t)(rec >> (8 * q)) & 0xFFu;
+                        const float2 cs = food_cs(food_rot_[((size_t)w * kMaxPkg + q) * kNumChunks + c]);
+                        food[nf++] = make_float4((float)(xy & 15u) + (float)((c % kChunksX) * kChunkW),
+                                                 (float)(xy >> 4) + (float)((c / kChunksX) * kChunkW), cs.x, cs.y);
+                    }
+                }
+            }
+            const float py = render_sample(j, inv);
+            hit.clear();
+            for (const RenderAgent &r : ag) {
+                const float dy = py - r.y;
+                if (dy * dy <= kAgentR2) hit.push_back(r);
+            }
+            const size_t pix0 = ((size_t)img * Hp + j) * Wp;
+            for (uint32_t i = 0; i < Wp; ++i) {
+                const float px = render_sample(i, inv);
+                uint32_t code = kRenderNoSlot;
+                for (const RenderAgent &r : hit) {
+                    const float dx = px - r.x, dy = py - r.y;
+                    if (render_disc_hit(dx, dy * dy)) {
+                        code = render_agent_code(r, dx, dy);
+                        break;
+                    }
+                }
+                if (code == kRenderNoSlot) code |= render_ground(px, py, food, nf) << 16;
+                if (out.cls) out.cls[pix0 + i] = (uint8_t)render_code_cls(code);
+                if (out.slot) out.slot[pix0 + i] = (int16_t)(uint16_t)(code & 0xFFFFu);
+                if (out.rgb) {
+                    const uint32_t c = render_code_rgb(code);
+                    uint8_t *o = out.rgb + (pix0 + i) * 3;
+                    o[0] = (uint8_t)c;
+                    o[1] = (uint8_t)(c >> 8);
+                    o[2] = (uint8_t)(c >> 16);
+                }
+            }
+        }
+    };
+    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(threads_, rows / 64));
+    if (T == 1) return work(0, rows);
+    std::vector<std::thread> th;
+    th.reserve(T);
+    for (unsigned t = 0; t < T; ++t) th.emplace_back(work, rows * t / T, rows * (t + 1) / T);
+    for (auto &t : th) t.join();
+}
+
 void Sim::step()
 {
     if (armed_) reset_pass();

@@ -12,6 +12,7 @@
 #include "../../include/mbots.h"
 #include "mbots_device.hpp"
 #include "mbots_traj.hpp"
+#include "mbots_render.hpp"
 
 #include <cstdint>
 #include <memory>
@@ -88,6 +89,10 @@ public:
     // null), and compute over the n pushed tables
     void traj_push(const TrajWin &w, uint32_t slot, const float *value) const;
     static void traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n);
+    // rasteriser (mbots_render.hpp; arguments already checked): image i of
+    // world worlds[i] (null: world i) into out's non-null arrays, the images
+    // split over the host threads
+    void render(const uint32_t *worlds, uint32_t k, uint32_t scale, const RenderOut &out) const;
     const mbots_config &config() const { return cfg_; }
 
 private:

@@ -105,6 +105,47 @@ MB_HD uint8_t depth_u8(float t)
 }
 
 // ---------------------------------------------------------------------------
+// The rasteriser's palette (mbots_render_worlds; DESIGN.md "Rasteriser"): one
+// 0xBBGGRR word per class code, shared by the kernel, the CPU mode and
+// mbots_render_palette.  Classes: 0 floor, 1 wall, 2 food, 3 unused, 4..7 the
+// body of species 1..4, 8..11 the heading mark of species 1..4 (white).
+// ---------------------------------------------------------------------------
+constexpr int kRenderClasses = 12;
+constexpr uint32_t kClsFloor = 0, kClsWall = 1, kClsFood = 2, kClsBody = 4, kClsMark = 8;
+constexpr uint32_t rgb_word(uint32_t r, uint32_t g, uint32_t b) { return r | (g << 8) | (b << 16); }
+
+MB_HD uint32_t render_palette(uint32_t cls)
+{
+    switch (cls) {
+    case 0: return rgb_word(16, 16, 20);       // floor
+    case 1: return rgb_word(128, 128, 128);    // wall
+    case 2: return rgb_word(40, 200, 60);      // food
+    case 4: return rgb_word(230, 60, 50);      // species 1: red
+    case 5: return rgb_word(60, 110, 240);     // species 2: blue
+    case 6: return rgb_word(240, 200, 40);     // species 3: yellow
+    case 7: return rgb_word(200, 70, 220);     // species 4: magenta
+    case 8: case 9: case 10: case 11: return rgb_word(255, 255, 255);   // heading marks
+    default: return 0u;
+    }
+}
+
+// a body's brightness from its health: k = 64 + 191 min(max(health, 0), 100) / 100
+MB_HD uint32_t render_shade(int32_t health)
+{
+    const int32_t hc = health < 0 ? 0 : health > 100 ? 100 : health;
+    return (uint32_t)(64 + (191 * hc) / 100);
+}
+
+// a pixel's 0xBBGGRR word: the palette entry, a body's channels scaled by k / 255
+MB_HD uint32_t render_rgb(uint32_t cls, uint32_t k)
+{
+    const uint32_t p = render_palette(cls);
+    if (cls < kClsBody || cls >= kClsMark) return p;
+    const uint32_t r = ((p & 255u) * k) / 255u, g = (((p >> 8) & 255u) * k) / 255u, b = ((p >> 16) * k) / 255u;
+    return rgb_word(r, g, b);
+}
+
+// ---------------------------------------------------------------------------
 // Wave-level helpers (wave64)
 // ---------------------------------------------------------------------------
 // a wave-uniform value in an SGPR: the compiler cannot prove that the world

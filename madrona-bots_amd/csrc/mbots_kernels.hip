@@ -26,6 +26,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "mbots_ray.hpp"
+#include "mbots_render.hpp"
 
 namespace mbots {
 
@@ -3389,6 +3390,238 @@ hipError_t launch_traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n
         hipLaunchKernelGGL(traj_next_scatter_kernel, dim3(bx, n - 1), dim3(256), 0, st, w);
     }
     hipLaunchKernelGGL(traj_sweep_kernel, dim3(bx, n), dim3(256), 0, st, w, P, n);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Rasteriser (mbots_render_worlds; the per-(pixel, object) predicates are
+// mbots_render.hpp's, shared with the CPU mode).  A 256-thread block owns a
+// band of whole image rows of one image -- kQuads * 1024 pixels, a contiguous
+// stretch of every output -- and a thread kQuads quads of 4 consecutive pixels
+// of one row (quad q * 256 + tid of the band), so a wave's stores are one
+// contiguous run of 4 (cls), 8 (slot) and 12 (rgb) bytes per lane.  A band is 8
+// rows (kQuads = scale) except at scale 1, where 32 rows (kRenderQuads1 = 4)
+// spread the block's fixed work -- the food staging, the barriers -- over four
+// times the pixels: 848 us against 1433 (8 rows), 989 (16), 950 (48) and 1511
+// (96, no cull left) for 65536 worlds' class maps (DESIGN.md "Rasteriser").
+//   Food: wave 0 stages the world's live packages once (stage_food: cos / sin
+// once per package) and keeps those that can reach the band; a quad tests only
+// those that can reach it.
+//   Agents, a gather in ascending slots: a pass examines kRenderStage = 256
+// slots, one per thread, and compacts those whose disc can reach the band into
+// LDS in slot order (wave ballots and the four waves' counts); then every
+// thread tests its pixels that no earlier slot has claimed against the staged
+// agents in order, and a hit is final -- the lowest slot, as the spec asks.  A
+// world of more than 256 agents takes further passes over the same pixels,
+// whose codes stay in registers (one word per pixel: slot, class, shade).
+//   6 KiB of LDS and kQuads * 4 code registers, so the block count per CU is
+// bounded by waves, not by LDS, in every capacity class.
+// ---------------------------------------------------------------------------
+constexpr int kRenderThreads = 256;
+constexpr int kRenderStage = 256;        // agent slots examined per pass
+constexpr int kRenderQuads1 = 4;         // quads per thread at scale 1
+static_assert(kRenderStage == kRenderThreads, "a pass stages one slot per thread");
+
+struct RenderLDS {
+    float ax[kRenderStage], ay[kRenderStage], hx[kRenderStage], hy[kRenderStage];
+    uint32_t info[kRenderStage];
+    float2 fobj[kMaxFood], frot[kMaxFood];   // stage_food's output: every live package
+    float4 food[kMaxFood];                   // those that can reach the band: X, Y, cos, sin
+    int nfood;
+    int wcount[kRenderThreads / 64];
+};
+
+// three dwords at a 4-byte aligned address (the outputs' guaranteed alignment)
+struct __attribute__((aligned(4))) RenderDw3 {
+    uint32_t a, b, c;
+};
+struct __attribute__((aligned(4))) RenderDw2 {
+    uint32_t a, b;
+};
+
+// kQuads: quads per thread; a band is kQuads * 1024 pixels = 8 kQuads / kScale rows
+template <int kScale, int kQuads>
+__global__ __launch_bounds__(kRenderThreads) void render_kernel(SimState S, const uint32_t *__restrict__ worlds,
+                                                                RenderOut out)
+{
+    __shared__ RenderLDS L;
+    constexpr uint32_t kW = kRenderW * kScale, kH = kRenderH * kScale;
+    constexpr uint32_t kQuadsPerRow = kW / 4;
+    constexpr uint32_t kRenderBandRows = (uint32_t)kQuads * kRenderThreads / kQuadsPerRow;
+    constexpr uint32_t kBands = kH / kRenderBandRows;
+    static_assert(kRenderBandRows * kQuadsPerRow == (uint32_t)kQuads * kRenderThreads && kBands * kRenderBandRows == kH,
+                  "bands of whole rows tile the image");
+    constexpr float kInv = 1.0f / (float)kScale;
+    const uint32_t img = blockIdx.x / kBands, band = blockIdx.x % kBands;
+    const uint32_t w = worlds ? worlds[img] : img;
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t row0 = band * kRenderBandRows;
+    const float ylo = render_sample(row0, kInv), yhi = render_sample(row0 + kRenderBandRows - 1, kInv);
+
+    if (wave == 0) {
+        uint64_t rec = 0ull;
+        uint32_t rot[kMaxPkg] = {};
+        if (lane < kNumChunks) {
+            rec = S.food[(size_t)w * kNumChunks + lane];
+#pragma unroll
+            for (int k = 0; k < kMaxPkg; ++k) rot[k] = S.food_rot[(size_t)w * kNumPkg + k * kNumChunks + lane];
+        }
+        const int nf = stage_food(rec, rot, lane, L.fobj, L.frot);
+        wave_sync();
+        bool keep = false;
+        float2 o = make_float2(0.0f, 0.0f), cs = o;
+        if ((int)lane < nf) {
+            o = L.fobj[lane];
+            cs = L.frot[lane];
+            keep = render_reaches(o.y, ylo, yhi, kRenderFoodReach);
+        }
+        const uint64_t m = ballot64(keep);
+        if (keep) L.food[rank_below(m)] = make_float4(o.x, o.y, cs.x, cs.y);
+        if (lane == 0) L.nfood = __popcll(m);
+    }
+
+    uint32_t code[kQuads][4];
+#pragma unroll
+    for (int q = 0; q < kQuads; ++q)
+#pragma unroll
+        for (int p = 0; p < 4; ++p) code[q][p] = kRenderNoSlot;
+
+    // every column of the first pass's slot in one batch of independent loads,
+    // without waiting for n (slots past n are stale and never used): a block's
+    // life is a chain of memory latencies, not arithmetic
+    const size_t base = (size_t)w * S.cap;
+    float x = 0.0f, y = 0.0f, rw = 1.0f, rz = 0.0f;
+    int32_t sp = 1, hp = 0;
+    const auto load = [&](int a) {
+        x = S.x[base + a];
+        y = S.y[base + a];
+        rw = S.rw[base + a];
+        rz = S.rz[base + a];
+        sp = S.species[base + a];
+        hp = S.health[base + a];
+    };
+    if (tid < S.cap) load((int)tid);
+    const int n = min(S.n[w], (int)S.cap);
+    for (int a0 = 0; a0 < n; a0 += kRenderStage) {
+        const int a = a0 + (int)tid;
+        if (a0 > 0 && a < n) load(a);
+        const bool keep = a < n && render_reaches(y, ylo, yhi, kRenderAgentReach);
+        const uint64_t m = ballot64(keep);
+        if (lane == 0) L.wcount[wave] = __popcll(m);
+        // (also: every thread has left the last pass's pixel loop before the
+        // stage is rewritten below)
+        __syncthreads();
+        int off = (int)rank_below(m), cnt = 0;
+#pragma unroll
+        for (uint32_t v = 0; v < kRenderThreads / 64; ++v) {
+            const int c = L.wcount[v];
+            off += v < wave ? c : 0;
+            cnt += c;
+        }
+        if (keep) {
+            const RenderAgent r = render_agent((uint32_t)a, x, y, rw, rz, sp, hp);
+            L.ax[off] = r.x;
+            L.ay[off] = r.y;
+            L.hx[off] = r.hx;
+            L.hy[off] = r.hy;
+            L.info[off] = r.info;
+        }
+        __syncthreads();
+        for (int e = 0; e < cnt; ++e) {
+            RenderAgent r;   // (the same address in every lane: LDS broadcasts)
+            r.x = L.ax[e];
+            r.y = L.ay[e];
+            r.hx = L.hx[e];
+            r.hy = L.hy[e];
+            r.info = L.info[e];
+#pragma unroll
+            for (int q = 0; q < kQuads; ++q) {
+                const uint32_t quad = (uint32_t)q * kRenderThreads + tid;
+                const uint32_t row = row0 + quad / kQuadsPerRow, col = (quad % kQuadsPerRow) * 4u;
+                const float dy = render_sample(row, kInv) - r.y, dy2 = dy * dy;
+                // (dx * dx + dy2 >= dy2: no pixel of the row otherwise; nor of a
+                // quad whose samples all lie more than 1 > kAgentR to one side)
+                const bool in_x = render_reaches(r.x, render_sample(col, kInv), render_sample(col + 3, kInv),
+                                                 kRenderAgentReach);
+                if ((dy2 <= kAgentR2) & in_x) {
+#pragma unroll
+                    for (int p = 0; p < 4; ++p) {
+                        const float dx = render_sample(col + p, kInv) - r.x;
+                        if (code[q][p] == kRenderNoSlot && render_disc_hit(dx, dy2))
+                            code[q][p] = render_agent_code(r, dx, dy);
+                    }
+                }
+            }
+        }
+    }
+    __syncthreads();   // the food list (a world without agents has met no barrier yet)
+
+    const int nf = L.nfood;
+    const size_t ibase = (size_t)img * ((size_t)kW * kH) + (size_t)row0 * kW;
+#pragma unroll
+    for (int q = 0; q < kQuads; ++q) {
+        const uint32_t quad = (uint32_t)q * kRenderThreads + tid;
+        const uint32_t row = row0 + quad / kQuadsPerRow, col = (quad % kQuadsPerRow) * 4u;
+        const float py = render_sample(row, kInv);
+        const float px0 = render_sample(col, kInv), px3 = render_sample(col + 3, kInv);
+        // render_ground for the quad: only the packages that can reach it
+        // (render_reaches, as for the band), the wall only where a sample can
+        // lie in it -- within 0.2 of the border: pixel indices 0 and 1 at most,
+        // and none at all below scale 4
+        bool food[4] = {false, false, false, false};
+        for (int k = 0; k < nf; ++k) {
+            const float4 f = L.food[k];
+            const bool in_y = render_reaches(f.y, py, py, kRenderFoodReach);
+            const bool in_x = render_reaches(f.x, px0, px3, kRenderFoodReach);
+            if (in_y & in_x) {
+#pragma unroll
+                for (int p = 0; p < 4; ++p) food[p] |= render_food_hit(render_sample(col + p, kInv), py, f.x, f.y, f.z, f.w);
+            }
+        }
+        constexpr bool kWallShows = 0.5f * kInv <= kInLo;
+        const bool edge = kWallShows && ((row < 2u) | (row + 2u >= kH) | (col == 0u) | (col + 4u == kW));
+        uint32_t cl[4], sl[4];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) {
+            uint32_t c = code[q][p];
+            if (c == kRenderNoSlot) {
+                const uint32_t g = food[p] ? kClsFood
+                                   : (edge && in_wall_box(render_sample(col + p, kInv), py)) ? kClsWall : kClsFloor;
+                c |= g << 16;
+                code[q][p] = c;
+            }
+            cl[p] = render_code_cls(c);
+            sl[p] = c & 0xFFFFu;
+        }
+        const size_t pix = ibase + (size_t)quad * 4u;
+        if (out.cls)
+            *reinterpret_cast<uint32_t *>(out.cls + pix) = cl[0] | (cl[1] << 8) | (cl[2] << 16) | (cl[3] << 24);
+        if (out.slot)
+            *reinterpret_cast<RenderDw2 *>(out.slot + pix) = RenderDw2{sl[0] | (sl[1] << 16), sl[2] | (sl[3] << 16)};
+        if (out.rgb) {
+            uint32_t rgb[4];
+#pragma unroll
+            for (int p = 0; p < 4; ++p) rgb[p] = render_code_rgb(code[q][p]);
+            *reinterpret_cast<RenderDw3 *>(out.rgb + pix * 3u) =
+                RenderDw3{rgb[0] | (rgb[1] << 24), (rgb[1] >> 8) | (rgb[2] << 16), (rgb[2] >> 16) | (rgb[3] << 8)};
+        }
+    }
+}
+
+hipError_t launch_render(const SimState &S, const uint32_t *worlds, uint32_t k, uint32_t scale, const RenderOut &out,
+                         hipStream_t st)
+{
+    if (!render_scale_ok(scale) || k == 0) return hipErrorInvalidValue;
+    const uint32_t quads = scale == 1 ? (uint32_t)kRenderQuads1 : scale;   // per thread
+    const uint64_t blocks = (uint64_t)k * (kRenderH * scale * (kRenderW * scale / 4) / (quads * kRenderThreads));
+    if (blocks >= (1ull << 31)) return hipErrorInvalidValue;
+    const dim3 grid((uint32_t)blocks), blk(kRenderThreads);
+    switch (scale) {
+    case 1: hipLaunchKernelGGL((render_kernel<1, kRenderQuads1>), grid, blk, 0, st, S, worlds, out); break;
+    case 2: hipLaunchKernelGGL((render_kernel<2, 2>), grid, blk, 0, st, S, worlds, out); break;
+    case 4: hipLaunchKernelGGL((render_kernel<4, 4>), grid, blk, 0, st, S, worlds, out); break;
+    default: hipLaunchKernelGGL((render_kernel<8, 8>), grid, blk, 0, st, S, worlds, out); break;
+    }
     return hipGetLastError();
 }
 

@@ -3,6 +3,7 @@
 
 #include "mbots_device.hpp"
 #include "mbots_traj.hpp"
+#include "mbots_render.hpp"
 #include "../../include/mbots.h"
 
 namespace mbots {
@@ -240,5 +241,11 @@ hipError_t launch_rebuild_learner(const RebuildPlan &p, const int32_t *src, uint
 hipError_t launch_traj_push(const SimState &S, const TrajWin &w, uint32_t slot, const float *reward,
                             const float *value, const int32_t *reset_mark, hipStream_t st);
 hipError_t launch_traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n, uint32_t max_count, hipStream_t st);
+
+// rasteriser (mbots_render.hpp): k images of 96 scale x 128 scale pixels in one
+// launch, image i of world worlds[i] (device memory; null: world i) as the
+// state stands in stream order; out's non-null arrays receive them
+hipError_t launch_render(const SimState &S, const uint32_t *worlds, uint32_t k, uint32_t scale, const RenderOut &out,
+                         hipStream_t st);
 
 }  // namespace mbots

@@ -94,6 +94,10 @@ struct mbots_handle {
     int32_t *flag_stage = nullptr;    // mbots_reset_worlds: pinned host / device staging of
     int32_t *flag_stage_dev = nullptr;   // one value per world, and the event after its last
     hipEvent_t ev_stage = nullptr;    // upload
+    uint32_t *render_list = nullptr;      // mbots_render_worlds: pinned host / device staging of
+    uint32_t *render_list_dev = nullptr;  // its world list (grown on demand), and the event
+    uint32_t render_list_cap = 0;         // after its last upload
+    hipEvent_t ev_render_list = nullptr;
     int32_t *sensor_index = nullptr;  // scratch for sensorIndexTensor
     uint32_t *h_totals = nullptr;     // pinned mirror of S.totals
     hipEvent_t ev_totals = nullptr;
@@ -1031,6 +1035,9 @@ int mbots_destroy(mbots_handle *h)
     if (h->flag_stage) (void)hipHostFree(h->flag_stage);
     if (h->flag_stage_dev) (void)hipFree(h->flag_stage_dev);
     if (h->ev_stage) (void)hipEventDestroy(h->ev_stage);
+    if (h->render_list) (void)hipHostFree(h->render_list);
+    if (h->render_list_dev) (void)hipFree(h->render_list_dev);
+    if (h->ev_render_list) (void)hipEventDestroy(h->ev_render_list);
     if (h->arena.base) (void)hipFree(h->arena.base);
     for (char *p : h->retired) (void)hipFree(p);
     delete h;
@@ -2480,6 +2487,84 @@ int mbots_set_episode_length(mbots_handle *h, uint32_t steps)
         if (int rc = arm(h, h->last_stream)) return rc;
     }
     h->ep_len = steps;
+    return MBOTS_OK;
+}
+
+// ---- rasteriser (include/mbots.h "Rasteriser"; DESIGN.md "Rasteriser") ----
+int mbots_render_palette(uint8_t rgb[36])
+{
+    if (!rgb) return fail(MBOTS_E_INVALID, "null argument");
+    for (uint32_t c = 0; c < (uint32_t)mbots::kRenderClasses; ++c) {
+        const uint32_t p = mbots::render_palette(c);
+        rgb[3 * c] = (uint8_t)p;
+        rgb[3 * c + 1] = (uint8_t)(p >> 8);
+        rgb[3 * c + 2] = (uint8_t)(p >> 16);
+    }
+    return MBOTS_OK;
+}
+
+int mbots_render_worlds(mbots_handle *h, const uint32_t *worlds, uint32_t k, uint32_t scale,
+                        const mbots_render_out *out, void *stream)
+{
+    if (!h || !out) return fail(MBOTS_E_INVALID, "null argument");
+    if (!out->cls && !out->slot && !out->rgb) return fail(MBOTS_E_INVALID, "mbots_render_worlds: no output asked for");
+    if (!mbots::render_scale_ok(scale))
+        return fail(MBOTS_E_INVALID, "mbots_render_worlds: scale " + std::to_string(scale) + " is not 1, 2, 4 or 8");
+    if (((uintptr_t)out->cls | (uintptr_t)out->slot | (uintptr_t)out->rgb) & 3u)
+        return fail(MBOTS_E_INVALID, "mbots_render_worlds: the outputs must be 4-byte aligned");
+    // (the shard ghost is world num_worlds: never rendered)
+    for (uint32_t i = 0; worlds && i < k; ++i)
+        if (worlds[i] >= h->cfg.num_worlds)
+            return fail(MBOTS_E_RANGE, "mbots_render_worlds: world " + std::to_string(worlds[i]) + " of " +
+                                           std::to_string(h->cfg.num_worlds));
+    if (!worlds && k > h->cfg.num_worlds)
+        return fail(MBOTS_E_RANGE, "mbots_render_worlds: " + std::to_string(k) + " worlds of " +
+                                       std::to_string(h->cfg.num_worlds));
+    if ((uint64_t)k * (mbots::kRenderH * scale) >= (1ull << 31))
+        return fail(MBOTS_E_INVALID, "mbots_render_worlds: too many images for one call");
+    if (k == 0) return MBOTS_OK;
+    const mbots::RenderOut ro{out->cls, out->slot, out->rgb};
+    if (h->cpu) {
+        h->cpu->render(worlds, k, scale, ro);
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = as_stream(stream);
+    if (capturing(st))
+        return fail(MBOTS_E_INVALID, "mbots_render_worlds cannot be captured into a graph (its world list is "
+                                     "uploaded from the host, and a replay would read the state halves the capture "
+                                     "recorded): render between replays");
+    if (int rc = use_stream(h, st)) return rc;
+    // In stream order the call follows the last step's K1 and K2 (on the
+    // swapped schedule the caller's stream joined them after K2) and runs
+    // beside its sensor, which writes nothing the kernel reads.  The next
+    // step's K1 and reset pass, which overwrite what it reads, start after
+    // everything enqueued here (the same stream, or ev_caller): no wait of its
+    // own is needed (DESIGN.md "Rasteriser").
+    const uint32_t *list = nullptr;
+    if (worlds) {
+        if (k > h->render_list_cap) {
+            // (rare: the last render may still read the old list)
+            HIP_TRY(hipDeviceSynchronize());
+            if (h->render_list) (void)hipHostFree(h->render_list);
+            if (h->render_list_dev) (void)hipFree(h->render_list_dev);
+            h->render_list = h->render_list_dev = nullptr;
+            h->render_list_cap = 0;
+            const uint32_t cap = std::max<uint32_t>(k, 64u);
+            HIP_TRY(hipHostMalloc((void **)&h->render_list, (size_t)cap * sizeof(uint32_t), hipHostMallocDefault));
+            HIP_TRY(hipMalloc((void **)&h->render_list_dev, (size_t)cap * sizeof(uint32_t)));
+            h->render_list_cap = cap;
+            if (!h->ev_render_list) HIP_TRY(hipEventCreateWithFlags(&h->ev_render_list, hipEventDisableTiming));
+        } else {
+            HIP_TRY(hipEventSynchronize(h->ev_render_list));   // the last upload has left the pinned list
+        }
+        memcpy(h->render_list, worlds, (size_t)k * sizeof(uint32_t));
+        HIP_TRY(hipMemcpyAsync(h->render_list_dev, h->render_list, (size_t)k * sizeof(uint32_t), hipMemcpyHostToDevice,
+                               st));
+        HIP_TRY(hipEventRecord(h->ev_render_list, st));
+        list = h->render_list_dev;
+    }
+    HIP_TRY(mbots::launch_render(h->S, list, k, scale, ro, st));
     return MBOTS_OK;
 }
 

@@ -12,6 +12,11 @@ GPU; like learn/env.py:12-15 the default picks cpu when no GPU is present).
 
     python madrona-bots_amd/harness/rollout.py --worlds 4096 --steps 100
     python madrona-bots_amd/harness/rollout.py --worlds 64 --exec-mode cpu
+    python madrona-bots_amd/harness/rollout.py --worlds 64 --steps 200 --frames run.npy --frame-world 3
+
+--frames PATH writes what one world looked like after each timed step: the
+uint8 [steps, H, W, 3] stack of SimManager.render_worlds images (a top-down
+RGB frame per step, rendered on the manager's device behind the step) as .npy.
 """
 import argparse
 import json
@@ -43,11 +48,32 @@ def construct_obs(sim, start, end, prev=False):
                       sim.surrounding_tensor(prev).to_torch()[start:end, :]), dim=1)
 
 
-def random_rollout(sim, steps, seed=1234, shift_per_species=False, device=None, fused=False):
+class FrameRecorder:
+    """One world's top-down RGB frame per step: record(t) renders the world as
+    it stands into row t of a [steps, H, W, 3] uint8 stack on the manager's
+    device (SimManager.render_worlds with out=: no allocation, no host
+    synchronisation); save(path) writes the stack as .npy."""
+
+    def __init__(self, sim, steps, world=0, scale=4):
+        self.sim, self.world, self.scale = sim, [int(world)], int(scale)
+        self.stack = torch.zeros((steps, 96 * self.scale, 128 * self.scale, 3), dtype=torch.uint8,
+                                 device=sim.device)
+
+    def record(self, t):
+        self.sim.render_worlds(self.world, self.scale, out={"rgb": self.stack[t:t + 1]})
+
+    def save(self, path):
+        import numpy as np
+        with open(path, "wb") as f:      # (np.save on a name appends ".npy")
+            np.save(f, self.stack.cpu().numpy())
+
+
+def random_rollout(sim, steps, seed=1234, shift_per_species=False, device=None, fused=False, after_step=None):
     """Random-action rollout (BASELINE config 2).  shift_per_species=True
     reproduces the reference's shift inside the species loop.
     fused=True builds the observation rows with sim.construct_obs (one kernel
-    for all species, sliced per species) instead of the 5-way torch.cat."""
+    for all species, sliced per species) instead of the 5-way torch.cat.
+    after_step(t), when given, runs right behind each step() (FrameRecorder.record)."""
     gen = torch.Generator(device=device if device is not None else "cpu").manual_seed(seed)
     stats = {"steps": 0, "agent_steps": 0, "step_s": 0.0, "obs_rows": 0}
     for t in range(steps):
@@ -56,6 +82,8 @@ def random_rollout(sim, steps, seed=1234, shift_per_species=False, device=None, 
         if device is not None and device.type == "cuda":
             torch.cuda.synchronize(device)
         stats["step_s"] += time.perf_counter() - t0
+        if after_step is not None:
+            after_step(t)
         offsets = species_offsets(sim)
         action = sim.action_tensor(False).to_torch()
         new_actions = []
@@ -181,6 +209,11 @@ def main():
     ap.add_argument("--fused", action="store_true", help="sim.construct_obs instead of torch.cat")
     ap.add_argument("--exec-mode", default="auto", choices=("auto", "hip", "cpu"),
                     help="auto: hip when a GPU is present, else cpu (learn/env.py:12-15)")
+    ap.add_argument("--frames", metavar="PATH", help="write one world's RGB frame per step as a "
+                                                     "[steps, H, W, 3] uint8 .npy")
+    ap.add_argument("--frame-world", type=int, default=0, help="the world --frames shows (default 0)")
+    ap.add_argument("--frame-scale", type=int, default=4, choices=(1, 2, 4, 8),
+                    help="pixels per cell of --frames (default 4: 384 x 512; the wall shows from 4 up)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import madrona_bots as mb
@@ -188,7 +221,10 @@ def main():
     dev = torch.device("cuda", 0) if mode == "hip" else torch.device("cpu")
     sim = mb.SimManager(0, a.worlds, a.seed, a.agents, exec_mode=mode)
     random_rollout(sim, 5, device=dev, fused=a.fused)
-    st = random_rollout(sim, a.steps, device=dev, fused=a.fused)
+    frames = FrameRecorder(sim, a.steps, a.frame_world, a.frame_scale) if a.frames else None
+    st = random_rollout(sim, a.steps, device=dev, fused=a.fused, after_step=frames.record if frames else None)
+    if frames:
+        frames.save(a.frames)
     # the reference's "Average FPS for simulator" = num_worlds / mean step time
     print(json.dumps({"worlds": a.worlds, "exec_mode": mode, "steps": st["steps"],
                       "world_steps_per_s": a.worlds * st["steps"] / st["step_s"],

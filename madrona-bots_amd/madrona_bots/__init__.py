@@ -28,7 +28,8 @@ import torch  # loads the HIP runtime libmbots.so links against (same soname)
 
 __all__ = ["SimManager", "ScriptBotsViewer", "Tensor", "madrona", "ExportID", "ExecMode", "unpack_rollout",
            "unpack_learner", "rebuild_learner", "CapacityWarning", "CapacityError", "MAX_CAPACITY",
-           "CAPACITY_CLASSES", "TrajectoryWindow"]
+           "CAPACITY_CLASSES", "TrajectoryWindow", "RENDER_PALETTE", "RENDER_SCALES", "CLS_FLOOR", "CLS_WALL",
+           "CLS_FOOD", "CLS_BODY", "CLS_MARK"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmbots.so")
@@ -50,6 +51,10 @@ class _Config(ctypes.Structure):
 class _LearnerOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in
                 ("obs", "prev_obs", "reward", "stats", "action", "hidden", "prev_hidden")]
+
+
+class _RenderOut(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_void_p) for k in ("cls", "slot", "rgb")]
 
 
 class _CTensor(ctypes.Structure):
@@ -111,6 +116,8 @@ def _load():
         "mbots_traj_clear": [vp, i32],
         "mbots_traj_num_tables": [vp, P(u32)],
         "mbots_traj_view": [vp, i32, u32, P(_CTensor)],
+        "mbots_render_worlds": [vp, vp, u32, u32, P(_RenderOut), vp],
+        "mbots_render_palette": [P(ctypes.c_uint8)],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -133,6 +140,22 @@ def _check(rc):
 _W_CAPACITY, _E_CAPACITY = 1, -5   # include/mbots.h MBOTS_W_CAPACITY / MBOTS_E_CAPACITY
 MAX_CAPACITY = 4096                # MBOTS_MAX_CAPACITY
 CAPACITY_CLASSES = (128, 256, 512, 1024, 2048, 4096)   # the kernels' slot classes
+
+
+# the rasteriser's class codes (include/mbots.h MBOTS_RENDER_*): a body is
+# CLS_BODY + species - 1 (4..7), a heading mark CLS_MARK + species - 1 (8..11)
+CLS_FLOOR, CLS_WALL, CLS_FOOD, CLS_BODY, CLS_MARK = 0, 1, 2, 4, 8
+RENDER_SCALES = (1, 2, 4, 8)
+RENDER_H, RENDER_W = 96, 128       # image rows / columns at scale 1
+
+
+def _render_palette():
+    import numpy as np
+    buf = (ctypes.c_uint8 * 36)()
+    _check(_lib.mbots_render_palette(buf))
+    pal = np.frombuffer(bytes(buf), dtype=np.uint8).reshape(12, 3).copy()
+    pal.setflags(write=False)
+    return pal
 
 
 def _capacity_class(need):
@@ -195,6 +218,8 @@ def _exec_mode(v):
         raise ValueError(f"unknown exec_mode {v}")
     return v
 
+
+RENDER_PALETTE = _render_palette()   # uint8 [12, 3]: RGB per class code (mbots_render_palette)
 
 OBS_DIM = 69   # learn/env.py:19
 # TK_* indices of mbots_kernel_times
@@ -894,6 +919,53 @@ class SimManager:
         _check(_lib.mbots_set_world_state(self._h, int(world_idx), ctypes.c_void_p(xyr.ctypes.data),
                                           len(xyr), ctypes.c_void_p(fd.ctypes.data), len(fd)))
 
+    def render_worlds(self, worlds=None, scale=4, *, rgb=True, cls=False, slot=False, out=None):
+        """Top-down images of `worlds` (local indices, any order, duplicates
+        allowed; None: every exported world) as they stand in stream order
+        (mbots_render_worlds; one kernel launch, no host synchronisation with
+        the step): a dict of tensors on the manager's device with the keys
+        asked for -- "rgb" uint8 [k, H, W, 3], "cls" uint8 [k, H, W] (CLS_*),
+        "slot" int16 [k, H, W] (the agent slot of world_state(), -1 none) --
+        H = 96 scale, W = 128 scale, scale in RENDER_SCALES, row 0 at y ~ 0.
+        `out`: a dict of contiguous tensors of those shapes to write into
+        (its keys select the outputs).  Scales 1 and 2 show no wall (the point
+        samples do not reach it); a critic's map is cls at scale 1."""
+        import numpy as np
+        scale = int(scale)
+        if worlds is None:
+            k, wptr, w = self.num_worlds, None, None
+        else:
+            if isinstance(worlds, torch.Tensor):
+                worlds = worlds.detach().cpu().numpy()
+            w = np.asarray(list(worlds) if not isinstance(worlds, np.ndarray) else worlds).reshape(-1)
+            if w.size and (w.min() < 0 or w.max() >= 2 ** 32):
+                raise ValueError("madrona_bots: world index out of range")
+            w = np.ascontiguousarray(w, dtype=np.uint32)
+            k, wptr = int(w.size), (w.ctypes.data if w.size else None)
+        H, W = RENDER_H * scale, RENDER_W * scale
+        spec = {"rgb": ((k, H, W, 3), torch.uint8), "cls": ((k, H, W), torch.uint8),
+                "slot": ((k, H, W), torch.int16)}
+        if out is None:
+            if scale not in RENDER_SCALES:
+                raise RuntimeError(f"madrona_bots: scale {scale} is not one of {RENDER_SCALES}")
+            want = [key for key, on in (("rgb", rgb), ("cls", cls), ("slot", slot)) if on]
+            out = {key: torch.empty(spec[key][0], dtype=spec[key][1], device=self.device) for key in want}
+        else:
+            for key, t in out.items():
+                if key not in spec:
+                    raise ValueError(f"out: unknown key {key!r}")
+                if t.dtype != spec[key][1] or tuple(t.shape) != spec[key][0] or t.device != self.device \
+                        or not t.is_contiguous():
+                    raise ValueError(f"out[{key!r}] must be a contiguous {spec[key][1]} {spec[key][0]} tensor "
+                                     f"on {self.device}")
+        ro = _RenderOut(**{key: (out[key].data_ptr() if key in out and out[key].numel() else None)
+                           for key in ("cls", "slot", "rgb")})
+        if k == 0 and out:
+            return out
+        _check(_lib.mbots_render_worlds(self._h, ctypes.c_void_p(wptr), k, scale, ctypes.byref(ro),
+                                        self._stream()))
+        return out
+
     def dump_worlds(self, path, worlds):
         """Write world_state() of each world in `worlds` to one .npz
         (keys "w<idx>/<field>") for offline inspection -- the build's
@@ -1094,8 +1166,9 @@ class ScriptBotsViewer:
     ScriptBotsViewer`` (learn/training_loop.py:8, learn/env_app.py:2,
     learn/app.py:1) -- and constructing it raises.  Headless training takes the
     training loop's other branch (``TrainLoopManager`` over ``SimManager``,
-    training_loop.py:15-26, :172-173); ``SimManager.world_state`` /
-    ``dump_worlds`` replace the viewer's readback for offline inspection."""
+    training_loop.py:15-26, :172-173); ``SimManager.render_worlds`` draws the
+    worlds without a window, ``SimManager.world_state`` / ``dump_worlds`` replace
+    the viewer's readback for offline inspection."""
 
     def __init__(self, gpu_id, num_worlds, rand_seed, init_num_agents_per_world, window_width,
                  window_height):

@@ -5,9 +5,9 @@ between steps -- shifts, Prev views, a capacity growth, chained windows, a
 second compute -- changes a bit.  4 worlds of 8 agents, windows of 7 to 12
 tables, under a breed- and shoot-heavy action stream chosen (seed and length,
 tests/traj_util.py) so that the window holds births, deaths and survivors,
-which every scenario asserts."""
-import ctypes
-
+which every scenario asserts.  The chained-window, second-compute, shard and
+error bodies are tests/traj_util.py's: tests/test_traj_gpu.py runs them on the
+device."""
 import numpy as np
 import pytest
 import torch
@@ -164,147 +164,20 @@ def test_auto_growth_mid_window_changes_nothing():
 
 
 def test_chained_windows_keep_every_transition():
-    """Two windows of 6 tables chained by clear(keep_last=True) hold the
-    transitions of one window of 11; with lambda 0 the advantages of those
-    transitions are the same bits too (no bootstrapping across the cut)."""
-    params = (0.99, 0.0, -1.0)
-    mgr, big = tu.scenario_plain(tu.cpu, True, steps=10)
-    whole = tu.to_numpy(big.compute(*params))
-    tu.assert_scenario(whole)
-    m2 = tu.cpu()
-    win = tu.run_window(m2, steps=5, horizon=6, with_values=True)
-    first = tu.to_numpy(win.compute(*params))
-    with pytest.raises(RuntimeError, match=r"status -1"):
-        win.push()                                            # full
-    win.clear(keep_last=True)
-    assert win.num_tables == 1
-    tu.run_window(m2, steps=5, with_values=True, win=win, first_table=False, t0=5)
-    second = tu.to_numpy(win.compute(*params))
-    for part, off in ((first, 0), (second, 5)):
-        assert part["rows"] == whole["rows"][off:off + 6]
-        for t in range(6):
-            for k in ("world", "reward", "value"):
-                assert np.array_equal(tu.bits(part[k][t]), tu.bits(whole[k][off + t])), (k, off, t)
-        for t in range(1, 6):
-            assert np.array_equal(part["link"][t], whole["link"][off + t])
-        for t in range(5):
-            for k in ("next", "end", "adv", "ret"):
-                assert np.array_equal(tu.bits(part[k][t]), tu.bits(whole[k][off + t])), (k, off, t)
+    tu.chained_windows_keep_every_transition(tu.cpu)
 
 
 def test_compute_twice_gives_the_same_bits(plain, plain_result):
     mgr, win = plain[True]
-    win.compute(*tu.PARAMS[0])
-    again = tu.to_numpy(win.compute(*tu.PARAMS[1]))
-    tu.assert_same(again, plain_result[True])
-
-
-def _gather(parts, counts):
-    """harness/gather.py's reassembly: species-major, per species rank-major.
-    parts[k]: rank k's rows, counts[k]: its rows per species."""
-    out = []
-    for s in range(4):
-        for x, c in zip(parts, counts):
-            lo = int(sum(c[:s]))
-            out.append(x[lo:lo + int(c[s])])
-    return np.concatenate(out)
+    tu.compute_twice_gives_the_same_bits(win, plain_result[True])
 
 
 def test_two_shards_equal_one_manager():
-    """Worlds 0-1 with the shard ghost and worlds 2-3 without, in one process,
-    on the identity-keyed synthetic stream (10 steps in, where the stream's
-    window holds births and deaths); value: each row's x position, an
-    identity-carried quantity every manager can hand over."""
-    pre = 10
-    mgrs = [tu.cpu(), tu.cpu(2, shard_ghost=True), tu.cpu(2, world_offset=2)]
-    wins, counts = [], [[], [], []]
-    for i, m in enumerate(mgrs):
-        for t in range(pre):
-            m.write_synthetic_actions(1234, t, False)
-            m.step()
-        win = m.trajectory_window(10, 4096)
-
-        def push(m=m, win=win, i=i):
-            win.push(m.position_tensor(False).to_torch()[:, 0].contiguous())
-            counts[i].append(m.species_count_tensor().to_torch().cpu().numpy().sum(0))
-        push()
-        for t in range(pre, pre + 9):
-            m.write_synthetic_actions(1234, t, False)
-            m.step()
-            push()
-        wins.append(win)
-    one, a, b = (tu.to_numpy(w.compute(*tu.PARAMS[1])) for w in wins)
-    tu.assert_scenario(one)
-    for t in range(10):
-        assert one["rows"][t] == a["rows"][t] + b["rows"][t]
-        assert a["rows"][t] == mgrs[1].num_agents() or t < 9      # the ghost's rows are not recorded
-        for k in ("world", "end", "adv", "ret"):
-            got = _gather([a[k][t], b[k][t]], [counts[1][t], counts[2][t]])
-            assert np.array_equal(tu.bits(got), tu.bits(one[k][t])), (k, t)
-        if t:
-            for part in (a, b):
-                assert (part["link"][t] < part["rows"][t - 1]).all(), t
-    assert mgrs[1].num_rows() > mgrs[1].num_agents()              # the ghost has rows of its own
+    tu.two_shards_equal_one_manager(tu.cpu)
 
 
 def test_errors_and_emptying():
-    import madrona_bots as mb
-    mgr = tu.cpu()
-    with pytest.raises(RuntimeError, match=r"status -1"):
-        mgr.trajectory_window(1, 64)
-    win = mgr.trajectory_window(4, 33)
-    with pytest.raises(RuntimeError):
-        mgr.trajectory_window(4, 64)                               # one per manager
-    with pytest.raises(RuntimeError, match=r"status -1"):
-        win.compute(0.9)                                           # empty
-    with pytest.raises(ValueError):
-        win.push(torch.zeros(3))                                   # fewer values than rows
-    win.push()
-    blob = mgr.save_checkpoint()
-    rows = [mgr.num_agents()]
-    for t in range(3):
-        mgr.write_actions(tu.breed_shoot(mgr.num_agents(), t).to(mgr.device))
-        mgr.step()
-        win.push()
-        rows.append(mgr.num_agents())
-    assert rows[-1] == 34 and max(rows[:3]) == 33                  # the last table is one row too many
-    with pytest.raises(RuntimeError, match=r"status -1"):
-        win.push()                                                 # full
-    for _ in range(2):                                             # ... and stays unusable
-        with pytest.raises(RuntimeError, match=r"status -4"):
-            win.compute(0.9)
-    with pytest.raises(RuntimeError):
-        win.view(win.END, 0)
-    win.clear()
-    assert win.num_tables == 0
-    mgr.load_checkpoint(blob)                                      # back to 32 rows
-    win.push()
-    mgr.write_actions(tu.breed_shoot(mgr.num_agents(), 0).to(mgr.device))
-    mgr.step()
-    win.push()
-    res = tu.to_numpy(win.compute(0.9))
-    assert res["rows"] == rows[:2]
-    tu.check_against_restatement(res, [np.zeros(tu.W, np.int32)] * 2, 0.9, 1.0, 0.0)
-    # a load and a set_world_state empty the window
-    mgr.load_checkpoint(blob)
-    assert win.num_tables == 0
-    win.push()
-    ws = mgr.world_state(0)
-    mgr.set_world_state(0, ws["position"], ws["rotation_wz"], ws["food"])
-    assert win.num_tables == 0
-    win.push()
-    win.compute(0.9)
-    with pytest.raises(RuntimeError, match=r"status -4"):
-        win.view(win.LINK, 1)                                      # table 1 is outside the window
-    # views after close are refused, by the object and by the library
-    h = mgr._h
-    win.close()
-    with pytest.raises(RuntimeError, match="closed"):
-        win.view(win.LINK, 0)
-    ct = mb._CTensor()
-    assert mb._lib.mbots_traj_view(h, 0, 0, ctypes.byref(ct)) == -1
-    assert mb._lib.mbots_traj_push(h, None, None) == -1
-    mgr.trajectory_window(4, 64).close()                           # and a new one can be opened
+    tu.errors_and_emptying(tu.cpu)
 
 
 def test_a_window_arms_nothing():

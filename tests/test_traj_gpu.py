@@ -2,7 +2,10 @@
 and traj_sweep_kernel of csrc/mbots_kernels.hip): HIP mode equals CPU mode
 bitwise on every view, in the scenarios of tests/test_traj_cpu.py, above the
 K1-finder mode's world count, and with the push and the compute on side
-streams.  The CPU mode is held against the numpy restatement there."""
+streams.  The CPU mode is held against the numpy restatement there.  The
+paths that file alone used to run -- the ring after clear(keep_last), a second
+compute, shards with world_offset and the ghost, a truncated table, emptying on
+load and set_world_state -- run here through the same bodies (traj_util)."""
 import numpy as np
 import pytest
 import torch
@@ -137,3 +140,35 @@ def test_push_and_compute_are_refused_under_capture():
         win.push()
         out = win.compute(0.99)
         assert out["rows"] == [64 * tu.A, mgr.num_agents()]
+
+
+# ---- the device halves of tests/test_traj_cpu.py's window paths (the bodies
+# are traj_util's, run there with the CPU-mode factory) ----------------------
+def test_chained_windows_keep_every_transition_on_device():
+    """The ring on the device: clear(keep_last) leaves base != 0 and the second
+    window's pushes and sweeps wrap around the slots."""
+    tu.chained_windows_keep_every_transition(tu.hip)
+
+
+def test_compute_twice_gives_the_same_bits_on_device():
+    """A second compute rewrites next / end / adv / ret in place: the third
+    result equals the first, and the numpy restatement."""
+    mgr, win = tu.scenario_plain(tu.hip, True)
+    first = tu.to_numpy(win.compute(*tu.PARAMS[1]))
+    again = tu.compute_twice_gives_the_same_bits(win, first)
+    tu.assert_scenario(again)
+    tu.check_against_restatement(again, [np.zeros(tu.W, np.int32)] * len(again["rows"]), *tu.PARAMS[1])
+
+
+def test_two_shards_equal_one_manager_on_device():
+    """world_offset in the push kernel's world column and in the sweep's mark
+    lookup, and the ghost's rows left out of the pushed table."""
+    tu.two_shards_equal_one_manager(tu.hip)
+
+
+def test_errors_and_emptying_on_device():
+    """A table of more rows than max_rows on the device: the push kernel's
+    r < lim guard keeps the neighbouring slot intact, compute refuses with
+    status -4 until the table has left; a load and set_world_state empty the
+    window."""
+    tu.errors_and_emptying(tu.hip)

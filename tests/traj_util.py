@@ -1,7 +1,10 @@
 """Helpers of the trajectory-window tests (test_traj_*.py): the action stream,
 a recorder that runs a manager through a window, and the numpy restatement of
 include/mbots.h "Trajectory window" the sweeps are held against."""
+import ctypes
+
 import numpy as np
+import pytest
 import torch
 
 W, A = 4, 8          # worlds, init_num_agents_per_world
@@ -256,3 +259,199 @@ def scenario_growth(make, capacity):
     win = run_window(mgr, steps=GROW_STEPS, with_values=True, t0=GROW_PRE,
                      actions=lambda n, t: (breed_turning if t < GROW_PRE + 4 else breed_shoot)(n, t))
     return mgr, win, cap0
+
+
+# ---- bodies both execution modes run (make: cpu or hip) --------------------
+def chained_windows_keep_every_transition(make):
+    """Two windows of 6 tables chained by clear(keep_last=True) hold the
+    transitions of one window of 11; with lambda 0 the advantages of those
+    transitions are the same bits too (no bootstrapping across the cut)."""
+    params = (0.99, 0.0, -1.0)
+    mgr, big = scenario_plain(make, True, steps=10)
+    whole = to_numpy(big.compute(*params))
+    assert_scenario(whole)
+    m2 = make()
+    win = run_window(m2, steps=5, horizon=6, with_values=True)
+    first = to_numpy(win.compute(*params))
+    with pytest.raises(RuntimeError, match=r"status -1"):
+        win.push()                                            # full
+    win.clear(keep_last=True)
+    assert win.num_tables == 1
+    run_window(m2, steps=5, with_values=True, win=win, first_table=False, t0=5)
+    second = to_numpy(win.compute(*params))
+    for part, off in ((first, 0), (second, 5)):
+        assert part["rows"] == whole["rows"][off:off + 6]
+        for t in range(6):
+            for k in ("world", "reward", "value"):
+                assert np.array_equal(bits(part[k][t]), bits(whole[k][off + t])), (k, off, t)
+        for t in range(1, 6):
+            assert np.array_equal(part["link"][t], whole["link"][off + t])
+        for t in range(5):
+            for k in ("next", "end", "adv", "ret"):
+                assert np.array_equal(bits(part[k][t]), bits(whole[k][off + t])), (k, off, t)
+
+
+def compute_twice_gives_the_same_bits(win, expected):
+    """A compute with the first parameter set, then one with the second on the
+    same pushed tables: `expected`, that window's result at the second set."""
+    win.compute(*PARAMS[0])
+    again = to_numpy(win.compute(*PARAMS[1]))
+    assert_same(again, expected)
+    return again
+
+
+def _gather(parts, counts):
+    """harness/gather.py's reassembly: species-major, per species rank-major.
+    parts[k]: rank k's rows, counts[k]: its rows per species."""
+    out = []
+    for s in range(4):
+        for x, c in zip(parts, counts):
+            lo = int(sum(c[:s]))
+            out.append(x[lo:lo + int(c[s])])
+    return np.concatenate(out)
+
+
+def two_shards_equal_one_manager(make):
+    """Worlds 0-1 with the shard ghost and worlds 2-3 without, in one process,
+    on the identity-keyed synthetic stream (10 steps in, where the stream's
+    window holds births and deaths); value: each row's x position, an
+    identity-carried quantity every manager can hand over."""
+    pre = 10
+    mgrs = [make(), make(2, shard_ghost=True), make(2, world_offset=2)]
+    wins, counts = [], [[], [], []]
+    for i, m in enumerate(mgrs):
+        for t in range(pre):
+            m.write_synthetic_actions(1234, t, False)
+            m.step()
+        win = m.trajectory_window(10, 4096)
+
+        def push(m=m, win=win, i=i):
+            win.push(m.position_tensor(False).to_torch()[:, 0].contiguous())
+            counts[i].append(m.species_count_tensor().to_torch().cpu().numpy().sum(0))
+        push()
+        for t in range(pre, pre + 9):
+            m.write_synthetic_actions(1234, t, False)
+            m.step()
+            push()
+        wins.append(win)
+    one, a, b = (to_numpy(w.compute(*PARAMS[1])) for w in wins)
+    assert_scenario(one)
+    for t in range(10):
+        assert one["rows"][t] == a["rows"][t] + b["rows"][t]
+        assert a["rows"][t] == mgrs[1].num_agents() or t < 9      # the ghost's rows are not recorded
+        for k in ("world", "end", "adv", "ret"):
+            got = _gather([a[k][t], b[k][t]], [counts[1][t], counts[2][t]])
+            assert np.array_equal(bits(got), bits(one[k][t])), (k, t)
+        if t:
+            for part in (a, b):
+                assert (part["link"][t] < part["rows"][t - 1]).all(), t
+    assert mgrs[1].num_rows() > mgrs[1].num_agents()              # the ghost has rows of its own
+    # world is global: the second shard's rows name worlds 2 and 3 only
+    assert all(set(np.unique(x)) <= {0, 1} for x in a["world"])
+    assert all(set(np.unique(x)) == {2, 3} for x in b["world"])
+
+
+def errors_and_emptying(make):
+    import madrona_bots as mb
+    mgr = make()
+    with pytest.raises(RuntimeError, match=r"status -1"):
+        mgr.trajectory_window(1, 64)
+    win = mgr.trajectory_window(4, 33)
+    with pytest.raises(RuntimeError):
+        mgr.trajectory_window(4, 64)                               # one per manager
+    with pytest.raises(RuntimeError, match=r"status -1"):
+        win.compute(0.9)                                           # empty
+    with pytest.raises(ValueError):
+        win.push(torch.zeros(3))                                   # fewer values than rows
+    win.push()
+    blob = mgr.save_checkpoint()
+    rows = [mgr.num_agents()]
+    for t in range(3):
+        mgr.write_actions(breed_shoot(mgr.num_agents(), t).to(mgr.device))
+        mgr.step()
+        win.push()
+        rows.append(mgr.num_agents())
+    assert rows[-1] == 34 and max(rows[:3]) == 33                  # the last table is one row too many
+    with pytest.raises(RuntimeError, match=r"status -1"):
+        win.push()                                                 # full
+    for _ in range(2):                                             # ... and stays unusable
+        with pytest.raises(RuntimeError, match=r"status -4"):
+            win.compute(0.9)
+    with pytest.raises(RuntimeError):
+        win.view(win.END, 0)
+    win.clear()
+    assert win.num_tables == 0
+    mgr.load_checkpoint(blob)                                      # back to 32 rows
+    win.push()
+    mgr.write_actions(breed_shoot(mgr.num_agents(), 0).to(mgr.device))
+    mgr.step()
+    win.push()
+    res = to_numpy(win.compute(0.9))
+    assert res["rows"] == rows[:2]
+    check_against_restatement(res, [np.zeros(W, np.int32)] * 2, 0.9, 1.0, 0.0)
+    # a load and a set_world_state empty the window
+    mgr.load_checkpoint(blob)
+    assert win.num_tables == 0
+    win.push()
+    ws = mgr.world_state(0)
+    mgr.set_world_state(0, ws["position"], ws["rotation_wz"], ws["food"])
+    assert win.num_tables == 0
+    win.push()
+    win.compute(0.9)
+    with pytest.raises(RuntimeError, match=r"status -4"):
+        win.view(win.LINK, 1)                                      # table 1 is outside the window
+    # views after close are refused, by the object and by the library
+    h = mgr._h
+    win.close()
+    with pytest.raises(RuntimeError, match="closed"):
+        win.view(win.LINK, 0)
+    ct = mb._CTensor()
+    assert mb._lib.mbots_traj_view(h, 0, 0, ctypes.byref(ct)) == -1
+    assert mb._lib.mbots_traj_push(h, None, None) == -1
+    mgr.trajectory_window(4, 64).close()                           # and a new one can be opened
+    truncated_table_leaves_its_neighbour(mgr, blob, rows)
+
+
+def truncated_table_leaves_its_neighbour(mgr, blob, rows):
+    """The same run (blob: its first table; rows: 32, .., 33, 34) through a
+    ring of 3 slots of 33 rows.  Tables 0 to 2 fill slots 0 to 2; after
+    clear(keep_last) the 34-row table goes into slot 0, whose row 33 would be
+    row 0 of slot 1.  Slot 1's pushed columns (still table 1's) must hold what
+    they held, compute must refuse with status -4 until the table has left the
+    window, and the window works again afterwards."""
+    mgr.load_checkpoint(blob)
+    win = mgr.trajectory_window(3, 33)
+    win.push(values_for(rows[0], 0).to(mgr.device))
+    for t in range(2):
+        mgr.write_actions(breed_shoot(mgr.num_agents(), t).to(mgr.device))
+        mgr.step()
+        win.push(values_for(rows[t + 1], t + 1).to(mgr.device))
+    win.compute(0.9)
+    keys = (("link", win.LINK), ("world", win.WORLD), ("reward", win.REWARD), ("value", win.VALUE))
+    slot1 = {k: win.view(what, 1) for k, what in keys}             # views of slot 1's storage
+    held = {k: v.detach().cpu().numpy().copy() for k, v in slot1.items()}
+    assert all(len(v) == rows[1] for v in held.values())
+    assert held["value"].any() and held["reward"].any() and (held["link"] != 0).any()
+    win.clear(keep_last=True)
+    mgr.write_actions(breed_shoot(mgr.num_agents(), 2).to(mgr.device))
+    mgr.step()
+    assert mgr.num_agents() == rows[3] == 34
+    v = torch.full((34,), 7.5)                                     # (no stored value or reward is 7.5)
+    win.push(v.to(mgr.device))
+    assert win.num_tables == 2
+    for _ in range(2):
+        with pytest.raises(RuntimeError, match=r"status -4"):
+            win.compute(0.9)
+    if mgr.device.type != "cpu":
+        torch.cuda.synchronize()
+    for k, v in slot1.items():
+        assert np.array_equal(bits(v.detach().cpu().numpy()), bits(held[k])), k
+    win.clear(keep_last=True)                                      # the truncated table is table 0 now
+    with pytest.raises(RuntimeError, match=r"status -4"):
+        win.compute(0.9)
+    win.clear()                                                    # ... and now it has left
+    mgr.load_checkpoint(blob)
+    win.push()
+    res = to_numpy(win.compute(0.9))
+    assert res["rows"] == [rows[0]] and (res["end"][0] == 3).all()
+    win.close()

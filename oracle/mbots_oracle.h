@@ -7,13 +7,28 @@
  * bench.py.  Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline
  * leg may load it.  The product (madrona-bots_amd/) never links or calls it.
  *
- * PARITY STATUS: "parity unpinned" for the arithmetic that lives in the
- * un-vendored Madrona submodule (RNG, quaternion math, raycast sensor, ECS
- * creation/sort order) -- the reference cannot be built or imported in this
- * container and ships no golden vectors.  Those
- * pieces follow the build's written spec.  Everything
- * else restates the cited reference lines; boundary shapes are pinned by the
- * reference checkpoints (obs width 69, action width 6: tests/golden/).
+ * PARITY STATUS.  The simulation part is held bitwise to the reference's own
+ * compiled sim.cpp, run on the stand-in engine of oracle/refbuild/
+ * (tests/test_reference_pin.py live, tests/golden/reference_*.npz recorded;
+ * DESIGN.md section 7).  The engine itself (the un-vendored Madrona submodule)
+ * stays the build's written spec, "parity unpinned":
+ *
+ *   pinned by the reference's compiled code | decided by the build's spec
+ *   ----------------------------------------+-----------------------------------
+ *   every expression, branch, constant and  | RNG (Threefry-2x32-20, key
+ *   cast of the step and shift systems      | schedule, sampleUniform, sampleI32)
+ *   RNG draw counts, the discarded draws    | quaternion arithmetic
+ *   the quirks ((uint32_t)(len*2.f), the    | iteration, creation and deletion
+ *   clamp order, health > 10 after +20,     | order; the observation sort
+ *   hitEnemy = hitFriendly, rewards[id],    | the consume contention outcome
+ *   SpeciesCount before the respawns)       | the memory behind rewards[4]
+ *   initWorld, makeAgent, the Sim           | the sensor and the finder
+ *   constructor's key                       | capacity; dead agents' rows (B.4),
+ *   the chunk helpers, FoodPackage::consume | new rows (B.13), the first export
+ *   the order of the step and shift graphs  | resets and episodes
+ *
+ * Boundary shapes are pinned by the reference checkpoints (obs width 69, action
+ * width 6: tests/golden/).
  *
  * RESETS AND EPISODES: the oracle restates them too, written from
  * INTEGRATION.md "Episodes and resets" and the reference's key schedule

@@ -5,7 +5,12 @@
 # (tests/c_host/grow_asan.c, also under UndefinedBehaviorSanitizer) and of the
 # episode entry points (tests/c_host/reset_host.c, likewise) and of the trajectory
 # window (tests/c_host/traj_host.c, likewise) through the C ABI, against a libmbots built with -Xarch_host -fsanitize=address,undefined
-# (the device code is not instrumented).
+# (the device code is not instrumented).  Where the reference's simulation
+# source lies on the machine (REF, default /root/reference), also a short
+# lock-step of the oracle with that source on the stand-in engine
+# (tests/c_host/ref_lockstep_asan.cpp; oracle/Makefile), all of it under both
+# sanitizers: the reference's read of rewards[4] must stay inside
+# the stand-in's own storage.
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 d=$(mktemp -d)
@@ -24,4 +29,13 @@ ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $d/
 /opt/rocm/llvm/bin/clang -g -fsanitize=address,undefined -std=c99 -I$ROOT/include $ROOT/tests/c_host/traj_host.c \
     -L$d -lmbots_asan -Wl,-rpath,$d -o $d/traj_host
 ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $d/traj_host
+REF=${REF:-/root/reference}
+if [ -f $REF/src/sim/sim.cpp ]; then
+    make -s -C $ROOT/oracle REF=$REF REF_OUT=$d/ref \
+        REF_EXTRA="-g -O1 -fsanitize=address,undefined -fno-sanitize-recover=undefined" \
+        $d/ref/ref_lockstep_asan
+    ASAN_OPTIONS=detect_leaks=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 $d/ref/ref_lockstep_asan
+else
+    echo "asan_host: no reference source at $REF: ref_lockstep_asan not run"
+fi
 rm -rf $d

@@ -22,6 +22,17 @@
    per-step digests only (the tables themselves would be ~35 MB).  Checked
    against the HIP path in tests/test_parity_horizon.py.
 
+4. reference_w8_a32_s69.npz, reference_w4_a32_s69_breed.npz,
+   reference_w4_a32_s69_shoot.npz -- what the REFERENCE's own simulation code
+   computed (its sim.cpp compiled against the stand-in engine of
+   oracle/refbuild/, `make -C oracle ref`), recorded from that side of a
+   lock-step run (tests/ref_lockstep.py): the same per-step digests and final
+   tables.  The sensor is outside that code, so the semantic and depth rows are
+   the oracle's, written into it; the species counts are counted from its agent
+   table (it exports them before the respawns).  Written only where
+   oracle/_ref/libmbots_ref.so exists.  tests/test_golden.py holds the oracle
+   and the CPU mode to them, tests/test_parity_gpu.py the device.
+
     python tests/golden/make_golden.py
 """
 import glob
@@ -84,6 +95,59 @@ def save_fixture(name, W, A, seed, steps, reward_fixed, cap):
             "cap": cap, "action_seed": 1234, "write_hidden": True, "log": log}
     np.savez_compressed(os.path.join(HERE, name + ".npz"), meta=json.dumps(meta), **arrays)
     print(f"{name}: {sim.num_agents()} agents after {steps} steps")
+
+
+# name, worlds, agents, seed, stream, steps (None: until a world passes 128 agents), cap for the replay
+REF_FIXTURES = [
+    ("reference_w8_a32_s69", 8, 32, 69, "synthetic", 24, 128),
+    ("reference_w4_a32_s69_breed", 4, 32, 69, "breed_heavy", None, 256),
+    ("reference_w4_a32_s69_shoot", 4, 32, 69, "shoot_heavy", 60, 128),
+]
+
+
+def save_reference_fixture(name, W, A, seed, stream, steps, cap):
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from golden_util import STREAMS
+    from ref_lockstep import LockStep
+    ls = LockStep(W, seed, A, cap=cap)
+    ref = ls.ref
+
+    def counts():
+        return np.array([np.bincount(ref.world_state(w)["species"], minlength=5)[1:] for w in range(W)], np.int32)
+
+    def digests():
+        out = {}
+        for i, nm in enumerate(NAMES):
+            out[nm] = digest(ref.column(i))
+            out["prev_" + nm] = digest(ref.column(i, True))
+        out["species_count"] = digest(counts())
+        return out
+
+    log = [("init", ref.num_agents(), digests())]
+    t = 0
+    while (t < steps) if steps is not None else (ls.peak_world <= 128):
+        if stream == "synthetic":
+            ls.synthetic(1234, True)
+        else:
+            ls.write_actions(STREAMS[stream](ref.num_agents(), t))
+        ls.step()
+        log.append((f"step{t}", ref.num_agents(), digests()))
+        ls.shift()
+        log.append((f"shift{t}", ref.num_agents(), digests()))
+        t += 1
+    assert ls.orc.overflow() == 0
+    arrays = {nm: ref.column(i) for i, nm in enumerate(NAMES)}
+    arrays.update({"prev_" + nm: ref.column(i, True) for i, nm in enumerate(NAMES)})
+    arrays["species_count"] = counts()
+    arrays["species_count_before_respawn"] = ref.species_count()
+    meta = {"worlds": W, "agents": A, "seed": seed, "steps": t, "reward_fixed": False, "cap": cap,
+            "action_seed": 1234, "write_hidden": True, "stream": stream, "log": log,
+            "side": "the reference's sim.cpp on the stand-in engine (oracle/refbuild), lock-step with the "
+                    "oracle; semantic and depth rows are the oracle's (the sensor is outside that code)",
+            "events": {k: int(getattr(ls, k)) for k in ("births", "deaths", "respawns", "friendly", "enemy", "ate",
+                                                        "peak_world")}}
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), meta=json.dumps(meta), **arrays)
+    print(f"{name}: {ref.num_agents()} agents after {t} steps, {meta['events']}")
 
 
 HORIZON = ("oracle_w4096_a32_s69_h120", 4096, 32, 69, 120)
@@ -174,6 +238,12 @@ def main():
     for fx in FIXTURES:
         save_fixture(*fx)
     save_horizon(*HORIZON)
+    import pyref
+    if pyref.available():
+        for fx in REF_FIXTURES:
+            save_reference_fixture(*fx)
+    else:
+        print("oracle/_ref/libmbots_ref.so is not built: the reference_*.npz fixtures are left as they are")
 
 
 if __name__ == "__main__":

@@ -134,43 +134,27 @@ def test_parity_lazy_shift_unobserved(shifts):
 # ---------------------------------------------------------------------------
 # golden fixtures (tests/golden, generated by the oracle) through the HIP path
 # ---------------------------------------------------------------------------
-@pytest.mark.parametrize("name", ["oracle_w4_a32_s69", "oracle_w8_a4_s7_fixed"])
+@pytest.mark.parametrize("name", ["oracle_w4_a32_s69", "oracle_w8_a4_s7_fixed", "reference_w8_a32_s69",
+                                  "reference_w4_a32_s69_breed", "reference_w4_a32_s69_shoot"])
 def test_hip_matches_golden_fixture(name):
+    """oracle_*: the oracle's recorded output.  reference_*: what the
+    reference's own simulation code recorded on the stand-in engine (the default
+    stream, a breed-heavy one that takes a world past 128 agents in the 256-slot
+    class, a shoot-heavy one); read from tests/golden/ only."""
     import madrona_bots as mb
-    from golden_util import load_fixture, table_digests
+    from golden_util import load_fixture, run_digests_manager
     meta, arrays = load_fixture(name)
     mgr = mb.SimManager(0, meta["worlds"], meta["seed"], meta["agents"],
                         agent_capacity=meta["cap"], reward_fixed=meta["reward_fixed"])
-    acc = {"species": "species_tensor", "pos": "position_tensor", "health": "health_tensor",
-           "surround": "surrounding_tensor", "reward": "reward_tensor",
-           "action": "action_tensor", "stats": "stats_tensor",
-           "hidden": "hidden_state_tensor", "semantic": "semantic_tensor"}
-
-    def get(nm, prev):
-        if nm == "depth":   # not exported without fix_depth_alias: reuse the oracle's
-            return np.zeros(0)
-        a = getattr(mgr, acc[nm])(prev).to_torch().cpu().numpy()
-        if nm == "health":
-            a = a.view(np.int32)
-        return a
-
-    def digests():
-        d = table_digests(get, mgr.species_count_tensor().to_torch().cpu().numpy())
-        return d
-
-    log = [["init", mgr.num_agents(), digests()]]
-    for t in range(meta["steps"]):
-        mgr.write_synthetic_actions(meta["action_seed"], t, meta["write_hidden"])
-        mgr.step()
-        log.append([f"step{t}", mgr.num_agents(), digests()])
-        mgr.shift_observations()
-        log.append([f"shift{t}", mgr.num_agents(), digests()])
+    log, get = run_digests_manager(mgr, meta)
+    assert len(log) == len(meta["log"])
     for (tag, n, dg), (tag2, n2, dg2) in zip(meta["log"], log):
         assert tag == tag2 and n == n2, (tag, n, n2)
         bad = [k for k in dg if "depth" not in k and dg[k] != dg2[k]]
         assert not bad, f"{name} {tag}: columns differ from golden: {bad}"
     for nm in ("species", "pos", "reward", "semantic"):
         assert np.array_equal(get(nm, False), arrays[nm])
+    assert mgr.overflow() == 0
 
 
 # ---------------------------------------------------------------------------

@@ -452,8 +452,10 @@ int mbots_set_episode_length(mbots_handle *h, uint32_t steps);
  *   MBOTS_TRAJ_WORLD   int32  the row's global world index
  * and, per world, whether the step that produced table t re-initialised it (an
  * armed manager's reset pass leaves the mark; an unarmed manager has none).
- * The window stores no observations: the learner keeps its own tensors in each
- * step's row order and gathers them with these maps.
+ * A window opened without flags stores no observations: the learner keeps its
+ * own tensors in each step's row order and gathers them with these maps (or
+ * has the window record and batch them: "Sequences for a recurrent learner"
+ * below).
  *
  * A manager holds at most one window; it is off until mbots_traj_open, and a
  * manager that never opens one enqueues in mbots_step exactly what it always
@@ -510,10 +512,91 @@ int mbots_set_episode_length(mbots_handle *h, uint32_t steps);
  * tables now in the window; else MBOTS_E_INVALID; t outside the window:
  * MBOTS_E_RANGE.  mbots_traj_close frees the window (after the device has
  * drained); every entry point but mbots_traj_open then returns
- * MBOTS_E_INVALID. */
+ * MBOTS_E_INVALID.
+ *
+ * Sequences for a recurrent learner (all opt-in: mbots_traj_open is
+ * mbots_traj_open_ex with flags 0, and such a window keeps its 32 bytes per
+ * row slot, its launches and its results).  mbots_traj_open_ex flags:
+ *   MBOTS_TRAJ_SEQ        two more int32 columns per row slot (+8 B),
+ *                         MBOTS_TRAJ_SEQ_ID and MBOTS_TRAJ_SEQ_POS (views 8, 9),
+ *                         and the calls below.  Either flag below implies it.
+ *   MBOTS_TRAJ_REC_OBS    each push also stores the row's rollout record -- the
+ *                         content of mbots_pack_rollout, 64 B or 96 B with
+ *                         MBOTS_FLAG_FIX_DEPTH_ALIAS -- in the ring slot
+ *                         ([max_rows] contiguous records).  That part of the push
+ *                         follows the step's sensor, as mbots_pack_rollout does;
+ *                         the link / reward / value / world part still follows
+ *                         the export of the rows only (two launches).
+ *   MBOTS_TRAJ_REC_STATE  each push also stores HiddenState (16 f32: what the
+ *                         learner wrote before the step, carried through the
+ *                         sort, zero for a newborn) and a one-byte mask of the
+ *                         Action that led into the row (bit i: Action[r][i] != 0),
+ *                         +65 B, read where mbots_pack_learner reads the two
+ *                         columns and behind the same waits.
+ * The recorded bytes live in the same ring: clear(keep_last) still moves
+ * nothing, the ghost's rows are never recorded, a truncated table is recorded
+ * truncated, growths leave everything intact.  With all flags a row slot takes
+ * 32 + 8 + 64 + 65 = 169 B (201 B with the real depth).
+ *
+ * A sequence is a maximal lifeline inside the n computed tables: it starts at
+ * (t0, q0) with t0 == 0 or no predecessor (LINK < 0 or not a row of table
+ * t0 - 1), follows NEXT and ends at the first row whose END != 0; rows of
+ * table n - 1 belong to their sequences (the bootstrap element).  Every row of
+ * every table lies in exactly one sequence.  Sequences are numbered 0 .. S - 1
+ * in ascending (t0, q0) order, whatever the scheduling.
+ *
+ * mbots_traj_sequences(h, S_out, stream) fills SEQ_ID (the row's sequence) and
+ * SEQ_POS (k = t - t0) for every row and returns S: the window's second host
+ * synchronisation.  MBOTS_E_INVALID without MBOTS_TRAJ_SEQ, without a compute
+ * of the tables now in the window, or under capture.  A later compute with
+ * other parameters leaves the sequences valid; a push or a clear does not.
+ *
+ * mbots_traj_batch(h, lo, hi, out, stream) materialises sequences [lo, hi),
+ * B = hi - lo, L = n of the last compute, start-aligned and time-major: element
+ * k of column b is the row of table t0[b] + k.  Every pointer of `out` may be
+ * NULL and is then skipped; the arrays are memory of the manager's device (host
+ * memory in CPU mode), 4-byte aligned:
+ *   rows       int32 [L, B]      the row in table t0[b] + k; -1 past the end
+ *   t0, len, end  int32 [B]      start table, length (1..L), END code of the
+ *                                last element (1, 2 or 3)
+ *   obs        f32 [L, B, 69]    mbots_construct_obs of the stored record, bit
+ *                                for bit (MBOTS_TRAJ_REC_OBS); 0.0 past the end
+ *   reward, value, adv, ret  f32 [L, B]  the window's columns; 0.0 past the end
+ *   action_in  uint8 [L, B]      the stored mask (MBOTS_TRAJ_REC_STATE); 0
+ *   hidden0    f32 [B, 16]       HiddenState stored at the start row
+ * No host synchronisation (when obs is asked for without both rows and t0, the
+ * missing part of the index goes to a scratch buffer the window grows on demand
+ * -- the caller's own array is still written --; a growth waits for the
+ * device).  A field whose flag is
+ * off, no mbots_traj_sequences of the tables now in the window, or stream
+ * capture: MBOTS_E_INVALID; hi > S or lo > hi: MBOTS_E_RANGE.
+ *
+ * mbots_traj_gather(h, lo, hi, tables, n_tables, row_bytes, out, stream): the
+ * same gather for the learner's own per-step tensors.  tables[t] (host array of
+ * n_tables == n pointers) is [N_t, row_bytes] on the manager's device,
+ * row_bytes a multiple of 4, at most 1024; out is [L, B, row_bytes], zero bytes
+ * past the end.  The pointer list is uploaded, stream-ordered, to a buffer the
+ * window owns.  Host waits: the index of a gather always goes to the window's
+ * scratch buffer, so the first call, and every call whose L * B + B exceeds
+ * what an earlier batch or gather needed, waits for the device and allocates;
+ * every later call waits only until the previous gather's pointer list has
+ * left its pinned staging (as mbots_render_worlds does for its list), never
+ * for a step.  Errors as for mbots_traj_batch. */
 enum mbots_traj_view_id {
     MBOTS_TRAJ_LINK = 0, MBOTS_TRAJ_NEXT = 1, MBOTS_TRAJ_END = 2, MBOTS_TRAJ_WORLD = 3,
-    MBOTS_TRAJ_REWARD = 4, MBOTS_TRAJ_VALUE = 5, MBOTS_TRAJ_ADV = 6, MBOTS_TRAJ_RET = 7
+    MBOTS_TRAJ_REWARD = 4, MBOTS_TRAJ_VALUE = 5, MBOTS_TRAJ_ADV = 6, MBOTS_TRAJ_RET = 7,
+    MBOTS_TRAJ_SEQ_ID = 8, MBOTS_TRAJ_SEQ_POS = 9
+};
+#define MBOTS_TRAJ_SEQ       1u
+#define MBOTS_TRAJ_REC_OBS   2u
+#define MBOTS_TRAJ_REC_STATE 4u
+struct mbots_traj_batch {   /* (a struct tag: the name is the call's too) */
+    int32_t *rows;                         /* [L, B] */
+    int32_t *t0, *len, *end;               /* [B] */
+    float *obs;                            /* [L, B, 69] */
+    float *reward, *value, *adv, *ret;     /* [L, B] */
+    uint8_t *action_in;                    /* [L, B] */
+    float *hidden0;                        /* [B, 16] */
 };
 #define MBOTS_TRAJ_END_NONE   0
 #define MBOTS_TRAJ_END_DIED   1
@@ -529,6 +612,11 @@ int mbots_traj_clear(mbots_handle *h, int32_t keep_last);
 /* tables pushed since the last clear (host state) */
 int mbots_traj_num_tables(mbots_handle *h, uint32_t *out);
 int mbots_traj_view(mbots_handle *h, int32_t what, uint32_t t, mbots_tensor *out);
+int mbots_traj_open_ex(mbots_handle *h, uint32_t horizon, uint64_t max_rows, uint32_t flags);
+int mbots_traj_sequences(mbots_handle *h, uint64_t *S_out /* may be NULL */, void *stream);
+int mbots_traj_batch(mbots_handle *h, uint64_t lo, uint64_t hi, const struct mbots_traj_batch *out, void *stream);
+int mbots_traj_gather(mbots_handle *h, uint64_t lo, uint64_t hi, const void *const *tables, uint32_t n_tables,
+                      uint32_t row_bytes, void *out, void *stream);
 
 /* Rasteriser: top-down images of chosen worlds, as they stand after the last
  * step (or after create, load, reset-and-step, set_world_state or growth).  The

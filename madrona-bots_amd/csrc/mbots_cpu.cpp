@@ -608,6 +608,67 @@ void Sim::traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n)
         for (uint32_t q = 0; q < rows(t); ++q) traj_sweep(w, P, n, t, q);
 }
 
+// launch_traj_sequences as loops: the starts counted per 256-row block, the
+// counts scanned in (table, block) order, then each start's offset + rank
+uint32_t Sim::traj_sequences(const TrajWin &w, uint32_t n, uint32_t max_count)
+{
+    auto rows = [&](uint32_t t) { return w.count[traj_slot(w, t)]; };
+    const uint32_t bx = std::max((max_count + kTrajBlock - 1u) / kTrajBlock, 1u);
+    for (uint32_t t = 0; t < n; ++t)
+        for (uint32_t b = 0; b < bx; ++b) {
+            uint32_t c = 0;
+            for (uint32_t q = b * kTrajBlock; q < std::min(rows(t), (b + 1u) * kTrajBlock); ++q)
+                c += traj_is_start(w, t, q) ? 1u : 0u;
+            w.blk[t * bx + b] = c;
+        }
+    uint32_t S = 0;
+    for (uint32_t i = 0; i < n * bx; ++i) {
+        const uint32_t c = w.blk[i];
+        w.blk[i] = S;
+        S += c;
+    }
+    for (uint32_t t = 0; t < n; ++t)
+        for (uint32_t b = 0; b < bx; ++b) {
+            uint32_t rank = 0;
+            for (uint32_t q = b * kTrajBlock; q < std::min(rows(t), (b + 1u) * kTrajBlock); ++q)
+                if (traj_is_start(w, t, q)) traj_seq_walk(w, n, t, q, w.blk[t * bx + b] + rank++);
+        }
+    return S;
+}
+
+// launch_traj_batch as loops (o.rows / o.t0 non-null whenever obs is)
+void Sim::traj_batch(const TrajWin &w, const TrajBatch &o, uint32_t lo, uint64_t B, uint32_t n, float *obs)
+{
+    if (B == 0) return;
+    const uint64_t R = (uint64_t)n * B;
+    if (o.rows) std::fill(o.rows, o.rows + R, -1);
+    for (float *p : {o.reward, o.value, o.adv, o.ret})
+        if (p) std::fill(p, p + R, 0.0f);
+    if (o.action_in) std::fill(o.action_in, o.action_in + R, (uint8_t)0);
+    for (uint32_t t = 0; t < n; ++t)
+        for (uint32_t q = 0; q < w.count[traj_slot(w, t)]; ++q) traj_batch_row(w, o, lo, B, t, q);
+    if (!obs) return;
+    const bool depth = w.rec_bytes > 64u;
+    for (uint64_t r = 0; r < R; ++r) {
+        const uint8_t *rec = traj_batch_record(w, o.rows, o.t0, B, r);
+        uint32_t *dst = reinterpret_cast<uint32_t *>(obs) + r * 69u;
+        for (uint32_t c = 0; c < 69u; ++c) dst[c] = rec ? traj_obs_bits(rec, depth, c) : 0u;
+    }
+}
+
+void Sim::traj_gather(const int32_t *rows, const int32_t *t0, uint64_t B, uint32_t n, const void *const *tables,
+                      uint32_t row_bytes, void *out)
+{
+    const uint64_t R = (uint64_t)n * B;
+    for (uint64_t o = 0; o < R; ++o) {
+        char *dst = static_cast<char *>(out) + o * row_bytes;
+        const int32_t q = rows[o];
+        if (q < 0) memset(dst, 0, row_bytes);
+        else memcpy(dst, static_cast<const char *>(tables[(uint32_t)t0[o % B] + (uint32_t)(o / B)]) + (size_t)q * row_bytes,
+                    row_bytes);
+    }
+}
+
 // render_kernel's images on the host: the same predicates (mbots_render.hpp),
 // the agents of a row in ascending slots with the first hit final.  The image
 // rows of all k images are split over the threads.

@@ -89,6 +89,10 @@ public:
     // null), and compute over the n pushed tables
     void traj_push(const TrajWin &w, uint32_t slot, const float *value) const;
     static void traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n);
+    static uint32_t traj_sequences(const TrajWin &w, uint32_t n, uint32_t max_count);   // returns S
+    static void traj_batch(const TrajWin &w, const TrajBatch &o, uint32_t lo, uint64_t B, uint32_t n, float *obs);
+    static void traj_gather(const int32_t *rows, const int32_t *t0, uint64_t B, uint32_t n,
+                            const void *const *tables, uint32_t row_bytes, void *out);
     // rasteriser (mbots_render.hpp; arguments already checked): image i of
     // world worlds[i] (null: world i) into out's non-null arrays, the images
     // split over the host threads

@@ -3394,6 +3394,217 @@ hipError_t launch_traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n
 }
 
 // ---------------------------------------------------------------------------
+// Sequences and batches of the trajectory window (mbots_traj_sequences,
+// mbots_traj_batch, mbots_traj_gather; element bodies in mbots_traj.hpp).
+// Numbering: the sequence starts of every 256-row block are counted (wave64
+// ballots and popcounts), one block scans the counts in (table, block) order,
+// and each start then takes its block's offset plus its rank in the block and
+// walks `next` forward.  No atomic decides an index, no block waits for
+// another, every loop is bounded by n.  A batch is one scatter of the rows
+// whose sequence lies in [lo, hi); its obs rows are decoded from the stored
+// records, gathered by index into LDS (unpack_rollout_kernel's shape with an
+// indexed source and zero rows for padding).
+// ---------------------------------------------------------------------------
+// the calling thread's rank among the block's starts; total: their number
+__device__ __forceinline__ uint32_t traj_start_rank(bool start, uint32_t *s_wave, uint32_t &total)
+{
+    const unsigned long long bal = __ballot(start);
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    if (lane == 0) s_wave[wv] = (uint32_t)__popcll(bal);
+    __syncthreads();
+    uint32_t before = 0;
+    total = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kTrajBlock / 64u; ++k) {
+        if (k < wv) before += s_wave[k];
+        total += s_wave[k];
+    }
+    return before + (uint32_t)__popcll(bal & ((1ull << lane) - 1ull));
+}
+// grid (x: 256-row blocks, y: tables 0 .. n - 1)
+__global__ __launch_bounds__(256) void traj_seq_count_kernel(TrajWin w)
+{
+    __shared__ uint32_t s_wave[kTrajBlock / 64u];
+    const uint32_t t = blockIdx.y, q = blockIdx.x * kTrajBlock + threadIdx.x;
+    const bool start = q < w.count[traj_slot(w, t)] && traj_is_start(w, t, q);
+    uint32_t total;
+    (void)traj_start_rank(start, s_wave, total);
+    if (threadIdx.x == 0) w.blk[t * gridDim.x + blockIdx.x] = total;
+}
+// one block: blk[0 .. M) becomes its exclusive scan, blk[tot] the total
+__global__ __launch_bounds__(1024) void traj_seq_scan_kernel(uint32_t *blk, uint32_t M, uint32_t tot)
+{
+    __shared__ uint32_t s_wave[16];
+    const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < M; base += 1024u) {
+        const uint32_t i = base + threadIdx.x;
+        const uint32_t v = i < M ? blk[i] : 0u;
+        uint32_t x = v;
+#pragma unroll
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t y = __shfl_up(x, d, 64);
+            if (lane >= d) x += y;
+        }
+        if (lane == 63u) s_wave[wv] = x;
+        __syncthreads();
+        uint32_t before = 0, total = 0;
+#pragma unroll
+        for (uint32_t k = 0; k < 16u; ++k) {
+            if (k < wv) before += s_wave[k];
+            total += s_wave[k];
+        }
+        if (i < M) blk[i] = carry + before + x - v;
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) blk[tot] = carry;
+}
+__global__ __launch_bounds__(256) void traj_seq_walk_kernel(TrajWin w, uint32_t n)
+{
+    __shared__ uint32_t s_wave[kTrajBlock / 64u];
+    const uint32_t t = blockIdx.y, q = blockIdx.x * kTrajBlock + threadIdx.x;
+    const bool start = q < w.count[traj_slot(w, t)] && traj_is_start(w, t, q);
+    uint32_t total;
+    const uint32_t rank = traj_start_rank(start, s_wave, total);
+    if (start) traj_seq_walk(w, n, t, q, w.blk[t * gridDim.x + blockIdx.x] + rank);
+}
+__global__ __launch_bounds__(256) void traj_batch_scatter_kernel(TrajWin w, TrajBatch o, uint32_t lo, uint64_t B)
+{
+    const uint32_t t = blockIdx.y, q = blockIdx.x * kTrajBlock + threadIdx.x;
+    if (q < w.count[traj_slot(w, t)]) traj_batch_row(w, o, lo, B, t, q);
+}
+
+// obs [L, B, 69] of a batch: output rows (k, b) in tiles of 64; each row's
+// record is gathered by index into LDS in 16-B granules (a record is
+// contiguous; padding: zeros, which decode to a zero row), then the tile's
+// 64 x 69 floats are written as coalesced 16-B streaming stores.  A partial
+// tile and an unaligned `out` take the scalar stores.
+__global__ __launch_bounds__(256) void traj_batch_obs_kernel(TrajWin w, const int32_t *rows, const int32_t *t0,
+                                                             uint64_t B, uint64_t R, float *out)
+{
+    constexpr int kW = kRolloutBytesDepth / 16;
+    __shared__ uint4 s_rec[kObsRows * kW];
+    __shared__ const uint4 *s_src[kObsRows];
+    const uint32_t gpr = w.rec_bytes / 16u;
+    const bool depth = w.rec_bytes == (uint32_t)kRolloutBytesDepth;
+    const uint64_t ntile = (R + kObsRows - 1) / kObsRows;
+    const uint32_t t = threadIdx.x;
+    const uint8_t *sb = reinterpret_cast<const uint8_t *>(s_rec);
+    auto val = [&](uint32_t i) {
+        const uint32_t r = i / kObsDim, c = i - r * kObsDim;
+        return traj_obs_bits(sb + (size_t)r * kW * 16, depth, c);
+    };
+    for (uint64_t b = blockIdx.x; b < ntile; b += gridDim.x) {
+        const uint64_t r0 = b * kObsRows;
+        const uint32_t nr = (uint32_t)min((uint64_t)kObsRows, R - r0);
+        if (t < nr) s_src[t] = reinterpret_cast<const uint4 *>(traj_batch_record(w, rows, t0, B, r0 + t));
+        __syncthreads();
+        for (uint32_t g = t; g < nr * gpr; g += 256) {
+            const uint32_t r = g / gpr, k = g - r * gpr;
+            const uint4 *src = s_src[r];
+            s_rec[r * kW + k] = src ? src[k] : make_uint4(0u, 0u, 0u, 0u);
+        }
+        __syncthreads();
+        float *o = out + r0 * kObsDim;
+        if (nr == (uint32_t)kObsRows && (reinterpret_cast<uintptr_t>(out) & 15u) == 0) {
+            for (uint32_t g = t; g < kObsRows * kObsDim / 4; g += 256)
+                st_stream(reinterpret_cast<uint4 *>(o) + g,
+                          make_uint4(val(4 * g), val(4 * g + 1), val(4 * g + 2), val(4 * g + 3)), MB_OBS_NT != 0);
+        } else {
+            for (uint32_t i = t; i < nr * kObsDim; i += 256) o[i] = __uint_as_float(val(i));
+        }
+        __syncthreads();
+    }
+}
+
+// the caller's per-table tensors along a batch: word c of output row (k, b)
+// from tables[t0[b] + k][rows[k][b]], zero for padding
+__global__ __launch_bounds__(256) void traj_gather_kernel(const int32_t *rows, const int32_t *t0, uint64_t B,
+                                                          uint64_t R, const uint32_t *const *tables, uint32_t words,
+                                                          uint32_t *out)
+{
+    const uint64_t total = R * words, stride = (uint64_t)gridDim.x * blockDim.x;
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const uint64_t o = i / words;
+        const uint32_t c = (uint32_t)(i - o * words);
+        const int32_t q = rows[o];
+        uint32_t v = 0u;
+        if (q >= 0) v = tables[(uint32_t)t0[o % B] + (uint32_t)(o / B)][(size_t)q * words + c];
+        out[i] = v;
+    }
+}
+
+// the push's opt-in state part (HiddenState and the Action mask of rows [0, N))
+__global__ __launch_bounds__(256) void traj_push_state_kernel(TrajWin w, uint32_t slot, const uint32_t *totals,
+                                                              const int32_t *action, const float *hidden)
+{
+    const uint32_t N = totals[0];
+    const uint32_t lim = N < w.max_rows ? N : w.max_rows;
+    const uint32_t g0 = blockIdx.x * blockDim.x + threadIdx.x, stride = gridDim.x * blockDim.x;
+    for (uint32_t r = g0; r < lim; r += stride) traj_push_mask(w, slot, r, action);
+    for (uint64_t g = g0; g < 4ull * lim; g += stride) traj_push_hidden(w, slot, (size_t)g, hidden);
+}
+
+hipError_t launch_traj_push_state(const SimState &S, const TrajWin &w, uint32_t slot, const ObsTable &t,
+                                  hipStream_t st)
+{
+    if (slot >= w.horizon || !w.hidden || !w.amask) return hipErrorInvalidValue;
+    const uint32_t blocks = (uint32_t)std::min<uint64_t>((4ull * w.max_rows + 255u) / 256u, 8192u);
+    hipLaunchKernelGGL(traj_push_state_kernel, dim3(blocks), dim3(256), 0, st, w, slot, S.totals, t.action, t.hidden);
+    return hipGetLastError();
+}
+
+hipError_t launch_traj_sequences(const TrajWin &w, uint32_t n, uint32_t max_count, hipStream_t st)
+{
+    if (n == 0 || n > w.horizon || max_count > w.max_rows || !w.seq_id) return hipErrorInvalidValue;
+    const uint32_t cap = (w.max_rows + kTrajBlock - 1u) / kTrajBlock;   // blk: [horizon][cap] and the total
+    const uint32_t bx = std::max((max_count + kTrajBlock - 1u) / kTrajBlock, 1u);
+    hipLaunchKernelGGL(traj_seq_count_kernel, dim3(bx, n), dim3(256), 0, st, w);
+    hipLaunchKernelGGL(traj_seq_scan_kernel, dim3(1), dim3(1024), 0, st, w.blk, n * bx, w.horizon * cap);
+    hipLaunchKernelGGL(traj_seq_walk_kernel, dim3(bx, n), dim3(256), 0, st, w, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_traj_batch(const TrajWin &w, const TrajBatch &o, uint32_t lo, uint64_t B, uint32_t n,
+                             uint32_t max_count, float *obs, hipStream_t st)
+{
+    if (n == 0 || n > w.horizon || max_count > w.max_rows || !w.seq_id) return hipErrorInvalidValue;
+    if (B == 0 || max_count == 0) return hipSuccess;
+    const uint64_t R = (uint64_t)n * B;
+    hipError_t e = hipSuccess;
+    auto fill = [&](void *p, int v, size_t bytes) {
+        if (p && e == hipSuccess) e = hipMemsetAsync(p, v, bytes, st);
+    };
+    fill(o.rows, 0xFF, R * 4);
+    fill(o.reward, 0, R * 4);
+    fill(o.value, 0, R * 4);
+    fill(o.adv, 0, R * 4);
+    fill(o.ret, 0, R * 4);
+    fill(o.action_in, 0, R);
+    if (e != hipSuccess) return e;
+    const uint32_t bx = (max_count + kTrajBlock - 1u) / kTrajBlock;
+    hipLaunchKernelGGL(traj_batch_scatter_kernel, dim3(bx, n), dim3(256), 0, st, w, o, lo, B);
+    if (obs) {
+        if (!w.rec || !o.rows || !o.t0) return hipErrorInvalidValue;
+        const unsigned blocks = (unsigned)std::min<uint64_t>((R + kObsRows - 1) / kObsRows, 16384);
+        hipLaunchKernelGGL(traj_batch_obs_kernel, dim3(blocks), dim3(256), 0, st, w, o.rows, o.t0, B, R, obs);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_traj_gather(const int32_t *rows, const int32_t *t0, uint64_t B, uint32_t n,
+                              const void *const *tables, uint32_t row_bytes, void *out, hipStream_t st)
+{
+    if (B == 0 || n == 0 || row_bytes == 0) return hipSuccess;
+    const uint64_t R = (uint64_t)n * B, total = R * (row_bytes / 4u);
+    const unsigned blocks = (unsigned)std::min<uint64_t>((total + 255) / 256, 16384);
+    hipLaunchKernelGGL(traj_gather_kernel, dim3(blocks), dim3(256), 0, st, rows, t0, B, R,
+                       reinterpret_cast<const uint32_t *const *>(tables), row_bytes / 4u, static_cast<uint32_t *>(out));
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
 // Rasteriser (mbots_render_worlds; the per-(pixel, object) predicates are
 // mbots_render.hpp's, shared with the CPU mode).  A 256-thread block owns a
 // band of whole image rows of one image -- kQuads * 1024 pixels, a contiguous

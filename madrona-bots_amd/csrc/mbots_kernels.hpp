@@ -241,6 +241,21 @@ hipError_t launch_rebuild_learner(const RebuildPlan &p, const int32_t *src, uint
 hipError_t launch_traj_push(const SimState &S, const TrajWin &w, uint32_t slot, const float *reward,
                             const float *value, const int32_t *reset_mark, hipStream_t st);
 hipError_t launch_traj_compute(const TrajWin &w, const TrajParams &P, uint32_t n, uint32_t max_count, hipStream_t st);
+// the window's opt-in parts: the push of HiddenState and the Action mask (`t`:
+// the current table as its readers see it); the numbering of the sequences of
+// the n computed tables (count, scan, walk; the total lands in
+// w.blk[horizon * ceil(max_rows / 256)]); a batch of the sequences
+// [lo, lo + B) -- padding fills, the scatter and, with `obs`, the record
+// decode, which reads o.rows / o.t0 --; and the gather of the caller's own
+// per-table rows (`tables`: n device pointers in device memory) along a
+// batch's rows / t0
+hipError_t launch_traj_push_state(const SimState &S, const TrajWin &w, uint32_t slot, const ObsTable &t,
+                                  hipStream_t st);
+hipError_t launch_traj_sequences(const TrajWin &w, uint32_t n, uint32_t max_count, hipStream_t st);
+hipError_t launch_traj_batch(const TrajWin &w, const TrajBatch &o, uint32_t lo, uint64_t B, uint32_t n,
+                             uint32_t max_count, float *obs, hipStream_t st);
+hipError_t launch_traj_gather(const int32_t *rows, const int32_t *t0, uint64_t B, uint32_t n,
+                              const void *const *tables, uint32_t row_bytes, void *out, hipStream_t st);
 
 // rasteriser (mbots_render.hpp): k images of 96 scale x 128 scale pixels in one
 // launch, image i of world worlds[i] (device memory; null: world i) as the

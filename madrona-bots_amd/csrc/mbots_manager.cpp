@@ -181,6 +181,17 @@ struct mbots_handle {
         bool computed = false;        // next / end / adv / ret are those of the n tables
         std::vector<int64_t> rows;    // N_t of table t < known
         uint32_t *h_count = nullptr;  // pinned staging of w.count (HIP mode)
+        // the opt-in parts (mbots_traj_open_ex)
+        uint32_t flags = 0;
+        bool seq_valid = false;       // SEQ_ID / SEQ_POS are those of the computed tables
+        uint32_t S = 0;               // their sequences
+        uint32_t mx = 0;              // the largest N_t of the computed tables
+        uint32_t *h_S = nullptr;      // pinned staging of S
+        int32_t *idx = nullptr;       // index scratch of a batch / gather ([L][B] rows, [B] t0) when the
+        uint64_t idx_cap = 0;         // caller gives no arrays of its own: grown on demand (int32 entries)
+        const void **tabs = nullptr;  // mbots_traj_gather's pointer list: the window's device buffer
+        const void **h_tabs = nullptr;   // ([horizon]), its pinned staging and the event after the
+        hipEvent_t ev_tabs = nullptr;    // last upload
     } traj;
     std::vector<char *> retired;      // arenas earlier growths left (views taken then still read
                                       // them): freed by mbots_release_retired / mbots_destroy
@@ -659,6 +670,26 @@ void traj_empty(mbots_handle *h)
     h->traj.n = h->traj.known = 0;
     h->traj.w.base = 0;
     h->traj.computed = false;
+    h->traj.seq_valid = false;
+}
+
+// everything a window holds beside its main allocation (HIP mode: after the
+// device has drained)
+void traj_free_extras(mbots_handle *h)
+{
+    auto &tj = h->traj;
+    if (h->cpu) {
+        std::free(tj.idx);
+    } else {
+        if (tj.idx) (void)hipFree(tj.idx);
+        if (tj.tabs) (void)hipFree((void *)tj.tabs);
+        if (tj.h_tabs) (void)hipHostFree((void *)tj.h_tabs);
+        if (tj.ev_tabs) (void)hipEventDestroy(tj.ev_tabs);
+    }
+    tj.idx = nullptr;
+    tj.idx_cap = 0;
+    tj.tabs = tj.h_tabs = nullptr;
+    tj.ev_tabs = nullptr;
 }
 
 }  // namespace
@@ -1014,6 +1045,7 @@ int mbots_destroy(mbots_handle *h)
     if (!h) return MBOTS_OK;
     if (h->cpu) {
         std::free(h->traj.mem);
+        traj_free_extras(h);
         delete h;
         return MBOTS_OK;
     }
@@ -1021,6 +1053,8 @@ int mbots_destroy(mbots_handle *h)
     (void)hipDeviceSynchronize();
     if (h->traj.mem) (void)hipFree(h->traj.mem);
     if (h->traj.h_count) (void)hipHostFree(h->traj.h_count);
+    if (h->traj.h_S) (void)hipHostFree(h->traj.h_S);
+    traj_free_extras(h);
     if (h->reset_mark) (void)hipFree(h->reset_mark);
     for (auto &p : h->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : h->pool) (void)hipEventDestroy(e);
@@ -2629,8 +2663,16 @@ int mbots_kernel_times(mbots_handle *h, double ms[MBOTS_TK_COUNT], uint64_t laun
 // ---- the trajectory window (include/mbots.h "Trajectory window") ----
 int mbots_traj_open(mbots_handle *h, uint32_t horizon, uint64_t max_rows)
 {
+    return mbots_traj_open_ex(h, horizon, max_rows, 0u);
+}
+
+int mbots_traj_open_ex(mbots_handle *h, uint32_t horizon, uint64_t max_rows, uint32_t flags)
+{
     if (!h) return fail(MBOTS_E_INVALID, "null handle");
     auto &tj = h->traj;
+    if (flags & ~(uint32_t)(MBOTS_TRAJ_SEQ | MBOTS_TRAJ_REC_OBS | MBOTS_TRAJ_REC_STATE))
+        return fail(MBOTS_E_INVALID, "unknown trajectory window flags");
+    if (flags & (MBOTS_TRAJ_REC_OBS | MBOTS_TRAJ_REC_STATE)) flags |= MBOTS_TRAJ_SEQ;   // (recorded to be batched)
     if (tj.open) return fail(MBOTS_E_INVALID, "the manager already holds a trajectory window: close it first");
     if (horizon < 2 || horizon > 65535u) return fail(MBOTS_E_INVALID, "horizon must be in [2, 65535]");
     if (max_rows == 0 || max_rows >= (1ull << 31)) return fail(MBOTS_E_INVALID, "max_rows must be in [1, 2^31)");
@@ -2638,7 +2680,15 @@ int mbots_traj_open(mbots_handle *h, uint32_t horizon, uint64_t max_rows)
     auto pad = [](size_t b) { return (b + 255) & ~size_t(255); };
     const size_t col = pad((size_t)horizon * max_rows * 4), marks = pad((size_t)horizon * Wx * 4),
                  counts = pad((size_t)horizon * 4);
-    const size_t bytes = 8 * col + marks + counts;
+    // the opt-in parts follow the flagless layout, which stays as it is
+    const bool seq = (flags & MBOTS_TRAJ_SEQ) != 0, rec_obs = (flags & MBOTS_TRAJ_REC_OBS) != 0,
+               rec_state = (flags & MBOTS_TRAJ_REC_STATE) != 0;
+    const uint32_t rec_bytes = (h->cfg.flags & MBOTS_FLAG_FIX_DEPTH_ALIAS) ? MBOTS_ROLLOUT_BYTES_DEPTH : MBOTS_ROLLOUT_BYTES;
+    const size_t slots = (size_t)horizon * max_rows;
+    const size_t blks = pad(((size_t)horizon * ((max_rows + mbots::kTrajBlock - 1) / mbots::kTrajBlock) + 1) * 4),
+                 recs = pad(slots * rec_bytes), hid = pad(slots * mbots::kTrajHidden * 4), masks = pad(slots);
+    const size_t bytes = 8 * col + marks + counts + (seq ? 2 * col + blks : 0) + (rec_obs ? recs : 0) +
+                         (rec_state ? hid + masks : 0);
     char *mem = nullptr;
     if (h->cpu) {
         mem = static_cast<char *>(std::calloc(bytes, 1));
@@ -2653,6 +2703,7 @@ int mbots_traj_open(mbots_handle *h, uint32_t horizon, uint64_t max_rows)
         hipError_t e = hipMemset(mem, 0, bytes);
         if (e == hipSuccess && !tj.h_count)
             e = hipHostMalloc((void **)&tj.h_count, 65535u * sizeof(uint32_t), hipHostMallocDefault);
+        if (e == hipSuccess && seq && !tj.h_S) e = hipHostMalloc((void **)&tj.h_S, sizeof(uint32_t), hipHostMallocDefault);
         if (e != hipSuccess) {
             (void)hipFree(mem);
             return fail(MBOTS_E_HIP, std::string("trajectory window: ") + hipGetErrorString(e));
@@ -2667,6 +2718,23 @@ int mbots_traj_open(mbots_handle *h, uint32_t horizon, uint64_t max_rows)
     w.adv = (float *)take(col);     w.ret = (float *)take(col);
     w.mark = (int32_t *)take(marks);
     w.count = (uint32_t *)take(counts);
+    w.seq_id = w.seq_pos = nullptr;
+    w.blk = nullptr;
+    w.rec = nullptr;
+    w.hidden = nullptr;
+    w.amask = nullptr;
+    if (seq) {
+        w.seq_id = (int32_t *)take(col);
+        w.seq_pos = (int32_t *)take(col);
+        w.blk = (uint32_t *)take(blks);
+    }
+    if (rec_obs) w.rec = (uint8_t *)take(recs);
+    if (rec_state) {
+        w.hidden = (float *)take(hid);
+        w.amask = (uint8_t *)take(masks);
+    }
+    w.rec_bytes = rec_bytes;
+    tj.flags = flags;
     w.horizon = horizon;
     w.max_rows = (uint32_t)max_rows;
     w.Wx = Wx;
@@ -2691,6 +2759,8 @@ int mbots_traj_close(mbots_handle *h)
         HIP_TRY(hipDeviceSynchronize());   // its last push / compute, on whatever stream
         HIP_TRY(hipFree(tj.mem));
     }
+    traj_free_extras(h);
+    tj.flags = 0;
     tj.mem = nullptr;
     tj.w = mbots::TrajWin{};
     tj.open = false;
@@ -2709,6 +2779,18 @@ int mbots_traj_push(mbots_handle *h, const float *value, void *stream)
     const uint32_t slot = mbots::traj_slot(tj.w, tj.n);
     if (h->cpu) {
         h->cpu->traj_push(tj.w, slot, value);
+        const mbots::cpu::Table &t = h->cpu->table();
+        const uint32_t lim = std::min<uint32_t>(h->cpu->num_agents(), tj.w.max_rows);
+        if (tj.w.rec) {
+            const bool fixd = (h->cfg.flags & MBOTS_FLAG_FIX_DEPTH_ALIAS) != 0;
+            pack_rollout_host(t.sem.data(), fixd ? t.depth.data() : nullptr, t.health.data(), t.pos.data(),
+                              t.sur.data(), t.reward.data(), t.stats.data(), lim,
+                              tj.w.rec + (size_t)slot * tj.w.max_rows * tj.w.rec_bytes);
+        }
+        if (tj.w.hidden) {
+            for (uint32_t r = 0; r < lim; ++r) mbots::traj_push_mask(tj.w, slot, r, t.action.data());
+            for (size_t g = 0; g < (size_t)4 * lim; ++g) mbots::traj_push_hidden(tj.w, slot, g, t.hidden.data());
+        }
         tj.rows[tj.n] = tj.w.count[slot];
         tj.known = tj.n + 1;
     } else {
@@ -2721,9 +2803,32 @@ int mbots_traj_push(mbots_handle *h, const float *value, void *stream)
         // after the step's K3a (this stream's order), which wrote the
         // provenance and the Reward column; not after its sensor
         HIP_TRY(mbots::launch_traj_push(h->S, tj.w, slot, h->T[h->tb].reward, value, h->reset_mark, st));
+        int rc;
+        if (tj.w.hidden) {
+            // Action / HiddenState where mbots_pack_learner reads them: the step's
+            // deferred move of the two, then the sensor (and what it moved)
+            const int owed = pending_mask(h);
+            if ((rc = materialize_cur_ah(h, st, 3))) return rc;
+            note_use(h, mbots::kMoveAH, owed);
+        }
+        if (tj.w.hidden || tj.w.rec) {
+            if ((rc = wait_sensor(h, st))) return rc;   // the semantic / depth rows come from K3b
+        }
+        // (timed like mbots_pack_rollout / mbots_pack_learner: mbots_kernel_times sees them)
+        if (tj.w.rec && (rc = timed(h, MBOTS_TK_OBS, st, [&] {
+                return mbots::launch_pack_rollout(h->S, h->T[h->tb],
+                                                  tj.w.rec + (size_t)slot * tj.w.max_rows * tj.w.rec_bytes,
+                                                  tj.w.max_rows, st);
+            })))
+            return rc;
+        if (tj.w.hidden && (rc = timed(h, MBOTS_TK_OBS, st, [&] {
+                return mbots::launch_traj_push_state(h->S, tj.w, slot, h->T[h->tb], st);
+            })))
+            return rc;
     }
     ++tj.n;
     tj.computed = false;
+    tj.seq_valid = false;
     return MBOTS_OK;
 }
 
@@ -2761,6 +2866,7 @@ int mbots_traj_compute(mbots_handle *h, float gamma, float lambda, float death_r
                                        std::to_string(tj.w.max_rows) + ": clear the window (or reopen it larger)");
     }
     tj.known = tj.n;
+    tj.mx = mx;
     volatile float gl = gamma * lambda;   // rounded once
     const mbots::TrajParams P{gamma, gl, death_reward};
     if (h->cpu) mbots::cpu::Sim::traj_compute(tj.w, P, tj.n);
@@ -2786,6 +2892,7 @@ int mbots_traj_clear(mbots_handle *h, int32_t keep_last)
     tj.rows[0] = rows_last;
     tj.known = known ? 1u : 0u;
     tj.computed = false;
+    tj.seq_valid = false;
     return MBOTS_OK;
 }
 
@@ -2815,6 +2922,13 @@ int mbots_traj_view(mbots_handle *h, int32_t what, uint32_t t, mbots_tensor *out
     case MBOTS_TRAJ_END: col = w.end; derived = true; break;
     case MBOTS_TRAJ_ADV: col = w.adv; dtype = MBOTS_DTYPE_FLOAT32; derived = true; break;
     case MBOTS_TRAJ_RET: col = w.ret; dtype = MBOTS_DTYPE_FLOAT32; derived = true; break;
+    case MBOTS_TRAJ_SEQ_ID: case MBOTS_TRAJ_SEQ_POS:
+        if (!w.seq_id) return fail(MBOTS_E_INVALID, "the window was opened without MBOTS_TRAJ_SEQ");
+        if (t < tj.n && !tj.seq_valid)
+            return fail(MBOTS_E_INVALID, "seq_id / seq_pos exist after mbots_traj_sequences of the computed tables");
+        col = what == MBOTS_TRAJ_SEQ_ID ? w.seq_id : w.seq_pos;
+        derived = true;
+        break;
     default: return fail(MBOTS_E_INVALID, "unknown trajectory view " + std::to_string(what));
     }
     if (t >= tj.n || (what == MBOTS_TRAJ_NEXT && t + 1 >= tj.n))
@@ -2828,6 +2942,139 @@ int mbots_traj_view(mbots_handle *h, int32_t what, uint32_t t, mbots_tensor *out
     out->device = h->cpu ? -1 : h->device;
     out->dims[0] = tj.rows[t];
     out->dims[1] = 1;
+    return MBOTS_OK;
+}
+
+int mbots_traj_sequences(mbots_handle *h, uint64_t *S_out, void *stream)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    auto &tj = h->traj;
+    if (!tj.open) return fail(MBOTS_E_INVALID, "no trajectory window is open");
+    if (!tj.w.seq_id) return fail(MBOTS_E_INVALID, "the window was opened without MBOTS_TRAJ_SEQ");
+    if (!tj.computed)
+        return fail(MBOTS_E_INVALID, "mbots_traj_sequences follows an mbots_traj_compute of the tables now in the window");
+    if (h->cpu) {
+        tj.S = mbots::cpu::Sim::traj_sequences(tj.w, tj.n, tj.mx);
+    } else {
+        HIP_TRY(hipSetDevice(h->device));
+        hipStream_t st = as_stream(stream);
+        if (capturing(st))
+            return fail(MBOTS_E_INVALID, "mbots_traj_sequences returns the sequence count to the host and cannot be "
+                                         "captured into a graph");
+        if (int rc = use_stream(h, st)) return rc;
+        HIP_TRY(mbots::launch_traj_sequences(tj.w, tj.n, tj.mx, st));
+        const size_t tot = (size_t)tj.w.horizon * ((tj.w.max_rows + mbots::kTrajBlock - 1) / mbots::kTrajBlock);
+        HIP_TRY(hipMemcpyAsync(tj.h_S, tj.w.blk + tot, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        tj.S = *tj.h_S;
+    }
+    tj.seq_valid = true;
+    if (S_out) *S_out = tj.S;
+    return MBOTS_OK;
+}
+
+namespace {
+// the index scratch of a batch / gather: room for `entries` int32
+int traj_scratch(mbots_handle *h, uint64_t entries)
+{
+    auto &tj = h->traj;
+    if (entries <= tj.idx_cap) return MBOTS_OK;
+    if (h->cpu) {
+        std::free(tj.idx);
+        tj.idx = static_cast<int32_t *>(std::malloc(entries * 4));
+    } else {
+        HIP_TRY(hipDeviceSynchronize());   // a queued batch may still read the old one
+        if (tj.idx) (void)hipFree(tj.idx);
+        tj.idx = nullptr;
+        if (hipMalloc((void **)&tj.idx, entries * 4) != hipSuccess) {
+            (void)hipGetLastError();
+            tj.idx = nullptr;
+        }
+    }
+    tj.idx_cap = tj.idx ? entries : 0;
+    return tj.idx ? MBOTS_OK : fail(MBOTS_E_NOMEM, "allocation of the batch index failed");
+}
+
+// the checks mbots_traj_batch and mbots_traj_gather share; *st_out: the stream
+int traj_batch_enter(mbots_handle *h, uint64_t lo, uint64_t hi, void *stream, hipStream_t *st_out)
+{
+    auto &tj = h->traj;
+    if (!tj.open) return fail(MBOTS_E_INVALID, "no trajectory window is open");
+    if (!tj.w.seq_id) return fail(MBOTS_E_INVALID, "the window was opened without MBOTS_TRAJ_SEQ");
+    if (!tj.seq_valid || !tj.computed)
+        return fail(MBOTS_E_INVALID, "a batch follows mbots_traj_sequences of the tables now in the window");
+    if (lo > hi || hi > tj.S)
+        return fail(MBOTS_E_RANGE, "sequences [" + std::to_string(lo) + ", " + std::to_string(hi) + ") are not within [0, " +
+                                       std::to_string(tj.S) + ")");
+    *st_out = as_stream(stream);
+    if (h->cpu) return MBOTS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    if (capturing(*st_out)) return fail(MBOTS_E_INVALID, "a batch of the trajectory window cannot be captured into a graph");
+    return use_stream(h, *st_out);
+}
+}  // namespace
+
+int mbots_traj_batch(mbots_handle *h, uint64_t lo, uint64_t hi, const struct mbots_traj_batch *out, void *stream)
+{
+    if (!h || !out) return fail(MBOTS_E_INVALID, "null argument");
+    auto &tj = h->traj;
+    hipStream_t st = nullptr;
+    if (tj.open && out->obs && !tj.w.rec)
+        return fail(MBOTS_E_INVALID, "obs needs a window opened with MBOTS_TRAJ_REC_OBS");
+    if (tj.open && (out->action_in || out->hidden0) && !tj.w.hidden)
+        return fail(MBOTS_E_INVALID, "action_in / hidden0 need a window opened with MBOTS_TRAJ_REC_STATE");
+    if (int rc = traj_batch_enter(h, lo, hi, stream, &st)) return rc;
+    const uint64_t B = hi - lo;
+    if (B == 0) return MBOTS_OK;
+    mbots::TrajBatch o{out->rows, out->t0, out->len, out->end, out->reward, out->value,
+                       out->adv,  out->ret, out->action_in, out->hidden0};
+    if (out->obs && (!o.rows || !o.t0)) {   // the decode's index: the missing part in the window's scratch
+        if (int rc = traj_scratch(h, (uint64_t)tj.n * B + B)) return rc;
+        if (!o.rows) o.rows = tj.idx;
+        if (!o.t0) o.t0 = tj.idx + (uint64_t)tj.n * B;
+    }
+    if (h->cpu) mbots::cpu::Sim::traj_batch(tj.w, o, (uint32_t)lo, B, tj.n, out->obs);
+    else HIP_TRY(mbots::launch_traj_batch(tj.w, o, (uint32_t)lo, B, tj.n, tj.mx, out->obs, st));
+    return MBOTS_OK;
+}
+
+int mbots_traj_gather(mbots_handle *h, uint64_t lo, uint64_t hi, const void *const *tables, uint32_t n_tables,
+                      uint32_t row_bytes, void *out, void *stream)
+{
+    if (!h || !tables || !out) return fail(MBOTS_E_INVALID, "null argument");
+    auto &tj = h->traj;
+    hipStream_t st = nullptr;
+    if (row_bytes == 0 || (row_bytes & 3u) || row_bytes > 1024u)
+        return fail(MBOTS_E_INVALID, "row_bytes must be a multiple of 4 in [4, 1024]");
+    if (int rc = traj_batch_enter(h, lo, hi, stream, &st)) return rc;
+    if (n_tables != tj.n)
+        return fail(MBOTS_E_INVALID, "mbots_traj_gather takes one table per computed table (" + std::to_string(tj.n) + ")");
+    for (uint32_t t = 0; t < tj.n; ++t)
+        if (!tables[t] && tj.rows[t]) return fail(MBOTS_E_INVALID, "null table");
+    const uint64_t B = hi - lo;
+    if (B == 0) return MBOTS_OK;
+    if (int rc = traj_scratch(h, (uint64_t)tj.n * B + B)) return rc;
+    mbots::TrajBatch o{};
+    o.rows = tj.idx;
+    o.t0 = tj.idx + (uint64_t)tj.n * B;
+    if (h->cpu) {
+        mbots::cpu::Sim::traj_batch(tj.w, o, (uint32_t)lo, B, tj.n, nullptr);
+        mbots::cpu::Sim::traj_gather(o.rows, o.t0, B, tj.n, tables, row_bytes, out);
+        return MBOTS_OK;
+    }
+    if (!tj.tabs || !tj.h_tabs || !tj.ev_tabs) {   // (all three, or an earlier failure left a part)
+        if (!tj.tabs) HIP_TRY(hipMalloc((void **)&tj.tabs, (size_t)tj.w.horizon * sizeof(void *)));
+        if (!tj.h_tabs)
+            HIP_TRY(hipHostMalloc((void **)&tj.h_tabs, (size_t)tj.w.horizon * sizeof(void *), hipHostMallocDefault));
+        if (!tj.ev_tabs) HIP_TRY(hipEventCreateWithFlags(&tj.ev_tabs, hipEventDisableTiming));
+    } else {
+        HIP_TRY(hipEventSynchronize(tj.ev_tabs));   // the last upload has left the pinned list
+    }
+    memcpy(tj.h_tabs, tables, (size_t)tj.n * sizeof(void *));
+    HIP_TRY(hipMemcpyAsync(tj.tabs, tj.h_tabs, (size_t)tj.n * sizeof(void *), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(tj.ev_tabs, st));
+    HIP_TRY(mbots::launch_traj_batch(tj.w, o, (uint32_t)lo, B, tj.n, tj.mx, nullptr, st));
+    HIP_TRY(mbots::launch_traj_gather(o.rows, o.t0, B, tj.n, tj.tabs, row_bytes, out, st));
     return MBOTS_OK;
 }
 

@@ -57,6 +57,11 @@ class _RenderOut(ctypes.Structure):
     _fields_ = [(k, ctypes.c_void_p) for k in ("cls", "slot", "rgb")]
 
 
+class _TrajBatch(ctypes.Structure):   # struct mbots_traj_batch
+    _fields_ = [(k, ctypes.c_void_p) for k in ("rows", "t0", "len", "end", "obs", "reward", "value", "adv", "ret",
+                                               "action_in", "hidden0")]
+
+
 class _CTensor(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("device", ctypes.c_int32),
                 ("dims", ctypes.c_int64 * 2)]
@@ -116,6 +121,10 @@ def _load():
         "mbots_traj_clear": [vp, i32],
         "mbots_traj_num_tables": [vp, P(u32)],
         "mbots_traj_view": [vp, i32, u32, P(_CTensor)],
+        "mbots_traj_open_ex": [vp, u32, ctypes.c_uint64, u32],
+        "mbots_traj_sequences": [vp, P(ctypes.c_uint64), vp],
+        "mbots_traj_batch": [vp, ctypes.c_uint64, ctypes.c_uint64, P(_TrajBatch), vp],
+        "mbots_traj_gather": [vp, ctypes.c_uint64, ctypes.c_uint64, P(vp), u32, u32, vp, vp],
         "mbots_render_worlds": [vp, vp, u32, u32, P(_RenderOut), vp],
         "mbots_render_palette": [P(ctypes.c_uint8)],
     }
@@ -725,14 +734,21 @@ class SimManager:
         self._episode_length = int(steps)
 
     # -- multi-step returns -------------------------------------------------
-    def trajectory_window(self, horizon, max_rows):
-        """Open the manager's trajectory window (mbots_traj_open): up to
+    def trajectory_window(self, horizon, max_rows, *, sequences=False, record_obs=False, record_state=False):
+        """Open the manager's trajectory window (mbots_traj_open_ex): up to
         `horizon` consecutive tables of up to `max_rows` rows each.  Returns a
-        TrajectoryWindow; one per manager, until its close()."""
+        TrajectoryWindow; one per manager, until its close().  The opt-in
+        parts behind TrajectoryWindow.sequences() / batch() / gather():
+        sequences (MBOTS_TRAJ_SEQ), record_obs (each push stores the rows'
+        rollout records, MBOTS_TRAJ_REC_OBS), record_state (HiddenState and the
+        Action mask, MBOTS_TRAJ_REC_STATE); a record_* implies sequences."""
         if self._traj is not None:
             raise RuntimeError("madrona_bots: the manager already holds a trajectory window")
-        _check(_lib.mbots_traj_open(self._h, int(horizon), int(max_rows)))
-        self._traj = TrajectoryWindow(self, int(horizon), int(max_rows))
+        flags = (TrajectoryWindow.FLAG_SEQ if sequences or record_obs or record_state else 0) | \
+                (TrajectoryWindow.FLAG_REC_OBS if record_obs else 0) | \
+                (TrajectoryWindow.FLAG_REC_STATE if record_state else 0)
+        _check(_lib.mbots_traj_open_ex(self._h, int(horizon), int(max_rows), flags))
+        self._traj = TrajectoryWindow(self, int(horizon), int(max_rows), flags)
         return self._traj
 
     def set_action(self, agent_idx, forward, backward, rotate_left, rotate_right, shoot, breed):
@@ -1046,18 +1062,26 @@ class TrajectoryWindow:
     world indices and the caller's value estimates; compute() returns, per
     pushed table, the maps and sweeps as torch views of the window's storage.
     The learner keeps its own per-step tensors (observations, log-probs) in each
-    step's row order and gathers them with "next" / lifelines()."""
+    step's row order and gathers them with "next" / lifelines() -- or opens the
+    window with record_obs / record_state and takes padded sequence batches
+    from sequences() / batch() / gather()."""
 
     LINK, NEXT, END, WORLD, REWARD, VALUE, ADV, RET = range(8)   # enum mbots_traj_view_id
     END_NONE, END_DIED, END_RESET, END_WINDOW = range(4)
     _KEYS = (("link", LINK), ("next", NEXT), ("end", END), ("world", WORLD), ("reward", REWARD),
              ("value", VALUE), ("adv", ADV), ("ret", RET))
 
-    def __init__(self, mgr, horizon, max_rows):
+    SEQ_ID, SEQ_POS = 8, 9
+    FLAG_SEQ, FLAG_REC_OBS, FLAG_REC_STATE = 1, 2, 4   # MBOTS_TRAJ_SEQ, _REC_OBS, _REC_STATE
+    OBS_DIM, HIDDEN_DIM = 69, 16
+
+    def __init__(self, mgr, horizon, max_rows, flags=0):
         self._mgr = weakref.ref(mgr)   # (the manager holds the window: no cycle)
         self.horizon = horizon
         self.max_rows = max_rows
+        self.flags = flags
         self._last = None
+        self._S = None                 # sequences of the last sequences(), None: stale
 
     def _live(self):
         m = self._mgr() if self._mgr is not None else None
@@ -1091,6 +1115,7 @@ class TrajectoryWindow:
             ptr = value.data_ptr()
         _check(_lib.mbots_traj_push(m._h, ctypes.c_void_p(ptr), m._stream()))
         self._last = None
+        self._S = None
 
     def view(self, what, t):
         """One column of table t as a [N_t, 1] torch view (mbots_traj_view)."""
@@ -1140,11 +1165,112 @@ class TrajectoryWindow:
             out.append(cur)
         return torch.stack(out)
 
+    def sequences(self):
+        """Number the sequences of the computed tables (mbots_traj_sequences;
+        needs sequences=True and a compute(); the window's second host
+        synchronisation): fills the SEQ_ID / SEQ_POS views and returns S.  A
+        sequence is a maximal lifeline inside the window, numbered in
+        ascending (start table, start row) order."""
+        m = self._live()
+        S = ctypes.c_uint64()
+        _check(_lib.mbots_traj_sequences(m._h, ctypes.byref(S), m._stream()))
+        self._S = int(S.value)
+        return self._S
+
+    def _batch_keys(self):
+        off = ((), ("obs",))[not self.flags & self.FLAG_REC_OBS] + \
+              ((), ("action_in", "hidden0"))[not self.flags & self.FLAG_REC_STATE]
+        return [k for k, _ in _TrajBatch._fields_ if k not in off]
+
+    def _batch_range(self, lo, hi):
+        """(lo, hi, L) of a batch / gather; the library's refusal when no
+        sequences() of the tables now in the window has run."""
+        m = self._live()
+        if self._S is None or self._last is None:
+            _check(_lib.mbots_traj_batch(m._h, 0, 0, ctypes.byref(_TrajBatch()), m._stream()))
+            raise RuntimeError("madrona_bots: batch() / gather() follow this object's compute() and sequences()")
+        lo = int(lo)
+        hi = self._S if hi is None else int(hi)
+        if not 0 <= lo <= hi <= self._S:   # (the library's refusal)
+            _check(_lib.mbots_traj_batch(m._h, lo, hi, ctypes.byref(_TrajBatch()), m._stream()))
+            raise RuntimeError(f"madrona_bots: sequences [{lo}, {hi}) are not within [0, {self._S})")
+        return lo, hi, len(self._last["rows"])
+
+    def batch(self, lo=0, hi=None, keys=None, out=None):
+        """Sequences [lo, hi) (hi None: S) as padded, start-aligned, time-major
+        tensors on the manager's device (mbots_traj_batch; no host
+        synchronisation), B = hi - lo, L = the computed tables: "rows" int32
+        [L, B] (-1 past a sequence's end); "t0", "len", "end" int32 [B];
+        "obs" float32 [L, B, 69] (record_obs); "reward", "value", "adv", "ret"
+        float32 [L, B]; "action_in" uint8 [L, B] and "hidden0" float32 [B, 16]
+        (record_state); zeros past the end.  keys: the fields wanted (default:
+        all the window's flags allow).  out: a dict of contiguous tensors of
+        those shapes to write into (its keys select the fields).  obs[:len[b],
+        b] with lengths len is what pack_padded_sequence(enforce_sorted=False)
+        takes."""
+        m = self._live()
+        lo, hi, L = self._batch_range(lo, hi)
+        B = hi - lo
+        f32, i32 = torch.float32, torch.int32
+        spec = {"rows": ((L, B), i32), "t0": ((B,), i32), "len": ((B,), i32), "end": ((B,), i32),
+                "obs": ((L, B, self.OBS_DIM), f32), "reward": ((L, B), f32), "value": ((L, B), f32),
+                "adv": ((L, B), f32), "ret": ((L, B), f32), "action_in": ((L, B), torch.uint8),
+                "hidden0": ((B, self.HIDDEN_DIM), f32)}
+        if out is None:
+            want = self._batch_keys() if keys is None else list(keys)
+            for key in want:
+                if key not in spec:
+                    raise ValueError(f"keys: unknown key {key!r}")
+            out = {key: torch.empty(spec[key][0], dtype=spec[key][1], device=m.device) for key in want}
+        else:
+            for key, t in out.items():
+                if key not in spec:
+                    raise ValueError(f"out: unknown key {key!r}")
+                if t.dtype != spec[key][1] or tuple(t.shape) != spec[key][0] or t.device != m.device \
+                        or not t.is_contiguous():
+                    raise ValueError(f"out[{key!r}] must be a contiguous {spec[key][1]} {spec[key][0]} tensor "
+                                     f"on {m.device}")
+        # (an empty tensor's pointer may be null: a field asked for is always handed over)
+        tb = _TrajBatch(**{key: (t.data_ptr() or 1) if B else 1 for key, t in out.items()})
+        _check(_lib.mbots_traj_batch(m._h, lo, hi, ctypes.byref(tb), m._stream()))
+        return out
+
+    def gather(self, tensors, lo=0, hi=None, out=None):
+        """The learner's own per-table tensors along sequences [lo, hi)
+        (mbots_traj_gather): `tensors` is a list of one contiguous tensor per
+        computed table, [N_t, C] or [N_t], of one 4-byte dtype, on the
+        manager's device and in that table's row order; returns [L, B, C] of
+        that dtype, row (k, b) the row of table t0[b] + k, zeros past the end."""
+        m = self._live()
+        lo, hi, L = self._batch_range(lo, hi)
+        B = hi - lo
+        tensors = list(tensors)
+        rows = self._last["rows"]
+        if len(tensors) != L:
+            raise ValueError(f"gather() takes one tensor per computed table ({L})")
+        dt = tensors[0].dtype
+        C = int(tensors[0].numel() // rows[0]) if rows[0] else (tensors[0].shape[1] if tensors[0].dim() > 1 else 1)
+        if dt.itemsize != 4 or not 1 <= C <= 256:
+            raise ValueError("gather() takes tensors of a 4-byte dtype with 1 to 256 columns")
+        for t, x in enumerate(tensors):
+            if x.dtype != dt or x.device != m.device or not x.is_contiguous() or x.numel() != rows[t] * C:
+                raise ValueError(f"tensors[{t}] must be a contiguous {dt} [{rows[t]}, {C}] tensor on {m.device}")
+        if out is None:
+            out = torch.empty((L, B, C), dtype=dt, device=m.device)
+        elif out.dtype != dt or tuple(out.shape) != (L, B, C) or out.device != m.device or not out.is_contiguous():
+            raise ValueError(f"out must be a contiguous {dt} {(L, B, C)} tensor on {m.device}")
+        if B == 0:
+            return out
+        ptrs = (ctypes.c_void_p * L)(*[x.data_ptr() or None for x in tensors])
+        _check(_lib.mbots_traj_gather(m._h, lo, hi, ptrs, L, 4 * C, ctypes.c_void_p(out.data_ptr()), m._stream()))
+        return out
+
     def clear(self, keep_last=False):
         """Empty the window (mbots_traj_clear); keep_last: its newest table
         becomes table 0 of the next window, so consecutive windows chain."""
         _check(_lib.mbots_traj_clear(self._live()._h, 1 if keep_last else 0))
         self._last = None
+        self._S = None
 
     def close(self):
         """Free the window (mbots_traj_close); its views must not be used

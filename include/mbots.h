@@ -676,6 +676,86 @@ int mbots_render_worlds(mbots_handle *h, const uint32_t *worlds /* NULL: worlds 
                         uint32_t k, uint32_t scale, const mbots_render_out *out, void *stream);
 int mbots_render_palette(uint8_t rgb[36]);
 
+/* Acting on the device: per-species policy nets, sampling and the action write
+ * in one stream-ordered call (DESIGN.md "Device actor" is the specification).
+ *
+ * A net (one per species 1..4) is a trunk of 1..4 Linear layers of one output
+ * width H (a multiple of 16 in [16, 128]), each with an activation code --
+ * 0 identity, 1 ReLU, 2 LeakyReLU(0.01), 3 Tanh, 4 ELU(1), 5 LogSigmoid --, an
+ * actor head Linear(H, H), ReLU, Linear(H, 6), a critic head Linear(H, H), ReLU,
+ * Linear(H, 1) and, when memory.weight is not NULL, a memory head Linear(H, 16),
+ * Tanh, whose output becomes the row's HiddenState.  Its input is the row's 69
+ * floats of mbots_construct_obs(prev = 0), bit for bit, followed by the row's 16
+ * HiddenState floats when flags has MBOTS_POLICY_MEMORY_IN (trunk[0].in is 69
+ * or 85 accordingly).  Weights are [out][in] row-major f32 (torch's layout),
+ * bias [out] or NULL for zeros; the act field of the head layers is ignored.
+ * Every Linear output is bias[j] followed by fmaf(x[k], W[j][k], acc) for k
+ * ascending, so both execution modes and any sharding give the same bits.
+ *
+ * mbots_policy_set(h, species, net, stream): pointers are memory of the
+ * manager's device (host memory in CPU mode), read in stream order on `stream`
+ * (they may be freed stream-ordered after the call).  The first call for a
+ * species, and a call whose widths, depth or heads differ from the net in
+ * place, allocates (after the device has drained) and is refused under stream
+ * capture; a call with the same architecture only re-uploads on `stream` --
+ * what a learner does after every optimiser step -- and is capturable.  A
+ * captured mbots_policy_act pins the architecture in place at capture time.
+ * MBOTS_E_INVALID for any width, depth, code or NULL weight outside the above.
+ * mbots_policy_clear(h, species) removes the net (after the device has
+ * drained; refused under capture).
+ *
+ * mbots_policy_act(h, flags, action_out, logp_out, value_out, out_rows, stream):
+ * every table row -- mbots_num_rows(): the shard ghost's too -- of the current
+ * table through its species' net; the action is sampled from the softmax of
+ * the six logits (MBOTS_ACT_GREEDY: the first maximal logit) with
+ *   u = u01(threefry2x32(seed, draw, global world, (species - 1) << 16 | k).x),
+ * k the row's index inside its (world, species) segment, so N shards draw what
+ * one device draws.  Unless MBOTS_ACT_NO_WRITE, Action receives the one-hot and
+ * (nets with a memory head) HiddenState the head's output, exactly as
+ * mbots_write_actions(rows = mbots_num_rows()) of the same values would.  The
+ * outputs (device memory, host memory in CPU mode; any may be NULL) receive
+ * rows [0, min(rows, out_rows)): action int32, logp and value f32, [rows, 1].
+ * The reads follow the last step's sensor as mbots_construct_obs does, the
+ * writes order themselves as mbots_write_actions does; the call allocates
+ * nothing, never waits for the host (the row counts are read on the device) and
+ * can be captured into a graph next to mbots_step.  MBOTS_E_INVALID unless all
+ * four species have a net.
+ *
+ * The draw counter (uint32, device memory) is read by every mbots_policy_act
+ * and advanced by one after it in stream order, so a replayed graph draws
+ * fresh numbers.  mbots_policy_draw(h, set, value): set != 0 stores *value
+ * (stream-ordered after the manager's last call), else *value receives the
+ * counter (a host wait); MBOTS_E_INVALID under capture.  It starts at 0 and is
+ * not part of a checkpoint.
+ *
+ * mbots_policy_activation(act, x, y, n, device, stream): learner side, no
+ * manager: y[i] = the actor's own activation `act` of x[i] (codes 0..5; 6 the
+ * actor's exp, 7 its log), device >= 0: device memory of that GPU on `stream`,
+ * device == -1: host memory.  Both give the same bits. */
+#define MBOTS_POLICY_MEMORY_IN  1u
+#define MBOTS_ACT_GREEDY    1u
+#define MBOTS_ACT_NO_WRITE  2u
+#define MBOTS_POLICY_MAX_TRUNK 4
+struct mbots_policy_layer {
+    uint32_t in, out;        /* widths */
+    int32_t act;             /* activation code (trunk layers) */
+    const float *weight;     /* [out][in] row-major */
+    const float *bias;       /* [out], or NULL: zeros */
+};
+struct mbots_policy_net {
+    uint32_t n_trunk;        /* 1..4 */
+    struct mbots_policy_layer trunk[MBOTS_POLICY_MAX_TRUNK];
+    struct mbots_policy_layer actor[2], critic[2];
+    struct mbots_policy_layer memory;   /* weight NULL: no memory head */
+    uint32_t flags;          /* MBOTS_POLICY_MEMORY_IN */
+};
+int mbots_policy_set(mbots_handle *h, uint32_t species /* 1..4 */, const struct mbots_policy_net *net, void *stream);
+int mbots_policy_clear(mbots_handle *h, uint32_t species);
+int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float *logp_out, float *value_out,
+                     uint64_t out_rows, void *stream);
+int mbots_policy_draw(mbots_handle *h, int32_t set, uint32_t *value);
+int mbots_policy_activation(int32_t act, const float *x, float *y, uint64_t n, int32_t device, void *stream);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That

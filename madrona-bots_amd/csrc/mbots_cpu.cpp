@@ -913,6 +913,64 @@ void Sim::construct_obs(bool prev, float *out, uint64_t out_rows) const
     }
 }
 
+// the device actor on host threads: the kernel's k-ordered fmaf chains, pads included
+namespace {
+inline void policy_layer_host(const PolLayer &L, int act, const float *in, float *out)
+{
+    for (uint32_t j = 0; j < L.out; ++j) {
+        const float *wr = L.w + (size_t)j * L.kp;
+        float acc = L.b[j];
+        for (uint32_t k = 0; k < L.kp; ++k) acc = pol_fma(in[k], wr[k], acc);
+        out[j] = pol_activation(act, acc);
+    }
+}
+}  // namespace
+
+void Sim::policy_act(const PolNets &nets, uint32_t flags, uint32_t draw, int32_t *action_out, float *logp_out,
+                     float *value_out, uint64_t out_rows)
+{
+    Table &t = T_[tb_];
+    const bool fixd = (cfg_.flags & MBOTS_FLAG_FIX_DEPTH_ALIAS) != 0;
+    const uint8_t *dep = fixd ? t.depth.data() : reinterpret_cast<const uint8_t *>(t.sem.data());
+    const bool write = !(flags & kActNoWrite), greedy = (flags & kActGreedy) != 0;
+    for_worlds([&](uint32_t w) {
+        float a[kPolMaxH + 4], b[kPolMaxH + 4], hid[kPolMaxH], z[16], v[1], mem[kHidden];
+        for (int s = 0; s < kNumSpecies; ++s) {
+            const PolNet &net = nets.net[s];
+            const int32_t base = row_base_[(size_t)w * kNumSpecies + s], cnt = scount_[(size_t)w * kNumSpecies + s];
+            for (int32_t k = 0; k < cnt; ++k) {
+                const size_t r = (size_t)(base + k);
+                pol_row_input(a, dep + r * kSensor, t.sem.data() + r * kSensor, t.health[r], &t.pos[r * 2],
+                              &t.sur[r * 2], (net.flags & kPolMemoryIn) ? &t.hidden[r * kHidden] : nullptr,
+                              net.trunk[0].kp);
+                float *cur = a, *oth = b;
+                for (uint32_t l = 0; l < net.n_trunk; ++l) {
+                    policy_layer_host(net.trunk[l], (int)net.trunk[l].act, cur, oth);
+                    std::swap(cur, oth);
+                }
+                policy_layer_host(net.actor[0], kActRelu, cur, hid);
+                policy_layer_host(net.actor[1], kActIdentity, hid, z);
+                policy_layer_host(net.critic[0], kActRelu, cur, hid);
+                policy_layer_host(net.critic[1], kActIdentity, hid, v);
+                if (net.has_memory) policy_layer_host(net.memory, kActTanh, cur, mem);
+                const float u = pol_uniform(cfg_.rand_seed, draw, cfg_.world_offset + w, (uint32_t)s + 1u, (uint32_t)k);
+                float logp;
+                const int32_t act = pol_sample(z, u, greedy, &logp);
+                if (write) {
+                    for (int i = 0; i < kPolActions; ++i) t.action[r * 6 + i] = act == i ? 1 : 0;
+                    if (net.has_memory)
+                        for (int i = 0; i < kHidden; ++i) t.hidden[r * kHidden + i] = mem[i];
+                }
+                if (r < out_rows) {
+                    if (action_out) action_out[r] = act;
+                    if (logp_out) logp_out[r] = logp;
+                    if (value_out) value_out[r] = v[0];
+                }
+            }
+        }
+    });
+}
+
 void Sim::world_state(uint32_t w, float *xy_rwrz, int32_t *sp_hp_finder, uint64_t *food,
                       uint32_t *food_rot, int32_t *n_out) const
 {

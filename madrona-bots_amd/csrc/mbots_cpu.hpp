@@ -13,6 +13,7 @@
 #include "mbots_device.hpp"
 #include "mbots_traj.hpp"
 #include "mbots_render.hpp"
+#include "mbots_policy.hpp"
 
 #include <cstdint>
 #include <memory>
@@ -97,6 +98,13 @@ public:
     // world worlds[i] (null: world i) into out's non-null arrays, the images
     // split over the host threads
     void render(const uint32_t *worlds, uint32_t k, uint32_t scale, const RenderOut &out) const;
+    // device actor (mbots_policy.hpp), the HIP kernel as loops over the host
+    // threads: every table row (the shard ghost's included) through its
+    // species' net -- layers held as [nt * 16][kp] rows --, sampled with the
+    // draw counter's value `draw`; writes Action / HiddenState unless
+    // kActNoWrite, and rows [0, out_rows) of the non-null outputs
+    void policy_act(const PolNets &nets, uint32_t flags, uint32_t draw, int32_t *action_out, float *logp_out,
+                    float *value_out, uint64_t out_rows);
     const mbots_config &config() const { return cfg_; }
 
 private:

@@ -4,6 +4,7 @@
 #include "mbots_device.hpp"
 #include "mbots_traj.hpp"
 #include "mbots_render.hpp"
+#include "mbots_policy.hpp"
 #include "../../include/mbots.h"
 
 namespace mbots {
@@ -262,5 +263,19 @@ hipError_t launch_traj_gather(const int32_t *rows, const int32_t *t0, uint64_t B
 // state stands in stream order; out's non-null arrays receive them
 hipError_t launch_render(const SimState &S, const uint32_t *worlds, uint32_t k, uint32_t scale, const RenderOut &out,
                          hipStream_t st);
+
+// device actor (mbots_policy.hpp; kernels in mbots_policy.hip): one persistent
+// launch over every table row (the shard ghost's included) of the current
+// table `t` -- hidden_in: its HiddenState column as readers see it; flags:
+// kActGreedy / kActNoWrite; draw: the device's draw counter; the [out_rows]
+// outputs may be null; max_rows: the table's row slots --, the counter's
+// advance, the upload of a net's layers into fragment order, and the
+// activations of mbots_policy_activation
+hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *hidden_in, const PolNets &nets,
+                             uint32_t flags, const uint32_t *draw, int32_t *action_out, float *logp_out,
+                             float *value_out, uint32_t out_rows, uint32_t max_rows, hipStream_t st);
+hipError_t launch_policy_draw_next(uint32_t *draw, hipStream_t st);
+hipError_t launch_policy_repack(const PolUploads &U, hipStream_t st);
+hipError_t launch_policy_activation(int act, const float *x, float *y, uint64_t n, hipStream_t st);
 
 }  // namespace mbots

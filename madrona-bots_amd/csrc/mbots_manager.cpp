@@ -193,6 +193,15 @@ struct mbots_handle {
         const void **h_tabs = nullptr;   // ([horizon]), its pinned staging and the event after the
         hipEvent_t ev_tabs = nullptr;    // last upload
     } traj;
+    // the device actor (include/mbots.h "Acting on the device"): per species one
+    // allocation of its own holding the uploaded layers (fragment order in HIP
+    // mode, padded rows in CPU mode), so growths leave it alone
+    struct Policy {
+        mbots::PolNets nets{};
+        float *mem[mbots::kNumSpecies] = {};
+        uint32_t *draw = nullptr;     // the device's draw counter (HIP mode)
+        uint32_t draw_host = 0;       // CPU mode's
+    } pol;
     std::vector<char *> retired;      // arenas earlier growths left (views taken then still read
                                       // them): freed by mbots_release_retired / mbots_destroy
 };
@@ -1046,11 +1055,14 @@ int mbots_destroy(mbots_handle *h)
     if (h->cpu) {
         std::free(h->traj.mem);
         traj_free_extras(h);
+        for (float *p : h->pol.mem) std::free(p);
         delete h;
         return MBOTS_OK;
     }
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
+    for (float *p : h->pol.mem) if (p) (void)hipFree(p);
+    if (h->pol.draw) (void)hipFree(h->pol.draw);
     if (h->traj.mem) (void)hipFree(h->traj.mem);
     if (h->traj.h_count) (void)hipHostFree(h->traj.h_count);
     if (h->traj.h_S) (void)hipHostFree(h->traj.h_S);
@@ -3075,6 +3087,255 @@ int mbots_traj_gather(mbots_handle *h, uint64_t lo, uint64_t hi, const void *con
     HIP_TRY(hipEventRecord(tj.ev_tabs, st));
     HIP_TRY(mbots::launch_traj_batch(tj.w, o, (uint32_t)lo, B, tj.n, tj.mx, nullptr, st));
     HIP_TRY(mbots::launch_traj_gather(o.rows, o.t0, B, tj.n, tj.tabs, row_bytes, out, st));
+    return MBOTS_OK;
+}
+
+// ---- the device actor (include/mbots.h "Acting on the device") ----
+// the layers of a net in upload order: trunk, actor, critic, memory
+static std::vector<mbots::PolLayer *> policy_layers(mbots::PolNet &n)
+{
+    std::vector<mbots::PolLayer *> v;
+    for (uint32_t l = 0; l < n.n_trunk; ++l) v.push_back(&n.trunk[l]);
+    v.push_back(&n.actor[0]);
+    v.push_back(&n.actor[1]);
+    v.push_back(&n.critic[0]);
+    v.push_back(&n.critic[1]);
+    if (n.has_memory) v.push_back(&n.memory);
+    return v;
+}
+
+// the widths of `src` checked and laid out (no storage yet)
+static int policy_describe(const mbots_policy_net *src, mbots::PolNet &n)
+{
+    using namespace mbots;
+    n = PolNet{};
+    if (src->n_trunk < 1 || src->n_trunk > (uint32_t)kPolMaxTrunk)
+        return fail(MBOTS_E_INVALID, "a policy net has 1..4 trunk layers");
+    if (src->flags & ~MBOTS_POLICY_MEMORY_IN) return fail(MBOTS_E_INVALID, "unknown policy net flags");
+    const uint32_t H = src->trunk[0].out, in0 = (src->flags & MBOTS_POLICY_MEMORY_IN) ? kPolObs + kHidden : kPolObs;
+    if (H < 16 || H > (uint32_t)kPolMaxH || H % 16u)
+        return fail(MBOTS_E_INVALID, "the trunk width must be a multiple of 16 in [16, 128], not " + std::to_string(H));
+    auto lay = [&](const mbots_policy_layer &s, PolLayer &d, uint32_t in, uint32_t out, const char *what) {
+        if (s.in != in || s.out != out)
+            return fail(MBOTS_E_INVALID, std::string(what) + " must be Linear(" + std::to_string(in) + ", " +
+                                             std::to_string(out) + "), not (" + std::to_string(s.in) + ", " +
+                                             std::to_string(s.out) + ")");
+        if (!s.weight) return fail(MBOTS_E_INVALID, std::string(what) + ": null weight");
+        d.in = in;
+        d.out = out;
+        d.kp = pol_kp(in);
+        d.nt = (out + 15u) / 16u;
+        d.act = 0;
+        return MBOTS_OK;
+    };
+    n.n_trunk = src->n_trunk;
+    n.H = H;
+    n.flags = src->flags;
+    n.has_memory = src->memory.weight ? 1u : 0u;
+    for (uint32_t l = 0; l < n.n_trunk; ++l) {
+        if (int rc = lay(src->trunk[l], n.trunk[l], l ? H : in0, H, "a trunk layer")) return rc;
+        if (src->trunk[l].act < 0 || src->trunk[l].act > kActLogSigmoid)
+            return fail(MBOTS_E_INVALID, "unknown activation code " + std::to_string(src->trunk[l].act));
+        n.trunk[l].act = (uint32_t)src->trunk[l].act;
+    }
+    if (int rc = lay(src->actor[0], n.actor[0], H, H, "the actor's first layer")) return rc;
+    if (int rc = lay(src->actor[1], n.actor[1], H, kPolActions, "the actor's second layer")) return rc;
+    if (int rc = lay(src->critic[0], n.critic[0], H, H, "the critic's first layer")) return rc;
+    if (int rc = lay(src->critic[1], n.critic[1], H, 1, "the critic's second layer")) return rc;
+    if (n.has_memory)
+        if (int rc = lay(src->memory, n.memory, H, kHidden, "the memory head")) return rc;
+    n.set = 1;
+    return MBOTS_OK;
+}
+
+static bool policy_same_arch(mbots::PolNet &a, mbots::PolNet &b)
+{
+    if (!a.set || !b.set || a.n_trunk != b.n_trunk || a.H != b.H || a.flags != b.flags || a.has_memory != b.has_memory)
+        return false;
+    for (uint32_t l = 0; l < a.n_trunk; ++l)
+        if (a.trunk[l].in != b.trunk[l].in || a.trunk[l].act != b.trunk[l].act) return false;
+    return true;
+}
+
+int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_policy_net *net, void *stream)
+{
+    using namespace mbots;
+    if (!h || !net) return fail(MBOTS_E_INVALID, "null argument");
+    if (species < 1 || species > (uint32_t)kNumSpecies) return fail(MBOTS_E_INVALID, "species must be 1..4");
+    PolNet n;
+    if (int rc = policy_describe(net, n)) return rc;
+    PolNet &cur = h->pol.nets.net[species - 1];
+    hipStream_t st = nullptr;
+    if (!h->cpu) {
+        HIP_TRY(hipSetDevice(h->device));
+        st = as_stream(stream);
+        if (int rc = use_stream(h, st)) return rc;
+    }
+    std::vector<PolLayer *> L = policy_layers(n);
+    if (!policy_same_arch(cur, n)) {
+        size_t floats = 0;
+        for (PolLayer *l : L) floats += ((pol_w_floats(*l) + 63u) & ~size_t(63)) + ((pol_b_floats(*l) + 63u) & ~size_t(63));
+        float *mem = nullptr;
+        if (h->cpu) {
+            mem = static_cast<float *>(std::malloc(floats * sizeof(float)));
+            if (!mem) return fail(MBOTS_E_NOMEM, "policy net allocation failed");
+            std::free(h->pol.mem[species - 1]);
+        } else {
+            if (capturing(st))
+                return fail(MBOTS_E_INVALID, "a policy net of a new architecture allocates: set it before the capture "
+                                             "begins (a net of the same architecture is re-uploaded in place)");
+            HIP_TRY(hipDeviceSynchronize());   // a queued act may still read the net in place
+            if (!h->pol.draw) {
+                HIP_TRY(hipMalloc((void **)&h->pol.draw, 256));
+                HIP_TRY(hipMemset(h->pol.draw, 0, 256));
+            }
+            if (hipMalloc((void **)&mem, floats * sizeof(float)) != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(MBOTS_E_NOMEM, "policy net allocation failed");
+            }
+            if (h->pol.mem[species - 1]) (void)hipFree(h->pol.mem[species - 1]);
+        }
+        h->pol.mem[species - 1] = mem;
+        for (PolLayer *l : L) {
+            l->w = mem;
+            mem += (pol_w_floats(*l) + 63u) & ~size_t(63);
+            l->b = mem;
+            mem += (pol_b_floats(*l) + 63u) & ~size_t(63);
+        }
+        cur = n;
+    }
+    // the weights into the storage in place
+    std::vector<PolLayer *> D = policy_layers(cur);
+    std::vector<const mbots_policy_layer *> S;
+    for (uint32_t l = 0; l < net->n_trunk; ++l) S.push_back(&net->trunk[l]);
+    S.push_back(&net->actor[0]);
+    S.push_back(&net->actor[1]);
+    S.push_back(&net->critic[0]);
+    S.push_back(&net->critic[1]);
+    if (cur.has_memory) S.push_back(&net->memory);
+    if (h->cpu) {
+        for (size_t i = 0; i < D.size(); ++i) {
+            const PolLayer &d = *D[i];
+            for (uint32_t j = 0; j < d.nt * 16u; ++j) {
+                for (uint32_t k = 0; k < d.kp; ++k)
+                    d.w[(size_t)j * d.kp + k] = (j < d.out && k < d.in) ? S[i]->weight[(size_t)j * d.in + k] : 0.0f;
+                d.b[j] = (j < d.out && S[i]->bias) ? S[i]->bias[j] : 0.0f;
+            }
+        }
+        return MBOTS_OK;
+    }
+    PolUploads U{};
+    for (size_t i = 0; i < D.size(); ++i) {
+        const PolLayer &d = *D[i];
+        U.l[i] = PolUpload{S[i]->weight, S[i]->bias, d.w, d.b, d.in, d.out, d.kp, d.nt};
+    }
+    U.n = (uint32_t)D.size();
+    HIP_TRY(launch_policy_repack(U, st));
+    return MBOTS_OK;
+}
+
+int mbots_policy_clear(mbots_handle *h, uint32_t species)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    if (species < 1 || species > (uint32_t)mbots::kNumSpecies) return fail(MBOTS_E_INVALID, "species must be 1..4");
+    if (h->cpu) {
+        std::free(h->pol.mem[species - 1]);
+    } else if (h->pol.mem[species - 1]) {
+        HIP_TRY(hipSetDevice(h->device));
+        if (capturing_now(h)) return fail(MBOTS_E_INVALID, "a policy net cannot be cleared during a graph capture");
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(h->pol.mem[species - 1]);
+    }
+    h->pol.mem[species - 1] = nullptr;
+    h->pol.nets.net[species - 1] = mbots::PolNet{};
+    return MBOTS_OK;
+}
+
+int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float *logp_out, float *value_out,
+                     uint64_t out_rows, void *stream)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    if (flags & ~(MBOTS_ACT_GREEDY | MBOTS_ACT_NO_WRITE)) return fail(MBOTS_E_INVALID, "unknown act flags");
+    for (int s = 0; s < mbots::kNumSpecies; ++s)
+        if (!h->pol.nets.net[s].set)
+            return fail(MBOTS_E_INVALID, "species " + std::to_string(s + 1) + " has no policy net (mbots_policy_set)");
+    if (out_rows > 0xFFFFFFFFull) out_rows = 0xFFFFFFFFull;
+    if (h->cpu) {
+        h->cpu->policy_act(h->pol.nets, flags, h->pol.draw_host, action_out, logp_out, value_out, out_rows);
+        h->pol.draw_host += 1u;
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = as_stream(stream);
+    int rc = use_stream(h, st);
+    if (rc) return rc;
+    const int tb = h->tb;
+    const int owed = pending_mask(h);
+    // the inputs: the sensor's rows (mbots_construct_obs), and HiddenState where
+    // its readers find it (the step's deferred move done; a column a fused shift
+    // left aliased is read in its Prev storage, not copied)
+    if ((rc = wait_sensor(h, st))) return rc;
+    if ((rc = materialize_cur_ah(h, st, 0))) return rc;
+    note_use(h, mbots::kMoveAH, owed);
+    const mbots::ObsTable view = src_view(h, tb);
+    bool writes_hidden = false;
+    for (int s = 0; s < mbots::kNumSpecies; ++s) writes_hidden |= h->pol.nets.net[s].has_memory != 0;
+    const bool write = !(flags & MBOTS_ACT_NO_WRITE);
+    // a net without a memory head leaves its rows' HiddenState as it is: if the
+    // column is written at all (another species' head) while still aliased, the
+    // rows it keeps are copied out first, as mbots_write_actions does for a part
+    bool all_hidden = true;
+    for (int s = 0; s < mbots::kNumSpecies; ++s) all_hidden &= h->pol.nets.net[s].has_memory != 0;
+    if (write && writes_hidden && !all_hidden && h->h_alias[tb])
+        if ((rc = materialize_cur_ah(h, st, 2))) return rc;
+    const float *hidden_in = h->h_alias[tb] ? view.hidden : h->T[tb].hidden;
+    rc = timed(h, MBOTS_TK_ACTIONS, st, [&] {
+        return mbots::launch_policy_act(h->S, h->T[tb], hidden_in, h->pol.nets, flags, h->pol.draw, action_out,
+                                        logp_out, value_out, (uint32_t)out_rows,
+                                        (uint32_t)((uint64_t)h->S.W * h->S.cap), st);
+    });
+    if (rc) return rc;
+    HIP_TRY(mbots::launch_policy_draw_next(h->pol.draw, st));
+    if (write) {
+        h->a_alias[tb] = false;
+        if (writes_hidden) h->h_alias[tb] = false;
+    }
+    return MBOTS_OK;
+}
+
+int mbots_policy_draw(mbots_handle *h, int32_t set, uint32_t *value)
+{
+    if (!h || !value) return fail(MBOTS_E_INVALID, "null argument");
+    if (h->cpu) {
+        if (set) h->pol.draw_host = *value;
+        else *value = h->pol.draw_host;
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    if (capturing_now(h)) return fail(MBOTS_E_INVALID, "the draw counter cannot be read or set during a graph capture");
+    if (!h->pol.draw) {
+        HIP_TRY(hipMalloc((void **)&h->pol.draw, 256));
+        HIP_TRY(hipMemset(h->pol.draw, 0, 256));
+    }
+    if (set) {
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->pol.draw, (int)*value, 1, h->last_stream));
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipMemcpyAsync(value, h->pol.draw, sizeof(uint32_t), hipMemcpyDeviceToHost, h->last_stream));
+    HIP_TRY(hipStreamSynchronize(h->last_stream));
+    return MBOTS_OK;
+}
+
+int mbots_policy_activation(int32_t act, const float *x, float *y, uint64_t n, int32_t device, void *stream)
+{
+    if ((!x || !y) && n) return fail(MBOTS_E_INVALID, "null argument");
+    if (act < 0 || act > mbots::kActLog) return fail(MBOTS_E_INVALID, "unknown activation code " + std::to_string(act));
+    if (device < 0) {
+        for (uint64_t i = 0; i < n; ++i) y[i] = mbots::pol_activation(act, x[i]);
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(mbots::launch_policy_activation(act, x, y, n, as_stream(stream)));
     return MBOTS_OK;
 }
 

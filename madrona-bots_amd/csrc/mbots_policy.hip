@@ -1,0 +1,385 @@
+// mbots_policy.hip -- the device actor's kernels (mbots_policy.hpp; DESIGN.md
+// "Device actor"): per-species policy nets on v_mfma_f32_16x16x4_f32, action
+// sampling from the counter RNG and the Action / HiddenState write, one
+// persistent launch over 64-row tiles of the current table.
+#include "mbots_kernels.hpp"
+#include "mbots_policy.hpp"
+
+#include <algorithm>
+
+namespace mbots {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kPolRows = 64;        // rows per tile (a block of 4 waves)
+constexpr int kPolStride = 132;     // floats per LDS row: 128 + 4, so the 16 rows x 4 k of an A
+                                    // fragment and the 16 x 4 results of a C tile each hit 64 banks
+constexpr int kPolLogitStride = 8, kPolMemStride = 16;
+// two activation tiles, the heads' outputs, and three words per row for the row's world
+constexpr size_t kPolLds =
+    (2 * kPolRows * kPolStride + kPolRows * (kPolLogitStride + 1 + kPolMemStride + 3)) * sizeof(float);
+
+// One Linear over the tile's 64 rows: out[r][j] = act(bias[j] + sum_k x[r][k] W[j][k]),
+// k ascending.  Wave (wv - woff) & 3 takes column tiles jt = that, that + 4 for
+// all four 16-row tiles: up to 8 independent accumulators per k-step, the
+// layer's weights read once per block, straight from L2 in fragment order (64
+// contiguous floats per (k-step, column tile)).  The C operand starts as the
+// broadcast bias; columns >= L.out (the heads' pads) are never stored.
+__device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const float *src, float *dst,
+                                          uint32_t dst_stride, uint32_t wv, uint32_t woff, uint32_t lane)
+{
+    const uint32_t nt = L.nt, nks = L.kp >> 2;
+    const uint32_t j0 = (wv - woff) & 3u, j1 = j0 + 4u;
+    if (j0 >= nt) return;
+    const bool two = j1 < nt;
+    const uint32_t c = lane & 15u, q = lane >> 4;
+    f32x4 acc0[4], acc1[4];
+    {
+        const float b0 = L.b[j0 * 16u + c], b1 = two ? L.b[j1 * 16u + c] : 0.0f;
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            acc0[mt] = f32x4{b0, b0, b0, b0};
+            acc1[mt] = f32x4{b1, b1, b1, b1};
+        }
+    }
+    const float *wp0 = L.w + (size_t)j0 * 64u + lane, *wp1 = L.w + (size_t)j1 * 64u + lane;
+    const size_t wstep = (size_t)nt * 64u;
+    const float *xa = src + c * kPolStride + q;
+    // (a guarded register ring loading the B fragments four k-steps ahead
+    // measured slower, 5.9 against 5.0 ms at 65536 worlds; the branch-free pair
+    // below 4.85 against 4.90 for one k-step per pass)
+    if (two) {
+        // two k-steps per pass (nks is even), the next pass's B fragments loaded
+        // before this pass's MFMAs (the last pass reloads its own: no branch)
+        float n00 = wp0[0], n01 = wp0[wstep], n10 = wp1[0], n11 = wp1[wstep];
+        for (uint32_t ks = 0; ks < nks; ks += 2u) {
+            const float b00 = n00, b01 = n01, b10 = n10, b11 = n11;
+            const size_t kn = (size_t)min(ks + 2u, nks - 2u) * wstep;
+            n00 = wp0[kn];
+            n01 = wp0[kn + wstep];
+            n10 = wp1[kn];
+            n11 = wp1[kn + wstep];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const float a = xa[mt * 16 * kPolStride + 4u * ks];
+                acc0[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b00, acc0[mt], 0, 0, 0);
+                acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b10, acc1[mt], 0, 0, 0);
+            }
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const float a = xa[mt * 16 * kPolStride + 4u * ks + 4u];
+                acc0[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b01, acc0[mt], 0, 0, 0);
+                acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b11, acc1[mt], 0, 0, 0);
+            }
+        }
+    } else {
+        for (uint32_t ks = 0; ks < nks; ++ks) {
+            const float b0 = wp0[ks * wstep];
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                const float a = xa[mt * 16 * kPolStride + 4u * ks];
+                acc0[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc0[mt], 0, 0, 0);
+            }
+        }
+    }
+    // C / D: column lane & 15, row (lane >> 4) * 4 + register
+    const uint32_t col0 = j0 * 16u + c, col1 = j1 * 16u + c;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const uint32_t row = (uint32_t)mt * 16u + q * 4u + (uint32_t)r;
+            if (col0 < L.out) dst[row * dst_stride + col0] = pol_activation(act, acc0[mt][r]);
+            if (two && col1 < L.out) dst[row * dst_stride + col1] = pol_activation(act, acc1[mt][r]);
+        }
+}
+
+struct PolActArgs {
+    const uint32_t *totals;
+    const int32_t *scount, *row_base;
+    const uint8_t *depth;
+    const int8_t *sem;
+    const int32_t *health;
+    const float *pos, *sur;
+    const float *hidden_in;     // the HiddenState column as its readers see it
+    int32_t *action;            // null: MBOTS_ACT_NO_WRITE
+    float *hidden_out;
+    int32_t *action_out;        // [out_rows] each, any may be null
+    float *logp_out, *value_out;
+    const uint32_t *draw;
+    uint32_t out_rows, W, Wx, world_offset, seed, greedy;
+};
+
+__global__ __launch_bounds__(256, 2) void policy_act_kernel(PolActArgs A, PolNets P)
+{
+    extern __shared__ float s_pol[];
+    float *buf0 = s_pol, *buf1 = s_pol + kPolRows * kPolStride;
+    float *s_logit = buf1 + kPolRows * kPolStride;
+    float *s_val = s_logit + kPolRows * kPolLogitStride;
+    float *s_mem = s_val + kPolRows;
+    uint32_t *s_win = reinterpret_cast<uint32_t *>(s_mem + kPolRows * kPolMemStride);
+    uint32_t *s_w = s_win + kPolRows, *s_k = s_w + kPolRows;
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+
+    // the table's eight species segments: the exported rows of species 1..4,
+    // then the shard ghost's (after row N); a tile never straddles two
+    uint32_t seg_len[8], seg_start[8];
+    {
+        uint32_t run = 0;
+        for (int s = 0; s < 4; ++s) {
+            seg_len[s] = uniform(A.totals[1 + s]);
+            seg_start[s] = run;
+            run += seg_len[s];
+        }
+        run = uniform(A.totals[0]);
+        for (int s = 0; s < 4; ++s) {
+            seg_len[4 + s] = A.W > A.Wx ? uniform((uint32_t)A.scount[4u * A.Wx + s]) : 0u;
+            seg_start[4 + s] = run;
+            run += seg_len[4 + s];
+        }
+    }
+    const uint32_t draw = uniform(*A.draw);
+
+    for (uint32_t tile = blockIdx.x;; tile += gridDim.x) {
+        uint32_t seg = 0, rest = tile;
+        for (; seg < 8u; ++seg) {
+            const uint32_t nt = (seg_len[seg] + kPolRows - 1u) / kPolRows;
+            if (rest < nt) break;
+            rest -= nt;
+        }
+        if (seg >= 8u) break;
+        const uint32_t sp = seg & 3u;   // species - 1
+        const uint32_t r0 = seg_start[seg] + rest * kPolRows;
+        const uint32_t nr = min((uint32_t)kPolRows, seg_len[seg] - rest * kPolRows);
+        const PolNet &net = P.net[sp];
+        const bool mem_in = (net.flags & kPolMemoryIn) != 0u;
+
+        // ---- stage the tile's inputs, coalesced, as the f32 tile X[64][Kp] ----
+        {
+            const uint32_t row = (t & 127u) >> 1, half = t & 1u;
+            float *x = buf0 + row * kPolStride + (t < 128u ? 0u : 35u) + half * 16u;
+            if (row < nr) {
+                const uint4 g = t < 128u ? reinterpret_cast<const uint4 *>(A.depth + (size_t)r0 * kSensor)[t]
+                                         : reinterpret_cast<const uint4 *>(A.sem + (size_t)r0 * kSensor)[t - 128u];
+                const uint32_t wds[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const uint32_t b = (wds[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+                    x[i] = t < 128u ? (float)b : (float)(int8_t)b;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 16; ++i) x[i] = 0.0f;
+            }
+        }
+        if (t < (uint32_t)kPolRows) {
+            float *x = buf0 + t * kPolStride;
+            int32_t hp = 0;
+            float2 ps = make_float2(0.0f, 0.0f), su = ps;
+            if (t < nr) {
+                hp = A.health[r0 + t];
+                ps = reinterpret_cast<const float2 *>(A.pos)[r0 + t];
+                su = reinterpret_cast<const float2 *>(A.sur)[r0 + t];
+            }
+            x[32] = __int_as_float(hp);
+            x[33] = ps.x;
+            x[34] = ps.y;
+            x[67] = su.x;
+            x[68] = su.y;
+            if (!mem_in) x[69] = x[70] = x[71] = 0.0f;
+            else x[85] = x[86] = x[87] = 0.0f;
+        }
+        if (mem_in) {
+            const uint32_t row = t >> 2, g = t & 3u;
+            float4 h = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (row < nr) h = reinterpret_cast<const float4 *>(A.hidden_in + (size_t)r0 * kHidden)[t];
+            float *x = buf0 + row * kPolStride + kPolObs + 4u * g;
+            x[0] = h.x;
+            x[1] = h.y;
+            x[2] = h.z;
+            x[3] = h.w;
+        }
+        // ---- wave 3: each row's world and its index k inside the (world, species)
+        // segment, for the epilogue's RNG key.  The first row's world by a 64-ary
+        // search of row_base (three rounds at 65536 worlds), then the next 64
+        // worlds' bases as a window in LDS that the rows bisect ----
+        if (wv == 3u) {
+            const uint32_t r = r0 + lane;
+            uint32_t w = A.Wx, k = 0;
+            if (seg >= 4u) {
+                k = r - (uint32_t)A.row_base[4u * A.Wx + sp];
+            } else {
+                uint32_t lo = 0, n = A.Wx;   // the world lies in [lo, lo + n), row_base[lo] <= r0
+                while (n > 1u) {
+                    const uint32_t step = (n + 63u) >> 6, end = lo + n, p = lo + (lane + 1u) * step;
+                    const bool ok = p < end && (uint32_t)A.row_base[4u * p + sp] <= r0;
+                    lo += (uint32_t)__popcll(ballot64(ok)) * step;
+                    n = min(step, end - lo);
+                }
+                const uint32_t w0 = lo, pw = w0 + 1u + lane;
+                s_win[lane] = pw < A.Wx ? (uint32_t)A.row_base[4u * pw + sp] : 0xFFFFFFFFu;
+                wave_sync();
+                if (lane < nr) {
+                    uint32_t c = 0;   // window entries <= r: the row's world is w0 + c
+                    for (uint32_t s = 32u; s; s >>= 1)
+                        if (s_win[c + s - 1u] <= r) c += s;
+                    if (c == 63u && s_win[63] <= r) c = 64u;
+                    w = w0 + c;
+                    if (c == 64u) {   // past the window (a long run of worlds without the species)
+                        uint32_t hi = A.Wx;
+                        while (hi - w > 1u) {
+                            const uint32_t mid = (w + hi) >> 1;
+                            if ((uint32_t)A.row_base[4u * mid + sp] <= r) w = mid;
+                            else hi = mid;
+                        }
+                    }
+                    k = r - (uint32_t)A.row_base[4u * w + sp];
+                }
+            }
+            s_w[lane] = w;
+            s_k[lane] = k;
+        }
+        __syncthreads();
+
+        // ---- trunk: ping-pong between the two tiles ----
+        float *cur = buf0, *oth = buf1;
+        for (uint32_t l = 0; l < net.n_trunk; ++l) {
+            pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            float *sw = cur;
+            cur = oth;
+            oth = sw;
+        }
+        // ---- heads, all reading the trunk's last tile `cur` ----
+        pol_layer(net.actor[0], kActRelu, cur, oth, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(net.actor[1], kActIdentity, oth, s_logit, kPolLogitStride, wv, 0u, lane);
+        if (net.has_memory) pol_layer(net.memory, kActTanh, cur, s_mem, kPolMemStride, wv, 1u, lane);
+        __syncthreads();
+        pol_layer(net.critic[0], kActRelu, cur, oth, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(net.critic[1], kActIdentity, oth, s_val, 1u, wv, 0u, lane);
+        __syncthreads();
+
+        // ---- epilogue: sample, log-probability, the table's writes ----
+        if (t < nr) {
+            const uint32_t r = r0 + t;
+            const uint32_t w = s_w[t], k = s_k[t];
+            float z[kPolActions];
+#pragma unroll
+            for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
+            const float u = pol_uniform(A.seed, draw, A.world_offset + w, sp + 1u, k);
+            float logp;
+            const int32_t a = pol_sample(z, u, A.greedy != 0u, &logp);
+            if (A.action) {
+                int2 *o = reinterpret_cast<int2 *>(A.action + (size_t)r * 6u);
+                o[0] = make_int2(a == 0, a == 1);
+                o[1] = make_int2(a == 2, a == 3);
+                o[2] = make_int2(a == 4, a == 5);
+            }
+            if (r < A.out_rows) {
+                if (A.action_out) A.action_out[r] = a;
+                if (A.logp_out) A.logp_out[r] = logp;
+                if (A.value_out) A.value_out[r] = s_val[t];
+            }
+        }
+        if (net.has_memory && A.hidden_out) {
+            const uint32_t row = t >> 2, g = t & 3u;
+            if (row < nr) {
+                const float *m = s_mem + row * kPolMemStride + 4u * g;
+                reinterpret_cast<float4 *>(A.hidden_out + (size_t)r0 * kHidden)[t] = make_float4(m[0], m[1], m[2], m[3]);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+__global__ void policy_draw_next_kernel(uint32_t *draw) { *draw += 1u; }
+
+// weights into the fragment order / the padded bias, one block column per layer
+__global__ __launch_bounds__(256) void policy_repack_kernel(PolUploads U)
+{
+    const PolUpload &L = U.l[blockIdx.y];
+    const uint32_t nw = L.kp * L.nt * 16u, nb = L.nt * 16u;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nw + nb; i += gridDim.x * 256u) {
+        if (i < nw) {
+            const uint32_t l = i & 63u, f = i >> 6, jt = f % L.nt, ks = f / L.nt;
+            const uint32_t j = jt * 16u + (l & 15u), k = 4u * ks + (l >> 4);
+            L.w_dst[i] = (j < L.out && k < L.in) ? L.w_src[(size_t)j * L.in + k] : 0.0f;
+        } else {
+            const uint32_t j = i - nw;
+            L.b_dst[j] = (j < L.out && L.b_src) ? L.b_src[j] : 0.0f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void policy_activation_kernel(int act, const float *x, float *y, uint64_t n)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
+        y[i] = pol_activation(act, x[i]);
+}
+
+hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *hidden_in, const PolNets &nets,
+                             uint32_t flags, const uint32_t *draw, int32_t *action_out, float *logp_out,
+                             float *value_out, uint32_t out_rows, uint32_t max_rows, hipStream_t st)
+{
+    static bool lds_set = false;
+    if (!lds_set) {
+        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel),
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolLds);
+        if (e != hipSuccess) return e;
+        lds_set = true;
+    }
+    PolActArgs A{};
+    A.totals = S.totals;
+    A.scount = S.scount;
+    A.row_base = S.row_base;
+    A.sem = t.sem;
+    A.depth = (S.flags & kFlagFixDepth) ? t.depth : reinterpret_cast<const uint8_t *>(t.sem);
+    A.health = t.health;
+    A.pos = t.pos;
+    A.sur = t.sur;
+    A.hidden_in = hidden_in;
+    const bool write = !(flags & kActNoWrite);
+    A.action = write ? t.action : nullptr;
+    A.hidden_out = write ? t.hidden : nullptr;
+    A.action_out = action_out;
+    A.logp_out = logp_out;
+    A.value_out = value_out;
+    A.draw = draw;
+    A.out_rows = out_rows;
+    A.W = S.W;
+    A.Wx = S.Wx;
+    A.world_offset = S.world_offset;
+    A.seed = S.seed;
+    A.greedy = (flags & kActGreedy) ? 1u : 0u;
+    // persistent: two blocks per compute unit at most (the LDS tile), never more
+    // blocks than the table can hold tiles (8 segments, each with a ragged one)
+    const uint64_t tiles = (uint64_t)max_rows / kPolRows + 8u;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(tiles, 512u);
+    hipLaunchKernelGGL(policy_act_kernel, dim3(blocks), dim3(256), kPolLds, st, A, nets);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_draw_next(uint32_t *draw, hipStream_t st)
+{
+    hipLaunchKernelGGL(policy_draw_next_kernel, dim3(1), dim3(1), 0, st, draw);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_repack(const PolUploads &U, hipStream_t st)
+{
+    if (U.n == 0) return hipSuccess;
+    hipLaunchKernelGGL(policy_repack_kernel, dim3(32, U.n), dim3(256), 0, st, U);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_activation(int act, const float *x, float *y, uint64_t n, hipStream_t st)
+{
+    if (n == 0) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255u) / 256u, 4096u);
+    hipLaunchKernelGGL(policy_activation_kernel, dim3(blocks), dim3(256), 0, st, act, x, y, n);
+    return hipGetLastError();
+}
+
+}  // namespace mbots

@@ -1,0 +1,276 @@
+// mbots_policy.hpp -- the device actor (include/mbots.h "Acting on the
+// device"; DESIGN.md "Device actor"): the arithmetic of the per-species policy
+// nets, their activations and the action sampling, shared by the HIP kernel
+// (mbots_kernels.hip) and the CPU mode's loops (mbots_cpu.cpp) so that both
+// give the same bits.
+//
+// Everything here is built from + - * /, fmaf, comparisons and integer
+// operations on the bits only -- no libm / ocml transcendental -- so the host
+// build (-ffp-contract=off) and the device round every step alike.
+#pragma once
+
+#include "mbots_device.hpp"
+
+#include <cmath>
+#include <cstdint>
+
+namespace mbots {
+
+constexpr int kPolObs = 69;            // construct_obs(prev = False) floats of a row
+constexpr int kPolActions = 6;
+constexpr int kPolMaxH = 128;          // trunk width: a multiple of 16 in [16, 128]
+constexpr int kPolMaxTrunk = 4;
+constexpr int kPolLayers = kPolMaxTrunk + 5;   // trunk, actor 2, critic 2, memory
+constexpr uint32_t kPolMemoryIn = 1u;  // MBOTS_POLICY_MEMORY_IN
+constexpr uint32_t kActGreedy = 1u, kActNoWrite = 2u;   // MBOTS_ACT_*
+// activation codes (mbots_policy_layer.act; 6 and 7 only through
+// mbots_policy_activation)
+constexpr int kActIdentity = 0, kActRelu = 1, kActLeaky = 2, kActTanh = 3, kActElu = 4, kActLogSigmoid = 5,
+              kActExp = 6, kActLog = 7;
+
+// input width rounded up to the k-step of the matrix instruction
+MB_HD uint32_t pol_kp(uint32_t in) { return (in + 3u) & ~3u; }
+
+MB_HD float pol_fma(float a, float b, float c)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __fmaf_rn(a, b, c);
+#else
+    return std::fmaf(a, b, c);
+#endif
+}
+
+// ln 2 in two parts: n * kLn2Hi is exact for |n| < 512
+constexpr float kLn2Hi = 0.693145751953125f, kLn2Lo = 1.42860654e-6f, kLog2e = 1.44269504f;
+
+MB_HD float pol_pow2(int32_t n) { return u2f((uint32_t)(n + 127) << 23); }   // n in [-126, 127]
+
+// range reduction of exp: y = n ln 2 + r, |r| <= ln 2 / 2 (+ a rounding)
+MB_HD float pol_reduce(float y, int32_t &n)
+{
+    const float t = y * kLog2e;
+    n = (int32_t)(t + (t < 0.0f ? -0.5f : 0.5f));
+    const float nf = (float)n;
+    return pol_fma(nf, -kLn2Lo, pol_fma(nf, -kLn2Hi, y));
+}
+// exp(r) - 1 on the reduced range: r + r^2 (1/2 + r/6 + ... + r^6/8!)
+MB_HD float pol_expm1_r(float r)
+{
+    float q = 1.0f / 40320.0f;
+    q = pol_fma(q, r, 1.0f / 5040.0f);
+    q = pol_fma(q, r, 1.0f / 720.0f);
+    q = pol_fma(q, r, 1.0f / 120.0f);
+    q = pol_fma(q, r, 1.0f / 24.0f);
+    q = pol_fma(q, r, 1.0f / 6.0f);
+    q = pol_fma(q, r, 0.5f);
+    return pol_fma(r * r, q, r);
+}
+
+// exp(x): 2^n (1 + expm1(r)), the scale applied in two exact-or-once-rounded
+// halves so that results down to the subnormals round once
+MB_HD float pol_exp(float x)
+{
+    if (!(x == x)) return x;
+    if (x > 88.72284f) return u2f(0x7F800000u);
+    if (x < -104.0f) return 0.0f;
+    int32_t n;
+    const float r = pol_reduce(x, n);
+    const float p = pol_expm1_r(r) + 1.0f;
+    const int32_t n1 = n >> 1, n2 = n - n1;
+    return (p * pol_pow2(n1)) * pol_pow2(n2);
+}
+
+// exp(y) - 1 for y in [-18, 19]: near 0 (n == 0) the series itself, else
+// (2^n - 1) + 2^n expm1(r) in one fmaf (2^n - 1 is exact up to n = 24)
+MB_HD float pol_expm1(float y)
+{
+    int32_t n;
+    const float r = pol_reduce(y, n);
+    const float e = pol_expm1_r(r);
+    if (n == 0) return e;
+    const float s = pol_pow2(n);
+    return pol_fma(s, e, s - 1.0f);
+}
+
+// log(1 + f) for f in [sqrt(1/2) - 1, sqrt(2) - 1]: s = f / (2 + f),
+// log(1 + f) = 2 atanh(s) = f - s (f - 2 P), P = s^2/3 + s^4/5 + ... + s^12/13
+MB_HD float pol_log1p_f(float f)
+{
+    const float s = f / (2.0f + f), z = s * s;
+    float p = 1.0f / 13.0f;
+    p = pol_fma(p, z, 1.0f / 11.0f);
+    p = pol_fma(p, z, 1.0f / 9.0f);
+    p = pol_fma(p, z, 1.0f / 7.0f);
+    p = pol_fma(p, z, 1.0f / 5.0f);
+    p = pol_fma(p, z, 1.0f / 3.0f);
+    p = p * z;
+    return pol_fma(-s, pol_fma(-2.0f, p, f), f);
+}
+MB_HD float pol_log_kf(int32_t k, float f)
+{
+    const float kf = (float)k;
+    return pol_fma(kf, kLn2Hi, pol_fma(kf, kLn2Lo, pol_log1p_f(f)));
+}
+
+// log(x), x > 0 (x = 2^k m, m in [sqrt(1/2), sqrt(2)), f = m - 1 exact)
+MB_HD float pol_log(float x)
+{
+    if (!(x == x)) return x;
+    if (x < 0.0f) return u2f(0x7FC00000u);
+    if (x == 0.0f) return u2f(0xFF800000u);
+    uint32_t b = f2u(x);
+    if (b >= 0x7F800000u) return x;
+    int32_t k = 0;
+    if (b < 0x00800000u) {   // subnormal: scaled up exactly first
+        b = f2u(x * 33554432.0f);
+        k = -25;
+    }
+    k += (int32_t)(b >> 23) - 127;
+    float m = u2f((b & 0x007FFFFFu) | 0x3F800000u);
+    if (m > 1.41421356f) {
+        m = m * 0.5f;
+        k += 1;
+    }
+    return pol_log_kf(k, m - 1.0f);
+}
+
+// log(1 + e) for e in [0, 1] with no rounding of 1 + e: f is e itself, or
+// (e - 1) / 2 against k = 1 (both exact)
+MB_HD float pol_log1p_01(float e)
+{
+    if (e < 0.41421356f) return pol_log1p_f(e);
+    return pol_log_kf(1, (e - 1.0f) * 0.5f);
+}
+
+MB_HD float pol_tanh(float x)
+{
+    if (!(x == x)) return x;
+    const float a = x < 0.0f ? -x : x;
+    float t = 1.0f;
+    if (a < 9.1f) {
+        const float e = pol_expm1(a + a);
+        t = e / (e + 2.0f);
+    }
+    return x < 0.0f ? -t : t;
+}
+
+MB_HD float pol_elu(float x)
+{
+    if (x > 0.0f || !(x == x)) return x;
+    if (x < -18.0f) return -1.0f;
+    return pol_expm1(x);
+}
+
+// log(sigmoid(x)) = min(x, 0) - log(1 + exp(-|x|))
+MB_HD float pol_logsigmoid(float x)
+{
+    if (!(x == x)) return x;
+    const float a = x < 0.0f ? -x : x;
+    const float l = pol_log1p_01(pol_exp(-a));
+    return x < 0.0f ? x - l : -l;
+}
+
+MB_HD float pol_activation(int code, float x)
+{
+    switch (code) {
+    case kActRelu: return x > 0.0f ? x : 0.0f;
+    case kActLeaky: return x >= 0.0f ? x : 0.01f * x;
+    case kActTanh: return pol_tanh(x);
+    case kActElu: return pol_elu(x);
+    case kActLogSigmoid: return pol_logsigmoid(x);
+    case kActExp: return pol_exp(x);
+    case kActLog: return pol_log(x);
+    default: return x;
+    }
+}
+
+// the row's uniform: keyed by (seed, draw) and counted by (global world,
+// species, index inside the (world, species) segment), so a shard ghost's rows
+// draw what the next rank draws for them
+MB_HD float pol_uniform(uint32_t seed, uint32_t draw, uint32_t gw, uint32_t species /* 1..4 */, uint32_t k)
+{
+    return u01(threefry2x32(seed, draw, gw, ((species - 1u) << 16) | k).x);
+}
+
+// softmax sampling of the six logits: returns the action, *logp its log
+// probability.  Prefix sums are plain f32 adds in index order.
+MB_HD int32_t pol_sample(const float z[kPolActions], float u, bool greedy, float *logp)
+{
+    float m = z[0];
+    int32_t am = 0;
+    for (int i = 1; i < kPolActions; ++i)
+        if (z[i] > m) {
+            m = z[i];
+            am = i;
+        }
+    float c[kPolActions];
+    float run = 0.0f;
+    for (int i = 0; i < kPolActions; ++i) {
+        run = run + pol_exp(z[i] - m);
+        c[i] = run;
+    }
+    const float s = c[kPolActions - 1];
+    int32_t a = am;
+    if (!greedy) {
+        const float us = u * s;
+        a = kPolActions - 1;
+        for (int i = kPolActions - 2; i >= 0; --i)
+            if (us < c[i]) a = i;
+    }
+    float za = z[0];
+    for (int i = 1; i < kPolActions; ++i)
+        if (i == a) za = z[i];
+    *logp = (za - m) - pol_log(s);
+    return a;
+}
+
+// ---- the nets as the kernel and the CPU loops read them ----
+// One Linear: the HIP path holds W in the B-fragment order of
+// v_mfma_f32_16x16x4_f32 -- [kp / 4][nt][64] with lane l of k-step ks and
+// column tile jt holding W[jt * 16 + (l & 15)][4 ks + (l >> 4)] -- and the
+// bias padded to nt * 16; the CPU mode holds W as [nt * 16][kp] rows.  Pads
+// are +0 on both sides.
+struct PolLayer {
+    float *w, *b;
+    uint32_t in, out, kp, nt, act;
+};
+struct PolNet {
+    uint32_t set, n_trunk, H, flags;   // flags: kPolMemoryIn
+    uint32_t has_memory, pad[3];
+    PolLayer trunk[kPolMaxTrunk], actor[2], critic[2], memory;
+};
+struct PolNets {
+    PolNet net[kNumSpecies];
+};
+MB_HD size_t pol_w_floats(const PolLayer &l) { return (size_t)l.kp * l.nt * 16u; }
+MB_HD size_t pol_b_floats(const PolLayer &l) { return (size_t)l.nt * 16u; }
+
+// the repack / pad of one layer's weights at upload (src: [out][in] row-major)
+struct PolUpload {
+    const float *w_src, *b_src;
+    float *w_dst, *b_dst;
+    uint32_t in, out, kp, nt;
+};
+struct PolUploads {
+    PolUpload l[kPolLayers];
+    uint32_t n;
+};
+
+// the 69 (with `hidden`: 85) input floats of a row from the table's columns, padded with +0 to kp
+MB_HD void pol_row_input(float *x, const uint8_t *dep, const int8_t *sem, int32_t hp, const float *pos,
+                         const float *sur, const float *hidden /* null: none */, uint32_t kp)
+{
+    for (int k = 0; k < kSensor; ++k) x[k] = (float)dep[k];
+    x[32] = u2f((uint32_t)hp);
+    x[33] = pos[0];
+    x[34] = pos[1];
+    for (int k = 0; k < kSensor; ++k) x[35 + k] = (float)sem[k];
+    x[67] = sur[0];
+    x[68] = sur[1];
+    uint32_t n = kPolObs;
+    if (hidden)
+        for (int k = 0; k < kHidden; ++k) x[n++] = hidden[k];
+    while (n < kp) x[n++] = 0.0f;
+}
+
+}  // namespace mbots

@@ -29,7 +29,7 @@ import torch  # loads the HIP runtime libmbots.so links against (same soname)
 __all__ = ["SimManager", "ScriptBotsViewer", "Tensor", "madrona", "ExportID", "ExecMode", "unpack_rollout",
            "unpack_learner", "rebuild_learner", "CapacityWarning", "CapacityError", "MAX_CAPACITY",
            "CAPACITY_CLASSES", "TrajectoryWindow", "RENDER_PALETTE", "RENDER_SCALES", "CLS_FLOOR", "CLS_WALL",
-           "CLS_FOOD", "CLS_BODY", "CLS_MARK"]
+           "CLS_FOOD", "CLS_BODY", "CLS_MARK", "PolicyNet", "policy_activation", "ACTIVATIONS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmbots.so")
@@ -60,6 +60,16 @@ class _RenderOut(ctypes.Structure):
 class _TrajBatch(ctypes.Structure):   # struct mbots_traj_batch
     _fields_ = [(k, ctypes.c_void_p) for k in ("rows", "t0", "len", "end", "obs", "reward", "value", "adv", "ret",
                                                "action_in", "hidden0")]
+
+
+class _PolicyLayer(ctypes.Structure):   # struct mbots_policy_layer
+    _fields_ = [("in_", ctypes.c_uint32), ("out", ctypes.c_uint32), ("act", ctypes.c_int32),
+                ("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p)]
+
+
+class _PolicyNet(ctypes.Structure):     # struct mbots_policy_net
+    _fields_ = [("n_trunk", ctypes.c_uint32), ("trunk", _PolicyLayer * 4), ("actor", _PolicyLayer * 2),
+                ("critic", _PolicyLayer * 2), ("memory", _PolicyLayer), ("flags", ctypes.c_uint32)]
 
 
 class _CTensor(ctypes.Structure):
@@ -127,6 +137,11 @@ def _load():
         "mbots_traj_gather": [vp, ctypes.c_uint64, ctypes.c_uint64, P(vp), u32, u32, vp, vp],
         "mbots_render_worlds": [vp, vp, u32, u32, P(_RenderOut), vp],
         "mbots_render_palette": [P(ctypes.c_uint8)],
+        "mbots_policy_set": [vp, u32, P(_PolicyNet), vp],
+        "mbots_policy_clear": [vp, u32],
+        "mbots_policy_act": [vp, u32, vp, vp, vp, ctypes.c_uint64, vp],
+        "mbots_policy_draw": [vp, i32, P(u32)],
+        "mbots_policy_activation": [i32, vp, vp, ctypes.c_uint64, i32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -509,6 +524,7 @@ class SimManager:
         self._ktiming = False
         self._gen = 0                # bumped when the columns' storage moves (a growth)
         self._traj = None            # the open TrajectoryWindow, if any
+        self._policy = [None] * 4    # the PolicyNet set per species (set_policy)
         self._episode_length = int(episode_length)
         if not 0 <= self._episode_length < 2 ** 32:
             raise ValueError("episode_length must be in [0, 2^32)")
@@ -586,6 +602,13 @@ class SimManager:
             raise
         if self._ktiming:
             self.enable_kernel_timing(True)
+        if any(n is not None for n in self._policy):   # the nets and the draw counter follow the hand-over
+            draw = ctypes.c_uint32()
+            _check(_lib.mbots_policy_draw(old[1], 0, ctypes.byref(draw)))
+            for sp, n in enumerate(self._policy):
+                if n is not None:
+                    self._set_policy_one(sp + 1, n)
+            _check(_lib.mbots_policy_draw(self._h, 1, ctypes.byref(draw)))
         del old                      # (freed now unless a view still holds it)
 
     def _stream(self):
@@ -869,6 +892,121 @@ class SimManager:
                                         ctypes.c_void_p(m.data_ptr() if m is not None else None), rows,
                                         self._stream()))
 
+    # -- acting on the device -------------------------------------------------
+    def _set_policy_one(self, species, net):
+        dev = self.device
+
+        def layer(spec):
+            w, b, act = spec
+            w = w.detach().to(device=dev, dtype=torch.float32).contiguous()
+            b = None if b is None else b.detach().to(device=dev, dtype=torch.float32).contiguous()
+            keep.extend((w, b))
+            return _PolicyLayer(w.shape[1], w.shape[0], act, w.data_ptr(), None if b is None else b.data_ptr())
+
+        keep = []
+        c = _PolicyNet()
+        c.n_trunk = len(net.trunk)
+        for i, spec in enumerate(net.trunk):
+            c.trunk[i] = layer(spec)
+        for i in range(2):
+            c.actor[i] = layer(net.actor[i])
+            c.critic[i] = layer(net.critic[i])
+        if net.memory is not None:
+            c.memory = layer(net.memory)
+        c.flags = 1 if net.memory_in else 0
+        # (the upload reads the tensors in stream order on torch's current
+        # stream, where the caching allocator also orders their release)
+        _check(_lib.mbots_policy_set(self._h, int(species), ctypes.byref(c), self._stream()))
+        self._policy[species - 1] = net
+
+    def set_policy(self, net, species=None):
+        """Give species 1..4 their policy nets (PolicyNet): one net for every
+        species, a list of four, or one net for `species`.  The first call, or
+        a net of another architecture, allocates; calling again with the same
+        architecture -- after every optimiser step -- only re-uploads the
+        weights, stream-ordered on torch's current stream (mbots_policy_set)."""
+        if species is not None:
+            if isinstance(net, (list, tuple)):
+                raise ValueError("one PolicyNet for one species")
+            nets = {int(species): net}
+        elif isinstance(net, (list, tuple)):
+            if len(net) != 4:
+                raise ValueError("a list of policy nets holds one per species (4)")
+            nets = {i + 1: n for i, n in enumerate(net)}
+        else:
+            nets = {i + 1: net for i in range(4)}
+        for sp, n in nets.items():
+            if not isinstance(n, PolicyNet):
+                raise TypeError("set_policy takes PolicyNet objects (PolicyNet.from_torch)")
+            if not 1 <= sp <= 4:
+                raise ValueError("species must be 1..4")
+        for sp, n in nets.items():
+            self._set_policy_one(sp, n)
+
+    def clear_policy(self, species=None):
+        for sp in ([int(species)] if species is not None else [1, 2, 3, 4]):
+            _check(_lib.mbots_policy_clear(self._h, sp))
+            self._policy[sp - 1] = None
+
+    def act(self, greedy=False, write=True, out=None):
+        """One stream-ordered call for policy(construct_obs()) -> sample ->
+        write_actions(): every table row (the shard ghost's too) runs its
+        species' net, an action is sampled from the manager's counter RNG
+        (greedy: the first maximal logit), and -- unless write=False -- Action
+        receives the one-hot and HiddenState the memory head's output.  Returns
+        {"action": int32 [N, 1], "logp": float32 [N, 1], "value": float32
+        [N, 1]} on `device` for the N exported rows.  `out`: a dict of such
+        tensors with at least N rows to write into (required while the stream
+        is being captured into a graph, where N is not known to the host; the
+        tensors are then returned whole)."""
+        capturing = self.exec_mode == ExecMode.HIP and torch.cuda.is_current_stream_capturing()
+        if out is None:
+            if capturing:
+                raise ValueError("act() under graph capture needs out= (the row count is not known to the host)")
+            n = self.num_agents()
+            out = {"action": torch.empty((n, 1), dtype=torch.int32, device=self.device),
+                   "logp": torch.empty((n, 1), dtype=torch.float32, device=self.device),
+                   "value": torch.empty((n, 1), dtype=torch.float32, device=self.device)}
+            rows = n
+        else:
+            rows = None
+            for k, dt in (("action", torch.int32), ("logp", torch.float32), ("value", torch.float32)):
+                t = out.get(k)
+                if t is None:
+                    continue
+                if t.dtype != dt or t.device != self.device or not t.is_contiguous() or t.dim() != 2 \
+                        or t.shape[1] != 1 or (rows is not None and t.shape[0] != rows):
+                    raise ValueError(f"out[{k!r}] must be a contiguous {dt} [rows, 1] tensor on {self.device}, "
+                                     "all of the same rows")
+                rows = t.shape[0]
+            n = None if capturing else self.num_agents()
+            if rows is not None and n is not None and rows < n:
+                raise ValueError(f"out tensors must hold at least {n} rows")
+
+        def ptr(k):
+            t = out.get(k)
+            return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+        flags = (1 if greedy else 0) | (0 if write else 2)
+        _check(_lib.mbots_policy_act(self._h, flags, ptr("action"), ptr("logp"), ptr("value"), rows or 0,
+                                     self._stream()))
+        if n is None:
+            return out
+        return {k: (t[:n] if t is not None else None) for k, t in out.items()}
+
+    @property
+    def policy_draw(self):
+        """The draw counter of act(): read by every act() and advanced by one
+        after it (so a replayed graph draws fresh numbers); set it back to
+        reproduce a rollout.  Not part of a checkpoint."""
+        v = ctypes.c_uint32()
+        _check(_lib.mbots_policy_draw(self._h, 0, ctypes.byref(v)))
+        return v.value
+
+    @policy_draw.setter
+    def policy_draw(self, value):
+        v = ctypes.c_uint32(int(value) & 0xFFFFFFFF)
+        _check(_lib.mbots_policy_draw(self._h, 1, ctypes.byref(v)))
+
     def save_checkpoint(self, path=None):
         """Live simulator state as bytes (and to `path` if given); see
         load_checkpoint.  Not in the reference."""
@@ -1052,6 +1190,132 @@ class SimManager:
         n = (ctypes.c_uint64 * len(KERNELS))()
         _check(_lib.mbots_kernel_times(self._h, ms, n))
         return {k: (ms[i], n[i]) for i, k in enumerate(KERNELS)}
+
+
+# activation codes of the device actor (include/mbots.h; 6 and 7: its own exp
+# and log, through policy_activation only)
+ACTIVATIONS = {"Identity": 0, "ReLU": 1, "LeakyReLU": 2, "Tanh": 3, "ELU": 4, "LogSigmoid": 5, "exp": 6, "log": 7}
+
+
+def _activation_code(m, where):
+    nn = torch.nn
+    if isinstance(m, nn.ReLU):
+        return 1
+    if isinstance(m, nn.LeakyReLU):
+        if m.negative_slope != 0.01:
+            raise ValueError(f"{where}: LeakyReLU is supported with negative_slope 0.01 only, not {m.negative_slope}")
+        return 2
+    if isinstance(m, nn.Tanh):
+        return 3
+    if isinstance(m, nn.ELU):
+        if m.alpha != 1.0:
+            raise ValueError(f"{where}: ELU is supported with alpha 1 only, not {m.alpha}")
+        return 4
+    if isinstance(m, nn.LogSigmoid):
+        return 5
+    if isinstance(m, nn.Identity):
+        return 0
+    return None
+
+
+class PolicyNet:
+    """One species' net for SimManager.set_policy / act(): trunk, a list of
+    (weight [out, in], bias [out] or None, activation code) for 1..4 Linear
+    layers of one width H (a multiple of 16 in [16, 128]); actor and critic,
+    two (weight, bias, 0) layers each -- Linear(H, H), ReLU, Linear(H, 6 / 1);
+    memory, a (weight [16, H], bias, 0) Linear followed by Tanh whose output
+    becomes HiddenState, or None; memory_in: the row's 16 HiddenState floats
+    follow its 69 observation floats as the input.  The tensors are referenced,
+    not copied: set_policy() uploads their values of that moment."""
+
+    def __init__(self, trunk, actor, critic, memory=None, memory_in=False):
+        self.trunk, self.actor, self.critic = list(trunk), list(actor), list(critic)
+        self.memory, self.memory_in = memory, bool(memory_in)
+        if not 1 <= len(self.trunk) <= 4:
+            raise ValueError(f"a policy net has 1..4 trunk Linear layers, not {len(self.trunk)}")
+        if len(self.actor) != 2 or len(self.critic) != 2:
+            raise ValueError("actor and critic are Linear, ReLU, Linear")
+
+    @staticmethod
+    def _linears(seq, name):
+        """[(weight, bias, code)] of a Sequential of Linear layers, each with at
+        most one supported activation after it."""
+        nn = torch.nn
+        mods = list(seq) if isinstance(seq, nn.Sequential) else [seq]
+        out = []
+        for i, m in enumerate(mods):
+            where = f"{name}[{i}] ({type(m).__name__})"
+            if isinstance(m, nn.Linear):
+                out.append([m.weight, m.bias, 0, False])
+                continue
+            code = _activation_code(m, where)
+            if code is None:
+                raise ValueError(f"{where}: only Linear, ReLU, LeakyReLU, Tanh, ELU, LogSigmoid and Identity are "
+                                 "supported by the device actor")
+            if not out or out[-1][3]:
+                raise ValueError(f"{where}: an activation must follow a Linear layer, one at most")
+            out[-1][2], out[-1][3] = code, True
+        return [(w, b, c) for w, b, c, _ in out]
+
+    @classmethod
+    def from_torch(cls, feature, actor, critic, memory=None, memory_in=False):
+        """From nn.Sequential stacks of Linear plus {Tanh, ELU, LogSigmoid,
+        LeakyReLU, ReLU}: the reference's a2c_nets.feature / .actor / .critic
+        load unchanged (its recurrent module is not executed: see
+        INTEGRATION.md).  memory: Sequential(Linear(H, 16), Tanh) or None."""
+        trunk = cls._linears(feature, "feature")
+        heads = []
+        for name, seq, width in (("actor", actor, 6), ("critic", critic, 1)):
+            ls = cls._linears(seq, name)
+            if len(ls) != 2 or ls[0][2] != 1 or ls[1][2] != 0:
+                raise ValueError(f"{name}: expected Linear, ReLU, Linear (as the reference builds it)")
+            if ls[1][0].shape[0] != width:
+                raise ValueError(f"{name}: the last Linear must have {width} outputs, not {ls[1][0].shape[0]}")
+            heads.append([(w, b, 0) for w, b, _ in ls])
+        mem = None
+        if memory is not None:
+            ls = cls._linears(memory, "memory")
+            if len(ls) != 1 or ls[0][2] != 3 or ls[0][0].shape[0] != 16:
+                raise ValueError("memory: expected Linear(H, 16), Tanh")
+            mem = (ls[0][0], ls[0][1], 0)
+        net = cls(trunk, heads[0], heads[1], mem, memory_in)
+        net._validate()
+        return net
+
+    def _validate(self):
+        H = self.trunk[0][0].shape[0]
+        if H % 16 or not 16 <= H <= 128:
+            raise ValueError(f"feature[0] (Linear): the trunk width must be a multiple of 16 in [16, 128], not {H}")
+        want = 85 if self.memory_in else 69
+        for i, (w, _, _) in enumerate(self.trunk):
+            if tuple(w.shape) != (H, want):
+                raise ValueError(f"feature Linear {i}: expected weight [{H}, {want}], not {list(w.shape)}")
+            want = H
+        for name, head, width in (("actor", self.actor, 6), ("critic", self.critic, 1)):
+            if tuple(head[0][0].shape) != (H, H) or tuple(head[1][0].shape) != (width, H):
+                raise ValueError(f"{name}: expected Linear({H}, {H}), ReLU, Linear({H}, {width})")
+        if self.memory is not None and tuple(self.memory[0].shape) != (16, H):
+            raise ValueError(f"memory: expected Linear({H}, 16)")
+
+
+def policy_activation(act, x):
+    """The device actor's own activation (a name of ACTIVATIONS or its code)
+    of a float32 tensor, on the tensor's device: what act() computes, bit for
+    bit, in both execution modes (mbots_policy_activation)."""
+    code = ACTIVATIONS[act] if isinstance(act, str) else int(act)
+    x = x.contiguous()
+    if x.dtype != torch.float32:
+        raise ValueError("policy_activation takes float32")
+    y = torch.empty_like(x)
+    if x.is_cuda:
+        with torch.cuda.device(x.device):
+            _check(_lib.mbots_policy_activation(code, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
+                                                x.numel(), x.device.index,
+                                                ctypes.c_void_p(_raw_stream(x.device.index))))
+    else:
+        _check(_lib.mbots_policy_activation(code, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
+                                            x.numel(), -1, None))
+    return y
 
 
 class TrajectoryWindow:

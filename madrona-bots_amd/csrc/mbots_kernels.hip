@@ -1163,6 +1163,10 @@ __device__ __forceinline__ void export_world(const SimState &S, const ObsTable &
         // old row: K1's obsrow_out (the sensor reads it beside this kernel);
         // the new row goes to obsrow, which the next K1 reads
         S.src_of[r] = old;
+        // the composed row map of lazy HiddenState (DESIGN.md "Lazy
+        // HiddenState"): this row's row in the table the stretch began with;
+        // map_in is the last step's buffer, never this step's
+        if (!init && S.map_out) S.map_out[r] = S.map_in ? (old >= 0 ? S.map_in[old] : -1) : old;
         S.obsrow[base + i] = row;
         constexpr bool nt = (MB_NT & 4) != 0;
         st_stream(nxt.species + r, sp, nt);
@@ -1304,15 +1308,27 @@ __device__ __forceinline__ void gather_seg(const MoveSeg &sg, uint32_t N, const 
 // the fused shift (DESIGN.md "Deferred Prev moves"): Action / HiddenState
 // gathered from the other half into the Prev columns (the current ones are
 // left as their views: DESIGN.md "Aliased current Action / HiddenState")
+// (rows_out: the lazy shift leaves HiddenState out and records the table's row
+// count for the gather that materialises it later)
 __global__ __launch_bounds__(256) void shift_move_kernel(const uint32_t *totals, const int32_t *src_of,
-                                                         MoveArgs args)
+                                                         MoveArgs args, uint32_t *rows_out)
 {
     const MoveSeg &sg = args.seg[blockIdx.y];
     const uint32_t N = totals[kTotRows];
+    if (rows_out && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) *rows_out = N;
     if (sg.width == 8 && sg.ipr == 3) gather_seg<uint2, 3>(sg, N, src_of);
     else if (sg.width == 16 && sg.ipr == 4) gather_seg<uint4, 4>(sg, N, src_of);
     else if (sg.width == 16 && sg.ipr == 2) gather_seg<uint4, 2>(sg, N, src_of);
     else move_rows(totals, src_of, args);
+}
+
+// lazy HiddenState materialised: dst[r] = base[map[r]] (0 where map[r] < 0) over
+// the *rows rows the lazy shift recorded -- 0 after the gather has run once, so
+// a replayed graph that recorded it repeats nothing
+__global__ __launch_bounds__(256) void materialize_hidden_kernel(const uint32_t *rows, const int32_t *map,
+                                                                 MoveSeg sg)
+{
+    gather_seg<uint4, 4>(sg, *rows, map);
 }
 
 // ---------------------------------------------------------------------------
@@ -2910,7 +2926,7 @@ hipError_t launch_export_rows(const SimState &S, const ObsTable &nxt, int init, 
 #error "MB_PROBE_SHIFT drops moves: a probe build (scripts/build_var.sh -DMB_PROBE_BUILD) only"
 #endif
 hipError_t launch_move(const SimState &S, const ObsTable &cur, const ObsTable &nxt, int prev_lazy,
-                       int parts, hipStream_t st)
+                       int parts, hipStream_t st, uint32_t *lazy_rows)
 {
     MoveArgs m{};
     int k = 0;
@@ -2929,7 +2945,7 @@ hipError_t launch_move(const SimState &S, const ObsTable &cur, const ObsTable &n
         if (MB_PROBE_SHIFT == 3) parts &= ~kMoveSensor;
 #else
         add(nxt.paction, cur.action, 8, 3);
-        add(nxt.phidden, cur.hidden, 16, 4);
+        if (!lazy_rows) add(nxt.phidden, cur.hidden, 16, 4);
 #endif
     }
     if (parts & kMoveSensor) {
@@ -2971,9 +2987,20 @@ hipError_t launch_move(const SimState &S, const ObsTable &cur, const ObsTable &n
                             ? std::max(256u, std::min(std::min(full, (unsigned)MB_MOVE_SMALL_CAP), S.W / 2u))
                             : full;
     if (parts & kMoveAHShift)
-        hipLaunchKernelGGL(shift_move_kernel, dim3(bx, k), dim3(256), 0, st, S.totals, S.src_of, m);
+        hipLaunchKernelGGL(shift_move_kernel, dim3(bx, k), dim3(256), 0, st, S.totals, S.src_of, m, lazy_rows);
     else
         hipLaunchKernelGGL(move_kernel, dim3(bx, k), dim3(256), 0, st, S.totals, S.src_of, m);
+    return hipGetLastError();
+}
+hipError_t launch_materialize_hidden(const SimState &S, const uint32_t *rows, const int32_t *map, const float *base,
+                                     float *dst, hipStream_t st)
+{
+    const MoveSeg sg{dst, base, 16u, 4u, 0u};
+    const unsigned bx = MB_MOVE_SMALL && S.W < 65536u
+                            ? std::max(256u, std::min(std::min((unsigned)MB_MOVE_BLOCKS, (unsigned)MB_MOVE_SMALL_CAP),
+                                                      S.W / 2u))
+                            : (unsigned)MB_MOVE_BLOCKS;
+    hipLaunchKernelGGL(materialize_hidden_kernel, dim3(bx), dim3(256), 0, st, rows, map, sg);
     return hipGetLastError();
 }
 // a dispatch whose completion records `done`: carried by the dispatch packet

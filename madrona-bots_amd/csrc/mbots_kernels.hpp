@@ -34,6 +34,11 @@ struct SimState {
     int32_t *row_base;              // [W][4] first export row of (world, species)
     int32_t *world_off;             // [W] world-major agent offsets
     int32_t *src_of;                // [W*cap] new export row -> old row (-1: new agent)
+    // lazy HiddenState (set by the host per step): K3a also stores the row map
+    // composed over the stretch, map_out[new] = map_in[old] (map_in null: old;
+    // old < 0: -1) -- two buffers by step parity, never the same one
+    const int32_t *map_in;
+    int32_t *map_out;
     uint32_t *overflow;             // [W] dropped births/respawns
     uint32_t *totals;               // [0] = N, [1..4] = per-species rows, [kTotRows] = table rows
                                     // incl. the shard ghost's (after row N), [kTotOverflow]
@@ -156,8 +161,13 @@ hipError_t launch_export_rows(const SimState &S, const ObsTable &nxt, int init, 
 // PrevAction / PrevHiddenState; the six other Prev* columns
 constexpr int kMoveAH = 1, kMoveAHShift = 2, kMoveSensor = 4, kMovePrevAH = 8, kMovePrev6 = 16;
 constexpr int kMoveAll = kMoveAH | kMoveSensor | kMovePrevAH | kMovePrev6;
+// (lazy_rows, with kMoveAHShift: the lazy shift -- Action only, and the row
+// count stored there for launch_materialize_hidden)
 hipError_t launch_move(const SimState &S, const ObsTable &cur, const ObsTable &nxt, int prev_lazy,
-                       int parts, hipStream_t st);
+                       int parts, hipStream_t st, uint32_t *lazy_rows = nullptr);
+// dst[r] = base[map[r]] (0 where map[r] < 0) for r < *rows: 64 B rows
+hipError_t launch_materialize_hidden(const SimState &S, const uint32_t *rows, const int32_t *map, const float *base,
+                                     float *dst, hipStream_t st);
 hipError_t launch_sensor(const SimState &S, const ObsTable &nxt, hipStream_t st,
                          hipEvent_t done = nullptr, bool plain_events = false);
 // shift modes: every Prev* column / Action + HiddenState only (lazy) / the six

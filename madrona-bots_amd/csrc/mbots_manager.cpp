@@ -145,6 +145,22 @@ struct mbots_handle {
     bool h_alias[2] = {false, false};
     bool prev_lazy[2] = {false, false};   // table half's six shift-owned Prev* columns are
                                           // still its current ones (lazy shift, K5)
+    // lazy HiddenState (DESIGN.md "Lazy HiddenState"): half hid_half's
+    // PrevHiddenState storage holds nothing; the column is hid_base[map[r]] (0
+    // where map[r] < 0) with map = hid_map2[hid_map], the row map K3a composes
+    // every step, and while h_alias[hid_half] holds HiddenState is that too.
+    // hid_base is one of the two PrevHiddenState storages and is not written
+    // while the state holds.  The lazy half is the current one after a lazy
+    // shift and the last one after a step; materialize_hidden ends the state
+    bool hid_lazy = false;
+    int hid_half = 0;
+    int hid_map = 0;
+    bool hid_map_plain = false;       // the last step stored src_of as its map (it ran not lazy):
+                                      // the map a stretch may begin with
+    const float *hid_base = nullptr;
+    int32_t *hid_map2[2] = {nullptr, nullptr};   // the maps of alternate steps (by parity)
+    uint32_t *hid_rows = nullptr;     // device word: the lazy half's row count (the lazy shift
+                                      // stores it; 0 once materialised)
     hipEvent_t ev_hop = nullptr;      // orders a call's stream after the last one used
     // the swapped schedule (above 8192 worlds unless MBOTS_SWAP=0): K1 and K2 on
     // the sensor's stream, the caller's stream joining after K2 (DESIGN.md 4
@@ -364,6 +380,11 @@ size_t layout(mbots_handle *h, Arena &a)
     S.row_base = h->row_base2[0];
     S.world_off = a.take<int32_t>(W);
     S.src_of = a.take<int32_t>(rows);
+    h->hid_map2[0] = a.take<int32_t>(rows);
+    h->hid_map2[1] = a.take<int32_t>(rows);
+    h->hid_rows = a.take<uint32_t>(1);
+    S.map_in = nullptr;
+    S.map_out = nullptr;
     S.overflow = a.take<uint32_t>(W);
     S.fork_ctr = a.take<uint32_t>(1);
     S.totals = a.take<uint32_t>(8);
@@ -525,6 +546,33 @@ int materialize_prev(mbots_handle *h, hipStream_t st)
     return MBOTS_OK;
 }
 
+// lazy HiddenState ends (DESIGN.md "Lazy HiddenState"): the lazy half's
+// PrevHiddenState gathered from the base along the composed map into its
+// storage -- the state a fused shift leaves (HiddenState its view while
+// h_alias holds), whichever half is lazy, so every deferred move that follows
+// finds real rows.  Never in place: when the base is that storage the rows go
+// to the other half's PrevHiddenState storage and the halves exchange the two
+// (that one is free while the state holds: the other half's PrevHiddenState
+// is dead after a shift, and owed -- written before it is read -- after a step)
+int materialize_hidden(mbots_handle *h, hipStream_t st)
+{
+    if (!h->hid_lazy) return MBOTS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const int hh = h->hid_half;
+    if (h->T[hh].phidden == h->hid_base) std::swap(h->T[hh].phidden, h->T[hh ^ 1].phidden);
+    const int rc = timed(h, MBOTS_TK_MOVE, st, [&] {
+        return mbots::launch_materialize_hidden(h->S, h->hid_rows, h->hid_map2[h->hid_map], h->hid_base,
+                                                h->T[hh].phidden, st);
+    });
+    if (rc) return rc;
+    // (a graph that recorded the gather repeats it over 0 rows: the state it
+    // ends is the host's, not the device's at a replay)
+    HIP_TRY(mbots::launch_raise_flag(h->hid_rows, 0u, st));
+    h->hid_lazy = false;
+    h->hid_base = nullptr;
+    return MBOTS_OK;
+}
+
 // the deferred K4 part: PrevAction / PrevHiddenState of the current half from
 // the other half, along the last step's src_of (both intact until the next
 // step's K3a / K4)
@@ -532,6 +580,7 @@ int materialize_cur_ah(mbots_handle *h, hipStream_t st, int alias_cols);
 int materialize_prev_ah(mbots_handle *h, hipStream_t st)
 {
     if (!h->ah_pending[h->tb]) return MBOTS_OK;
+    if (int rc = materialize_hidden(h, st)) return rc;   // (its source is the last half's PrevHiddenState)
     // the Prev storage holds the current columns (aliased): copied out before
     // the Prev move overwrites it
     const int cols = (h->a_alias[h->tb] ? 1 : 0) | (h->h_alias[h->tb] ? 2 : 0);
@@ -556,6 +605,9 @@ int sync_totals(mbots_handle *h);
 int materialize_cur_ah(mbots_handle *h, hipStream_t st, int alias_cols)
 {
     const int tb = h->tb;
+    // (lazy HiddenState: the move's source, or the column copied out)
+    if (h->cur_ah_pending[tb] || ((alias_cols & 2) && h->h_alias[tb]))
+        if (int rc = materialize_hidden(h, st)) return rc;
     if (h->cur_ah_pending[tb]) {
         HIP_TRY(hipSetDevice(h->device));
         const mbots::ObsTable src = src_view(h, tb ^ 1);
@@ -1173,6 +1225,14 @@ int mbots_step(mbots_handle *h, void *stream)
     int prefetch = h->forced;
     h->forced = 0;
     h->prefetched = prefetch;
+    // lazy HiddenState goes on only from a shift (the lazy half is then the
+    // current one, its map the last step's): after a step with no shift, before
+    // a prefetch of Action / HiddenState or their Prev columns, and under
+    // stream capture (a replay must not depend on the host's lazy state) it
+    // is materialised first
+    if (h->hid_lazy && (h->hid_half != h->tb || h->hid_map == par || capturing ||
+                        (prefetch & (mbots::kMoveAH | mbots::kMovePrevAH))))
+        if ((rc = materialize_hidden(h, st))) return rc;
     // no shift since the last step: its deferred Prev moves first
     if (h->six_pending[h->tb] && (rc = materialize_prev(h, st))) return rc;
     if ((rc = materialize_prev_ah(h, st))) return rc;
@@ -1321,6 +1381,16 @@ int mbots_step(mbots_handle *h, void *stream)
         HIP_TRY(mbots::launch_raise_flag(h->sig_join, epoch, h->aux));
         h->join_epoch = epoch;
     }
+    // K3a composes the row map of lazy HiddenState into this step's buffer from
+    // the last step's (the other one: the lazy half's map stays readable until
+    // the next shift moves on to this one); not lazy, it stores src_of there,
+    // the map a lazy shift begins a stretch with -- only where the next shift
+    // could begin one: HiddenState is a view now (nothing but a shift makes it
+    // one), so a loop that writes memory every step stores no map
+    const bool map_wanted = h->hid_lazy || (h->h_alias[h->tb] && h->cap_seen == 0 && !capturing);
+    h->S.map_out = map_wanted ? h->hid_map2[par] : nullptr;
+    h->S.map_in = h->hid_lazy ? h->hid_map2[h->hid_map] : nullptr;
+    h->hid_map_plain = map_wanted && !h->hid_lazy;
     if ((rc = timed(h, MBOTS_TK_EXPORT, st,
                     [&] { return mbots::launch_export_rows(h->S, nxt, 0, st); })))
         return rc;
@@ -1376,13 +1446,43 @@ int mbots_shift_observations(mbots_handle *h, void *stream)
     // (DESIGN.md "Lazy prev sensor").
     const int tb = h->tb;
     const bool fused = h->cur_ah_pending[tb];
+    // Lazy HiddenState (DESIGN.md "Lazy HiddenState"): the last half's
+    // HiddenState is still only a view -- of its PrevHiddenState storage (a
+    // fused shift's: nobody copied it out or wrote it since), or of the lazy
+    // column -- so this half's HiddenState / PrevHiddenState are those rows
+    // along src_of: not gathered but owed, as (base, composed map).  The base
+    // is that storage on entry and stays while the state goes on.  Not under
+    // stream capture, nor once a graph of this manager's steps exists (its
+    // replays read the columns in the storages they recorded).
+    const bool old_lazy = h->hid_lazy && h->hid_half == (tb ^ 1);
+    const bool lazy = fused && h->h_alias[tb ^ 1] && h->cap_seen == 0 && !capturing(st) &&
+                      (old_lazy || (!h->hid_lazy && h->hid_map_plain));
+    if (fused && h->hid_lazy && !lazy) {
+        // the last half's lazy PrevHiddenState: the source of HiddenState here
+        // while that is its view; else dead (this shift overwrites what derives
+        // from it), and its base is free again
+        if (h->h_alias[tb ^ 1]) {
+            if ((rc = materialize_hidden(h, st))) return rc;
+        } else {
+            h->hid_lazy = false;
+        }
+    }
     if (fused) {
         const mbots::ObsTable src = src_view(h, tb ^ 1);
         rc = timed(h, MBOTS_TK_SHIFT, st, [&] {
-            return mbots::launch_move(h->S, src, h->T[tb], 0, mbots::kMoveAHShift, st);
+            return mbots::launch_move(h->S, src, h->T[tb], 0, mbots::kMoveAHShift, st, lazy ? h->hid_rows : nullptr);
         });
+        if (rc == MBOTS_OK && lazy) {
+            if (!old_lazy) h->hid_base = h->T[tb ^ 1].phidden;
+            h->hid_lazy = true;
+            h->hid_half = tb;
+            h->hid_map = h->parity ^ 1;   // the last step's buffer
+        }
     } else if (!(h->a_alias[tb] && h->h_alias[tb])) {   // both aliased: already equal
         if ((rc = materialize_cur_ah(h, st, 3))) return rc;
+        // (HiddenState was written since a lazy shift: the lazy PrevHiddenState
+        // is overwritten here)
+        if (h->hid_lazy && h->hid_half == tb) h->hid_lazy = false;
         rc = timed(h, MBOTS_TK_SHIFT, st,
                    [&] { return mbots::launch_shift(h->S, h->T[tb], mbots::kShiftEager, st); });
     }
@@ -1438,6 +1538,7 @@ int mbots_export_on(mbots_handle *h, int32_t id, void *stream, mbots_tensor *out
         break;
     case MBOTS_EXPORT_PREV_ACTION: case MBOTS_EXPORT_PREV_HIDDEN_STATE:
         need = mbots::kMovePrevAH;
+        if (id == MBOTS_EXPORT_PREV_HIDDEN_STATE && (rc = materialize_hidden(h, st))) return rc;
         if ((rc = materialize_prev_ah(h, st))) return rc;
         break;
     case MBOTS_EXPORT_ACTION: case MBOTS_EXPORT_HIDDEN_STATE:
@@ -1674,6 +1775,7 @@ int mbots_pack_learner(mbots_handle *h, void *out, uint64_t out_rows, void *stre
     // moves the learner's reads need (and remembered, like the accessors', so
     // the next step prefetches them beside its sensor)
     const int owed = pending_mask(h);
+    if ((rc = materialize_hidden(h, st))) return rc;
     if ((rc = materialize_prev(h, st))) return rc;
     if ((rc = materialize_prev_ah(h, st))) return rc;
     if ((rc = materialize_cur_ah(h, st, 3))) return rc;
@@ -1980,7 +2082,8 @@ int mbots_save_checkpoint(mbots_handle *h, void *dst, uint64_t bytes)
     }
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = capture_guard(h, h->last_stream)) return rc;
-    int rc0 = materialize_prev(h, h->last_stream);
+    int rc0 = materialize_hidden(h, h->last_stream);
+    if (!rc0) rc0 = materialize_prev(h, h->last_stream);
     if (!rc0) rc0 = materialize_prev_ah(h, h->last_stream);
     if (!rc0) rc0 = materialize_cur_ah(h, h->last_stream, 3);
     if (!rc0) rc0 = materialize_psem(h, h->last_stream);
@@ -2040,6 +2143,9 @@ static int restored_reset(mbots_handle *h, bool sensed)
     h->cur_ah_pending[0] = h->cur_ah_pending[1] = false;
     h->psem_pending[0] = h->psem_pending[1] = false;
     h->a_alias[0] = h->a_alias[1] = h->h_alias[0] = h->h_alias[1] = false;
+    h->hid_lazy = false;
+    h->hid_map_plain = false;
+    h->hid_base = nullptr;
     h->forced = 0;
     h->prefetched = 0;
     h->steps = 1;
@@ -2159,12 +2265,14 @@ struct LayoutPtrs {
     mbots::ObsTable T[2];
     int32_t *row_base2[2], *sorder2[2], *obsrow_out2[2], *done_zeros, *reset_flags, *sensor_index;
     int32_t *episode, *age;
+    int32_t *hid_map2[2];
+    uint32_t *hid_rows;
 };
 LayoutPtrs layout_ptrs(const mbots_handle *h)
 {
     return {h->S, {h->T[0], h->T[1]}, {h->row_base2[0], h->row_base2[1]}, {h->sorder2[0], h->sorder2[1]},
             {h->obsrow_out2[0], h->obsrow_out2[1]}, h->done_zeros, h->reset_flags, h->sensor_index,
-            h->episode, h->age};
+            h->episode, h->age, {h->hid_map2[0], h->hid_map2[1]}, h->hid_rows};
 }
 void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
 {
@@ -2174,7 +2282,9 @@ void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
         h->row_base2[k] = p.row_base2[k];
         h->sorder2[k] = p.sorder2[k];
         h->obsrow_out2[k] = p.obsrow_out2[k];
+        h->hid_map2[k] = p.hid_map2[k];
     }
+    h->hid_rows = p.hid_rows;
     h->done_zeros = p.done_zeros;
     h->reset_flags = p.reset_flags;
     h->sensor_index = p.sensor_index;
@@ -2212,7 +2322,8 @@ int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
                                      "a new manager (or load a checkpoint into one) to change agent_capacity");
     if ((uint64_t)h->S.W * new_capacity >= (1ull << 31))
         return fail(MBOTS_E_INVALID, "num_worlds * agent_capacity >= 2^31");
-    int rc = materialize_prev(h, h->last_stream);
+    int rc = materialize_hidden(h, h->last_stream);
+    if (!rc) rc = materialize_prev(h, h->last_stream);
     if (!rc) rc = materialize_prev_ah(h, h->last_stream);
     if (!rc) rc = materialize_cur_ah(h, h->last_stream, 3);
     if (!rc) rc = materialize_psem(h, h->last_stream);
@@ -2637,7 +2748,7 @@ int mbots_schedule_info(mbots_handle *h, uint32_t out[4])
         return MBOTS_OK;
     }
     out[0] = (h->k1_finder ? 1u : 0u) | (h->sig_fork ? 2u : 0u) | (h->sig_join ? 4u : 0u) | (h->swap ? 8u : 0u) |
-             (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u);
+             (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u) | (h->hid_lazy ? 64u : 0u);
     out[1] = h->epoch;
     out[2] = h->epoch_wraps;
     out[3] = (uint32_t)h->steps;
@@ -3277,9 +3388,15 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
     if ((rc = wait_sensor(h, st))) return rc;
     if ((rc = materialize_cur_ah(h, st, 0))) return rc;
     note_use(h, mbots::kMoveAH, owed);
+    bool writes_hidden = false, reads_hidden = false;
+    for (int s = 0; s < mbots::kNumSpecies; ++s) {
+        writes_hidden |= h->pol.nets.net[s].has_memory != 0;
+        reads_hidden |= (h->pol.nets.net[s].flags & mbots::kPolMemoryIn) != 0u;
+    }
+    // (a lazy HiddenState column a net reads, or keeps rows of: real rows first;
+    // memoryless nets leave it lazy)
+    if ((reads_hidden || writes_hidden) && h->h_alias[tb] && (rc = materialize_hidden(h, st))) return rc;
     const mbots::ObsTable view = src_view(h, tb);
-    bool writes_hidden = false;
-    for (int s = 0; s < mbots::kNumSpecies; ++s) writes_hidden |= h->pol.nets.net[s].has_memory != 0;
     const bool write = !(flags & MBOTS_ACT_NO_WRITE);
     // a net without a memory head leaves its rows' HiddenState as it is: if the
     // column is written at all (another species' head) while still aliased, the

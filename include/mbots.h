@@ -756,6 +756,54 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
 int mbots_policy_draw(mbots_handle *h, int32_t set, uint32_t *value);
 int mbots_policy_activation(int32_t act, const float *x, float *y, uint64_t n, int32_t device, void *stream);
 
+/* Learning from what the actor did: a net evaluated on recorded (obs, action)
+ * rows, and the gradients of its parameters (DESIGN.md "Differentiable
+ * evaluate" is the specification).  Learner side, no manager: device >= 0 means
+ * device memory of that GPU on `stream`, device == -1 host memory on the host
+ * threads (MBOTS_CPU_THREADS); both give the same bits, whatever the grid or
+ * the thread count.  `net` is what mbots_policy_set takes, with the same
+ * checks; its pointers are read in stream order during the call.  The memory
+ * head takes no part and receives no gradient.
+ *
+ * mbots_policy_eval: obs [n][69] f32 (mbots_construct_obs rows), hidden [n][16]
+ * (MBOTS_POLICY_MEMORY_IN nets; else ignored, may be NULL), action int32 [n] in
+ * 0..5.  logp[r] and value[r] are bit for bit what mbots_policy_act returned
+ * for that row, net and action; entropy[r] is the softmax's.  Any output may
+ * be NULL.
+ *
+ * mbots_policy_grad: g_logp, g_value, g_entropy [n] are d loss / d output per
+ * row (NULL: zeros); every non-NULL pointer of `out` receives the gradient of
+ * the loss with respect to that weight ([out][in]) or bias ([out]); out->memory
+ * is ignored.  n == 0 writes zeros.  The sums run in a fixed order: rows in
+ * tiles of 64, tile i into accumulator i mod 256, each accumulator over its
+ * rows in ascending order, the accumulators added in ascending index.  No
+ * gradient is returned for obs or hidden.
+ *
+ * workspace: mbots_policy_grad_workspace(net, n, &bytes) bytes (enough for
+ * either call of this architecture at up to n rows), 16-byte aligned, of
+ * the same memory kind as the rows; its contents are scratch.  The calls
+ * allocate nothing and never wait for the host, so they can be captured into a
+ * graph.  An action outside 0..5 is refused on the host path (MBOTS_E_INVALID);
+ * on the device it is the caller's contract (such a row takes part as if no
+ * logit were its action's). */
+struct mbots_policy_grad_layer {
+    float *weight;           /* [out][in], or NULL: not wanted */
+    float *bias;             /* [out], or NULL */
+};
+struct mbots_policy_grads {
+    struct mbots_policy_grad_layer trunk[MBOTS_POLICY_MAX_TRUNK];
+    struct mbots_policy_grad_layer actor[2], critic[2];
+    struct mbots_policy_grad_layer memory;   /* ignored: the memory head receives no gradient */
+};
+int mbots_policy_grad_workspace(const struct mbots_policy_net *net, uint64_t n, uint64_t *bytes);
+int mbots_policy_eval(const struct mbots_policy_net *net, const float *obs, const float *hidden,
+                      const int32_t *action, uint64_t n, float *logp, float *value, float *entropy,
+                      void *workspace, uint64_t workspace_bytes, int32_t device, void *stream);
+int mbots_policy_grad(const struct mbots_policy_net *net, const float *obs, const float *hidden,
+                      const int32_t *action, uint64_t n, const float *g_logp, const float *g_value,
+                      const float *g_entropy, const struct mbots_policy_grads *out, void *workspace,
+                      uint64_t workspace_bytes, int32_t device, void *stream);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That

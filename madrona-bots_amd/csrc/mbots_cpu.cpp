@@ -971,6 +971,150 @@ void Sim::policy_act(const PolNets &nets, uint32_t flags, uint32_t draw, int32_t
     });
 }
 
+// ---- evaluate and its backward pass (DESIGN.md "Differentiable evaluate") ----
+namespace {
+unsigned host_threads()
+{
+    const char *e = getenv("MBOTS_CPU_THREADS");
+    const unsigned n = e ? (unsigned)atoi(e) : std::min(16u, std::thread::hardware_concurrency());
+    return n ? n : 1u;
+}
+
+// fn(i) for i in [0, n) on contiguous ranges over the host threads
+template <typename F> void par_for(uint64_t n, uint64_t grain, F &&fn)
+{
+    const unsigned T = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(host_threads(), n / std::max<uint64_t>(grain, 1)));
+    if (T == 1) {
+        for (uint64_t i = 0; i < n; ++i) fn(i);
+        return;
+    }
+    std::vector<std::thread> th;
+    th.reserve(T);
+    for (unsigned t = 0; t < T; ++t) {
+        const uint64_t lo = n * t / T, hi = n * (t + 1) / T;
+        th.emplace_back([&fn, lo, hi] {
+            for (uint64_t i = lo; i < hi; ++i) fn(i);
+        });
+    }
+    for (auto &t : th) t.join();
+}
+
+// one row's forward with every layer's output kept: y[0] the padded input,
+// y[l + 1] trunk layer l's output
+struct RowForward {
+    float y[kPolMaxTrunk + 1][kPolMaxH + 4], ha[kPolMaxH], hc[kPolMaxH], z[16], v[1];
+};
+
+void row_forward(const PolNet &net, const PolEvalIO &io, uint64_t r, RowForward &f)
+{
+    float *x = f.y[0];
+    const float *o = io.obs + r * kPolObs;
+    for (int k = 0; k < kPolObs; ++k) x[k] = o[k];
+    uint32_t n = kPolObs;
+    if (net.flags & kPolMemoryIn)
+        for (int k = 0; k < kHidden; ++k) x[n++] = io.hidden[r * kHidden + k];
+    while (n < net.trunk[0].kp) x[n++] = 0.0f;
+    for (uint32_t l = 0; l < net.n_trunk; ++l) policy_layer_host(net.trunk[l], (int)net.trunk[l].act, f.y[l], f.y[l + 1]);
+    const float *top = f.y[net.n_trunk];
+    policy_layer_host(net.actor[0], kActRelu, top, f.ha);
+    policy_layer_host(net.actor[1], kActIdentity, f.ha, f.z);
+    policy_layer_host(net.critic[0], kActRelu, top, f.hc);
+    policy_layer_host(net.critic[1], kActIdentity, f.hc, f.v);
+}
+
+// the layer's chains continued by one row: db[j] + d[j], fmaf(d[j], x[k], dW[j][k])
+inline void grad_w_row(const PolLayer &L, const float *d, const float *x, float *sw, float *sb)
+{
+    for (uint32_t j = 0; j < L.out; ++j) {
+        const float dj = d[j];
+        sb[j] = sb[j] + dj;
+        float *w = sw + (size_t)j * L.in;
+        for (uint32_t k = 0; k < L.in; ++k) w[k] = pol_fma(dj, x[k], w[k]);
+    }
+}
+// the layer's input gradient: g[k] = sum over j ascending of fmaf(d[j], W[j][k], .), from +0
+inline void grad_x_row(const PolLayer &L, const float *d, float *g)
+{
+    for (uint32_t k = 0; k < L.in; ++k) g[k] = 0.0f;
+    for (uint32_t j = 0; j < L.out; ++j) {
+        const float dj = d[j];
+        const float *w = L.w + (size_t)j * L.kp;
+        for (uint32_t k = 0; k < L.in; ++k) g[k] = pol_fma(dj, w[k], g[k]);
+    }
+}
+}  // namespace
+
+void policy_eval(const PolNet &net, const PolEvalIO &io)
+{
+    par_for(io.n, 64, [&](uint64_t r) {
+        RowForward f;
+        row_forward(net, io, r, f);
+        float logp, ent, dz[kPolActions];
+        pol_head(f.z, io.action[r], 0.0f, 0.0f, &logp, &ent, dz);
+        if (io.logp) io.logp[r] = logp;
+        if (io.value) io.value[r] = f.v[0];
+        if (io.entropy) io.entropy[r] = ent;
+    });
+}
+
+void policy_grad(const PolNet &net, const PolEvalIO &io, const PolGradSlabs &S, const PolGradOut &out)
+{
+    const uint64_t tiles = (io.n + kPolGradRows - 1u) / kPolGradRows;
+    const uint32_t T = net.n_trunk;
+    par_for(S.nacc, 1, [&](uint64_t a) {
+        float *slab = S.base + a * S.slab_floats;
+        std::fill(slab, slab + S.slab_floats, 0.0f);
+        RowForward f;
+        float d0[kPolMaxH], d1[kPolMaxH], ga[kPolMaxH], gc[kPolMaxH];
+        for (uint64_t tile = a; tile < tiles; tile += kPolGradAcc) {
+            const uint64_t r1 = std::min<uint64_t>(io.n, (tile + 1u) * kPolGradRows);
+            for (uint64_t r = tile * kPolGradRows; r < r1; ++r) {
+                row_forward(net, io, r, f);
+                float logp, ent, dz[kPolActions];
+                pol_head(f.z, io.action[r], io.g_logp ? io.g_logp[r] : 0.0f, io.g_entropy ? io.g_entropy[r] : 0.0f, &logp,
+                         &ent, dz);
+                const float dv[1] = {io.g_value ? io.g_value[r] : 0.0f};
+                const float *top = f.y[T];
+                // heads: second layers, then the hidden layers' gradients in place of ReLU's outputs
+                grad_w_row(net.actor[1], dz, f.ha, slab + S.w[kPolMaxTrunk + 1], slab + S.b[kPolMaxTrunk + 1]);
+                grad_w_row(net.critic[1], dv, f.hc, slab + S.w[kPolMaxTrunk + 3], slab + S.b[kPolMaxTrunk + 3]);
+                grad_x_row(net.actor[1], dz, d0);
+                grad_x_row(net.critic[1], dv, d1);
+                for (uint32_t k = 0; k < net.H; ++k) {
+                    d0[k] = d0[k] * pol_activation_grad(kActRelu, f.ha[k]);
+                    d1[k] = d1[k] * pol_activation_grad(kActRelu, f.hc[k]);
+                }
+                grad_w_row(net.actor[0], d0, top, slab + S.w[kPolMaxTrunk], slab + S.b[kPolMaxTrunk]);
+                grad_w_row(net.critic[0], d1, top, slab + S.w[kPolMaxTrunk + 2], slab + S.b[kPolMaxTrunk + 2]);
+                grad_x_row(net.actor[0], d0, ga);
+                grad_x_row(net.critic[0], d1, gc);
+                float *d = d0, *g = d1;
+                for (uint32_t k = 0; k < net.H; ++k)
+                    d[k] = (ga[k] + gc[k]) * pol_activation_grad((int)net.trunk[T - 1u].act, top[k]);
+                for (uint32_t l = T; l-- > 0u;) {
+                    grad_w_row(net.trunk[l], d, f.y[l], slab + S.w[l], slab + S.b[l]);
+                    if (l == 0u) break;
+                    grad_x_row(net.trunk[l], d, g);
+                    for (uint32_t k = 0; k < net.H; ++k)
+                        g[k] = g[k] * pol_activation_grad((int)net.trunk[l - 1u].act, f.y[l][k]);
+                    std::swap(d, g);
+                }
+            }
+        }
+    });
+    // the accumulators in ascending index
+    for (uint32_t l = 0; l < out.n; ++l) {
+        const uint64_t nw = out.w[l] ? (uint64_t)out.in[l] * out.out[l] : 0u, nb = out.b[l] ? out.out[l] : 0u;
+        par_for(nw + nb, 4096, [&](uint64_t i) {
+            const size_t off = i < nw ? S.w[l] + i : S.b[l] + (i - nw);
+            float acc = 0.0f;
+            for (uint32_t a = 0; a < S.nacc; ++a) acc = acc + S.base[(size_t)a * S.slab_floats + off];
+            if (i < nw) out.w[l][i] = acc;
+            else out.b[l][i - nw] = acc;
+        });
+    }
+}
+
 void Sim::world_state(uint32_t w, float *xy_rwrz, int32_t *sp_hp_finder, uint64_t *food,
                       uint32_t *food_rot, int32_t *n_out) const
 {

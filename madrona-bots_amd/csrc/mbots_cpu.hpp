@@ -149,5 +149,12 @@ private:
     std::vector<std::shared_ptr<void>> retired_;   // vectors earlier growths left (grow())
 };
 
+// evaluate and its backward pass on host threads (mbots_policy.hpp; no
+// simulator): `net` in the CPU mode's [nt * 16][kp] layout.  The gradient call
+// fills slabs.nacc slabs ([out][in] / [out] per layer), threads splitting the
+// accumulators, then adds them in ascending index into `out`.
+void policy_eval(const PolNet &net, const PolEvalIO &io);
+void policy_grad(const PolNet &net, const PolEvalIO &io, const PolGradSlabs &slabs, const PolGradOut &out);
+
 }  // namespace cpu
 }  // namespace mbots

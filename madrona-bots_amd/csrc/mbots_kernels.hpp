@@ -287,5 +287,13 @@ hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *
 hipError_t launch_policy_draw_next(uint32_t *draw, hipStream_t st);
 hipError_t launch_policy_repack(const PolUploads &U, hipStream_t st);
 hipError_t launch_policy_activation(int act, const float *x, float *y, uint64_t n, hipStream_t st);
+// evaluate and its backward pass (mbots_policy.hpp): `net` in fragment order,
+// `back` its transposed layers (trunk 1.., heads) in fragment order with +0
+// biases; the backward's persistent launch has slabs.nacc blocks, each with
+// kPolStashTiles tiles of `stash`, and is followed by the reduce into `out`
+hipError_t launch_policy_eval(const PolEvalIO &io, const PolNet &net, hipStream_t st);
+size_t policy_grad_stash_floats(uint32_t nacc);
+hipError_t launch_policy_grad(const PolEvalIO &io, const PolNet &net, const PolNet &back, const PolGradSlabs &slabs,
+                              float *stash, const PolGradOut &out, hipStream_t st);
 
 }  // namespace mbots

@@ -3259,6 +3259,16 @@ static int policy_describe(const mbots_policy_net *src, mbots::PolNet &n)
     return MBOTS_OK;
 }
 
+// the CPU mode's copy of one layer: [nt * 16][kp] rows and the bias, +0 pads
+static void policy_fill_host(const mbots::PolLayer &d, const mbots_policy_layer &s)
+{
+    for (uint32_t j = 0; j < d.nt * 16u; ++j) {
+        for (uint32_t k = 0; k < d.kp; ++k)
+            d.w[(size_t)j * d.kp + k] = (j < d.out && k < d.in) ? s.weight[(size_t)j * d.in + k] : 0.0f;
+        d.b[j] = (j < d.out && s.bias) ? s.bias[j] : 0.0f;
+    }
+}
+
 static bool policy_same_arch(mbots::PolNet &a, mbots::PolNet &b)
 {
     if (!a.set || !b.set || a.n_trunk != b.n_trunk || a.H != b.H || a.flags != b.flags || a.has_memory != b.has_memory)
@@ -3325,14 +3335,7 @@ int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_polic
     S.push_back(&net->critic[1]);
     if (cur.has_memory) S.push_back(&net->memory);
     if (h->cpu) {
-        for (size_t i = 0; i < D.size(); ++i) {
-            const PolLayer &d = *D[i];
-            for (uint32_t j = 0; j < d.nt * 16u; ++j) {
-                for (uint32_t k = 0; k < d.kp; ++k)
-                    d.w[(size_t)j * d.kp + k] = (j < d.out && k < d.in) ? S[i]->weight[(size_t)j * d.in + k] : 0.0f;
-                d.b[j] = (j < d.out && S[i]->bias) ? S[i]->bias[j] : 0.0f;
-            }
-        }
+        for (size_t i = 0; i < D.size(); ++i) policy_fill_host(*D[i], *S[i]);
         return MBOTS_OK;
     }
     PolUploads U{};
@@ -3453,6 +3456,185 @@ int mbots_policy_activation(int32_t act, const float *x, float *y, uint64_t n, i
     }
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(mbots::launch_policy_activation(act, x, y, n, as_stream(stream)));
+    return MBOTS_OK;
+}
+
+// ---- evaluate and its backward pass (include/mbots.h "Learning from what the
+// actor did") ----
+namespace {
+// where a call's pieces lie in the caller's workspace
+struct EvalPlan {
+    mbots::PolNet net, back;                  // w / b point into the workspace once bound
+    const mbots_policy_layer *src[mbots::kPolGradLayers];
+    mbots::PolLayer *fwd[mbots::kPolGradLayers], *bwd[mbots::kPolGradLayers];   // null: no such layer
+    mbots::PolGradSlabs slabs;                // base bound; the device's layout, or the CPU mode's
+    mbots::PolGradOut out;
+    size_t stash_off, floats;
+};
+
+int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, EvalPlan &P)
+{
+    using namespace mbots;
+    if (int rc = policy_describe(src, P.net)) return rc;
+    P.net.has_memory = 0;
+    P.back = PolNet{};
+    const uint32_t T = P.net.n_trunk;
+    for (int i = 0; i < kPolGradLayers; ++i) P.src[i] = nullptr, P.fwd[i] = nullptr, P.bwd[i] = nullptr;
+    for (uint32_t l = 0; l < T; ++l) {
+        P.src[l] = &src->trunk[l];
+        P.fwd[l] = &P.net.trunk[l];
+        if (l) P.bwd[l] = &P.back.trunk[l];
+    }
+    for (int i = 0; i < 2; ++i) {
+        P.src[kPolMaxTrunk + i] = &src->actor[i];
+        P.fwd[kPolMaxTrunk + i] = &P.net.actor[i];
+        P.bwd[kPolMaxTrunk + i] = &P.back.actor[i];
+        P.src[kPolMaxTrunk + 2 + i] = &src->critic[i];
+        P.fwd[kPolMaxTrunk + 2 + i] = &P.net.critic[i];
+        P.bwd[kPolMaxTrunk + 2 + i] = &P.back.critic[i];
+    }
+    size_t off = 0;
+    auto take = [&](size_t floats) {
+        float *p = ws ? ws + off : nullptr;
+        off += (floats + 63u) & ~size_t(63);
+        return p;
+    };
+    const uint64_t tiles = (n + kPolGradRows - 1u) / kPolGradRows;
+    P.slabs = PolGradSlabs{};
+    P.slabs.nacc = (uint32_t)std::min<uint64_t>(tiles, kPolGradAcc);
+    P.out = PolGradOut{};
+    P.out.n = kPolGradLayers;
+    size_t slab = 0, slab_cpu = 0;
+    for (int i = 0; i < kPolGradLayers; ++i) {
+        if (!P.fwd[i]) continue;
+        PolLayer &f = *P.fwd[i];
+        f.w = take(pol_w_floats(f));
+        f.b = take(pol_b_floats(f));
+        if (P.bwd[i]) {
+            PolLayer &b = *P.bwd[i];
+            b.in = f.out;
+            b.out = f.in;
+            b.kp = (b.in + 7u) & ~7u;   // an even number of k-steps, as the layer kernel's paired loop takes
+            b.nt = (b.out + 15u) / 16u;
+            b.w = take(pol_w_floats(b));
+            b.b = take(pol_b_floats(b));
+        }
+        P.out.in[i] = f.in;
+        P.out.out[i] = f.out;
+        P.out.kp[i] = f.kp;
+        // (the CPU mode's [out][in] slab is never larger than the device's tiles)
+        P.slabs.w[i] = (uint32_t)(cpu ? slab_cpu : slab);
+        slab += (size_t)f.nt * pol_grad_nkt(f.kp) * 256u;
+        slab_cpu += (size_t)f.out * f.in;
+        P.slabs.b[i] = (uint32_t)(cpu ? slab_cpu : slab);
+        slab += (size_t)f.nt * 16u;
+        slab_cpu += f.out;
+    }
+    P.slabs.slab_floats = cpu ? slab_cpu : slab;
+    P.slabs.base = take(slab * P.slabs.nacc);
+    P.stash_off = off;
+    take(policy_grad_stash_floats(P.slabs.nacc));
+    P.floats = off;
+    return MBOTS_OK;
+}
+
+int eval_check(const mbots_policy_net *net, const float *obs, const float *hidden, const int32_t *action, uint64_t n,
+               void *ws, uint64_t ws_bytes, int32_t device, EvalPlan &P)
+{
+    if (!net) return fail(MBOTS_E_INVALID, "null argument");
+    if (int rc = eval_plan(net, n, device < 0, static_cast<float *>(ws), P)) return rc;
+    if (n && (!obs || !action)) return fail(MBOTS_E_INVALID, "null obs or action");
+    if (n && (net->flags & MBOTS_POLICY_MEMORY_IN) && !hidden)
+        return fail(MBOTS_E_INVALID, "a net with MBOTS_POLICY_MEMORY_IN needs the rows' hidden floats");
+    if (!ws || ((uintptr_t)ws & 15u)) return fail(MBOTS_E_INVALID, "the workspace must be 16-byte aligned memory");
+    if (ws_bytes < P.floats * sizeof(float))
+        return fail(MBOTS_E_INVALID, "workspace of " + std::to_string(ws_bytes) + " bytes, " +
+                                         std::to_string(P.floats * sizeof(float)) + " needed (mbots_policy_grad_workspace)");
+    if (device < 0)
+        for (uint64_t r = 0; r < n; ++r)
+            if (action[r] < 0 || action[r] >= mbots::kPolActions)
+                return fail(MBOTS_E_INVALID, "action " + std::to_string(action[r]) + " of row " + std::to_string(r) +
+                                                 " is outside 0..5");
+    return MBOTS_OK;
+}
+
+// the weights into the workspace: fragment order on the device (the transposed
+// layers too when `back`), the CPU mode's rows on the host
+int eval_upload(const EvalPlan &P, bool back, int32_t device, hipStream_t st)
+{
+    using namespace mbots;
+    PolUploads U{}, B{};
+    for (int i = 0; i < kPolGradLayers; ++i) {
+        if (!P.fwd[i]) continue;
+        const PolLayer &f = *P.fwd[i];
+        if (device < 0) {
+            policy_fill_host(f, *P.src[i]);
+            continue;
+        }
+        U.l[U.n++] = PolUpload{P.src[i]->weight, P.src[i]->bias, f.w, f.b, f.in, f.out, f.kp, f.nt, 0u};
+        if (back && P.bwd[i]) {
+            const PolLayer &b = *P.bwd[i];
+            B.l[B.n++] = PolUpload{P.src[i]->weight, nullptr, b.w, b.b, b.in, b.out, b.kp, b.nt, 1u};
+        }
+    }
+    if (device < 0) return MBOTS_OK;
+    HIP_TRY(launch_policy_repack(U, st));
+    HIP_TRY(launch_policy_repack(B, st));
+    return MBOTS_OK;
+}
+}  // namespace
+
+int mbots_policy_grad_workspace(const struct mbots_policy_net *net, uint64_t n, uint64_t *bytes)
+{
+    if (!net || !bytes) return fail(MBOTS_E_INVALID, "null argument");
+    EvalPlan P;
+    if (int rc = eval_plan(net, n, false, nullptr, P)) return rc;
+    *bytes = P.floats * sizeof(float);
+    return MBOTS_OK;
+}
+
+int mbots_policy_eval(const struct mbots_policy_net *net, const float *obs, const float *hidden,
+                      const int32_t *action, uint64_t n, float *logp, float *value, float *entropy, void *workspace,
+                      uint64_t workspace_bytes, int32_t device, void *stream)
+{
+    EvalPlan P;
+    if (int rc = eval_check(net, obs, hidden, action, n, workspace, workspace_bytes, device, P)) return rc;
+    const mbots::PolEvalIO io{obs, hidden, action, nullptr, nullptr, nullptr, logp, value, entropy, n};
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    if (int rc = eval_upload(P, false, device, as_stream(stream))) return rc;
+    if (device < 0) {
+        mbots::cpu::policy_eval(P.net, io);
+        return MBOTS_OK;
+    }
+    HIP_TRY(mbots::launch_policy_eval(io, P.net, as_stream(stream)));
+    return MBOTS_OK;
+}
+
+int mbots_policy_grad(const struct mbots_policy_net *net, const float *obs, const float *hidden,
+                      const int32_t *action, uint64_t n, const float *g_logp, const float *g_value,
+                      const float *g_entropy, const struct mbots_policy_grads *out, void *workspace,
+                      uint64_t workspace_bytes, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (!out) return fail(MBOTS_E_INVALID, "null argument");
+    EvalPlan P;
+    if (int rc = eval_check(net, obs, hidden, action, n, workspace, workspace_bytes, device, P)) return rc;
+    for (uint32_t l = 0; l < P.net.n_trunk; ++l) P.out.w[l] = out->trunk[l].weight, P.out.b[l] = out->trunk[l].bias;
+    for (int i = 0; i < 2; ++i) {
+        P.out.w[kPolMaxTrunk + i] = out->actor[i].weight;
+        P.out.b[kPolMaxTrunk + i] = out->actor[i].bias;
+        P.out.w[kPolMaxTrunk + 2 + i] = out->critic[i].weight;
+        P.out.b[kPolMaxTrunk + 2 + i] = out->critic[i].bias;
+    }
+    const PolEvalIO io{obs, hidden, action, g_logp, g_value, g_entropy, nullptr, nullptr, nullptr, n};
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    if (int rc = eval_upload(P, true, device, as_stream(stream))) return rc;
+    if (device < 0) {
+        cpu::policy_grad(P.net, io, P.slabs, P.out);
+        return MBOTS_OK;
+    }
+    HIP_TRY(launch_policy_grad(io, P.net, P.back, P.slabs, static_cast<float *>(workspace) + P.stash_off, P.out,
+                               as_stream(stream)));
     return MBOTS_OK;
 }
 

@@ -1,7 +1,9 @@
 // mbots_policy.hip -- the device actor's kernels (mbots_policy.hpp; DESIGN.md
 // "Device actor"): per-species policy nets on v_mfma_f32_16x16x4_f32, action
 // sampling from the counter RNG and the Action / HiddenState write, one
-// persistent launch over 64-row tiles of the current table.
+// persistent launch over 64-row tiles of the current table; and the learner's
+// half (DESIGN.md "Differentiable evaluate"): the same nets on recorded rows,
+// and their parameter gradients from a persistent backward kernel.
 #include "mbots_kernels.hpp"
 #include "mbots_policy.hpp"
 
@@ -25,8 +27,15 @@ constexpr size_t kPolLds =
 // layer's weights read once per block, straight from L2 in fragment order (64
 // contiguous floats per (k-step, column tile)).  The C operand starts as the
 // broadcast bias; columns >= L.out (the heads' pads) are never stored.
+//
+// kBack (the backward pass's input gradients, L the transposed layer with a +0
+// bias): the epilogue stores (add[r][j] +) acc times the derivative of
+// activation `act` at the value dst[r][j] holds -- the forward's output, which
+// the gradient replaces in place; act < 0: no derivative factor.
+template <bool kBack = false>
 __device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const float *src, float *dst,
-                                          uint32_t dst_stride, uint32_t wv, uint32_t woff, uint32_t lane)
+                                          uint32_t dst_stride, uint32_t wv, uint32_t woff, uint32_t lane,
+                                          const float *add = nullptr)
 {
     const uint32_t nt = L.nt, nks = L.kp >> 2;
     const uint32_t j0 = (wv - woff) & 3u, j1 = j0 + 4u;
@@ -89,8 +98,25 @@ __device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const floa
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const uint32_t row = (uint32_t)mt * 16u + q * 4u + (uint32_t)r;
-            if (col0 < L.out) dst[row * dst_stride + col0] = pol_activation(act, acc0[mt][r]);
-            if (two && col1 < L.out) dst[row * dst_stride + col1] = pol_activation(act, acc1[mt][r]);
+            if constexpr (kBack) {
+                if (col0 < L.out) {
+                    float *o = dst + row * dst_stride + col0;
+                    float v = acc0[mt][r];
+                    if (add) v = add[row * dst_stride + col0] + v;
+                    if (act >= 0) v = v * pol_activation_grad(act, *o);
+                    *o = v;
+                }
+                if (two && col1 < L.out) {
+                    float *o = dst + row * dst_stride + col1;
+                    float v = acc1[mt][r];
+                    if (add) v = add[row * dst_stride + col1] + v;
+                    if (act >= 0) v = v * pol_activation_grad(act, *o);
+                    *o = v;
+                }
+            } else {
+                if (col0 < L.out) dst[row * dst_stride + col0] = pol_activation(act, acc0[mt][r]);
+                if (two && col1 < L.out) dst[row * dst_stride + col1] = pol_activation(act, acc1[mt][r]);
+            }
         }
 }
 
@@ -305,7 +331,8 @@ __global__ __launch_bounds__(256) void policy_repack_kernel(PolUploads U)
         if (i < nw) {
             const uint32_t l = i & 63u, f = i >> 6, jt = f % L.nt, ks = f / L.nt;
             const uint32_t j = jt * 16u + (l & 15u), k = 4u * ks + (l >> 4);
-            L.w_dst[i] = (j < L.out && k < L.in) ? L.w_src[(size_t)j * L.in + k] : 0.0f;
+            L.w_dst[i] = (j < L.out && k < L.in) ? (L.tr ? L.w_src[(size_t)k * L.out + j] : L.w_src[(size_t)j * L.in + k])
+                                                 : 0.0f;
         } else {
             const uint32_t j = i - nw;
             L.b_dst[j] = (j < L.out && L.b_src) ? L.b_src[j] : 0.0f;
@@ -317,6 +344,271 @@ __global__ __launch_bounds__(256) void policy_activation_kernel(int act, const f
 {
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
         y[i] = pol_activation(act, x[i]);
+}
+
+// ---- evaluate and its backward pass (mbots_policy.hpp; DESIGN.md "Differentiable
+// evaluate") ----
+constexpr int kPolTile = kPolRows * kPolStride;   // floats of one LDS tile
+constexpr int kPolStashTiles = kPolMaxTrunk - 1;  // outputs of all trunk layers but the last, per block
+constexpr size_t kPolEvalLds = (2 * kPolTile + kPolRows * (kPolLogitStride + 1)) * sizeof(float);
+constexpr size_t kPolGradLds = (4 * kPolTile + kPolRows * (kPolLogitStride + 1)) * sizeof(float);
+
+// the tile's inputs from the dense rows: X[64][kp], +0 for the pads and the rows past nr
+__device__ __forceinline__ void pol_stage_dense(float *x, const PolEvalIO &A, uint64_t r0, uint32_t nr, uint32_t kp,
+                                                bool mem_in, uint32_t t)
+{
+    for (uint32_t i = t; i < (uint32_t)kPolRows * kp; i += 256u) {
+        const uint32_t row = i / kp, k = i - row * kp;
+        float v = 0.0f;
+        if (row < nr) {
+            if (k < (uint32_t)kPolObs) v = A.obs[(r0 + row) * kPolObs + k];
+            else if (mem_in && k < (uint32_t)(kPolObs + kHidden)) v = A.hidden[(r0 + row) * kHidden + (k - kPolObs)];
+        }
+        x[row * kPolStride + k] = v;
+    }
+}
+
+__device__ __forceinline__ void pol_copy_tile(float *dst, const float *src, uint32_t t)
+{
+    for (uint32_t i = t; i < (uint32_t)kPolTile / 4u; i += 256u)
+        reinterpret_cast<float4 *>(dst)[i] = reinterpret_cast<const float4 *>(src)[i];
+}
+
+// One layer's parameter gradients over the tile: dW[j][k] continues its chain
+// fmaf(d[r][j], x[r][k], dW[j][k]) over the 64 rows in ascending order -- the
+// k-steps of the matrix instruction, A the transposed d, B the layer's input x
+// -- and db[j] its chain of adds.  The chains live in the block's slab (dW as
+// the C fragments of its 16 x 16 tiles) and start at +0 on the block's first
+// tile.  Wave w takes the out-feature tiles w and w + 4, four in-feature tiles
+// at a time; columns of x past kp and what they produce are never read back.
+__device__ __forceinline__ void pol_grad_w(const PolLayer &L, const float *d, const float *x, float *sw, float *sb,
+                                           bool first, uint32_t wv, uint32_t lane, uint32_t t)
+{
+    const uint32_t nt = L.nt, nkt = pol_grad_nkt(L.kp);
+    const uint32_t c = lane & 15u, q = lane >> 4;
+    for (uint32_t jt = wv; jt < nt; jt += 4u) {
+        const float *da = d + q * kPolStride + jt * 16u + c;
+        for (uint32_t kt0 = 0; kt0 < nkt; kt0 += 4u) {
+            const uint32_t nk = min(4u, nkt - kt0);
+            f32x4 acc[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                acc[u] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+                if (!first && (uint32_t)u < nk) {
+                    const float *p = sw + ((size_t)(jt * nkt + kt0 + u) * 4u) * 64u + lane;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) acc[u][r] = p[r * 64];
+                }
+            }
+            const float *xb = x + q * kPolStride + kt0 * 16u + c;
+            if (nk == 4u) {
+                for (uint32_t s = 0; s < (uint32_t)kPolRows / 4u; ++s) {
+                    const float a = da[s * 4u * kPolStride];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xb[s * 4u * kPolStride + u * 16], acc[u], 0, 0, 0);
+                }
+            } else {
+                for (uint32_t s = 0; s < (uint32_t)kPolRows / 4u; ++s) {
+                    const float a = da[s * 4u * kPolStride];
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if ((uint32_t)u < nk)
+                            acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xb[s * 4u * kPolStride + u * 16], acc[u], 0,
+                                                                          0, 0);
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                if ((uint32_t)u < nk) {
+                    float *p = sw + ((size_t)(jt * nkt + kt0 + u) * 4u) * 64u + lane;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) p[r * 64] = acc[u][r];
+                }
+        }
+    }
+    if (t < nt * 16u) {
+        float acc = first ? 0.0f : sb[t];
+        for (int r = 0; r < kPolRows; ++r) acc = acc + d[r * kPolStride + t];
+        sb[t] = acc;
+    }
+}
+
+struct PolGradDev {
+    PolNet back;          // the transposed layers (trunk 1.., heads), each with a +0 bias
+    PolGradSlabs slabs;
+    float *stash;         // [blocks][kPolStashTiles][kPolTile]
+};
+
+// kGrad false: logp, value and entropy of every row, grid-stride over the
+// tiles.  kGrad true: block b is accumulator b and takes the tiles b, b +
+// kPolGradAcc, ... in order: the forward again (outputs of the inner trunk
+// layers to the block's stash), d loss / d logits, then layer by layer from
+// the heads down the parameter gradients into the block's slab and the input
+// gradients in place of the layer outputs.
+template <bool kGrad>
+__global__ __launch_bounds__(256, kGrad ? 1 : 2) void policy_eval_kernel(PolEvalIO A, PolNet net, PolGradDev G)
+{
+    extern __shared__ float s_pol[];
+    float *buf0 = s_pol, *buf1 = s_pol + kPolTile;
+    float *tail = s_pol + (kGrad ? 4 : 2) * kPolTile;
+    float *s_logit = tail, *s_val = tail + kPolRows * kPolLogitStride;
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    const bool mem_in = (net.flags & kPolMemoryIn) != 0u;
+    const uint64_t tiles = (A.n + kPolRows - 1u) / kPolRows;
+    const uint64_t stride = kGrad ? (uint64_t)kPolGradAcc : (uint64_t)gridDim.x;
+    float *slab = kGrad ? G.slabs.base + (size_t)blockIdx.x * G.slabs.slab_floats : nullptr;
+    float *stash = kGrad ? G.stash + (size_t)blockIdx.x * kPolStashTiles * kPolTile : nullptr;
+
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += stride) {
+        const uint64_t r0 = tile * kPolRows;
+        const uint32_t nr = A.n - r0 < (uint64_t)kPolRows ? (uint32_t)(A.n - r0) : (uint32_t)kPolRows;
+        const bool first = tile == (uint64_t)blockIdx.x;
+        pol_stage_dense(buf0, A, r0, nr, net.trunk[0].kp, mem_in, t);
+        __syncthreads();
+        float *cur = buf0, *oth = buf1;
+        for (uint32_t l = 0; l < net.n_trunk; ++l) {
+            pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            float *sw = cur;
+            cur = oth;
+            oth = sw;
+            if (kGrad && l + 1u < net.n_trunk) pol_copy_tile(stash + (size_t)l * kPolTile, cur, t);
+        }
+        // the heads' hidden layers: each in a tile of its own when the backward pass needs them
+        float *ha = kGrad ? s_pol + 2 * kPolTile : oth, *hc = kGrad ? s_pol + 3 * kPolTile : oth;
+        pol_layer(net.actor[0], kActRelu, cur, ha, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(net.actor[1], kActIdentity, ha, s_logit, kPolLogitStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(net.critic[0], kActRelu, cur, hc, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(net.critic[1], kActIdentity, hc, s_val, 1u, wv, 0u, lane);
+        __syncthreads();
+
+        // ---- one row per thread: logp, entropy, and d loss / d logits | d value
+        // as the 16-column operands oth[:, 0:16] and oth[:, 16:32] (+0 pads) ----
+        if (t < (uint32_t)kPolRows) {
+            float dz[kPolActions] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, dv = 0.0f;
+            if (t < nr) {
+                const uint64_t r = r0 + t;
+                float z[kPolActions];
+#pragma unroll
+                for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
+                const float gl = kGrad && A.g_logp ? A.g_logp[r] : 0.0f, ge = kGrad && A.g_entropy ? A.g_entropy[r] : 0.0f;
+                float logp, ent;
+                pol_head(z, A.action[r], gl, ge, &logp, &ent, dz);
+                if (A.logp) A.logp[r] = logp;
+                if (A.value) A.value[r] = s_val[t];
+                if (A.entropy) A.entropy[r] = ent;
+                if (kGrad && A.g_value) dv = A.g_value[r];
+            }
+            if (kGrad) {
+                float *o = oth + t * kPolStride;
+#pragma unroll
+                for (int i = 0; i < 32; ++i) o[i] = 0.0f;
+                if (t < nr) {
+#pragma unroll
+                    for (int i = 0; i < kPolActions; ++i) o[i] = dz[i];
+                    o[16] = dv;
+                }
+            }
+        }
+        __syncthreads();
+        if constexpr (kGrad) {
+            const PolGradSlabs &S = G.slabs;
+            const uint32_t T = net.n_trunk;
+            // heads' second layers
+            pol_grad_w(net.actor[1], oth, ha, slab + S.w[kPolMaxTrunk + 1], slab + S.b[kPolMaxTrunk + 1], first, wv, lane, t);
+            pol_grad_w(net.critic[1], oth + 16, hc, slab + S.w[kPolMaxTrunk + 3], slab + S.b[kPolMaxTrunk + 3], first, wv,
+                       lane, t);
+            __syncthreads();
+            pol_layer<true>(G.back.actor[1], kActRelu, oth, ha, kPolStride, wv, 0u, lane);
+            pol_layer<true>(G.back.critic[1], kActRelu, oth + 16, hc, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            // heads' first layers; the trunk's last output receives the actor's input
+            // gradient plus the critic's, times its activation's derivative
+            pol_grad_w(net.actor[0], ha, cur, slab + S.w[kPolMaxTrunk], slab + S.b[kPolMaxTrunk], first, wv, lane, t);
+            pol_grad_w(net.critic[0], hc, cur, slab + S.w[kPolMaxTrunk + 2], slab + S.b[kPolMaxTrunk + 2], first, wv, lane,
+                       t);
+            pol_layer<true>(G.back.actor[0], -1, ha, oth, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            pol_layer<true>(G.back.critic[0], (int)net.trunk[T - 1u].act, hc, cur, kPolStride, wv, 0u, lane, oth);
+            __syncthreads();
+            // the trunk, last layer first: d in `cur`, the layer's input in `oth`
+            for (uint32_t l = T; l-- > 0u;) {
+                if (l == 0u) pol_stage_dense(oth, A, r0, nr, net.trunk[0].kp, mem_in, t);
+                else pol_copy_tile(oth, stash + (size_t)(l - 1u) * kPolTile, t);
+                __syncthreads();
+                pol_grad_w(net.trunk[l], cur, oth, slab + S.w[l], slab + S.b[l], first, wv, lane, t);
+                __syncthreads();
+                if (l == 0u) break;
+                pol_layer<true>(G.back.trunk[l], (int)net.trunk[l - 1u].act, cur, oth, kPolStride, wv, 0u, lane);
+                __syncthreads();
+                float *sw = cur;
+                cur = oth;
+                oth = sw;
+            }
+        }
+    }
+}
+
+// the accumulators added in ascending index, each gradient in its [out][in] / [out] layout
+__global__ __launch_bounds__(256) void policy_grad_reduce_kernel(PolGradSlabs S, PolGradOut O)
+{
+    const uint32_t l = blockIdx.y;
+    const uint32_t in = O.in[l], out = O.out[l], nkt = pol_grad_nkt(O.kp[l]);
+    const uint32_t nw = O.w[l] ? in * out : 0u, nb = O.b[l] ? out : 0u;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nw + nb; i += gridDim.x * 256u) {
+        size_t off;
+        if (i < nw) {
+            const uint32_t j = i / in, k = i - j * in;
+            const uint32_t jt = j >> 4, q = (j & 15u) >> 2, r = j & 3u, kt = k >> 4, c = k & 15u;
+            off = S.w[l] + ((size_t)(jt * nkt + kt) * 4u + r) * 64u + q * 16u + c;
+        } else {
+            off = S.b[l] + (i - nw);
+        }
+        float acc = 0.0f;
+        for (uint32_t a = 0; a < S.nacc; ++a) acc = acc + S.base[(size_t)a * S.slab_floats + off];
+        if (i < nw) O.w[l][i] = acc;
+        else O.b[l][i - nw] = acc;
+    }
+}
+
+template <bool kGrad> static hipError_t policy_eval_lds()
+{
+    static bool set = false;
+    if (set) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_eval_kernel<kGrad>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize,
+                                             (int)(kGrad ? kPolGradLds : kPolEvalLds));
+    if (e == hipSuccess) set = true;
+    return e;
+}
+
+hipError_t launch_policy_eval(const PolEvalIO &io, const PolNet &net, hipStream_t st)
+{
+    if (io.n == 0) return hipSuccess;
+    if (const hipError_t e = policy_eval_lds<false>()) return e;
+    const uint64_t tiles = (io.n + kPolRows - 1u) / kPolRows;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(tiles, 512u);
+    hipLaunchKernelGGL(policy_eval_kernel<false>, dim3(blocks), dim3(256), kPolEvalLds, st, io, net, PolGradDev{});
+    return hipGetLastError();
+}
+
+size_t policy_grad_stash_floats(uint32_t nacc) { return (size_t)nacc * kPolStashTiles * kPolTile; }
+
+hipError_t launch_policy_grad(const PolEvalIO &io, const PolNet &net, const PolNet &back, const PolGradSlabs &slabs,
+                              float *stash, const PolGradOut &out, hipStream_t st)
+{
+    if (slabs.nacc) {
+        if (const hipError_t e = policy_eval_lds<true>()) return e;
+        PolGradDev G{back, slabs, stash};
+        hipLaunchKernelGGL(policy_eval_kernel<true>, dim3(slabs.nacc), dim3(256), kPolGradLds, st, io, net, G);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3(16, out.n), dim3(256), 0, st, slabs, out);
+    return hipGetLastError();
 }
 
 hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *hidden_in, const PolNets &nets,

@@ -245,11 +245,12 @@ struct PolNets {
 MB_HD size_t pol_w_floats(const PolLayer &l) { return (size_t)l.kp * l.nt * 16u; }
 MB_HD size_t pol_b_floats(const PolLayer &l) { return (size_t)l.nt * 16u; }
 
-// the repack / pad of one layer's weights at upload (src: [out][in] row-major)
+// the repack / pad of one layer's weights at upload (src: [out][in] row-major;
+// tr: src is the [in][out] matrix this layer is the transpose of)
 struct PolUpload {
     const float *w_src, *b_src;
     float *w_dst, *b_dst;
-    uint32_t in, out, kp, nt;
+    uint32_t in, out, kp, nt, tr;
 };
 struct PolUploads {
     PolUpload l[kPolLayers];
@@ -272,5 +273,89 @@ MB_HD void pol_row_input(float *x, const uint8_t *dep, const int8_t *sem, int32_
         for (int k = 0; k < kHidden; ++k) x[n++] = hidden[k];
     while (n < kp) x[n++] = 0.0f;
 }
+
+// ---- evaluate: act()'s chain on recorded (obs, action) rows, and its backward
+// pass (DESIGN.md "Differentiable evaluate") ----
+// The summation order of the parameter gradients: rows are cut into tiles of
+// kPolGradRows, tile i belongs to accumulator i mod kPolGradAcc, an
+// accumulator's chain runs over its rows in ascending order (continued from
+// tile to tile), and the result is the accumulators added in ascending index.
+constexpr uint32_t kPolGradRows = 64, kPolGradAcc = 256;
+constexpr int kPolGradLayers = kPolMaxTrunk + 4;   // trunk, actor 2, critic 2 (the memory head takes no part)
+
+// d activation / d input, from the layer's output y
+MB_HD float pol_activation_grad(int code, float y)
+{
+    switch (code) {
+    case kActRelu: return y > 0.0f ? 1.0f : 0.0f;
+    case kActLeaky: return y >= 0.0f ? 1.0f : 0.01f;
+    case kActTanh: return pol_fma(-y, y, 1.0f);
+    case kActElu: return y > 0.0f ? 1.0f : y + 1.0f;
+    case kActLogSigmoid: return 1.0f - pol_exp(y);
+    default: return 1.0f;
+    }
+}
+
+// One row's softmax head: logp of action a, the entropy, and (g_logp, g_entropy
+// the upstream gradients) d loss / d logits.  m, the prefix sums and logp are
+// pol_sample's own expressions.
+MB_HD void pol_head(const float z[kPolActions], int32_t a, float g_logp, float g_entropy, float *logp,
+                    float *entropy, float dz[kPolActions])
+{
+    float m = z[0];
+    for (int i = 1; i < kPolActions; ++i)
+        if (z[i] > m) m = z[i];
+    float e[kPolActions];
+    float s = 0.0f;
+    for (int i = 0; i < kPolActions; ++i) {
+        e[i] = pol_exp(z[i] - m);
+        s = s + e[i];
+    }
+    const float ls = pol_log(s);
+    float p[kPolActions], lp[kPolActions];
+    float acc = 0.0f, la = 0.0f;
+    for (int i = 0; i < kPolActions; ++i) {
+        p[i] = e[i] / s;
+        lp[i] = (z[i] - m) - ls;
+        acc = pol_fma(p[i], lp[i], acc);
+        if (i == a) la = lp[i];
+    }
+    const float ent = -acc;
+    *logp = la;
+    *entropy = ent;
+    for (int i = 0; i < kPolActions; ++i) {
+        const float t1 = g_logp * ((i == a ? 1.0f : 0.0f) - p[i]);
+        const float t2 = (g_entropy * p[i]) * (lp[i] + ent);
+        dz[i] = t1 - t2;
+    }
+}
+
+// the rows an evaluate / its backward reads and writes (any output null: not wanted;
+// any g_* null: zeros)
+struct PolEvalIO {
+    const float *obs, *hidden;   // [n][69], [n][16] (memory_in nets)
+    const int32_t *action;       // [n]
+    const float *g_logp, *g_value, *g_entropy;
+    float *logp, *value, *entropy;
+    uint64_t n;
+};
+// where a gradient call keeps its partial sums: nacc slabs of slab_floats
+// each, layer l's dW at w[l] and db at b[l] inside a slab.  The device keeps dW
+// in the C-fragment order of its 16 x 16 tiles, [nt][nkt][4][64] (nkt the
+// 16-wide tiles of kp); the CPU mode as [out][in].
+struct PolGradSlabs {
+    float *base;
+    uint64_t slab_floats;
+    uint32_t w[kPolGradLayers], b[kPolGradLayers];
+    uint32_t nacc;
+};
+// the gradients as the caller wants them ([out][in] / [out], null: not wanted), in
+// the order trunk, actor, critic
+struct PolGradOut {
+    float *w[kPolGradLayers], *b[kPolGradLayers];
+    uint32_t in[kPolGradLayers], out[kPolGradLayers], kp[kPolGradLayers];
+    uint32_t n;
+};
+MB_HD uint32_t pol_grad_nkt(uint32_t kp) { return (kp + 15u) >> 4; }
 
 }  // namespace mbots

@@ -72,6 +72,15 @@ class _PolicyNet(ctypes.Structure):     # struct mbots_policy_net
                 ("critic", _PolicyLayer * 2), ("memory", _PolicyLayer), ("flags", ctypes.c_uint32)]
 
 
+class _PolicyGradLayer(ctypes.Structure):   # struct mbots_policy_grad_layer
+    _fields_ = [("weight", ctypes.c_void_p), ("bias", ctypes.c_void_p)]
+
+
+class _PolicyGrads(ctypes.Structure):   # struct mbots_policy_grads
+    _fields_ = [("trunk", _PolicyGradLayer * 4), ("actor", _PolicyGradLayer * 2), ("critic", _PolicyGradLayer * 2),
+                ("memory", _PolicyGradLayer)]
+
+
 class _CTensor(ctypes.Structure):
     _fields_ = [("data", ctypes.c_void_p), ("dtype", ctypes.c_int32), ("device", ctypes.c_int32),
                 ("dims", ctypes.c_int64 * 2)]
@@ -142,6 +151,10 @@ def _load():
         "mbots_policy_act": [vp, u32, vp, vp, vp, ctypes.c_uint64, vp],
         "mbots_policy_draw": [vp, i32, P(u32)],
         "mbots_policy_activation": [i32, vp, vp, ctypes.c_uint64, i32, vp],
+        "mbots_policy_grad_workspace": [P(_PolicyNet), ctypes.c_uint64, P(ctypes.c_uint64)],
+        "mbots_policy_eval": [P(_PolicyNet), vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, ctypes.c_uint64, i32, vp],
+        "mbots_policy_grad": [P(_PolicyNet), vp, vp, vp, ctypes.c_uint64, vp, vp, vp, P(_PolicyGrads), vp,
+                              ctypes.c_uint64, i32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -1298,6 +1311,128 @@ class PolicyNet:
                 raise ValueError(f"{name}: expected Linear({H}, {H}), ReLU, Linear({H}, {width})")
         if self.memory is not None and tuple(self.memory[0].shape) != (16, H):
             raise ValueError(f"memory: expected Linear({H}, 16)")
+
+    # -- learning from what act() did -----------------------------------------
+    def _named_params(self):
+        """[(name, tensor or None)]: weight and bias of every layer evaluate()
+        runs, in the order trunk, actor, critic (the memory head takes no part)."""
+        out = []
+        for name, layers in (("feature", self.trunk), ("actor", self.actor), ("critic", self.critic)):
+            for i, (w, b, _) in enumerate(layers):
+                out += [(f"{name} Linear {i} weight", w), (f"{name} Linear {i} bias", b)]
+        return out
+
+    def _c_net(self, params):
+        """struct mbots_policy_net over `params` (the tensors of _named_params())."""
+        c = _PolicyNet()
+        c.n_trunk = len(self.trunk)
+        codes = [code for _, _, code in self.trunk] + [0, 0, 0, 0]
+        slots = [c.trunk[i] for i in range(len(self.trunk))] + [c.actor[0], c.actor[1], c.critic[0], c.critic[1]]
+        for i, slot in enumerate(slots):
+            w, b = params[2 * i], params[2 * i + 1]
+            slot.in_, slot.out, slot.act = w.shape[1], w.shape[0], codes[i]
+            slot.weight, slot.bias = w.data_ptr(), None if b is None else b.data_ptr()
+        c.flags = 1 if self.memory_in else 0
+        return c
+
+    def evaluate(self, obs, action, hidden=None):
+        """(logp, value, entropy), float32 [n] each on obs's device, of the
+        recorded rows: obs float32 [n, 69] (construct_obs()), action int32
+        [n] or [n, 1] (act()'s), hidden float32 [n, 16] for a memory_in net.
+        logp and value are bit for bit what act() returned for these rows;
+        the result is differentiable with respect to the net's parameters
+        (the tensors this PolicyNet references: backward() leaves their .grad
+        for any torch optimiser, set_policy() uploads the stepped weights),
+        not to obs or hidden.  CUDA tensors run the HIP kernels, CPU tensors
+        the host threads; both give the same bits, whatever the grid or the
+        thread count (DESIGN.md "Differentiable evaluate")."""
+        self._validate()
+        dev = obs.device
+        if obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[1] != 69:
+            raise ValueError(f"obs must be float32 [n, 69], not {obs.dtype} {list(obs.shape)}")
+        n = obs.shape[0]
+        if action.dtype != torch.int32 or action.device != dev or action.numel() != n \
+                or action.dim() not in (1, 2) or action.shape[0] != n:
+            raise ValueError(f"action must be int32 [n] or [n, 1] on {dev} with obs's rows, not {action.dtype} "
+                             f"{list(action.shape)} on {action.device}")
+        if self.memory_in:
+            if hidden is None:
+                raise ValueError("a memory_in net needs hidden (float32 [n, 16])")
+            if hidden.dtype != torch.float32 or hidden.device != dev or tuple(hidden.shape) != (n, 16):
+                raise ValueError(f"hidden must be float32 [n, 16] on {dev}, not {hidden.dtype} {list(hidden.shape)} "
+                                 f"on {hidden.device}")
+            hidden = hidden.detach().contiguous()
+        else:
+            hidden = None
+        named = self._named_params()
+        for name, p in named:
+            if p is not None and (p.dtype != torch.float32 or p.device != dev):
+                raise ValueError(f"{name} must be float32 on {dev} (obs's device), not {p.dtype} on {p.device}")
+        present = [i for i, (_, p) in enumerate(named) if p is not None]
+        return _Evaluate.apply(self, obs.detach().contiguous(), action.detach().reshape(n).contiguous(), hidden,
+                               present, *[named[i][1] for i in present])
+
+
+_workspaces = {}   # (device, bytes) -> uint8 buffer: evaluate()'s scratch
+
+
+def _eval_call(net, obs, hidden, action, params, fn):
+    """The workspace and the device / stream arguments for one of the two
+    handle-free calls; fn(c_net, workspace pointer, bytes, device index, stream)."""
+    dev = obs.device
+    c = net._c_net(params)
+    need = ctypes.c_uint64()
+    _check(_lib.mbots_policy_grad_workspace(ctypes.byref(c), obs.shape[0], ctypes.byref(need)))
+    key = (dev, need.value)
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.empty(max(need.value, 64), dtype=torch.uint8, device=dev)
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            _check(fn(c, ctypes.c_void_p(ws.data_ptr()), need.value, dev.index, ctypes.c_void_p(_raw_stream(dev.index))))
+    else:
+        _check(fn(c, ctypes.c_void_p(ws.data_ptr()), need.value, -1, None))
+
+
+def _ptr(t):
+    return ctypes.c_void_p(None if t is None or t.numel() == 0 else t.data_ptr())
+
+
+class _Evaluate(torch.autograd.Function):
+    """PolicyNet.evaluate: mbots_policy_eval forward, mbots_policy_grad backward."""
+
+    @staticmethod
+    def forward(ctx, net, obs, action, hidden, present, *params):
+        full = [None] * (2 * (len(net.trunk) + 4))
+        for i, p in zip(present, params):
+            full[i] = p.detach().contiguous()
+        n = obs.shape[0]
+        logp, value, entropy = (torch.empty(n, dtype=torch.float32, device=obs.device) for _ in range(3))
+        _eval_call(net, obs, hidden, action, full, lambda c, ws, nb, d, st: _lib.mbots_policy_eval(
+            ctypes.byref(c), _ptr(obs), _ptr(hidden), _ptr(action), n, _ptr(logp), _ptr(value), _ptr(entropy), ws, nb,
+            d, st))
+        ctx.net, ctx.rows, ctx.present, ctx.full = net, (obs, action, hidden), present, full
+        ctx.set_materialize_grads(False)   # an output the loss does not use: no g_* (zeros)
+        return logp, value, entropy
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logp, g_value, g_entropy):
+        net, (obs, action, hidden), present, full = ctx.net, ctx.rows, ctx.present, ctx.full
+        n = obs.shape[0]
+        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_logp, g_value, g_entropy)]
+        grads = [None] * len(full)
+        for k, i in enumerate(present):
+            if ctx.needs_input_grad[5 + k]:
+                grads[i] = torch.empty_like(full[i])
+        out = _PolicyGrads()
+        slots = [out.trunk[i] for i in range(len(net.trunk))] + [out.actor[0], out.actor[1], out.critic[0], out.critic[1]]
+        for i, slot in enumerate(slots):
+            slot.weight, slot.bias = _ptr(grads[2 * i]).value, _ptr(grads[2 * i + 1]).value
+        _eval_call(net, obs, hidden, action, full, lambda c, ws, nb, d, st: _lib.mbots_policy_grad(
+            ctypes.byref(c), _ptr(obs), _ptr(hidden), _ptr(action), n, _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
+            ctypes.byref(out), ws, nb, d, st))
+        return (None, None, None, None, None) + tuple(grads[i] for i in present)
 
 
 def policy_activation(act, x):

@@ -845,7 +845,8 @@ int mbots_kernel_times(mbots_handle *h, double ms[MBOTS_TK_COUNT],
  * out[0] flags -- 1 K1-finder mode (the next K1 does not wait for the last
  * sensor), 2 fork by value, 4 join by value, 8 MBOTS_SWAP, 16 mixed capacity
  * classes (MBOTS_MIXED), 32 armed for episodes (both modes), 64 HiddenState is
- * lazy right now (owed as a row map, not stored: DESIGN.md); out[1] the last
+ * lazy right now (owed as a row map, not stored: DESIGN.md), 128 PrevAction is
+ * owed right now (the shift launched no gather: DESIGN.md); out[1] the last
  * value-wait epoch raised; out[2] how often the epochs restarted from 0;
  * out[3] steps run.  CPU mode: all 0 but the 32 of out[0] and out[3]. */
 int mbots_schedule_info(mbots_handle *h, uint32_t out[4]);
@@ -872,6 +873,10 @@ const char *mbots_last_error(void);
  *   rows (the sensor's chain sets the step's pace: -2 % against the forked
  *   schedule); MBOTS_SWAP=0 keeps K1 and K2 on the caller's stream and forks
  *   the sensor off after K2.
+ * MBOTS_LAZY_PREV_ACTION (read at mbots_create): by default ("1") a shift
+ *   that would gather Action alone launches nothing and owes PrevAction until
+ *   somebody reads it (the same columns, no kernel in the headline loop);
+ *   MBOTS_LAZY_PREV_ACTION=0 keeps the gather in every shift.
  * MBOTS_MIXED (read at mbots_create; agent_capacity above 128, outside the
  *   K1 finder mode): by default ("1") the 128-slot K1 and sensor run every
  *   world that fits them and the capacity class's kernels only the worlds K2

@@ -1033,6 +1033,10 @@ __global__ __launch_bounds__(1024) void scan_kernel(SimState S, int parity)
             rows += (uint32_t)(g.x + g.y + g.z + g.w);
         }
         S.totals[kTotRows] = rows;
+        if (S.rows_out) {   // the owed columns' gathers read them (mbots_step)
+            S.rows_out[0] = rows;
+            S.rows_out[2] = rows;
+        }
         *S.agent_steps += (unsigned long long)s_tot[4];
         // the host reads the row counts straight from pinned memory once the
         // event after K2 completes (no D2H copy on the step's stream)
@@ -1329,6 +1333,15 @@ __global__ __launch_bounds__(256) void materialize_hidden_kernel(const uint32_t 
                                                                  MoveSeg sg)
 {
     gather_seg<uint4, 4>(sg, *rows, map);
+}
+
+// owed PrevAction materialised (DESIGN.md "Owed PrevAction"): the fused shift's
+// Action gather, dst[r] = base[map[r]] (0 where map[r] < 0), run when asked
+// for, over the *rows rows K2 recorded (0 once it has run)
+__global__ __launch_bounds__(256) void materialize_action_kernel(const uint32_t *rows, const int32_t *map,
+                                                                 MoveSeg sg)
+{
+    gather_seg<uint2, 3>(sg, *rows, map);
 }
 
 // ---------------------------------------------------------------------------
@@ -3001,6 +3014,17 @@ hipError_t launch_materialize_hidden(const SimState &S, const uint32_t *rows, co
                                                       S.W / 2u))
                             : (unsigned)MB_MOVE_BLOCKS;
     hipLaunchKernelGGL(materialize_hidden_kernel, dim3(bx), dim3(256), 0, st, rows, map, sg);
+    return hipGetLastError();
+}
+hipError_t launch_materialize_action(const SimState &S, const uint32_t *rows, const int32_t *map, const int32_t *base,
+                                     int32_t *dst, hipStream_t st)
+{
+    const MoveSeg sg{dst, base, 8u, 3u, 0u};
+    const unsigned bx = MB_MOVE_SMALL && S.W < 65536u
+                            ? std::max(256u, std::min(std::min((unsigned)MB_MOVE_BLOCKS, (unsigned)MB_MOVE_SMALL_CAP),
+                                                      S.W / 2u))
+                            : (unsigned)MB_MOVE_BLOCKS;
+    hipLaunchKernelGGL(materialize_action_kernel, dim3(bx), dim3(256), 0, st, rows, map, sg);
     return hipGetLastError();
 }
 // a dispatch whose completion records `done`: carried by the dispatch packet

@@ -89,6 +89,10 @@ struct SimState {
     uint32_t list_par;              // the parity whose lists this launch reads (host-set)
     int32_t *big_k1, *big_s;
     uint32_t *big_cnt;
+    // the owed columns' row counts (set by the host per step, or null): K2 stores
+    // the table's rows (totals[kTotRows]) into rows_out[0] (lazy HiddenState)
+    // and rows_out[2] (owed PrevAction) -- words by step parity, two apart
+    uint32_t *rows_out;
 };
 
 // per-world episode state of an armed manager (reset_worlds_kernel)
@@ -168,6 +172,9 @@ hipError_t launch_move(const SimState &S, const ObsTable &cur, const ObsTable &n
 // dst[r] = base[map[r]] (0 where map[r] < 0) for r < *rows: 64 B rows
 hipError_t launch_materialize_hidden(const SimState &S, const uint32_t *rows, const int32_t *map, const float *base,
                                      float *dst, hipStream_t st);
+// the same over 24 B Action rows (owed PrevAction: map is a step's src_of)
+hipError_t launch_materialize_action(const SimState &S, const uint32_t *rows, const int32_t *map, const int32_t *base,
+                                     int32_t *dst, hipStream_t st);
 hipError_t launch_sensor(const SimState &S, const ObsTable &nxt, hipStream_t st,
                          hipEvent_t done = nullptr, bool plain_events = false);
 // shift modes: every Prev* column / Action + HiddenState only (lazy) / the six

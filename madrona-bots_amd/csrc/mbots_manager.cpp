@@ -160,7 +160,25 @@ struct mbots_handle {
     const float *hid_base = nullptr;
     int32_t *hid_map2[2] = {nullptr, nullptr};   // the maps of alternate steps (by parity)
     uint32_t *hid_rows = nullptr;     // device word: the lazy half's row count (the lazy shift
-                                      // stores it; 0 once materialised)
+                                      // stores it, or -- owed PrevAction on -- K2 of the step
+                                      // whose map the shift takes; 0 once materialised)
+    // owed PrevAction (DESIGN.md "Owed PrevAction"): half pa_half's PrevAction
+    // storage holds nothing; the column is pa_base[pa_src[r]] (0 where
+    // pa_src[r] < 0) over *pa_rows rows, and while a_alias[pa_half] holds its
+    // Action is that too.  pa_base is the last half's Action as the shift saw
+    // it (src_view), pa_src the src_of buffer of the step before that shift:
+    // neither is written while the state holds.  A lazy shift enters it instead
+    // of launching the Action gather; materialize_prev_action ends it
+    bool pa_on = true;                // MBOTS_LAZY_PREV_ACTION (read at create)
+    bool pa_lazy = false;
+    int pa_half = 0;
+    const int32_t *pa_base = nullptr;
+    const int32_t *pa_src = nullptr;
+    uint32_t *pa_rows = nullptr;
+    int32_t *src_of2[2] = {nullptr, nullptr};   // src_of of alternate steps (by parity): K3a
+                                                // writes this step's, S.src_of names it
+    uint32_t *lazy_rows = nullptr;    // device words K2 stores the table's rows into: [parity]
+                                      // for lazy HiddenState, [2 + parity] for owed PrevAction
     hipEvent_t ev_hop = nullptr;      // orders a call's stream after the last one used
     // the swapped schedule (above 8192 worlds unless MBOTS_SWAP=0): K1 and K2 on
     // the sensor's stream, the caller's stream joining after K2 (DESIGN.md 4
@@ -379,12 +397,16 @@ size_t layout(mbots_handle *h, Arena &a)
     h->row_base2[1] = a.take<int32_t>(W * kNumSpecies);
     S.row_base = h->row_base2[0];
     S.world_off = a.take<int32_t>(W);
-    S.src_of = a.take<int32_t>(rows);
+    h->src_of2[0] = a.take<int32_t>(rows);
+    h->src_of2[1] = a.take<int32_t>(rows);
+    S.src_of = h->src_of2[0];
     h->hid_map2[0] = a.take<int32_t>(rows);
     h->hid_map2[1] = a.take<int32_t>(rows);
-    h->hid_rows = a.take<uint32_t>(1);
+    h->lazy_rows = a.take<uint32_t>(5);   // ([4]: the word a lazy shift's own launch stores)
+    h->hid_rows = h->lazy_rows + 4;
     S.map_in = nullptr;
     S.map_out = nullptr;
+    S.rows_out = nullptr;
     S.overflow = a.take<uint32_t>(W);
     S.fork_ctr = a.take<uint32_t>(1);
     S.totals = a.take<uint32_t>(8);
@@ -573,6 +595,27 @@ int materialize_hidden(mbots_handle *h, hipStream_t st)
     return MBOTS_OK;
 }
 
+// owed PrevAction ends (DESIGN.md "Owed PrevAction"): the gather the shift
+// did not launch, base[src_of[r]] into the owed half's PrevAction storage (a
+// storage of the other half is the base: never in place).  What is left is
+// what the fused shift leaves: PrevAction real, Action its view while
+// a_alias holds (a whole-table writer has cleared it otherwise)
+int materialize_prev_action(mbots_handle *h, hipStream_t st)
+{
+    if (!h->pa_lazy) return MBOTS_OK;
+    HIP_TRY(hipSetDevice(h->device));
+    const int rc = timed(h, MBOTS_TK_MOVE, st, [&] {
+        return mbots::launch_materialize_action(h->S, h->pa_rows, h->pa_src, h->pa_base, h->T[h->pa_half].paction, st);
+    });
+    if (rc) return rc;
+    // (as materialize_hidden: a graph that recorded the gather repeats it over 0 rows)
+    HIP_TRY(mbots::launch_raise_flag(h->pa_rows, 0u, st));
+    h->pa_lazy = false;
+    h->pa_base = nullptr;
+    h->pa_src = nullptr;
+    return MBOTS_OK;
+}
+
 // the deferred K4 part: PrevAction / PrevHiddenState of the current half from
 // the other half, along the last step's src_of (both intact until the next
 // step's K3a / K4)
@@ -581,6 +624,7 @@ int materialize_prev_ah(mbots_handle *h, hipStream_t st)
 {
     if (!h->ah_pending[h->tb]) return MBOTS_OK;
     if (int rc = materialize_hidden(h, st)) return rc;   // (its source is the last half's PrevHiddenState)
+    if (int rc = materialize_prev_action(h, st)) return rc;   // (... and its PrevAction)
     // the Prev storage holds the current columns (aliased): copied out before
     // the Prev move overwrites it
     const int cols = (h->a_alias[h->tb] ? 1 : 0) | (h->h_alias[h->tb] ? 2 : 0);
@@ -608,6 +652,11 @@ int materialize_cur_ah(mbots_handle *h, hipStream_t st, int alias_cols)
     // (lazy HiddenState: the move's source, or the column copied out)
     if (h->cur_ah_pending[tb] || ((alias_cols & 2) && h->h_alias[tb]))
         if (int rc = materialize_hidden(h, st)) return rc;
+    // (owed PrevAction: the move's source view, or -- its base -- the storage
+    // the move writes; the column copied out; and whatever is owed by the
+    // last half, whose storages the caller's writes reach next)
+    if (h->pa_lazy && (h->cur_ah_pending[tb] || h->pa_half != tb || ((alias_cols & 1) && h->a_alias[tb])))
+        if (int rc = materialize_prev_action(h, st)) return rc;
     if (h->cur_ah_pending[tb]) {
         HIP_TRY(hipSetDevice(h->device));
         const mbots::ObsTable src = src_view(h, tb ^ 1);
@@ -1062,6 +1111,12 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
         const bool want = e && *e ? e[0] == '1' : MB_SWAP_DEFAULT != 0;
         h->swap = want && S.W > MB_VALUE_FORK_MAX && !h->k1_finder && !h->sig_fork && !h->sig_join;
     }
+    {
+        // MBOTS_LAZY_PREV_ACTION=0: a lazy shift launches its Action gather, as
+        // before the owed state (an A/B inside one build)
+        const char *e = std::getenv("MBOTS_LAZY_PREV_ACTION");
+        h->pa_on = !(e && e[0] == '0');
+    }
     if (h->swap) check(hipEventCreateWithFlags(&h->ev_caller, kSyncEvent), "hipEventCreateWithFlags");
     check(hipEventCreateWithFlags(&h->ev_join[0], kSyncEvent), "hipEventCreateWithFlags");
     check(hipEventCreateWithFlags(&h->ev_join[1], kSyncEvent), "hipEventCreateWithFlags");
@@ -1233,6 +1288,14 @@ int mbots_step(mbots_handle *h, void *stream)
     if (h->hid_lazy && (h->hid_half != h->tb || h->hid_map == par || capturing ||
                         (prefetch & (mbots::kMoveAH | mbots::kMovePrevAH))))
         if ((rc = materialize_hidden(h, st))) return rc;
+    // owed PrevAction likewise goes on only from a shift whose Action a
+    // whole-table writer has replaced since (else K1 reads the owed view), and
+    // never into the step whose K3a and K2 write the src_of buffer and the row
+    // count it holds (a shift in between has made it dead; not assumed)
+    if (h->pa_lazy && (h->pa_half != h->tb || h->a_alias[h->tb] || h->pa_src == h->src_of2[par] ||
+                       h->pa_rows == h->lazy_rows + 2 + par || capturing ||
+                       (prefetch & (mbots::kMoveAH | mbots::kMovePrevAH))))
+        if ((rc = materialize_prev_action(h, st))) return rc;
     // no shift since the last step: its deferred Prev moves first
     if (h->six_pending[h->tb] && (rc = materialize_prev(h, st))) return rc;
     if ((rc = materialize_prev_ah(h, st))) return rc;
@@ -1339,7 +1402,12 @@ int mbots_step(mbots_handle *h, void *stream)
     // this step's row counts are K2's: no host read of them before it (ADVICE r4:
     // cleared here, after every materialisation above that may sync the last ones)
     h->totals_ok = false;
+    // (owed PrevAction on: K2 also stores the table's rows where the gathers of
+    // the owed columns read them -- the shift that follows launches nothing.
+    // Not where a graph could replay the store over a count still in use)
+    h->S.rows_out = h->pa_on && h->cap_seen == 0 && !capturing ? h->lazy_rows + par : nullptr;
     rc = timed(h, MBOTS_TK_SCAN, kst, [&] { return mbots::launch_scan(h->S, par, kst, h->ev_totals, capturing); });
+    h->S.rows_out = nullptr;
     h->maxpop_stale = false;
     h->S.epoch = 0;
     if (rc) return rc;
@@ -1391,6 +1459,10 @@ int mbots_step(mbots_handle *h, void *stream)
     h->S.map_out = map_wanted ? h->hid_map2[par] : nullptr;
     h->S.map_in = h->hid_lazy ? h->hid_map2[h->hid_map] : nullptr;
     h->hid_map_plain = map_wanted && !h->hid_lazy;
+    // this step's src_of goes to this parity's buffer (the last step's, which an
+    // owed PrevAction may still read, stays); every reader from here on finds it
+    // as S.src_of
+    h->S.src_of = h->src_of2[par];
     if ((rc = timed(h, MBOTS_TK_EXPORT, st,
                     [&] { return mbots::launch_export_rows(h->S, nxt, 0, st); })))
         return rc;
@@ -1467,22 +1539,50 @@ int mbots_shift_observations(mbots_handle *h, void *stream)
             h->hid_lazy = false;
         }
     }
+    // Owed PrevAction (DESIGN.md "Owed PrevAction"): the last half's owed
+    // column is the source of Action here while that is still its view (nobody
+    // wrote it: real rows first); else it is dead -- this shift supersedes the
+    // Prev move that would have read it -- and its base and src_of are free
+    if (fused && h->pa_lazy) {
+        if (h->pa_half != (tb ^ 1) || h->a_alias[tb ^ 1]) {
+            if ((rc = materialize_prev_action(h, st))) return rc;
+        } else {
+            h->pa_lazy = false;
+        }
+    }
     if (fused) {
         const mbots::ObsTable src = src_view(h, tb ^ 1);
-        rc = timed(h, MBOTS_TK_SHIFT, st, [&] {
-            return mbots::launch_move(h->S, src, h->T[tb], 0, mbots::kMoveAHShift, st, lazy ? h->hid_rows : nullptr);
-        });
+        const int last = h->parity ^ 1;   // the last step's buffers
+        // the launch would gather Action alone: PrevAction (and Action, its
+        // view) owed as (that Action, the last step's src_of) instead, and no
+        // launch at all -- K2 stored both row counts
+        const bool owe = lazy && h->pa_on && h->S.src_of == h->src_of2[last];
+        if (lazy) h->hid_rows = h->lazy_rows + (owe ? last : 4);
+        if (!owe)
+            rc = timed(h, MBOTS_TK_SHIFT, st, [&] {
+                return mbots::launch_move(h->S, src, h->T[tb], 0, mbots::kMoveAHShift, st,
+                                          lazy ? h->hid_rows : nullptr);
+            });
         if (rc == MBOTS_OK && lazy) {
             if (!old_lazy) h->hid_base = h->T[tb ^ 1].phidden;
             h->hid_lazy = true;
             h->hid_half = tb;
-            h->hid_map = h->parity ^ 1;   // the last step's buffer
+            h->hid_map = last;
+        }
+        if (owe) {
+            h->pa_lazy = true;
+            h->pa_half = tb;
+            h->pa_base = src.action;
+            h->pa_src = h->S.src_of;
+            h->pa_rows = h->lazy_rows + 2 + last;
         }
     } else if (!(h->a_alias[tb] && h->h_alias[tb])) {   // both aliased: already equal
         if ((rc = materialize_cur_ah(h, st, 3))) return rc;
         // (HiddenState was written since a lazy shift: the lazy PrevHiddenState
         // is overwritten here)
         if (h->hid_lazy && h->hid_half == tb) h->hid_lazy = false;
+        // (... and Action since an owed shift: so is the owed PrevAction)
+        if (h->pa_lazy && h->pa_half == tb) h->pa_lazy = false;
         rc = timed(h, MBOTS_TK_SHIFT, st,
                    [&] { return mbots::launch_shift(h->S, h->T[tb], mbots::kShiftEager, st); });
     }
@@ -1539,6 +1639,7 @@ int mbots_export_on(mbots_handle *h, int32_t id, void *stream, mbots_tensor *out
     case MBOTS_EXPORT_PREV_ACTION: case MBOTS_EXPORT_PREV_HIDDEN_STATE:
         need = mbots::kMovePrevAH;
         if (id == MBOTS_EXPORT_PREV_HIDDEN_STATE && (rc = materialize_hidden(h, st))) return rc;
+        if (id == MBOTS_EXPORT_PREV_ACTION && (rc = materialize_prev_action(h, st))) return rc;
         if ((rc = materialize_prev_ah(h, st))) return rc;
         break;
     case MBOTS_EXPORT_ACTION: case MBOTS_EXPORT_HIDDEN_STATE:
@@ -1776,6 +1877,7 @@ int mbots_pack_learner(mbots_handle *h, void *out, uint64_t out_rows, void *stre
     // the next step prefetches them beside its sensor)
     const int owed = pending_mask(h);
     if ((rc = materialize_hidden(h, st))) return rc;
+    if ((rc = materialize_prev_action(h, st))) return rc;
     if ((rc = materialize_prev(h, st))) return rc;
     if ((rc = materialize_prev_ah(h, st))) return rc;
     if ((rc = materialize_cur_ah(h, st, 3))) return rc;
@@ -2083,6 +2185,7 @@ int mbots_save_checkpoint(mbots_handle *h, void *dst, uint64_t bytes)
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = capture_guard(h, h->last_stream)) return rc;
     int rc0 = materialize_hidden(h, h->last_stream);
+    if (!rc0) rc0 = materialize_prev_action(h, h->last_stream);
     if (!rc0) rc0 = materialize_prev(h, h->last_stream);
     if (!rc0) rc0 = materialize_prev_ah(h, h->last_stream);
     if (!rc0) rc0 = materialize_cur_ah(h, h->last_stream, 3);
@@ -2146,6 +2249,9 @@ static int restored_reset(mbots_handle *h, bool sensed)
     h->hid_lazy = false;
     h->hid_map_plain = false;
     h->hid_base = nullptr;
+    h->pa_lazy = false;
+    h->pa_base = nullptr;
+    h->pa_src = nullptr;
     h->forced = 0;
     h->prefetched = 0;
     h->steps = 1;
@@ -2265,14 +2371,15 @@ struct LayoutPtrs {
     mbots::ObsTable T[2];
     int32_t *row_base2[2], *sorder2[2], *obsrow_out2[2], *done_zeros, *reset_flags, *sensor_index;
     int32_t *episode, *age;
-    int32_t *hid_map2[2];
-    uint32_t *hid_rows;
+    int32_t *hid_map2[2], *src_of2[2];
+    uint32_t *hid_rows, *lazy_rows;
 };
 LayoutPtrs layout_ptrs(const mbots_handle *h)
 {
     return {h->S, {h->T[0], h->T[1]}, {h->row_base2[0], h->row_base2[1]}, {h->sorder2[0], h->sorder2[1]},
             {h->obsrow_out2[0], h->obsrow_out2[1]}, h->done_zeros, h->reset_flags, h->sensor_index,
-            h->episode, h->age, {h->hid_map2[0], h->hid_map2[1]}, h->hid_rows};
+            h->episode, h->age, {h->hid_map2[0], h->hid_map2[1]}, {h->src_of2[0], h->src_of2[1]},
+            h->hid_rows, h->lazy_rows};
 }
 void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
 {
@@ -2283,8 +2390,10 @@ void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
         h->sorder2[k] = p.sorder2[k];
         h->obsrow_out2[k] = p.obsrow_out2[k];
         h->hid_map2[k] = p.hid_map2[k];
+        h->src_of2[k] = p.src_of2[k];
     }
     h->hid_rows = p.hid_rows;
+    h->lazy_rows = p.lazy_rows;
     h->done_zeros = p.done_zeros;
     h->reset_flags = p.reset_flags;
     h->sensor_index = p.sensor_index;
@@ -2323,6 +2432,7 @@ int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
     if ((uint64_t)h->S.W * new_capacity >= (1ull << 31))
         return fail(MBOTS_E_INVALID, "num_worlds * agent_capacity >= 2^31");
     int rc = materialize_hidden(h, h->last_stream);
+    if (!rc) rc = materialize_prev_action(h, h->last_stream);
     if (!rc) rc = materialize_prev(h, h->last_stream);
     if (!rc) rc = materialize_prev_ah(h, h->last_stream);
     if (!rc) rc = materialize_cur_ah(h, h->last_stream, 3);
@@ -2604,6 +2714,7 @@ int mbots_reset_worlds(mbots_handle *h, const uint32_t *global_worlds, uint32_t 
     int rc = use_stream(h, st);
     if (rc) return rc;
     if ((rc = arm(h, st))) return rc;
+    if ((rc = materialize_prev_action(h, st))) return rc;   // (an unusual call: the owed column made real)
     const uint32_t W = h->S.W;   // (the shard ghost is world W - 1: global index world_offset + num_worlds)
     if (!h->flag_stage) {
         HIP_TRY(hipHostMalloc((void **)&h->flag_stage, (size_t)W * sizeof(int32_t), hipHostMallocDefault));
@@ -2748,7 +2859,8 @@ int mbots_schedule_info(mbots_handle *h, uint32_t out[4])
         return MBOTS_OK;
     }
     out[0] = (h->k1_finder ? 1u : 0u) | (h->sig_fork ? 2u : 0u) | (h->sig_join ? 4u : 0u) | (h->swap ? 8u : 0u) |
-             (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u) | (h->hid_lazy ? 64u : 0u);
+             (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u) | (h->hid_lazy ? 64u : 0u) |
+             (h->pa_lazy ? 128u : 0u);
     out[1] = h->epoch;
     out[2] = h->epoch_wraps;
     out[3] = (uint32_t)h->steps;

@@ -1188,14 +1188,15 @@ class SimManager:
     def schedule_info(self):
         """The step schedule in use (mbots_schedule_info): {"k1_finder",
         "fork_by_value", "join_by_value", "swap", "mixed_classes", "episodes_armed",
-        "hidden_lazy" (HiddenState is owed as a row map right now): bool,
+        "hidden_lazy" (HiddenState is owed as a row map right now),
+        "prev_action_lazy" (PrevAction is owed: the last shift launched no gather): bool,
         "epoch", "epoch_wraps", "steps": int}."""
         v = (ctypes.c_uint32 * 4)()
         _check(_lib.mbots_schedule_info(self._h, v))
         f = v[0]
         return {"k1_finder": bool(f & 1), "fork_by_value": bool(f & 2), "join_by_value": bool(f & 4),
                 "swap": bool(f & 8), "mixed_classes": bool(f & 16), "episodes_armed": bool(f & 32),
-                "hidden_lazy": bool(f & 64),
+                "hidden_lazy": bool(f & 64), "prev_action_lazy": bool(f & 128),
                 "epoch": int(v[1]),
                 "epoch_wraps": int(v[2]), "steps": int(v[3])}
 

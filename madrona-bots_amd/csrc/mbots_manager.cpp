@@ -18,6 +18,7 @@
 #include "../../include/mbots.h"
 #include "mbots_kernels.hpp"
 #include "mbots_cpu.hpp"
+#include "mbots_defer.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -74,8 +75,6 @@ struct mbots_handle {
     int device = 0;
     mbots::SimState S{};
     mbots::ObsTable T[2]{};
-    int tb = 0;
-    int parity = 0;                   // K1 -> K2 tile-count buffer of this step
     Arena arena;
     int32_t *done_zeros = nullptr;    // Done column (never written, sim.cpp:74-75, B.7)
     int32_t *reset_flags = nullptr;   // WorldReset singleton per world: the live flag array
@@ -128,57 +127,16 @@ struct mbots_handle {
     bool poisoned = false;            // a graph of an odd number of steps was captured: the
                                       // host's table bookkeeping no longer follows the device
     uint32_t ovf_reported = 0;        // capacity drops reported so far (MBOTS_W_CAPACITY)
-    // deferred K4 parts of a table half (moved from the other half along the
-    // last src_of when needed): PrevAction / PrevHiddenState, the six other
-    // Prev* columns (from the other half's current ones when six_lazy)
-    bool cur_ah_pending[2] = {false, false};   // Action / HiddenState themselves
-    bool psem_pending[2] = {false, false};     // the prev sensor (moved only when read: dead at
-                                               // the next step)
-    bool ah_pending[2] = {false, false};
-    bool six_pending[2] = {false, false};
-    bool six_lazy[2] = {false, false};
-    // the half's current Action / HiddenState column is its Prev column: a
-    // fused shift gathered the moved rows into PrevAction / PrevHiddenState only
-    // (the learner overwrites the current ones next); readers go through
-    // src_view, accessors copy first (materialize_cur_ah)
-    bool a_alias[2] = {false, false};
-    bool h_alias[2] = {false, false};
-    bool prev_lazy[2] = {false, false};   // table half's six shift-owned Prev* columns are
-                                          // still its current ones (lazy shift, K5)
-    // lazy HiddenState (DESIGN.md "Lazy HiddenState"): half hid_half's
-    // PrevHiddenState storage holds nothing; the column is hid_base[map[r]] (0
-    // where map[r] < 0) with map = hid_map2[hid_map], the row map K3a composes
-    // every step, and while h_alias[hid_half] holds HiddenState is that too.
-    // hid_base is one of the two PrevHiddenState storages and is not written
-    // while the state holds.  The lazy half is the current one after a lazy
-    // shift and the last one after a step; materialize_hidden ends the state
-    bool hid_lazy = false;
-    int hid_half = 0;
-    int hid_map = 0;
-    bool hid_map_plain = false;       // the last step stored src_of as its map (it ran not lazy):
-                                      // the map a stretch may begin with
-    const float *hid_base = nullptr;
-    int32_t *hid_map2[2] = {nullptr, nullptr};   // the maps of alternate steps (by parity)
-    uint32_t *hid_rows = nullptr;     // device word: the lazy half's row count (the lazy shift
-                                      // stores it, or -- owed PrevAction on -- K2 of the step
-                                      // whose map the shift takes; 0 once materialised)
-    // owed PrevAction (DESIGN.md "Owed PrevAction"): half pa_half's PrevAction
-    // storage holds nothing; the column is pa_base[pa_src[r]] (0 where
-    // pa_src[r] < 0) over *pa_rows rows, and while a_alias[pa_half] holds its
-    // Action is that too.  pa_base is the last half's Action as the shift saw
-    // it (src_view), pa_src the src_of buffer of the step before that shift:
-    // neither is written while the state holds.  A lazy shift enters it instead
-    // of launching the Action gather; materialize_prev_action ends it
+    // the deferred columns of the two table halves, the current half and the
+    // step parity (mbots_defer.hpp)
+    mbots::defer::Deferred defer;
     bool pa_on = true;                // MBOTS_LAZY_PREV_ACTION (read at create)
-    bool pa_lazy = false;
-    int pa_half = 0;
-    const int32_t *pa_base = nullptr;
-    const int32_t *pa_src = nullptr;
-    uint32_t *pa_rows = nullptr;
+    int32_t *hid_map2[2] = {nullptr, nullptr};   // lazy HiddenState's row maps of alternate steps (by parity)
     int32_t *src_of2[2] = {nullptr, nullptr};   // src_of of alternate steps (by parity): K3a
                                                 // writes this step's, S.src_of names it
     uint32_t *lazy_rows = nullptr;    // device words K2 stores the table's rows into: [parity]
                                       // for lazy HiddenState, [2 + parity] for owed PrevAction
+                                      // ([4]: the word a lazy shift's own launch stores)
     hipEvent_t ev_hop = nullptr;      // orders a call's stream after the last one used
     // the swapped schedule (above 8192 worlds unless MBOTS_SWAP=0): K1 and K2 on
     // the sensor's stream, the caller's stream joining after K2 (DESIGN.md 4
@@ -193,9 +151,6 @@ struct mbots_handle {
                                       // the join is then the sensor's event)
     bool totals_ok = false;           // h_totals holds the last step's counts (synchronised)
     bool maxpop_stale = false;        // no K2 since a checkpoint load: the tile maxima are old
-    int forced = 0;                   // deferred parts the caller's reads needed since the
-                                      // last step (kMove*): the next step prefetches them
-    int prefetched = 0;               // parts this step prefetched and no shift superseded
     uint64_t steps = 0;               // steps run
     hipStream_t last_stream = nullptr;
     bool timing = false;
@@ -402,8 +357,7 @@ size_t layout(mbots_handle *h, Arena &a)
     S.src_of = h->src_of2[0];
     h->hid_map2[0] = a.take<int32_t>(rows);
     h->hid_map2[1] = a.take<int32_t>(rows);
-    h->lazy_rows = a.take<uint32_t>(5);   // ([4]: the word a lazy shift's own launch stores)
-    h->hid_rows = h->lazy_rows + 4;
+    h->lazy_rows = a.take<uint32_t>(5);
     S.map_in = nullptr;
     S.map_out = nullptr;
     S.rows_out = nullptr;
@@ -450,8 +404,8 @@ hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 mbots::ObsTable src_view(const mbots_handle *h, int half)
 {
     mbots::ObsTable t = h->T[half];
-    if (h->a_alias[half]) t.action = t.paction;
-    if (h->h_alias[half]) t.hidden = t.phidden;
+    if (h->defer.action_aliased(half)) t.action = t.paction;
+    if (h->defer.hidden_aliased(half)) t.hidden = t.phidden;
     return t;
 }
 
@@ -545,177 +499,90 @@ int use_stream(mbots_handle *h, hipStream_t st)
     return MBOTS_OK;
 }
 
-// copy the six Prev* columns a lazy shift left as views of the current ones
-// (on the stream the caller uses next)
-int materialize_prev(mbots_handle *h, hipStream_t st)
-{
-    if (h->six_pending[h->tb]) {   // a step's deferred move (no shift since)
+// The device work of the deferred columns' rules (mbots_defer.hpp): each
+// operation on the stream the caller uses next, timed as a move
+int sync_totals(mbots_handle *h);
+struct DeferExec {
+    mbots_handle *h;
+    hipStream_t st;
+    template <class F> int run(int kind, F &&launch)
+    {
         HIP_TRY(hipSetDevice(h->device));
-        const int rc = timed(h, MBOTS_TK_MOVE, st, [&] {
-            return mbots::launch_move(h->S, h->T[h->tb ^ 1], h->T[h->tb], h->six_lazy[h->tb] ? 1 : 0,
-                                      mbots::kMovePrev6, st);
+        return timed(h, kind, st, launch);
+    }
+    int move(int part, bool six_lazy)
+    {
+        const int tb = h->defer.tb;
+        const mbots::ObsTable src = part == mbots::kMoveAH ? src_view(h, tb ^ 1) : h->T[tb ^ 1];
+        return run(MBOTS_TK_MOVE, [&] { return mbots::launch_move(h->S, src, h->T[tb], six_lazy ? 1 : 0, part, st); });
+    }
+    int move_shift(int word)
+    {
+        const int tb = h->defer.tb;
+        const mbots::ObsTable src = src_view(h, tb ^ 1);
+        return run(MBOTS_TK_SHIFT, [&] {
+            return mbots::launch_move(h->S, src, h->T[tb], 0, mbots::kMoveAHShift, st,
+                                      word >= 0 ? h->lazy_rows + word : nullptr);
         });
-        if (rc) return rc;
-        h->six_pending[h->tb] = false;
+    }
+    int shift(bool rest)
+    {
+        return run(rest ? MBOTS_TK_MOVE : MBOTS_TK_SHIFT, [&] {
+            return mbots::launch_shift(h->S, h->T[h->defer.tb], rest ? mbots::kShiftRest : mbots::kShiftEager, st);
+        });
+    }
+    int gather_hidden(int half, int map, int base_half, int word, bool exchange)
+    {
+        if (exchange) std::swap(h->T[0].phidden, h->T[1].phidden);
+        if (int rc = run(MBOTS_TK_MOVE, [&] {
+                return mbots::launch_materialize_hidden(h->S, h->lazy_rows + word, h->hid_map2[map],
+                                                        h->T[base_half].phidden, h->T[half].phidden, st);
+            }))
+            return rc;
+        // (a graph that recorded the gather repeats it over 0 rows: the state it
+        // ends is the host's, not the device's at a replay)
+        HIP_TRY(mbots::launch_raise_flag(h->lazy_rows + word, 0u, st));
         return MBOTS_OK;
     }
-    if (!h->prev_lazy[h->tb]) return MBOTS_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const int rc = timed(h, MBOTS_TK_MOVE, st,
-                         [&] { return mbots::launch_shift(h->S, h->T[h->tb], mbots::kShiftRest, st); });
-    if (rc) return rc;
-    h->prev_lazy[h->tb] = false;
-    return MBOTS_OK;
-}
-
-// lazy HiddenState ends (DESIGN.md "Lazy HiddenState"): the lazy half's
-// PrevHiddenState gathered from the base along the composed map into its
-// storage -- the state a fused shift leaves (HiddenState its view while
-// h_alias holds), whichever half is lazy, so every deferred move that follows
-// finds real rows.  Never in place: when the base is that storage the rows go
-// to the other half's PrevHiddenState storage and the halves exchange the two
-// (that one is free while the state holds: the other half's PrevHiddenState
-// is dead after a shift, and owed -- written before it is read -- after a step)
-int materialize_hidden(mbots_handle *h, hipStream_t st)
-{
-    if (!h->hid_lazy) return MBOTS_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const int hh = h->hid_half;
-    if (h->T[hh].phidden == h->hid_base) std::swap(h->T[hh].phidden, h->T[hh ^ 1].phidden);
-    const int rc = timed(h, MBOTS_TK_MOVE, st, [&] {
-        return mbots::launch_materialize_hidden(h->S, h->hid_rows, h->hid_map2[h->hid_map], h->hid_base,
-                                                h->T[hh].phidden, st);
-    });
-    if (rc) return rc;
-    // (a graph that recorded the gather repeats it over 0 rows: the state it
-    // ends is the host's, not the device's at a replay)
-    HIP_TRY(mbots::launch_raise_flag(h->hid_rows, 0u, st));
-    h->hid_lazy = false;
-    h->hid_base = nullptr;
-    return MBOTS_OK;
-}
-
-// owed PrevAction ends (DESIGN.md "Owed PrevAction"): the gather the shift
-// did not launch, base[src_of[r]] into the owed half's PrevAction storage (a
-// storage of the other half is the base: never in place).  What is left is
-// what the fused shift leaves: PrevAction real, Action its view while
-// a_alias holds (a whole-table writer has cleared it otherwise)
-int materialize_prev_action(mbots_handle *h, hipStream_t st)
-{
-    if (!h->pa_lazy) return MBOTS_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    const int rc = timed(h, MBOTS_TK_MOVE, st, [&] {
-        return mbots::launch_materialize_action(h->S, h->pa_rows, h->pa_src, h->pa_base, h->T[h->pa_half].paction, st);
-    });
-    if (rc) return rc;
-    // (as materialize_hidden: a graph that recorded the gather repeats it over 0 rows)
-    HIP_TRY(mbots::launch_raise_flag(h->pa_rows, 0u, st));
-    h->pa_lazy = false;
-    h->pa_base = nullptr;
-    h->pa_src = nullptr;
-    return MBOTS_OK;
-}
-
-// the deferred K4 part: PrevAction / PrevHiddenState of the current half from
-// the other half, along the last step's src_of (both intact until the next
-// step's K3a / K4)
-int materialize_cur_ah(mbots_handle *h, hipStream_t st, int alias_cols);
-int materialize_prev_ah(mbots_handle *h, hipStream_t st)
-{
-    if (!h->ah_pending[h->tb]) return MBOTS_OK;
-    if (int rc = materialize_hidden(h, st)) return rc;   // (its source is the last half's PrevHiddenState)
-    if (int rc = materialize_prev_action(h, st)) return rc;   // (... and its PrevAction)
-    // the Prev storage holds the current columns (aliased): copied out before
-    // the Prev move overwrites it
-    const int cols = (h->a_alias[h->tb] ? 1 : 0) | (h->h_alias[h->tb] ? 2 : 0);
-    if (cols) {
-        const int rc = materialize_cur_ah(h, st, cols);
-        if (rc) return rc;
+    int gather_prev_action(int half, int par, bool base_prev)
+    {
+        const mbots::ObsTable &b = h->T[half ^ 1];
+        if (int rc = run(MBOTS_TK_MOVE, [&] {
+                return mbots::launch_materialize_action(h->S, h->lazy_rows + 2 + par, h->src_of2[par],
+                                                        base_prev ? b.paction : b.action, h->T[half].paction, st);
+            }))
+            return rc;
+        HIP_TRY(mbots::launch_raise_flag(h->lazy_rows + 2 + par, 0u, st));   // (as gather_hidden)
+        return MBOTS_OK;
     }
-    HIP_TRY(hipSetDevice(h->device));
-    const int rc = timed(h, MBOTS_TK_MOVE, st, [&] {
-        return mbots::launch_move(h->S, h->T[h->tb ^ 1], h->T[h->tb], 0, mbots::kMovePrevAH, st);
-    });
-    if (rc) return rc;
-    h->ah_pending[h->tb] = false;
-    return MBOTS_OK;
-}
-
-// the deferred Action / HiddenState move of the current half (K1, the learner
-// and every accessor of the two columns need it; a shift fuses it); then the
-// columns of `alias_cols` (1 Action, 2 HiddenState) a fused shift left as
-// views of their Prev columns are copied out
-int sync_totals(mbots_handle *h);
-int materialize_cur_ah(mbots_handle *h, hipStream_t st, int alias_cols)
-{
-    const int tb = h->tb;
-    // (lazy HiddenState: the move's source, or the column copied out)
-    if (h->cur_ah_pending[tb] || ((alias_cols & 2) && h->h_alias[tb]))
-        if (int rc = materialize_hidden(h, st)) return rc;
-    // (owed PrevAction: the move's source view, or -- its base -- the storage
-    // the move writes; the column copied out; and whatever is owed by the
-    // last half, whose storages the caller's writes reach next)
-    if (h->pa_lazy && (h->cur_ah_pending[tb] || h->pa_half != tb || ((alias_cols & 1) && h->a_alias[tb])))
-        if (int rc = materialize_prev_action(h, st)) return rc;
-    if (h->cur_ah_pending[tb]) {
+    int copy_out(bool action, bool hidden)
+    {
         HIP_TRY(hipSetDevice(h->device));
-        const mbots::ObsTable src = src_view(h, tb ^ 1);
-        const int rc = timed(h, MBOTS_TK_MOVE, st, [&] {
-            return mbots::launch_move(h->S, src, h->T[tb], 0, mbots::kMoveAH, st);
+        if (int rc = sync_totals(h)) return rc;
+        const size_t N = h->h_totals[mbots::kTotRows];   // the shard ghost's rows included
+        const mbots::ObsTable &t = h->T[h->defer.tb];
+        return timed(h, MBOTS_TK_MOVE, st, [&] {
+            hipError_t e = hipSuccess;
+            if (action && N)
+                e = hipMemcpyAsync(t.action, t.paction, N * 6 * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
+            if (e == hipSuccess && hidden && N)
+                e = hipMemcpyAsync(t.hidden, t.phidden, N * mbots::kHidden * sizeof(float), hipMemcpyDeviceToDevice, st);
+            return e;
         });
-        if (rc) return rc;
-        h->cur_ah_pending[tb] = false;
     }
-    const bool ca = (alias_cols & 1) && h->a_alias[tb], ch = (alias_cols & 2) && h->h_alias[tb];
-    if (!ca && !ch) return MBOTS_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    int rc = sync_totals(h);
-    if (rc) return rc;
-    const size_t N = h->h_totals[mbots::kTotRows];   // the shard ghost's rows included
-    const mbots::ObsTable &t = h->T[tb];
-    rc = timed(h, MBOTS_TK_MOVE, st, [&] {
-        hipError_t e = hipSuccess;
-        if (ca && N) e = hipMemcpyAsync(t.action, t.paction, N * 6 * sizeof(int32_t), hipMemcpyDeviceToDevice, st);
-        if (e == hipSuccess && ch && N)
-            e = hipMemcpyAsync(t.hidden, t.phidden, N * mbots::kHidden * sizeof(float), hipMemcpyDeviceToDevice, st);
-        return e;
-    });
-    if (rc) return rc;
-    if (ca) h->a_alias[tb] = false;
-    if (ch) h->h_alias[tb] = false;
-    return MBOTS_OK;
-}
-
-// the deferred prev-sensor move of the current half (accessors of the prev
-// sensor, construct_obs(prev), checkpoints, the next step; a shift fuses it)
-int materialize_psem(mbots_handle *h, hipStream_t st)
+    int wait_prev_sensor()
+    {
+        HIP_TRY(hipSetDevice(h->device));
+        return ::wait_prev_sensor(h, st);
+    }
+};
+mbots::defer::Env defer_env(const mbots_handle *h, bool capturing)
 {
-    if (!h->psem_pending[h->tb]) return MBOTS_OK;
-    HIP_TRY(hipSetDevice(h->device));
-    if (int rc = wait_prev_sensor(h, st)) return rc;   // its source rows are that sensor's
-    const int rc = timed(h, MBOTS_TK_MOVE, st, [&] {
-        return mbots::launch_move(h->S, h->T[h->tb ^ 1], h->T[h->tb], 0, mbots::kMoveSensor, st);
-    });
-    if (rc) return rc;
-    h->psem_pending[h->tb] = false;
-    return MBOTS_OK;
+    return {capturing, h->cap_seen != 0, h->pa_on, h->k1_finder && MB_FINDER_PSEM_BY_SENSOR};
 }
-
-// deferred parts still owed by the current half (kMove* bits)
-int pending_mask(const mbots_handle *h)
-{
-    const int tb = h->tb;
-    return (h->cur_ah_pending[tb] ? mbots::kMoveAH : 0) | (h->psem_pending[tb] ? mbots::kMoveSensor : 0) |
-           (h->ah_pending[tb] ? mbots::kMovePrevAH : 0) | (h->six_pending[tb] ? mbots::kMovePrev6 : 0);
-}
-
-// a caller's read that needs the parts `need`: the ones the step deferred
-// (owed when the read came) or prefetched are remembered for the next step
-void note_use(mbots_handle *h, int need, int owed)
-{
-    h->forced |= need & (owed | h->prefetched);
-}
-
+static_assert(mbots::defer::kPartAH == mbots::kMoveAH && mbots::defer::kPartSensor == mbots::kMoveSensor &&
+                  mbots::defer::kPartPrevAH == mbots::kMovePrevAH && mbots::defer::kPartPrev6 == mbots::kMovePrev6,
+              "mbots_defer.hpp names launch_move's parts");
 // the stream the manager last launched on is being captured into a graph
 bool capturing_now(const mbots_handle *h)
 {
@@ -1150,8 +1017,8 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
     // the init scan counted the initial population as agent-steps; reset
     unsigned long long zero = 0;
     check(hipMemcpy(S.agent_steps, &zero, sizeof(zero), hipMemcpyHostToDevice), "hipMemcpy");
-    h->tb = 0;
-    h->parity = 1;   // the init scan consumed buffer 0 and cleared buffer 1
+    h->defer.tb = 0;
+    h->defer.parity = 1;   // the init scan consumed buffer 0 and cleared buffer 1
     *out = h;
     return rc;
 }
@@ -1270,42 +1137,17 @@ int mbots_step(mbots_handle *h, void *stream)
     }
     if ((rc = use_stream(h, st))) return rc;
     if (capturing) ++h->cap_steps;
-    const mbots::ObsTable &nxt = h->T[h->tb ^ 1];
-    const int par = h->parity;
-    const int lazy = h->prev_lazy[h->tb] ? 1 : 0;
-    // the parts the caller's reads forced last step (a learner that reads the
-    // observation and PrevHiddenState between step and shift, as
-    // training_loop.py:47-88 does): moved right after this step's K3a, beside
-    // the sensor, instead of behind the wait for it (DESIGN.md "Prefetch")
-    int prefetch = h->forced;
-    h->forced = 0;
-    h->prefetched = prefetch;
-    // lazy HiddenState goes on only from a shift (the lazy half is then the
-    // current one, its map the last step's): after a step with no shift, before
-    // a prefetch of Action / HiddenState or their Prev columns, and under
-    // stream capture (a replay must not depend on the host's lazy state) it
-    // is materialised first
-    if (h->hid_lazy && (h->hid_half != h->tb || h->hid_map == par || capturing ||
-                        (prefetch & (mbots::kMoveAH | mbots::kMovePrevAH))))
-        if ((rc = materialize_hidden(h, st))) return rc;
-    // owed PrevAction likewise goes on only from a shift whose Action a
-    // whole-table writer has replaced since (else K1 reads the owed view), and
-    // never into the step whose K3a and K2 write the src_of buffer and the row
-    // count it holds (a shift in between has made it dead; not assumed)
-    if (h->pa_lazy && (h->pa_half != h->tb || h->a_alias[h->tb] || h->pa_src == h->src_of2[par] ||
-                       h->pa_rows == h->lazy_rows + 2 + par || capturing ||
-                       (prefetch & (mbots::kMoveAH | mbots::kMovePrevAH))))
-        if ((rc = materialize_prev_action(h, st))) return rc;
-    // no shift since the last step: its deferred Prev moves first
-    if (h->six_pending[h->tb] && (rc = materialize_prev(h, st))) return rc;
-    if ((rc = materialize_prev_ah(h, st))) return rc;
-    if ((rc = materialize_cur_ah(h, st, 0))) return rc;
-    // (a prev sensor still owed is dead from here on: the new table's prev
-    // sensor is the last table's sensor rows, updateSensorOutputIdx
-    // sim.cpp:736-789, not its prev sensor -- so it is never moved)
+    const mbots::ObsTable &nxt = h->T[h->defer.tb ^ 1];
+    const int par = h->defer.parity;
+    // what the last step still owes the current half that this step reads, and
+    // this step's part of the deferred columns (mbots_defer.hpp begin_step)
+    const mbots::defer::Env env = defer_env(h, capturing);
+    mbots::defer::StepPlan plan;
+    DeferExec ex{h, st};
+    if ((rc = h->defer.begin_step(ex, env, plan))) return rc;
     // K1 reads the learner's actions through the half's view (an aliased
     // Action column is its PrevAction), and so do this step's moves
-    const mbots::ObsTable cur = src_view(h, h->tb);
+    const mbots::ObsTable cur = src_view(h, h->defer.tb);
     // K1 reads the finder slots the previous step's sensor wrote, and writes the
     // state half that sensor read; the halves swap after K1.
     // (under stream capture only a join recorded in the same capture is waited
@@ -1405,7 +1247,7 @@ int mbots_step(mbots_handle *h, void *stream)
     // (owed PrevAction on: K2 also stores the table's rows where the gathers of
     // the owed columns read them -- the shift that follows launches nothing.
     // Not where a graph could replay the store over a count still in use)
-    h->S.rows_out = h->pa_on && h->cap_seen == 0 && !capturing ? h->lazy_rows + par : nullptr;
+    h->S.rows_out = plan.store_rows ? h->lazy_rows + par : nullptr;
     rc = timed(h, MBOTS_TK_SCAN, kst, [&] { return mbots::launch_scan(h->S, par, kst, h->ev_totals, capturing); });
     h->S.rows_out = nullptr;
     h->maxpop_stale = false;
@@ -1426,10 +1268,9 @@ int mbots_step(mbots_handle *h, void *stream)
     else HIP_TRY(hipStreamWaitEvent(h->aux, h->ev_totals, 0));
     // (K1-finder mode: the sensor also moves the last table's sensor rows into
     // its rows' prev-sensor columns, so no caller-stream wait is needed for them)
-    const bool psem_by_sensor = h->k1_finder && MB_FINDER_PSEM_BY_SENSOR;
-    if (psem_by_sensor) {
-        h->S.psem_src = h->T[h->tb].sem;
-        h->S.pdepth_src = (h->cfg.flags & MBOTS_FLAG_FIX_DEPTH_ALIAS) ? h->T[h->tb].depth : nullptr;
+    if (env.psem_by_sensor) {
+        h->S.psem_src = h->T[h->defer.tb].sem;
+        h->S.pdepth_src = (h->cfg.flags & MBOTS_FLAG_FIX_DEPTH_ALIAS) ? h->T[h->defer.tb].depth : nullptr;
     }
     h->S.list_par = (uint32_t)par;   // (mixed classes: this step's K2 lists)
     rc = timed(h, MBOTS_TK_SENSOR, h->aux, [&] {
@@ -1449,16 +1290,9 @@ int mbots_step(mbots_handle *h, void *stream)
         HIP_TRY(mbots::launch_raise_flag(h->sig_join, epoch, h->aux));
         h->join_epoch = epoch;
     }
-    // K3a composes the row map of lazy HiddenState into this step's buffer from
-    // the last step's (the other one: the lazy half's map stays readable until
-    // the next shift moves on to this one); not lazy, it stores src_of there,
-    // the map a lazy shift begins a stretch with -- only where the next shift
-    // could begin one: HiddenState is a view now (nothing but a shift makes it
-    // one), so a loop that writes memory every step stores no map
-    const bool map_wanted = h->hid_lazy || (h->h_alias[h->tb] && h->cap_seen == 0 && !capturing);
-    h->S.map_out = map_wanted ? h->hid_map2[par] : nullptr;
-    h->S.map_in = h->hid_lazy ? h->hid_map2[h->hid_map] : nullptr;
-    h->hid_map_plain = map_wanted && !h->hid_lazy;
+    // K3a's part of lazy HiddenState: the row map it composes or stores
+    h->S.map_out = plan.map_out >= 0 ? h->hid_map2[plan.map_out] : nullptr;
+    h->S.map_in = plan.map_in >= 0 ? h->hid_map2[plan.map_in] : nullptr;
     // this step's src_of goes to this parity's buffer (the last step's, which an
     // owed PrevAction may still read, stays); every reader from here on finds it
     // as S.src_of
@@ -1469,28 +1303,13 @@ int mbots_step(mbots_handle *h, void *stream)
     // (the prev sensor is the sensor's own part in K1-finder mode; moved here
     // instead, its source rows are the last sensor's, which this step's K1 did
     // not wait for in that mode)
-    if (psem_by_sensor) prefetch &= ~mbots::kMoveSensor;
-    if ((prefetch & mbots::kMoveSensor) && (rc = wait_prev_sensor(h, st))) return rc;
-    if (prefetch && (rc = timed(h, MBOTS_TK_MOVE, st, [&] {
-                         return mbots::launch_move(h->S, cur, nxt, lazy, prefetch, st);
-                     })))
+    if ((plan.prefetch & mbots::kMoveSensor) && (rc = wait_prev_sensor(h, st))) return rc;
+    if (plan.prefetch && (rc = timed(h, MBOTS_TK_MOVE, st, [&] {
+                              return mbots::launch_move(h->S, cur, nxt, plan.lazy, plan.prefetch, st);
+                          })))
         return rc;
     ++h->steps;
-    h->parity ^= 1;
-    h->tb ^= 1;
-    const int nt = h->tb;
-    // the new half's Prev* columns: eight moves deferred (a shift overwrites them)
-    h->prev_lazy[nt] = false;
-    h->a_alias[nt] = h->h_alias[nt] = false;
-    h->cur_ah_pending[nt] = true;
-    h->psem_pending[nt] = !psem_by_sensor;
-    h->ah_pending[nt] = true;
-    h->six_pending[nt] = true;
-    h->six_lazy[nt] = lazy != 0;
-    if (prefetch & mbots::kMoveAH) h->cur_ah_pending[nt] = false;
-    if (prefetch & mbots::kMoveSensor) h->psem_pending[nt] = false;
-    if (prefetch & mbots::kMovePrevAH) h->ah_pending[nt] = false;
-    if (prefetch & mbots::kMovePrev6) h->six_pending[nt] = false;
+    h->defer.end_step(plan, env.psem_by_sensor);
     // capacity drops the device has published so far (K2's pinned mirror of a
     // recent step: no synchronisation)
     return capacity_report(h, __atomic_load_n(&h->h_totals[mbots::kTotOverflow], __ATOMIC_RELAXED));
@@ -1507,96 +1326,8 @@ int mbots_shift_observations(mbots_handle *h, void *stream)
     hipStream_t st = as_stream(stream);
     int rc = use_stream(h, st);
     if (rc) return rc;
-    // Action / HiddenState now; the other six Prev* columns stay views of the
-    // current ones until the next step or an accessor needs them (K5, lazy
-    // shift).  Action / HiddenState still in the other half: one gather writes their
-    // Prev copies, and the current columns become views of those (the learner
-    // overwrites them next; DESIGN.md "Aliased current Action / HiddenState")
-    // -- the fused shift.  The step's prev-sensor move is not the shift's
-    // (shiftObservationsSystem, sim.cpp:1001-1035, leaves the sensor alone):
-    // it stays owed until a reader needs it and dies at the next step
-    // (DESIGN.md "Lazy prev sensor").
-    const int tb = h->tb;
-    const bool fused = h->cur_ah_pending[tb];
-    // Lazy HiddenState (DESIGN.md "Lazy HiddenState"): the last half's
-    // HiddenState is still only a view -- of its PrevHiddenState storage (a
-    // fused shift's: nobody copied it out or wrote it since), or of the lazy
-    // column -- so this half's HiddenState / PrevHiddenState are those rows
-    // along src_of: not gathered but owed, as (base, composed map).  The base
-    // is that storage on entry and stays while the state goes on.  Not under
-    // stream capture, nor once a graph of this manager's steps exists (its
-    // replays read the columns in the storages they recorded).
-    const bool old_lazy = h->hid_lazy && h->hid_half == (tb ^ 1);
-    const bool lazy = fused && h->h_alias[tb ^ 1] && h->cap_seen == 0 && !capturing(st) &&
-                      (old_lazy || (!h->hid_lazy && h->hid_map_plain));
-    if (fused && h->hid_lazy && !lazy) {
-        // the last half's lazy PrevHiddenState: the source of HiddenState here
-        // while that is its view; else dead (this shift overwrites what derives
-        // from it), and its base is free again
-        if (h->h_alias[tb ^ 1]) {
-            if ((rc = materialize_hidden(h, st))) return rc;
-        } else {
-            h->hid_lazy = false;
-        }
-    }
-    // Owed PrevAction (DESIGN.md "Owed PrevAction"): the last half's owed
-    // column is the source of Action here while that is still its view (nobody
-    // wrote it: real rows first); else it is dead -- this shift supersedes the
-    // Prev move that would have read it -- and its base and src_of are free
-    if (fused && h->pa_lazy) {
-        if (h->pa_half != (tb ^ 1) || h->a_alias[tb ^ 1]) {
-            if ((rc = materialize_prev_action(h, st))) return rc;
-        } else {
-            h->pa_lazy = false;
-        }
-    }
-    if (fused) {
-        const mbots::ObsTable src = src_view(h, tb ^ 1);
-        const int last = h->parity ^ 1;   // the last step's buffers
-        // the launch would gather Action alone: PrevAction (and Action, its
-        // view) owed as (that Action, the last step's src_of) instead, and no
-        // launch at all -- K2 stored both row counts
-        const bool owe = lazy && h->pa_on && h->S.src_of == h->src_of2[last];
-        if (lazy) h->hid_rows = h->lazy_rows + (owe ? last : 4);
-        if (!owe)
-            rc = timed(h, MBOTS_TK_SHIFT, st, [&] {
-                return mbots::launch_move(h->S, src, h->T[tb], 0, mbots::kMoveAHShift, st,
-                                          lazy ? h->hid_rows : nullptr);
-            });
-        if (rc == MBOTS_OK && lazy) {
-            if (!old_lazy) h->hid_base = h->T[tb ^ 1].phidden;
-            h->hid_lazy = true;
-            h->hid_half = tb;
-            h->hid_map = last;
-        }
-        if (owe) {
-            h->pa_lazy = true;
-            h->pa_half = tb;
-            h->pa_base = src.action;
-            h->pa_src = h->S.src_of;
-            h->pa_rows = h->lazy_rows + 2 + last;
-        }
-    } else if (!(h->a_alias[tb] && h->h_alias[tb])) {   // both aliased: already equal
-        if ((rc = materialize_cur_ah(h, st, 3))) return rc;
-        // (HiddenState was written since a lazy shift: the lazy PrevHiddenState
-        // is overwritten here)
-        if (h->hid_lazy && h->hid_half == tb) h->hid_lazy = false;
-        // (... and Action since an owed shift: so is the owed PrevAction)
-        if (h->pa_lazy && h->pa_half == tb) h->pa_lazy = false;
-        rc = timed(h, MBOTS_TK_SHIFT, st,
-                   [&] { return mbots::launch_shift(h->S, h->T[tb], mbots::kShiftEager, st); });
-    }
-    if (rc == MBOTS_OK) {
-        // Action / HiddenState and every Prev* column but the sensor's are the
-        // shift's now: a later read of them is not the step's deferred move
-        h->prefetched &= mbots::kMoveSensor;
-        if (fused) h->a_alias[tb] = h->h_alias[tb] = true;
-        h->cur_ah_pending[tb] = false;
-        h->prev_lazy[tb] = true;
-        h->ah_pending[tb] = false;   // the shift wrote PrevAction / PrevHiddenState
-        h->six_pending[tb] = false;  // ... and made the six the current columns
-    }
-    return rc;
+    DeferExec ex{h, st};
+    return h->defer.shift(ex, defer_env(h, capturing(st)));
 }
 
 int mbots_num_agents(mbots_handle *h, uint32_t *out)
@@ -1628,33 +1359,22 @@ int mbots_export_on(mbots_handle *h, int32_t id, void *stream, mbots_tensor *out
     // the view's deferred copies and joins go on the reader's stream, after
     // everything the manager enqueued (the step may have run on another)
     if ((rc = use_stream(h, st))) return rc;
-    const int owed = pending_mask(h);
-    int need = 0;
+    int want = 0;   // the deferred column the view names: real rows in its storage first
     switch (id) {
     case MBOTS_EXPORT_PREV_SPECIES: case MBOTS_EXPORT_PREV_POSITION: case MBOTS_EXPORT_PREV_HEALTH:
     case MBOTS_EXPORT_PREV_SURROUNDING: case MBOTS_EXPORT_PREV_REWARD: case MBOTS_EXPORT_PREV_STATS:
-        need = mbots::kMovePrev6;
-        if ((rc = materialize_prev(h, st))) return rc;
-        break;
-    case MBOTS_EXPORT_PREV_ACTION: case MBOTS_EXPORT_PREV_HIDDEN_STATE:
-        need = mbots::kMovePrevAH;
-        if (id == MBOTS_EXPORT_PREV_HIDDEN_STATE && (rc = materialize_hidden(h, st))) return rc;
-        if (id == MBOTS_EXPORT_PREV_ACTION && (rc = materialize_prev_action(h, st))) return rc;
-        if ((rc = materialize_prev_ah(h, st))) return rc;
-        break;
-    case MBOTS_EXPORT_ACTION: case MBOTS_EXPORT_HIDDEN_STATE:
-        need = mbots::kMoveAH;
-        if ((rc = materialize_cur_ah(h, st, id == MBOTS_EXPORT_ACTION ? 1 : 2))) return rc;
-        break;
-    case MBOTS_EXPORT_PREV_SENSOR_SEMANTIC: case MBOTS_EXPORT_PREV_SENSOR_DEPTH:
-        need = mbots::kMoveSensor;
-        if ((rc = materialize_psem(h, st))) return rc;
-        if (h->k1_finder && (rc = wait_sensor(h, st))) return rc;   // the sensor moved them
-        break;
+        want = defer::kPrev6; break;
+    case MBOTS_EXPORT_PREV_ACTION: want = defer::kPrevAction; break;
+    case MBOTS_EXPORT_PREV_HIDDEN_STATE: want = defer::kPrevHidden; break;
+    case MBOTS_EXPORT_ACTION: want = defer::kAction; break;
+    case MBOTS_EXPORT_HIDDEN_STATE: want = defer::kHidden; break;
+    case MBOTS_EXPORT_PREV_SENSOR_SEMANTIC: case MBOTS_EXPORT_PREV_SENSOR_DEPTH: want = defer::kPrevSensor; break;
     default: break;
     }
-    note_use(h, need, owed);
-    const ObsTable &t = h->T[h->tb];
+    DeferExec ex{h, st};
+    if (want && (rc = h->defer.require(ex, want, defer::How::Rows))) return rc;
+    if (want == defer::kPrevSensor && h->k1_finder && (rc = wait_sensor(h, st))) return rc;   // the sensor moved them
+    const ObsTable &t = h->T[h->defer.tb];
     const bool fixd = (h->cfg.flags & MBOTS_FLAG_FIX_DEPTH_ALIAS) != 0;
     void *p = nullptr;
     int dt = MBOTS_DTYPE_INT32;
@@ -1737,11 +1457,10 @@ int mbots_set_action(mbots_handle *h, uint32_t row, const int32_t action[6])
         return MBOTS_OK;
     }
     HIP_TRY(hipSetDevice(h->device));
-    const int owed = pending_mask(h);
     hipStream_t st = h->last_stream;
-    if ((rc = materialize_cur_ah(h, st, 1))) return rc;
-    note_use(h, mbots::kMoveAH, owed);
-    HIP_TRY(hipMemcpyAsync(h->T[h->tb].action + (size_t)row * 6, action, 6 * sizeof(int32_t),
+    DeferExec ex{h, st};
+    if ((rc = h->defer.require(ex, mbots::defer::kAction, mbots::defer::How::Rows))) return rc;
+    HIP_TRY(hipMemcpyAsync(h->T[h->defer.tb].action + (size_t)row * 6, action, 6 * sizeof(int32_t),
                            hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     return MBOTS_OK;
@@ -1775,18 +1494,15 @@ int mbots_write_synthetic_actions(mbots_handle *h, uint32_t seed, uint32_t step,
     hipStream_t st = as_stream(stream);
     int rc = use_stream(h, st);
     if (rc) return rc;
-    const int owed = pending_mask(h);
     // the writer rewrites every live row's Action (and HiddenState with
     // write_hidden): an aliased column of those is simply written, not copied
-    if ((rc = materialize_cur_ah(h, st, 0))) return rc;
-    note_use(h, mbots::kMoveAH, owed);
-    rc = timed(h, MBOTS_TK_ACTIONS, st, [&] {
-        return mbots::launch_synthetic_actions(h->S, h->T[h->tb], seed, step, write_hidden, st);
+    DeferExec ex{h, st};
+    if ((rc = h->defer.require(ex, mbots::defer::kAction | (write_hidden ? mbots::defer::kHidden : 0),
+                               mbots::defer::How::WriteAll)))
+        return rc;
+    return timed(h, MBOTS_TK_ACTIONS, st, [&] {
+        return mbots::launch_synthetic_actions(h->S, h->T[h->defer.tb], seed, step, write_hidden, st);
     });
-    if (rc) return rc;
-    h->a_alias[h->tb] = false;
-    if (write_hidden) h->h_alias[h->tb] = false;
-    return MBOTS_OK;
 }
 
 int mbots_construct_obs(mbots_handle *h, int32_t prev, float *out, uint64_t out_rows, void *stream)
@@ -1801,7 +1517,6 @@ int mbots_construct_obs(mbots_handle *h, int32_t prev, float *out, uint64_t out_
     hipStream_t st = as_stream(stream);
     int rc = use_stream(h, st);
     if (rc) return rc;
-    const int owed = pending_mask(h);
     // current semantic rows come from K3b (and in K1-finder mode the prev ones too)
     if ((!prev || h->k1_finder) && (rc = wait_sensor(h, st))) return rc;
     // The previous rows' health / position / surrounding: while the step's
@@ -1810,13 +1525,14 @@ int mbots_construct_obs(mbots_handle *h, int32_t prev, float *out, uint64_t out_
     // nothing materialised: the shift that follows in training_loop.py:135
     // makes the six the current columns, so the move is never run); the prev
     // sensor is moved (and remembered for the next step's prefetch)
-    const bool gather6 = prev && h->six_pending[h->tb];
-    if (prev && (rc = materialize_psem(h, st))) return rc;
-    if (prev) note_use(h, mbots::kMoveSensor, owed);
+    const mbots::defer::Deferred &d = h->defer;
+    const bool gather6 = prev && d.six_owed();
+    DeferExec ex{h, st};
+    if (prev && (rc = h->defer.require(ex, mbots::defer::kPrevSensor, mbots::defer::How::Rows))) return rc;
     return timed(h, MBOTS_TK_OBS, st, [&] {
-        return mbots::launch_construct_obs(h->S, h->T[h->tb], prev, h->prev_lazy[h->tb] ? 1 : 0, out,
-                                           (uint32_t)out_rows, st, gather6 ? &h->T[h->tb ^ 1] : nullptr,
-                                           h->six_lazy[h->tb] ? 1 : 0);
+        return mbots::launch_construct_obs(h->S, h->T[d.tb], prev, d.prev_is_current() ? 1 : 0, out,
+                                           (uint32_t)out_rows, st, gather6 ? &h->T[d.tb ^ 1] : nullptr,
+                                           d.six_lazy() ? 1 : 0);
     });
 }
 
@@ -1846,7 +1562,7 @@ int mbots_pack_rollout(mbots_handle *h, void *out, uint64_t out_rows, void *stre
     if (rc) return rc;
     if ((rc = wait_sensor(h, st))) return rc;   // the semantic / depth rows come from K3b
     return timed(h, MBOTS_TK_OBS, st, [&] {
-        return mbots::launch_pack_rollout(h->S, h->T[h->tb], out, (uint32_t)out_rows, st);
+        return mbots::launch_pack_rollout(h->S, h->T[h->defer.tb], out, (uint32_t)out_rows, st);
     });
 }
 
@@ -1875,18 +1591,12 @@ int mbots_pack_learner(mbots_handle *h, void *out, uint64_t out_rows, void *stre
     // every column the record carries in its storage: the step's deferred
     // moves the learner's reads need (and remembered, like the accessors', so
     // the next step prefetches them beside its sensor)
-    const int owed = pending_mask(h);
-    if ((rc = materialize_hidden(h, st))) return rc;
-    if ((rc = materialize_prev_action(h, st))) return rc;
-    if ((rc = materialize_prev(h, st))) return rc;
-    if ((rc = materialize_prev_ah(h, st))) return rc;
-    if ((rc = materialize_cur_ah(h, st, 3))) return rc;
-    if ((rc = materialize_psem(h, st))) return rc;
-    note_use(h, mbots::kMovePrev6 | mbots::kMovePrevAH | mbots::kMoveAH | mbots::kMoveSensor, owed);
+    DeferExec ex{h, st};
+    if ((rc = h->defer.require_all(ex, true))) return rc;
     if ((rc = wait_sensor(h, st))) return rc;   // the sensor rows (and what it moved)
     return timed(h, MBOTS_TK_OBS, st, [&] {
-        return mbots::launch_pack_learner(h->S, h->T[h->tb], h->prev_lazy[h->tb] ? 1 : 0, out, (uint32_t)out_rows,
-                                          st);
+        return mbots::launch_pack_learner(h->S, h->T[h->defer.tb], h->defer.prev_is_current() ? 1 : 0, out,
+                                          (uint32_t)out_rows, st);
     });
 }
 
@@ -1909,12 +1619,13 @@ int mbots_pack_learner_slim(mbots_handle *h, void *out, uint64_t out_rows, void 
     // in the joined schedule the last sensor's rows, the source of a prev
     // sensor still owed, were waited for by this step's K1
     if ((rc = wait_sensor(h, st))) return rc;
-    const int tb = h->tb;
+    const int tb = h->defer.tb;
     const mbots::ObsTable &last = h->T[tb ^ 1];
     return timed(h, MBOTS_TK_OBS, st, [&] {
-        return mbots::launch_pack_learner_slim(h->S, h->T[tb], h->prev_lazy[tb] ? 1 : 0,
-                                               h->six_pending[tb] ? &last : nullptr, h->six_lazy[tb] ? 1 : 0,
-                                               h->psem_pending[tb] ? &last : nullptr, out, (uint32_t)out_rows, st);
+        const mbots::defer::Deferred &d = h->defer;
+        return mbots::launch_pack_learner_slim(h->S, h->T[tb], d.prev_is_current() ? 1 : 0,
+                                               d.six_owed() ? &last : nullptr, d.six_lazy() ? 1 : 0,
+                                               d.psem_owed() ? &last : nullptr, out, (uint32_t)out_rows, st);
     });
 }
 
@@ -2061,19 +1772,17 @@ int mbots_write_actions(mbots_handle *h, const int32_t *action, const float *hid
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
     if ((rc = use_stream(h, st))) return rc;
-    const int tb = h->tb;
-    const int owed = pending_mask(h);
+    const int tb = h->defer.tb;
     // a column written only in part keeps its other rows: copied out of an
     // aliased Prev storage first; a column written whole is simply written
-    const int part = (action && rows < R && h->a_alias[tb] ? 1 : 0) | (hidden && rows < R && h->h_alias[tb] ? 2 : 0);
-    if ((rc = materialize_cur_ah(h, st, part))) return rc;
-    note_use(h, mbots::kMoveAH, owed);
+    DeferExec ex{h, st};
+    if ((rc = h->defer.require(ex, (action ? mbots::defer::kAction : 0) | (hidden ? mbots::defer::kHidden : 0),
+                               rows < R ? mbots::defer::How::WritePart : mbots::defer::How::WriteAll)))
+        return rc;
     const mbots::ObsTable &t = h->T[tb];
     if (action && rows) HIP_TRY(hipMemcpyAsync(t.action, action, rows * 6 * sizeof(int32_t), hipMemcpyDefault, st));
     if (hidden && rows)
         HIP_TRY(hipMemcpyAsync(t.hidden, hidden, rows * mbots::kHidden * sizeof(float), hipMemcpyDefault, st));
-    if (action) h->a_alias[tb] = false;
-    if (hidden) h->h_alias[tb] = false;
     return MBOTS_OK;
 }
 
@@ -2169,7 +1878,7 @@ int mbots_checkpoint_size(mbots_handle *h, uint64_t *out)
     }
     int rc = sync_totals(h);
     if (rc) return rc;
-    *out = ckpt_bytes(ckpt_segments(h, h->T[h->tb], h->h_totals[mbots::kTotRows])) +
+    *out = ckpt_bytes(ckpt_segments(h, h->T[h->defer.tb], h->h_totals[mbots::kTotRows])) +
            (h->armed ? ckpt_bytes(ckpt_episode_segments(h)) - sizeof(CkptHeader) : 0);
     return MBOTS_OK;
 }
@@ -2184,18 +1893,13 @@ int mbots_save_checkpoint(mbots_handle *h, void *dst, uint64_t bytes)
     }
     HIP_TRY(hipSetDevice(h->device));
     if (int rc = capture_guard(h, h->last_stream)) return rc;
-    int rc0 = materialize_hidden(h, h->last_stream);
-    if (!rc0) rc0 = materialize_prev_action(h, h->last_stream);
-    if (!rc0) rc0 = materialize_prev(h, h->last_stream);
-    if (!rc0) rc0 = materialize_prev_ah(h, h->last_stream);
-    if (!rc0) rc0 = materialize_cur_ah(h, h->last_stream, 3);
-    if (!rc0) rc0 = materialize_psem(h, h->last_stream);
-    if (rc0) return rc0;
+    DeferExec ex{h, h->last_stream};
+    if (int rc0 = h->defer.require_all(ex, false)) return rc0;
     HIP_TRY(hipDeviceSynchronize());   // the sensor's finder / semantic rows included
     int rc = sync_totals(h);
     if (rc) return rc;
     const uint32_t n_rows = h->h_totals[mbots::kTotRows];   // the shard ghost's rows included
-    auto segs = ckpt_segments(h, h->T[h->tb], n_rows);
+    auto segs = ckpt_segments(h, h->T[h->defer.tb], n_rows);
     if (h->armed)
         for (const Seg &s : ckpt_episode_segments(h)) segs.push_back(s);
     const size_t need = ckpt_bytes(segs);
@@ -2234,26 +1938,11 @@ static int restored_reset(mbots_handle *h, bool sensed)
         HIP_TRY(hipMemset(h->S.big_cnt, 0, 4 * sizeof(uint32_t)));
         HIP_TRY(mbots::launch_build_lists(h->S, 1, nullptr));
     }
-    h->tb = 0;
-    h->parity = 0;
     h->last_join = -1;
     h->prev_join = -1;
     h->waited_serial = h->sensor_serial;   // (the device is idle)
     h->join_epoch = 0;
-    h->prev_lazy[0] = h->prev_lazy[1] = false;
-    h->ah_pending[0] = h->ah_pending[1] = false;
-    h->six_pending[0] = h->six_pending[1] = false;
-    h->cur_ah_pending[0] = h->cur_ah_pending[1] = false;
-    h->psem_pending[0] = h->psem_pending[1] = false;
-    h->a_alias[0] = h->a_alias[1] = h->h_alias[0] = h->h_alias[1] = false;
-    h->hid_lazy = false;
-    h->hid_map_plain = false;
-    h->hid_base = nullptr;
-    h->pa_lazy = false;
-    h->pa_base = nullptr;
-    h->pa_src = nullptr;
-    h->forced = 0;
-    h->prefetched = 0;
+    h->defer.reset();   // (half 0, parity 0, nothing deferred)
     h->steps = 1;
     h->sensed = sensed;
     hipStream_t st = nullptr;
@@ -2372,14 +2061,14 @@ struct LayoutPtrs {
     int32_t *row_base2[2], *sorder2[2], *obsrow_out2[2], *done_zeros, *reset_flags, *sensor_index;
     int32_t *episode, *age;
     int32_t *hid_map2[2], *src_of2[2];
-    uint32_t *hid_rows, *lazy_rows;
+    uint32_t *lazy_rows;
 };
 LayoutPtrs layout_ptrs(const mbots_handle *h)
 {
     return {h->S, {h->T[0], h->T[1]}, {h->row_base2[0], h->row_base2[1]}, {h->sorder2[0], h->sorder2[1]},
             {h->obsrow_out2[0], h->obsrow_out2[1]}, h->done_zeros, h->reset_flags, h->sensor_index,
             h->episode, h->age, {h->hid_map2[0], h->hid_map2[1]}, {h->src_of2[0], h->src_of2[1]},
-            h->hid_rows, h->lazy_rows};
+            h->lazy_rows};
 }
 void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
 {
@@ -2392,7 +2081,6 @@ void set_layout_ptrs(mbots_handle *h, const LayoutPtrs &p)
         h->hid_map2[k] = p.hid_map2[k];
         h->src_of2[k] = p.src_of2[k];
     }
-    h->hid_rows = p.hid_rows;
     h->lazy_rows = p.lazy_rows;
     h->done_zeros = p.done_zeros;
     h->reset_flags = p.reset_flags;
@@ -2431,18 +2119,14 @@ int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
                                      "a new manager (or load a checkpoint into one) to change agent_capacity");
     if ((uint64_t)h->S.W * new_capacity >= (1ull << 31))
         return fail(MBOTS_E_INVALID, "num_worlds * agent_capacity >= 2^31");
-    int rc = materialize_hidden(h, h->last_stream);
-    if (!rc) rc = materialize_prev_action(h, h->last_stream);
-    if (!rc) rc = materialize_prev(h, h->last_stream);
-    if (!rc) rc = materialize_prev_ah(h, h->last_stream);
-    if (!rc) rc = materialize_cur_ah(h, h->last_stream, 3);
-    if (!rc) rc = materialize_psem(h, h->last_stream);
+    DeferExec ex{h, h->last_stream};
+    int rc = h->defer.require_all(ex, false);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());   // the sensor's finder / semantic rows included
     if ((rc = sync_totals(h))) return rc;
     const uint32_t n_rows = h->h_totals[mbots::kTotRows];   // the shard ghost's rows included
     // the old storage: what a checkpoint would save, and the row provenance
-    const std::vector<Seg> from = ckpt_segments(h, h->T[h->tb], n_rows);
+    const std::vector<Seg> from = ckpt_segments(h, h->T[h->defer.tb], n_rows);
     const int32_t *src_of_old = h->S.src_of;
     const std::vector<Seg> ep_from = ckpt_episode_segments(h);
     const LayoutPtrs old = layout_ptrs(h);
@@ -2662,7 +2346,7 @@ int mbots_set_world_state(mbots_handle *h, uint32_t world, const float *xy_rwrz,
     memcpy(&hd, blob.data(), sizeof(hd));
     const SimState &S = h->S;
     const size_t cap = h->cfg.agent_capacity, base = (size_t)world * cap;
-    const auto segs = ckpt_segments(h, h->T[h->tb], hd.n_rows);
+    const auto segs = ckpt_segments(h, h->T[h->defer.tb], hd.n_rows);
     char *q = blob.data() + sizeof(hd);
     for (const Seg &s : segs) {   // the population first: nothing is patched on a mismatch
         if (s.p == S.n) {
@@ -2714,7 +2398,8 @@ int mbots_reset_worlds(mbots_handle *h, const uint32_t *global_worlds, uint32_t 
     int rc = use_stream(h, st);
     if (rc) return rc;
     if ((rc = arm(h, st))) return rc;
-    if ((rc = materialize_prev_action(h, st))) return rc;   // (an unusual call: the owed column made real)
+    DeferExec ex{h, st};
+    if ((rc = h->defer.require_prev_action_storage(ex))) return rc;   // (an unusual call: the owed column made real)
     const uint32_t W = h->S.W;   // (the shard ghost is world W - 1: global index world_offset + num_worlds)
     if (!h->flag_stage) {
         HIP_TRY(hipHostMalloc((void **)&h->flag_stage, (size_t)W * sizeof(int32_t), hipHostMallocDefault));
@@ -2859,8 +2544,8 @@ int mbots_schedule_info(mbots_handle *h, uint32_t out[4])
         return MBOTS_OK;
     }
     out[0] = (h->k1_finder ? 1u : 0u) | (h->sig_fork ? 2u : 0u) | (h->sig_join ? 4u : 0u) | (h->swap ? 8u : 0u) |
-             (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u) | (h->hid_lazy ? 64u : 0u) |
-             (h->pa_lazy ? 128u : 0u);
+             (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u) | (h->defer.hidden_lazy() ? 64u : 0u) |
+             (h->defer.prev_action_owed() ? 128u : 0u);
     out[1] = h->epoch;
     out[2] = h->epoch_wraps;
     out[3] = (uint32_t)h->steps;
@@ -3037,27 +2722,27 @@ int mbots_traj_push(mbots_handle *h, const float *value, void *stream)
         if (int rc = use_stream(h, st)) return rc;
         // after the step's K3a (this stream's order), which wrote the
         // provenance and the Reward column; not after its sensor
-        HIP_TRY(mbots::launch_traj_push(h->S, tj.w, slot, h->T[h->tb].reward, value, h->reset_mark, st));
+        HIP_TRY(mbots::launch_traj_push(h->S, tj.w, slot, h->T[h->defer.tb].reward, value, h->reset_mark, st));
         int rc;
         if (tj.w.hidden) {
             // Action / HiddenState where mbots_pack_learner reads them: the step's
             // deferred move of the two, then the sensor (and what it moved)
-            const int owed = pending_mask(h);
-            if ((rc = materialize_cur_ah(h, st, 3))) return rc;
-            note_use(h, mbots::kMoveAH, owed);
+            DeferExec ex{h, st};
+            if ((rc = h->defer.require(ex, mbots::defer::kAction | mbots::defer::kHidden, mbots::defer::How::Rows)))
+                return rc;
         }
         if (tj.w.hidden || tj.w.rec) {
             if ((rc = wait_sensor(h, st))) return rc;   // the semantic / depth rows come from K3b
         }
         // (timed like mbots_pack_rollout / mbots_pack_learner: mbots_kernel_times sees them)
         if (tj.w.rec && (rc = timed(h, MBOTS_TK_OBS, st, [&] {
-                return mbots::launch_pack_rollout(h->S, h->T[h->tb],
+                return mbots::launch_pack_rollout(h->S, h->T[h->defer.tb],
                                                   tj.w.rec + (size_t)slot * tj.w.max_rows * tj.w.rec_bytes,
                                                   tj.w.max_rows, st);
             })))
             return rc;
         if (tj.w.hidden && (rc = timed(h, MBOTS_TK_OBS, st, [&] {
-                return mbots::launch_traj_push_state(h->S, tj.w, slot, h->T[h->tb], st);
+                return mbots::launch_traj_push_state(h->S, tj.w, slot, h->T[h->defer.tb], st);
             })))
             return rc;
     }
@@ -3495,32 +3180,34 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
     hipStream_t st = as_stream(stream);
     int rc = use_stream(h, st);
     if (rc) return rc;
-    const int tb = h->tb;
-    const int owed = pending_mask(h);
+    const int tb = h->defer.tb;
+    namespace defer = mbots::defer;
+    DeferExec ex{h, st};
     // the inputs: the sensor's rows (mbots_construct_obs), and HiddenState where
     // its readers find it (the step's deferred move done; a column a fused shift
     // left aliased is read in its Prev storage, not copied)
     if ((rc = wait_sensor(h, st))) return rc;
-    if ((rc = materialize_cur_ah(h, st, 0))) return rc;
-    note_use(h, mbots::kMoveAH, owed);
-    bool writes_hidden = false, reads_hidden = false;
+    bool writes_hidden = false, reads_hidden = false, all_hidden = true;
     for (int s = 0; s < mbots::kNumSpecies; ++s) {
         writes_hidden |= h->pol.nets.net[s].has_memory != 0;
+        all_hidden &= h->pol.nets.net[s].has_memory != 0;
         reads_hidden |= (h->pol.nets.net[s].flags & mbots::kPolMemoryIn) != 0u;
     }
     // (a lazy HiddenState column a net reads, or keeps rows of: real rows first;
     // memoryless nets leave it lazy)
-    if ((reads_hidden || writes_hidden) && h->h_alias[tb] && (rc = materialize_hidden(h, st))) return rc;
-    const mbots::ObsTable view = src_view(h, tb);
+    if ((rc = h->defer.require(ex, defer::kAction | (reads_hidden || writes_hidden ? defer::kHidden : 0),
+                               defer::How::View)))
+        return rc;
     const bool write = !(flags & MBOTS_ACT_NO_WRITE);
     // a net without a memory head leaves its rows' HiddenState as it is: if the
     // column is written at all (another species' head) while still aliased, the
     // rows it keeps are copied out first, as mbots_write_actions does for a part
-    bool all_hidden = true;
-    for (int s = 0; s < mbots::kNumSpecies; ++s) all_hidden &= h->pol.nets.net[s].has_memory != 0;
-    if (write && writes_hidden && !all_hidden && h->h_alias[tb])
-        if ((rc = materialize_cur_ah(h, st, 2))) return rc;
-    const float *hidden_in = h->h_alias[tb] ? view.hidden : h->T[tb].hidden;
+    if (write && writes_hidden && !all_hidden && (rc = h->defer.require(ex, defer::kHidden, defer::How::WritePart)))
+        return rc;
+    const float *hidden_in = src_view(h, tb).hidden;
+    // (the columns the nets write whole are simply written)
+    if (write && (rc = h->defer.require(ex, defer::kAction | (writes_hidden ? defer::kHidden : 0), defer::How::WriteAll)))
+        return rc;
     rc = timed(h, MBOTS_TK_ACTIONS, st, [&] {
         return mbots::launch_policy_act(h->S, h->T[tb], hidden_in, h->pol.nets, flags, h->pol.draw, action_out,
                                         logp_out, value_out, (uint32_t)out_rows,
@@ -3528,10 +3215,6 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
     });
     if (rc) return rc;
     HIP_TRY(mbots::launch_policy_draw_next(h->pol.draw, st));
-    if (write) {
-        h->a_alias[tb] = false;
-        if (writes_hidden) h->h_alias[tb] = false;
-    }
     return MBOTS_OK;
 }
 

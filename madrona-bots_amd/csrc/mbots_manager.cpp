@@ -19,6 +19,7 @@
 #include "mbots_kernels.hpp"
 #include "mbots_cpu.hpp"
 #include "mbots_defer.hpp"
+#include "mbots_sched.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -99,20 +100,14 @@ struct mbots_handle {
     hipEvent_t ev_render_list = nullptr;
     int32_t *sensor_index = nullptr;  // scratch for sensorIndexTensor
     uint32_t *h_totals = nullptr;     // pinned mirror of S.totals
-    hipEvent_t ev_totals = nullptr;
-    hipStream_t aux = nullptr;        // internal stream of the K3b sensor (forked after K2)
-    hipEvent_t ev_join[2] = {nullptr, nullptr};   // K3b of alternate steps done (aux)
-    int last_join = -1;               // ev_join of the latest K3b, -1: none pending
-    unsigned long long join_capture = 0;   // stream-capture id it was recorded in (0: none)
-    int prev_join = -1;               // ev_join of the K3b before it (its rows are the other
-                                      // table half's), -1: none
-    unsigned long long prev_capture = 0;
-    uint64_t join_serial[2] = {0, 0}; // the sensor launch (1, 2, ...) each ev_join marks
-    uint64_t sensor_serial = 0;       // sensors launched
-    uint64_t waited_serial = 0;       // the newest sensor the manager's stream order has waited
-                                      // for (outside graph capture; every call follows the last)
-    bool k1_finder = false;           // K1 computes the finder slots (small world counts):
-                                      // the next K1 does not wait for the sensor
+    // the step's cross-queue ordering (mbots_sched.hpp), and the HIP objects its
+    // indices name: the sensor's internal stream (forked after K2), the events
+    // (ev[kTotals] also orders the host's reads of h_totals) and the signal
+    // words of the value waits (null: event waits)
+    mbots::sched::Schedule sched;
+    hipStream_t aux = nullptr;
+    hipEvent_t ev[mbots::sched::kNumEvents] = {};
+    uint32_t *sig[2] = {nullptr, nullptr};
     bool sensed = false;              // a sensor has run since init (the finder slots are then
                                       // the centre ray's, before it the init's "none")
     int32_t *row_base2[2] = {nullptr, nullptr};   // row bases / sensor order of alternate
@@ -121,11 +116,6 @@ struct mbots_handle {
     int32_t *obsrow_out2[2] = {nullptr, nullptr}; // K1's old-row column of alternate steps (in
                                                   // K1-finder mode the sensor reads the last
                                                   // step's while the next K1 writes)
-    unsigned long long cap_seen = 0;  // the stream capture the last captured step belonged to
-    hipStream_t cap_stream = nullptr; // the stream it was recorded on (live while capturing)
-    uint64_t cap_steps = 0;           // steps recorded into it (mbots_join wants an even count)
-    bool poisoned = false;            // a graph of an odd number of steps was captured: the
-                                      // host's table bookkeeping no longer follows the device
     uint32_t ovf_reported = 0;        // capacity drops reported so far (MBOTS_W_CAPACITY)
     // the deferred columns of the two table halves, the current half and the
     // step parity (mbots_defer.hpp)
@@ -137,22 +127,9 @@ struct mbots_handle {
     uint32_t *lazy_rows = nullptr;    // device words K2 stores the table's rows into: [parity]
                                       // for lazy HiddenState, [2 + parity] for owed PrevAction
                                       // ([4]: the word a lazy shift's own launch stores)
-    hipEvent_t ev_hop = nullptr;      // orders a call's stream after the last one used
-    // the swapped schedule (above 8192 worlds unless MBOTS_SWAP=0): K1 and K2 on
-    // the sensor's stream, the caller's stream joining after K2 (DESIGN.md 4
-    // "Which chain sets the pace")
-    bool swap = false;
-    hipEvent_t ev_caller = nullptr;   // the caller's stream at a step's start
-    uint32_t *sig_fork = nullptr;     // the fork's signal word (small world counts)
-    uint32_t *sig_join = nullptr;     // the join's (raised after the sensor)
-    uint32_t epoch = 0;               // the last epoch K2 raised (never 0)
-    uint32_t epoch_wraps = 0;         // times the epochs restarted from 0 (kEpochWrap)
-    uint32_t join_epoch = 0;          // the epoch raised after the last sensor (0: none;
-                                      // the join is then the sensor's event)
     bool totals_ok = false;           // h_totals holds the last step's counts (synchronised)
     bool maxpop_stale = false;        // no K2 since a checkpoint load: the tile maxima are old
     uint64_t steps = 0;               // steps run
-    hipStream_t last_stream = nullptr;
     bool timing = false;
     std::vector<TimedPair> pending;
     std::vector<hipEvent_t> pool;
@@ -197,71 +174,27 @@ struct mbots_handle {
 
 namespace {
 
-// The fork (K2 -> the sensor's queue) as a hipStreamWaitValue32 on a flag K2's
-// last block stores, instead of a wait on K2's completion signal: the hop is
-// ~3 us instead of ~7 (scripts/ubench/hop_latency.hip).  At small world
-// counts the step is a latency chain and that is -1 to -4 % at 4096 worlds;
-// from 16384 on the chip is throughput-bound from K1's end on and the flag's
-// fences cost about what the hop saves (±0 at 16384, +0.2-0.6 % at 65536), so
-// events there (profiles/r04_value_fork_small_ab.jsonl,
-// profiles/r04_value_waits_ab.jsonl, DESIGN_EXPERIMENTS.md round 4).
-#ifndef MB_VALUE_FORK_MAX
-#define MB_VALUE_FORK_MAX 8192
-#endif
-#ifndef MB_VALUE_JOIN
-#define MB_VALUE_JOIN 1   // the join too: a one-wave kernel after the sensor raises it
-#endif
-#ifndef MB_VALUE_JOIN_MAX
-#define MB_VALUE_JOIN_MAX 8192
-#endif
 #ifndef MB_FINDER_PSEM_BY_SENSOR
 #define MB_FINDER_PSEM_BY_SENSOR 1   // K1-finder mode: the sensor moves the prev-sensor rows itself
 #endif
-#ifndef MB_SWAP_DEFAULT
-#define MB_SWAP_DEFAULT 1   // MBOTS_SWAP's default (large world counts)
-#endif
-#ifndef MB_VALUE_ADAPT
-#define MB_VALUE_ADAPT 1   // value waits only while the host runs ahead of the device
-#endif
-// Up to this many worlds K1 computes the next step's finder slots itself
-// (world_finders), so the next K1 waits only for the caller's stream, not for
-// this step's sensor: the sensor chain and the caller chain of consecutive
-// steps overlap ("Small world counts")
-#ifndef MB_FINDER_AUX_LOW
-#define MB_FINDER_AUX_LOW 0
-#endif
-#ifndef MB_K1_FINDER_MAX
-#define MB_K1_FINDER_MAX 2048
-#endif
-// The runtime carries the wait as a polling kernel on the sensor's queue, which
-// spins until K2 (on the caller's queue) raises the flag: under a tool that runs
-// the device's kernels one at a time (rocprofv3 counter collection,
-// AMD_SERIALIZE_KERNEL) the poller can be dispatched first and never end, so
-// those keep the event wait (as does MBOTS_VALUE_FORK=0).
-// the value waits' epochs restart from 0 once they reach this (mbots_step)
-constexpr uint32_t kEpochWrap = 0x7FFFFFF0u;
 bool env_set(const char *name)
 {
     const char *v = std::getenv(name);
     return v && *v && std::strcmp(v, "0") != 0;
 }
-// (the list and the switch are documented in include/mbots.h, "Environment")
-bool value_waits_safe()
+// the environment's part of the schedule's choice (the list and the switches
+// are documented in include/mbots.h, "Environment")
+mbots::sched::Knobs sched_knobs()
 {
+    mbots::sched::Knobs k;
     const char *o = std::getenv("MBOTS_VALUE_FORK");
-    if (o && std::strcmp(o, "0") == 0) return false;
+    if (o && std::strcmp(o, "0") == 0) k.value_waits_safe = false;
     static const char *const kSerialising[] = MBOTS_SERIALISING_ENV;
     for (const char *name : kSerialising)
-        if (env_set(name)) return false;
-    return true;
-}
-// (K1-finder mode: the caller's chain no longer waits for the sensor, and the
-// value fork's 5.5 us enqueue lands on that chain's host time; an event fork
-// measured -5 % at 2048 worlds)
-bool fork_by_value(uint32_t W) { return W <= MB_VALUE_FORK_MAX && W > MB_K1_FINDER_MAX && value_waits_safe(); }
-bool join_by_value(uint32_t W)
-{
-    return MB_VALUE_JOIN && W <= MB_VALUE_JOIN_MAX && W > MB_K1_FINDER_MAX && value_waits_safe();
+        if (env_set(name)) k.value_waits_safe = false;
+    const char *e = std::getenv("MBOTS_SWAP");
+    if (e && *e) k.swap = e[0] == '1' ? 1 : 0;
+    return k;
 }
 
 bool mixed_wanted()
@@ -409,102 +342,114 @@ mbots::ObsTable src_view(const mbots_handle *h, int half)
     return t;
 }
 
-bool capturing(hipStream_t st);
-// make `st` wait for the last step's sensor (its rows, and the moves it did)
-int wait_sensor(mbots_handle *h, hipStream_t st)
+hipStream_t last_stream(const mbots_handle *h)
 {
-    if (h->last_join >= 0) {
-        HIP_TRY(hipStreamWaitEvent(st, h->ev_join[h->last_join], 0));
-        if (!capturing(st)) h->waited_serial = std::max(h->waited_serial, h->join_serial[h->last_join]);
+    return static_cast<hipStream_t>(const_cast<void *>(h->sched.last_stream));
+}
+
+// The executor of one call into the manager on stream `st`: the runtime calls
+// of the schedule's rules (mbots_sched.hpp) and the device work of the deferred
+// columns' rules (mbots_defer.hpp: each operation on the stream the caller uses
+// next, timed as a move).  The capture `st` is recorded into is asked of the
+// runtime once per call
+int sync_totals(mbots_handle *h);
+struct Exec {
+    mbots_handle *h;
+    hipStream_t st;
+    bool cap_known = false;
+    unsigned long long cap_id = 0;
+    int cap_rc = MBOTS_OK;
+
+    static int query_capture(hipStream_t s, unsigned long long &id)
+    {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        unsigned long long cid = 0;
+        id = 0;
+        const hipError_t e = hipStreamGetCaptureInfo(s, &cs, &cid);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(MBOTS_E_HIP, std::string("hipStreamGetCaptureInfo: ") + hipGetErrorString(e));
+        }
+        if (cs == hipStreamCaptureStatusActive) id = cid;
+        return MBOTS_OK;
     }
-    return MBOTS_OK;
-}
-
-// make `st` wait for the sensor before the last one, whose rows are the other
-// table half's (the prev-sensor moves read them).  Only needed when K1 does
-// not wait for the sensors (k1_finder): otherwise the last step's K1 did.
-// (Under stream capture, only an event recorded in the same capture.)
-int wait_prev_sensor(mbots_handle *h, hipStream_t st)
-{
-    if (!h->k1_finder || h->prev_join < 0) return MBOTS_OK;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    unsigned long long cid = 0;
-    HIP_TRY(hipStreamGetCaptureInfo(st, &cs, &cid));
-    const bool cap = cs == hipStreamCaptureStatusActive;
-    if (cap && h->prev_capture != cid) return MBOTS_OK;
-    // (one cross-queue wait per step: the shift's for its prev-sensor rows
-    // covers the next K1's)
-    if (!cap && h->waited_serial >= h->join_serial[h->prev_join]) return MBOTS_OK;
-    HIP_TRY(hipStreamWaitEvent(st, h->ev_join[h->prev_join], 0));
-    if (!cap) h->waited_serial = std::max(h->waited_serial, h->join_serial[h->prev_join]);
-    return MBOTS_OK;
-}
-
-bool capturing(hipStream_t st)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(st, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-}
-
-// A graph captured with an odd number of steps leaves the table halves and the
-// host's deferred-move bookkeeping out of step with the device after a replay
-// (ADVICE r3/r4): every device entry point refuses to run from then on --
-// checked here (use_stream, sync_totals and the entry points that use neither)
-// and by mbots_step when the next capture starts.
-// (only a capture that has ENDED with an odd count poisons; a call
-// on another stream while the capture is still recording is refused alone)
-bool capture_open(const mbots_handle *h)
-{
-    if (!h->cap_stream || !h->cap_seen) return false;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    unsigned long long cid = 0;
-    if (hipStreamGetCaptureInfo(h->cap_stream, &cs, &cid) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
+    hipStream_t queue(int q) const
+    {
+        switch (q) {
+        case mbots::sched::kSensor: return h->aux;
+        case mbots::sched::kLast: return last_stream(h);
+        case mbots::sched::kCapture: return static_cast<hipStream_t>(const_cast<void *>(h->sched.cap_stream));
+        default: return st;
+        }
     }
-    return cs == hipStreamCaptureStatusActive && cid == h->cap_seen;
-}
-
-int capture_guard(mbots_handle *h, hipStream_t st)
-{
-    static const char *kMsg = "the last graph capture recorded an odd number of steps, so the manager's "
-                              "table halves no longer follow the device; capture an even number of steps "
-                              "(ending with join()) and create a new manager";
-    if (h->poisoned) return fail(MBOTS_E_INVALID, kMsg);
-    if ((h->cap_steps & 1) && !capturing(st)) {
-        if (capture_open(h))
+    const void *caller() const { return st; }
+    int capture_of(int q, unsigned long long &id)
+    {
+        const hipStream_t s = queue(q);
+        if (s != st || q == mbots::sched::kCapture) return query_capture(s, id);
+        if (!cap_known) {
+            cap_rc = query_capture(st, cap_id);
+            cap_known = true;
+        }
+        id = cap_id;
+        return cap_rc;
+    }
+    bool capturing()
+    {
+        unsigned long long id = 0;
+        return capture_of(mbots::sched::kCaller, id) == MBOTS_OK && id != 0;
+    }
+    int record(int ev, int q)
+    {
+        HIP_TRY(hipEventRecord(h->ev[ev], queue(q)));
+        return MBOTS_OK;
+    }
+    int wait_event(int q, int ev)
+    {
+        HIP_TRY(hipStreamWaitEvent(queue(q), h->ev[ev], 0));
+        return MBOTS_OK;
+    }
+    int wait_value(int q, int sig, uint32_t epoch)
+    {
+        HIP_TRY(hipStreamWaitValue32(queue(q), h->sig[sig], epoch, hipStreamWaitValueGte, 0xFFFFFFFFu));
+        return MBOTS_OK;
+    }
+    int raise_join(uint32_t epoch)
+    {
+        HIP_TRY(mbots::launch_raise_flag(h->sig[mbots::sched::kJoin], epoch, h->aux));
+        return MBOTS_OK;
+    }
+    bool pending(int ev)
+    {
+        const bool busy = hipEventQuery(h->ev[ev]) == hipErrorNotReady;
+        (void)hipGetLastError();   // (hipEventQuery reports "not ready" as an error)
+        return busy;
+    }
+    int drain_and_zero()
+    {
+        HIP_TRY(hipDeviceSynchronize());
+        for (uint32_t *p : h->sig)
+            if (p) HIP_TRY(hipMemset(p, 0, 8));
+        HIP_TRY(hipDeviceSynchronize());
+        return MBOTS_OK;
+    }
+    int refuse(mbots::sched::Refusal why, uint64_t n)
+    {
+        switch (why) {
+        case mbots::sched::kCaptureElsewhere:
             return fail(MBOTS_E_INVALID, "a graph capture of this manager's steps is still recording on another "
                                          "stream: call the manager on the capturing stream, or after the "
                                          "capture has ended");
-        h->poisoned = true;
-        return fail(MBOTS_E_INVALID, kMsg);
+        case mbots::sched::kOddJoin:
+            return fail(MBOTS_E_INVALID, "a captured sequence must hold an even number of steps (" +
+                                             std::to_string(n) + " recorded)");
+        default:
+            return fail(MBOTS_E_INVALID, "the last graph capture recorded an odd number of steps, so the manager's "
+                                         "table halves no longer follow the device; capture an even number of steps "
+                                         "(ending with join()) and create a new manager");
+        }
     }
-    return MBOTS_OK;
-}
 
-// Every call enqueues on the caller's stream (torch's current stream); a call
-// on another stream than the previous one is ordered after everything the
-// manager enqueued there (an event hop), so steps, deferred copies and the
-// views they produce form one stream-ordered sequence whatever streams the
-// caller switches between.  (Not across a graph capture's boundary: a capture
-// cannot wait for work outside it.)
-int use_stream(mbots_handle *h, hipStream_t st)
-{
-    if (int rc = capture_guard(h, st)) return rc;
-    if (st != h->last_stream && !capturing(st) && !capturing(h->last_stream)) {
-        HIP_TRY(hipEventRecord(h->ev_hop, h->last_stream));
-        HIP_TRY(hipStreamWaitEvent(st, h->ev_hop, 0));
-    }
-    h->last_stream = st;
-    return MBOTS_OK;
-}
-
-// The device work of the deferred columns' rules (mbots_defer.hpp): each
-// operation on the stream the caller uses next, timed as a move
-int sync_totals(mbots_handle *h);
-struct DeferExec {
-    mbots_handle *h;
-    hipStream_t st;
     template <class F> int run(int kind, F &&launch)
     {
         HIP_TRY(hipSetDevice(h->device));
@@ -573,22 +518,27 @@ struct DeferExec {
     int wait_prev_sensor()
     {
         HIP_TRY(hipSetDevice(h->device));
-        return ::wait_prev_sensor(h, st);
+        return h->sched.wait_prev_sensor(*this);
     }
 };
+// `st` is being captured into a graph (an entry point that refuses it)
+bool capturing(mbots_handle *h, hipStream_t st) { return Exec{h, st}.capturing(); }
+// the poisoning check of an entry point that takes no stream: it runs on the
+// stream of the manager's last call
+int capture_guard(mbots_handle *h)
+{
+    Exec ex{h, last_stream(h)};
+    return h->sched.guard(ex, mbots::sched::kCaller);
+}
 mbots::defer::Env defer_env(const mbots_handle *h, bool capturing)
 {
-    return {capturing, h->cap_seen != 0, h->pa_on, h->k1_finder && MB_FINDER_PSEM_BY_SENSOR};
+    return {capturing, h->sched.graph_exists(), h->pa_on, h->sched.mode.k1_finder && MB_FINDER_PSEM_BY_SENSOR};
 }
 static_assert(mbots::defer::kPartAH == mbots::kMoveAH && mbots::defer::kPartSensor == mbots::kMoveSensor &&
                   mbots::defer::kPartPrevAH == mbots::kMovePrevAH && mbots::defer::kPartPrev6 == mbots::kMovePrev6,
               "mbots_defer.hpp names launch_move's parts");
 // the stream the manager last launched on is being captured into a graph
-bool capturing_now(const mbots_handle *h)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    return hipStreamIsCapturing(h->last_stream, &cs) == hipSuccess && cs == hipStreamCaptureStatusActive;
-}
+bool capturing_now(mbots_handle *h) { return capturing(h, last_stream(h)); }
 
 int sync_totals(mbots_handle *h)
 {
@@ -596,8 +546,8 @@ int sync_totals(mbots_handle *h)
     // same step skip the runtime calls (the reference loop reads ~10 views per
     // step and is host-bound at small world counts, scripts/refhost.py) -- not
     // once graphs exist, whose replays change the counts behind the host's back
-    if (int rc = capture_guard(h, h->last_stream)) return rc;
-    if (h->totals_ok && h->cap_seen == 0) return MBOTS_OK;
+    if (int rc = capture_guard(h)) return rc;
+    if (h->totals_ok && !h->sched.graph_exists()) return MBOTS_OK;
     HIP_TRY(hipSetDevice(h->device));
     // a host-side row count during stream capture would be the capture-time
     // count baked into every replay (and the event wait is not capturable)
@@ -606,7 +556,7 @@ int sync_totals(mbots_handle *h)
                     "needs the host-side agent count, which is not available while the stream is "
                     "captured into a graph: capture only step / shift_observations / "
                     "write_synthetic_actions / join (device-side writers), read accessors after replay");
-    HIP_TRY(hipEventSynchronize(h->ev_totals));
+    HIP_TRY(hipEventSynchronize(h->ev[mbots::sched::kTotals]));
     h->totals_ok = true;
     return MBOTS_OK;
 }
@@ -614,7 +564,7 @@ int sync_totals(mbots_handle *h)
 // episodes: every world's age is the manager's while no reset pass runs
 int fill_ages(mbots_handle *h, hipStream_t st)
 {
-    if (capturing(st))
+    if (capturing(h, st))
         return fail(MBOTS_E_INVALID, "the episode-step export of an unarmed manager cannot be captured into a graph");
     HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->age, (int)std::min<uint64_t>(h->age0, 0x7FFFFFFFu), h->S.W, st));
     return MBOTS_OK;
@@ -624,7 +574,7 @@ int fill_ages(mbots_handle *h, hipStream_t st)
 int arm(mbots_handle *h, hipStream_t st)
 {
     if (h->armed) return MBOTS_OK;
-    if (capturing(st))
+    if (capturing(h, st))
         return fail(MBOTS_E_INVALID, "a manager cannot be armed for episodes while its stream is being captured: "
                                      "export MBOTS_EXPORT_RESET, call mbots_reset_worlds or set an episode length "
                                      "before the capture begins");
@@ -637,7 +587,7 @@ int record_totals(mbots_handle *h, hipStream_t st)
 {
     HIP_TRY(hipMemcpyAsync(h->h_totals, h->S.totals, 8 * sizeof(uint32_t), hipMemcpyDeviceToHost,
                            st));
-    HIP_TRY(hipEventRecord(h->ev_totals, st));
+    HIP_TRY(hipEventRecord(h->ev[mbots::sched::kTotals], st));
     return MBOTS_OK;
 }
 
@@ -917,15 +867,17 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
     S.world_offset = cfg.world_offset;
     S.flags = cfg.flags;
     S.seed = cfg.rand_seed;
-    // (the K1 finder pass keeps camera slots in bytes: a <= 256-slot mode)
-    h->k1_finder = S.W <= MB_K1_FINDER_MAX && S.cap <= 256;
-    S.k1_finder = h->k1_finder ? 1u : 0u;
+    // the schedule the world count, the capacity and the environment ask for
+    // (mbots_sched.hpp choose; settled below, once the signal words exist)
+    h->sched.knobs = sched_knobs();
+    h->sched.mode = mbots::sched::choose(S.W, S.cap, true, true, h->sched.knobs);
+    S.k1_finder = h->sched.mode.k1_finder ? 1u : 0u;
     {
         // mixed capacity classes (round 6): above 128 slots the 128-slot K1
         // and sensor take every world that fits them and the class kernels
         // only the worlds K2 lists (DESIGN.md "Capacity"); MBOTS_MIXED=0 runs
         // every world in the class kernels
-        S.mixed = (mixed_wanted() && S.cap > (uint32_t)mbots::kSmallCap && !h->k1_finder) ? 1u : 0u;
+        S.mixed = (mixed_wanted() && S.cap > (uint32_t)mbots::kSmallCap && !h->sched.mode.k1_finder) ? 1u : 0u;
     }
 
     int rc = MBOTS_OK;
@@ -944,8 +896,8 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
     // only: no timestamps, and a device-scope release -- the host reads only the
     // pinned row counts, which K2 writes system-coherent and fences itself)
     constexpr unsigned kSyncEvent = hipEventDisableTiming | hipEventReleaseToDevice;
-    check(hipEventCreateWithFlags(&h->ev_totals, kSyncEvent), "hipEventCreateWithFlags");
-    check(hipEventCreateWithFlags(&h->ev_hop, kSyncEvent), "hipEventCreateWithFlags");
+    check(hipEventCreateWithFlags(&h->ev[mbots::sched::kTotals], kSyncEvent), "hipEventCreateWithFlags");
+    check(hipEventCreateWithFlags(&h->ev[mbots::sched::kHop], kSyncEvent), "hipEventCreateWithFlags");
     check(hipMalloc((void **)&h->reset_mark, (size_t)S.W * sizeof(int32_t)), "hipMalloc");
     if (rc == MBOTS_OK) check(hipMemset(h->reset_mark, 0, (size_t)S.W * sizeof(int32_t)), "hipMemset");
     {
@@ -960,23 +912,15 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
             }
             check(hipMemset(p, 0, 8), "hipMemset");
         };
-        if (fork_by_value((uint32_t)S.W)) signal_word(h->sig_fork);
-        if (join_by_value((uint32_t)S.W)) signal_word(h->sig_join);
-        S.sig_fork = h->sig_fork;
+        if (h->sched.mode.value_fork) signal_word(h->sig[mbots::sched::kFork]);
+        if (h->sched.mode.value_join) signal_word(h->sig[mbots::sched::kJoin]);
+        h->sched.mode = mbots::sched::choose(S.W, S.cap, h->sig[mbots::sched::kFork] != nullptr,
+                                             h->sig[mbots::sched::kJoin] != nullptr, h->sched.knobs);
+        S.sig_fork = h->sig[mbots::sched::kFork];
         // test hook: the epoch to count on from (near kEpochWrap, so a short
         // run crosses the wrap; include/mbots.h "Environment")
         if (const char *e = std::getenv("MBOTS_EPOCH_START"))
-            h->epoch = std::min<uint32_t>((uint32_t)std::strtoul(e, nullptr, 0), kEpochWrap);
-    }
-    {
-        // (the default above 8192 worlds since round 6: with the prev-sensor
-        // move lazy the caller's chain is the shorter one from the first steps
-        // on, and the swap takes both hops off the sensor's chain: -1.9 % in
-        // the driver's window, -2.1 % at steady state, interleaved on one box;
-        // MBOTS_SWAP=0 restores the forked schedule)
-        const char *e = std::getenv("MBOTS_SWAP");
-        const bool want = e && *e ? e[0] == '1' : MB_SWAP_DEFAULT != 0;
-        h->swap = want && S.W > MB_VALUE_FORK_MAX && !h->k1_finder && !h->sig_fork && !h->sig_join;
+            h->sched.epoch = std::min<uint32_t>((uint32_t)std::strtoul(e, nullptr, 0), mbots::sched::kEpochWrap);
     }
     {
         // MBOTS_LAZY_PREV_ACTION=0: a lazy shift launches its Action gather, as
@@ -984,9 +928,10 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
         const char *e = std::getenv("MBOTS_LAZY_PREV_ACTION");
         h->pa_on = !(e && e[0] == '0');
     }
-    if (h->swap) check(hipEventCreateWithFlags(&h->ev_caller, kSyncEvent), "hipEventCreateWithFlags");
-    check(hipEventCreateWithFlags(&h->ev_join[0], kSyncEvent), "hipEventCreateWithFlags");
-    check(hipEventCreateWithFlags(&h->ev_join[1], kSyncEvent), "hipEventCreateWithFlags");
+    if (h->sched.mode.swap)
+        check(hipEventCreateWithFlags(&h->ev[mbots::sched::kCallerEv], kSyncEvent), "hipEventCreateWithFlags");
+    check(hipEventCreateWithFlags(&h->ev[mbots::sched::kJoin0], kSyncEvent), "hipEventCreateWithFlags");
+    check(hipEventCreateWithFlags(&h->ev[mbots::sched::kJoin1], kSyncEvent), "hipEventCreateWithFlags");
     {
         // the sensor is the step's longer chain once the deferred Prev moves
         // left the caller's stream lighter: its stream gets the higher priority
@@ -995,7 +940,7 @@ int mbots_create(const mbots_config *cfg_in, mbots_handle **out)
         check(hipDeviceGetStreamPriorityRange(&least, &greatest), "hipDeviceGetStreamPriorityRange");
         // (K1-finder mode: the caller's chain is the longer one, the sensor's the
         // filler)
-        const int prio = h->k1_finder && MB_FINDER_AUX_LOW ? least : greatest;
+        const int prio = h->sched.mode.aux_low() ? least : greatest;
         check(hipStreamCreateWithPriority(&h->aux, hipStreamNonBlocking, prio),
               "hipStreamCreateWithPriority");
     }
@@ -1044,12 +989,8 @@ int mbots_destroy(mbots_handle *h)
     if (h->reset_mark) (void)hipFree(h->reset_mark);
     for (auto &p : h->pending) { (void)hipEventDestroy(p.a); (void)hipEventDestroy(p.b); }
     for (auto e : h->pool) (void)hipEventDestroy(e);
-    if (h->ev_totals) (void)hipEventDestroy(h->ev_totals);
-    if (h->ev_hop) (void)hipEventDestroy(h->ev_hop);
-    if (h->ev_caller) (void)hipEventDestroy(h->ev_caller);
-    if (h->sig_fork) (void)hipFree(h->sig_fork);
-    if (h->sig_join) (void)hipFree(h->sig_join);
-    for (auto e : h->ev_join) if (e) (void)hipEventDestroy(e);
+    for (auto e : h->ev) if (e) (void)hipEventDestroy(e);
+    for (auto p : h->sig) if (p) (void)hipFree(p);
     if (h->aux) (void)hipStreamDestroy(h->aux);
     if (h->h_totals) (void)hipHostFree(h->h_totals);
     if (h->flag_stage) (void)hipHostFree(h->flag_stage);
@@ -1115,10 +1056,10 @@ int mbots_step(mbots_handle *h, void *stream)
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
     int rc;
-    hipStreamCaptureStatus cap_status = hipStreamCaptureStatusNone;
+    Exec ex{h, st};
     unsigned long long cap_id = 0;
-    HIP_TRY(hipStreamGetCaptureInfo(st, &cap_status, &cap_id));
-    const bool capturing = cap_status == hipStreamCaptureStatusActive;
+    if ((rc = ex.capture_of(mbots::sched::kCaller, cap_id))) return rc;
+    const bool capturing = cap_id != 0;
     if (h->auto_cap) {
         // (the check reads the host-side population and a growth moves the
         // arena: neither can be part of a graph)
@@ -1128,77 +1069,28 @@ int mbots_step(mbots_handle *h, void *stream)
                                          "host and may move the manager's storage; disable it before capturing");
         if ((rc = auto_grow(h))) return rc;
     }
-    if (capturing && cap_id != h->cap_seen) {
-        // a new capture: the previous one must have held an even number of steps
-        if ((rc = capture_guard(h, nullptr))) return rc;
-        h->cap_seen = cap_id;
-        h->cap_stream = st;
-        h->cap_steps = 0;
-    }
-    if ((rc = use_stream(h, st))) return rc;
-    if (capturing) ++h->cap_steps;
+    // The launches in order -- reset pass, K1, (the halves) swap, K2, sensor,
+    // K3a, prefetch move -- each after what the schedule (mbots_sched.hpp) makes
+    // its queue wait for
+    mbots::sched::Schedule &sched = h->sched;
+    mbots::sched::Step sp;
+    if ((rc = sched.begin_step(ex, sp))) return rc;
     const mbots::ObsTable &nxt = h->T[h->defer.tb ^ 1];
     const int par = h->defer.parity;
     // what the last step still owes the current half that this step reads, and
     // this step's part of the deferred columns (mbots_defer.hpp begin_step)
     const mbots::defer::Env env = defer_env(h, capturing);
     mbots::defer::StepPlan plan;
-    DeferExec ex{h, st};
     if ((rc = h->defer.begin_step(ex, env, plan))) return rc;
     // K1 reads the learner's actions through the half's view (an aliased
     // Action column is its PrevAction), and so do this step's moves
     const mbots::ObsTable cur = src_view(h, h->defer.tb);
-    // K1 reads the finder slots the previous step's sensor wrote, and writes the
-    // state half that sensor read; the halves swap after K1.
-    // (under stream capture only a join recorded in the same capture is waited
-    // for: a replay starts after the previous launch of the graph completed)
-    // (small world counts, eagerly, while the device still runs the previous
-    // step: the flag a wave after the sensor raised.  A host that arrives after
-    // the sensor has finished -- a host-bound loop, where the value waits'
-    // extra enqueues would only add host time -- takes the event wait, and this
-    // step raises no flags.)
-    bool ahead = false;
-    if (!capturing && (h->sig_fork || h->sig_join) && MB_VALUE_ADAPT) {
-        ahead = h->last_join < 0 || hipEventQuery(h->ev_join[h->last_join]) == hipErrorNotReady;
-        (void)hipGetLastError();   // (hipEventQuery reports "not ready" as an error)
-    } else if (!capturing && (h->sig_fork || h->sig_join)) {
-        ahead = true;
-    }
-    const int before = h->last_join;                  // the last step's sensor (its rows are
-    const unsigned long long before_cap = h->join_capture;   // the current half's)
-    // MBOTS_SWAP=1: K1, K2 and the sensor on the internal stream with no hop
-    // between them; K1 after the last sensor (the same stream) and after what
-    // the caller enqueued so far (the learner's writes)
-    const bool swap = h->swap && !capturing;
-    const hipStream_t kst = swap ? h->aux : st;
-    if (swap) {
-        HIP_TRY(hipEventRecord(h->ev_caller, st));
-        HIP_TRY(hipStreamWaitEvent(h->aux, h->ev_caller, 0));
-    } else if (h->k1_finder) {
-        // K1 computed the finder slots this K1 reads; it must only not overwrite
-        // the state half the sensor before the last one may still read
-        if ((rc = wait_prev_sensor(h, st))) return rc;
-    } else if (!capturing && h->join_epoch != 0 && ahead) {
-        // ">=" (VERDICT r5 item 5): the flag only grows -- one writer, raised in
-        // step order on the sensor's queue -- so this wait passes whenever it is
-        // reached, even after a later step has raised the flag again; an
-        // equality wait would hang there (the round-5 probe's fork did)
-        HIP_TRY(hipStreamWaitValue32(st, h->sig_join, h->join_epoch, hipStreamWaitValueGte, 0xFFFFFFFFu));
-    } else if (h->last_join >= 0 && (!capturing || h->join_capture == cap_id)) {
-        HIP_TRY(hipStreamWaitEvent(st, h->ev_join[h->last_join], 0));
-        if (!capturing) h->waited_serial = std::max(h->waited_serial, h->join_serial[h->last_join]);
-    }
+    if ((rc = sched.before_k1(ex, sp))) return rc;
+    const hipStream_t kst = ex.queue(sp.kq);
     h->S.finder_from_state = h->sensed ? 0u : 1u;
     if (h->armed) {
-        // the reset pass (episodes), before K1 on K1's stream and after K1's
-        // waits: it writes the state half K1 reads, whose finder slots the last
-        // sensor wrote, and reads the flags the caller's stream wrote.  In
-        // K1-finder mode K1 does not wait for that sensor, which still reads
-        // this half: the pass does
-        if (h->k1_finder && h->last_join >= 0 && (!capturing || h->join_capture == cap_id)) {
-            HIP_TRY(hipStreamWaitEvent(kst, h->ev_join[h->last_join], 0));
-            if (!capturing) h->waited_serial = std::max(h->waited_serial, h->join_serial[h->last_join]);
-        }
+        // the reset pass (episodes), before K1 on K1's stream
+        if ((rc = sched.before_reset_pass(ex, sp))) return rc;
         const mbots::ResetArgs R{h->reset_flags, h->episode, h->age, h->ep_len, h->reset_mark};
         HIP_TRY(mbots::launch_reset_worlds(h->S, R, par, kst));
     } else {
@@ -1213,30 +1105,11 @@ int mbots_step(mbots_handle *h, void *stream)
         return rc;
     mbots::swap_state(h->S);
     // K2 writes the row counts into the pinned mirror; accessors and the
-    // sensor's stream wait on ev_totals, carried by K2's own dispatch
+    // sensor's stream wait on ev[kTotals], carried by K2's own dispatch
     // (under stream capture -- a caller recording steps into a HIP graph -- the
     // fork / join events are recorded by hipEventRecord, the capturable form)
-    // the fork by value (small world counts, eagerly): K2's last block raises
-    // this step's epoch (under capture replays would repeat it: the event then)
-    uint32_t epoch = 0;
-    if ((h->sig_fork || h->sig_join) && !capturing && ahead) {
-        if (h->epoch >= kEpochWrap) {
-            // both waits are "flag >= epoch": before the counter wraps, drain
-            // the device and restart both from 0 -- the resets complete before
-            // any later wait is enqueued (exercised by
-            // tests/test_robustness.py::test_value_wait_epoch_wrap through
-            // MBOTS_EPOCH_START)
-            HIP_TRY(hipDeviceSynchronize());
-            if (h->sig_fork) HIP_TRY(hipMemset(h->sig_fork, 0, 8));
-            if (h->sig_join) HIP_TRY(hipMemset(h->sig_join, 0, 8));
-            HIP_TRY(hipDeviceSynchronize());
-            h->epoch = 0;
-            h->join_epoch = 0;
-            ++h->epoch_wraps;
-        }
-        epoch = ++h->epoch;
-    }
-    h->S.epoch = h->sig_fork ? epoch : 0u;
+    if ((rc = sched.before_k2(ex, sp))) return rc;
+    h->S.epoch = sp.k2_epoch;
     // this step's row bases and sensor order go to the buffer the step before
     // last used (its sensor has been waited for: above, or by the event join)
     h->S.row_base = h->row_base2[par];
@@ -1248,24 +1121,15 @@ int mbots_step(mbots_handle *h, void *stream)
     // the owed columns read them -- the shift that follows launches nothing.
     // Not where a graph could replay the store over a count still in use)
     h->S.rows_out = plan.store_rows ? h->lazy_rows + par : nullptr;
-    rc = timed(h, MBOTS_TK_SCAN, kst, [&] { return mbots::launch_scan(h->S, par, kst, h->ev_totals, capturing); });
+    rc = timed(h, MBOTS_TK_SCAN, kst, [&] {
+        return mbots::launch_scan(h->S, par, kst, h->ev[mbots::sched::kTotals], sp.plain_records);
+    });
     h->S.rows_out = nullptr;
     h->maxpop_stale = false;
     h->S.epoch = 0;
     if (rc) return rc;
-    // fork after K2: the K3b sensor (VALU-bound; it derives the export rows from
-    // K2's row_base itself) runs on the aux stream while this stream goes on
-    // with K3a export, shift_observations and the learner's action writes --
-    // none of which reads the sensor rows or the finder slots.  The next step's
-    // K1 and the semantic/depth accessors wait for ev_join.
-    const int jcur = h->last_join == 0 ? 1 : 0;
-    // (">=": the fork flag only grows -- K2's last block raises each step's
-    // epoch in step order -- so the wait passes whenever the sensor's queue
-    // reaches it, also after a later K2 raised the flag again; equality would
-    // hang there)
-    if (swap) HIP_TRY(hipStreamWaitEvent(st, h->ev_totals, 0));   // K3a after K2 (the caller's join)
-    else if (epoch && h->sig_fork) HIP_TRY(hipStreamWaitValue32(h->aux, h->sig_fork, epoch, hipStreamWaitValueGte, 0xFFFFFFFFu));
-    else HIP_TRY(hipStreamWaitEvent(h->aux, h->ev_totals, 0));
+    // fork after K2: the sensor on its own stream
+    if ((rc = sched.before_sensor(ex, sp))) return rc;
     // (K1-finder mode: the sensor also moves the last table's sensor rows into
     // its rows' prev-sensor columns, so no caller-stream wait is needed for them)
     if (env.psem_by_sensor) {
@@ -1274,22 +1138,13 @@ int mbots_step(mbots_handle *h, void *stream)
     }
     h->S.list_par = (uint32_t)par;   // (mixed classes: this step's K2 lists)
     rc = timed(h, MBOTS_TK_SENSOR, h->aux, [&] {
-        return mbots::launch_sensor(h->S, nxt, h->aux, h->ev_join[jcur], capturing);
+        return mbots::launch_sensor(h->S, nxt, h->aux, h->ev[sp.join], sp.plain_records);
     });
     h->S.psem_src = nullptr;
     h->S.pdepth_src = nullptr;
     if (rc) return rc;
     h->sensed = true;
-    h->join_serial[jcur] = ++h->sensor_serial;
-    h->prev_join = before;
-    h->prev_capture = before_cap;
-    h->last_join = jcur;
-    h->join_capture = capturing ? cap_id : 0;
-    h->join_epoch = 0;
-    if (epoch && h->sig_join) {
-        HIP_TRY(mbots::launch_raise_flag(h->sig_join, epoch, h->aux));
-        h->join_epoch = epoch;
-    }
+    if ((rc = sched.after_sensor(ex, sp))) return rc;
     // K3a's part of lazy HiddenState: the row map it composes or stores
     h->S.map_out = plan.map_out >= 0 ? h->hid_map2[plan.map_out] : nullptr;
     h->S.map_in = plan.map_in >= 0 ? h->hid_map2[plan.map_in] : nullptr;
@@ -1303,7 +1158,7 @@ int mbots_step(mbots_handle *h, void *stream)
     // (the prev sensor is the sensor's own part in K1-finder mode; moved here
     // instead, its source rows are the last sensor's, which this step's K1 did
     // not wait for in that mode)
-    if ((plan.prefetch & mbots::kMoveSensor) && (rc = wait_prev_sensor(h, st))) return rc;
+    if ((plan.prefetch & mbots::kMoveSensor) && (rc = sched.wait_prev_sensor(ex))) return rc;
     if (plan.prefetch && (rc = timed(h, MBOTS_TK_MOVE, st, [&] {
                               return mbots::launch_move(h->S, cur, nxt, plan.lazy, plan.prefetch, st);
                           })))
@@ -1324,10 +1179,10 @@ int mbots_shift_observations(mbots_handle *h, void *stream)
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    int rc = use_stream(h, st);
+    Exec ex{h, st};
+    int rc = h->sched.enter(ex);
     if (rc) return rc;
-    DeferExec ex{h, st};
-    return h->defer.shift(ex, defer_env(h, capturing(st)));
+    return h->defer.shift(ex, defer_env(h, ex.capturing()));
 }
 
 int mbots_num_agents(mbots_handle *h, uint32_t *out)
@@ -1358,7 +1213,8 @@ int mbots_export_on(mbots_handle *h, int32_t id, void *stream, mbots_tensor *out
     if (rc) return rc;
     // the view's deferred copies and joins go on the reader's stream, after
     // everything the manager enqueued (the step may have run on another)
-    if ((rc = use_stream(h, st))) return rc;
+    Exec ex{h, st};
+    if ((rc = h->sched.enter(ex))) return rc;
     int want = 0;   // the deferred column the view names: real rows in its storage first
     switch (id) {
     case MBOTS_EXPORT_PREV_SPECIES: case MBOTS_EXPORT_PREV_POSITION: case MBOTS_EXPORT_PREV_HEALTH:
@@ -1371,9 +1227,8 @@ int mbots_export_on(mbots_handle *h, int32_t id, void *stream, mbots_tensor *out
     case MBOTS_EXPORT_PREV_SENSOR_SEMANTIC: case MBOTS_EXPORT_PREV_SENSOR_DEPTH: want = defer::kPrevSensor; break;
     default: break;
     }
-    DeferExec ex{h, st};
     if (want && (rc = h->defer.require(ex, want, defer::How::Rows))) return rc;
-    if (want == defer::kPrevSensor && h->k1_finder && (rc = wait_sensor(h, st))) return rc;   // the sensor moved them
+    if (want == defer::kPrevSensor && h->sched.mode.k1_finder && (rc = h->sched.wait_sensor(ex))) return rc;   // the sensor moved them
     const ObsTable &t = h->T[h->defer.tb];
     const bool fixd = (h->cfg.flags & MBOTS_FLAG_FIX_DEPTH_ALIAS) != 0;
     void *p = nullptr;
@@ -1403,11 +1258,11 @@ int mbots_export_on(mbots_handle *h, int32_t id, void *stream, mbots_tensor *out
     case MBOTS_EXPORT_SURROUNDING: p = t.sur; dt = MBOTS_DTYPE_FLOAT32; cols = 2; break;
     case MBOTS_EXPORT_PREV_SURROUNDING: p = t.psur; dt = MBOTS_DTYPE_FLOAT32; cols = 2; break;
     case MBOTS_EXPORT_SENSOR_SEMANTIC:
-        if ((rc = wait_sensor(h, st))) return rc;
+        if ((rc = h->sched.wait_sensor(ex))) return rc;
         p = t.sem; dt = MBOTS_DTYPE_INT8; cols = kSensor; break;
     // SensorDepth exports the semantic buffer (sim.cpp:102-104, B.1) unless fixed
     case MBOTS_EXPORT_SENSOR_DEPTH:
-        if ((rc = wait_sensor(h, st))) return rc;
+        if ((rc = h->sched.wait_sensor(ex))) return rc;
         p = fixd ? (void *)t.depth : (void *)t.sem; dt = MBOTS_DTYPE_UINT8; cols = kSensor; break;
     case MBOTS_EXPORT_PREV_SENSOR_SEMANTIC: p = t.psem; dt = MBOTS_DTYPE_INT8; cols = kSensor; break;
     case MBOTS_EXPORT_PREV_SENSOR_DEPTH:
@@ -1439,9 +1294,9 @@ int mbots_export(mbots_handle *h, int32_t id, mbots_tensor *out)
     if (h->cpu) return mbots_export_on(h, id, nullptr, out);
     // the reference's views are valid on any stream once the synchronous
     // step() returned (mgr.cpp:51-63): so are these, once this returns
-    const int rc = mbots_export_on(h, id, h->last_stream, out);
+    const int rc = mbots_export_on(h, id, last_stream(h), out);
     if (rc) return rc;
-    if (!capturing(h->last_stream)) HIP_TRY(hipStreamSynchronize(h->last_stream));
+    if (!capturing_now(h)) HIP_TRY(hipStreamSynchronize(last_stream(h)));
     return MBOTS_OK;
 }
 
@@ -1457,8 +1312,8 @@ int mbots_set_action(mbots_handle *h, uint32_t row, const int32_t action[6])
         return MBOTS_OK;
     }
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = h->last_stream;
-    DeferExec ex{h, st};
+    hipStream_t st = last_stream(h);
+    Exec ex{h, st};
     if ((rc = h->defer.require(ex, mbots::defer::kAction, mbots::defer::How::Rows))) return rc;
     HIP_TRY(hipMemcpyAsync(h->T[h->defer.tb].action + (size_t)row * 6, action, 6 * sizeof(int32_t),
                            hipMemcpyHostToDevice, st));
@@ -1492,11 +1347,11 @@ int mbots_write_synthetic_actions(mbots_handle *h, uint32_t seed, uint32_t step,
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    int rc = use_stream(h, st);
+    Exec ex{h, st};
+    int rc = h->sched.enter(ex);
     if (rc) return rc;
     // the writer rewrites every live row's Action (and HiddenState with
     // write_hidden): an aliased column of those is simply written, not copied
-    DeferExec ex{h, st};
     if ((rc = h->defer.require(ex, mbots::defer::kAction | (write_hidden ? mbots::defer::kHidden : 0),
                                mbots::defer::How::WriteAll)))
         return rc;
@@ -1515,10 +1370,11 @@ int mbots_construct_obs(mbots_handle *h, int32_t prev, float *out, uint64_t out_
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    int rc = use_stream(h, st);
+    Exec ex{h, st};
+    int rc = h->sched.enter(ex);
     if (rc) return rc;
     // current semantic rows come from K3b (and in K1-finder mode the prev ones too)
-    if ((!prev || h->k1_finder) && (rc = wait_sensor(h, st))) return rc;
+    if ((!prev || h->sched.mode.k1_finder) && (rc = h->sched.wait_sensor(ex))) return rc;
     // The previous rows' health / position / surrounding: while the step's
     // deferred move of the six Prev* columns is still owed, gathered from the
     // other half along src_of inside this launch (what the move would write,
@@ -1527,7 +1383,6 @@ int mbots_construct_obs(mbots_handle *h, int32_t prev, float *out, uint64_t out_
     // sensor is moved (and remembered for the next step's prefetch)
     const mbots::defer::Deferred &d = h->defer;
     const bool gather6 = prev && d.six_owed();
-    DeferExec ex{h, st};
     if (prev && (rc = h->defer.require(ex, mbots::defer::kPrevSensor, mbots::defer::How::Rows))) return rc;
     return timed(h, MBOTS_TK_OBS, st, [&] {
         return mbots::launch_construct_obs(h->S, h->T[d.tb], prev, d.prev_is_current() ? 1 : 0, out,
@@ -1558,9 +1413,10 @@ int mbots_pack_rollout(mbots_handle *h, void *out, uint64_t out_rows, void *stre
     if ((reinterpret_cast<uintptr_t>(out) & 15u) != 0) return fail(MBOTS_E_INVALID, "out must be 16-byte aligned");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    int rc = use_stream(h, st);
+    Exec ex{h, st};
+    int rc = h->sched.enter(ex);
     if (rc) return rc;
-    if ((rc = wait_sensor(h, st))) return rc;   // the semantic / depth rows come from K3b
+    if ((rc = h->sched.wait_sensor(ex))) return rc;   // the semantic / depth rows come from K3b
     return timed(h, MBOTS_TK_OBS, st, [&] {
         return mbots::launch_pack_rollout(h->S, h->T[h->defer.tb], out, (uint32_t)out_rows, st);
     });
@@ -1586,14 +1442,14 @@ int mbots_pack_learner(mbots_handle *h, void *out, uint64_t out_rows, void *stre
     if ((reinterpret_cast<uintptr_t>(out) & 15u) != 0) return fail(MBOTS_E_INVALID, "out must be 16-byte aligned");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    int rc = use_stream(h, st);
+    Exec ex{h, st};
+    int rc = h->sched.enter(ex);
     if (rc) return rc;
     // every column the record carries in its storage: the step's deferred
     // moves the learner's reads need (and remembered, like the accessors', so
     // the next step prefetches them beside its sensor)
-    DeferExec ex{h, st};
     if ((rc = h->defer.require_all(ex, true))) return rc;
-    if ((rc = wait_sensor(h, st))) return rc;   // the sensor rows (and what it moved)
+    if ((rc = h->sched.wait_sensor(ex))) return rc;   // the sensor rows (and what it moved)
     return timed(h, MBOTS_TK_OBS, st, [&] {
         return mbots::launch_pack_learner(h->S, h->T[h->defer.tb], h->defer.prev_is_current() ? 1 : 0, out,
                                           (uint32_t)out_rows, st);
@@ -1613,12 +1469,13 @@ int mbots_pack_learner_slim(mbots_handle *h, void *out, uint64_t out_rows, void 
     if ((reinterpret_cast<uintptr_t>(out) & 15u) != 0) return fail(MBOTS_E_INVALID, "out must be 16-byte aligned");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    int rc = use_stream(h, st);
+    Exec ex{h, st};
+    int rc = h->sched.enter(ex);
     if (rc) return rc;
     // the sensor rows (and in K1-finder mode the prev sensor rows it moved);
     // in the joined schedule the last sensor's rows, the source of a prev
     // sensor still owed, were waited for by this step's K1
-    if ((rc = wait_sensor(h, st))) return rc;
+    if ((rc = h->sched.wait_sensor(ex))) return rc;
     const int tb = h->defer.tb;
     const mbots::ObsTable &last = h->T[tb ^ 1];
     return timed(h, MBOTS_TK_OBS, st, [&] {
@@ -1771,11 +1628,11 @@ int mbots_write_actions(mbots_handle *h, const int32_t *action, const float *hid
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    if ((rc = use_stream(h, st))) return rc;
+    Exec ex{h, st};
+    if ((rc = h->sched.enter(ex))) return rc;
     const int tb = h->defer.tb;
     // a column written only in part keeps its other rows: copied out of an
     // aliased Prev storage first; a column written whole is simply written
-    DeferExec ex{h, st};
     if ((rc = h->defer.require(ex, (action ? mbots::defer::kAction : 0) | (hidden ? mbots::defer::kHidden : 0),
                                rows < R ? mbots::defer::How::WritePart : mbots::defer::How::WriteAll)))
         return rc;
@@ -1808,25 +1665,14 @@ int mbots_join(mbots_handle *h, void *stream)
     if (!h) return fail(MBOTS_E_INVALID, "null handle");
     if (h->cpu) return MBOTS_OK;   // synchronous: nothing outstanding
     HIP_TRY(hipSetDevice(h->device));
-    int rc = use_stream(h, as_stream(stream));
-    if (rc) return rc;
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    unsigned long long cid = 0;
-    HIP_TRY(hipStreamGetCaptureInfo(as_stream(stream), &cs, &cid));
-    // the table halves and the host's deferred-move bookkeeping alternate per
-    // step: a graph of an odd number of steps would leave them out of step
-    // with the device after every replay
-    if (cs == hipStreamCaptureStatusActive && cid == h->cap_seen && (h->cap_steps & 1))
-        return fail(MBOTS_E_INVALID, "a captured sequence must hold an even number of steps (" +
-                                         std::to_string(h->cap_steps) + " recorded)");
-    if (h->last_join >= 0) HIP_TRY(hipStreamWaitEvent(as_stream(stream), h->ev_join[h->last_join], 0));
-    return MBOTS_OK;
+    Exec ex{h, as_stream(stream)};
+    return h->sched.join(ex);
 }
 
 int mbots_record_sensor_done(mbots_handle *h, void *event)
 {
     if (!h || !event) return fail(MBOTS_E_INVALID, "null argument");
-    if (h->cpu || h->last_join < 0) return fail(MBOTS_E_INVALID, "no sensor launched on the device");
+    if (h->cpu || !h->sched.sensor_launched()) return fail(MBOTS_E_INVALID, "no sensor launched on the device");
     HIP_TRY(hipSetDevice(h->device));
     HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(event), h->aux));
     return MBOTS_OK;
@@ -1892,8 +1738,8 @@ int mbots_save_checkpoint(mbots_handle *h, void *dst, uint64_t bytes)
         return r ? fail(r, err) : MBOTS_OK;
     }
     HIP_TRY(hipSetDevice(h->device));
-    if (int rc = capture_guard(h, h->last_stream)) return rc;
-    DeferExec ex{h, h->last_stream};
+    if (int rc = capture_guard(h)) return rc;
+    Exec ex{h, last_stream(h)};
     if (int rc0 = h->defer.require_all(ex, false)) return rc0;
     HIP_TRY(hipDeviceSynchronize());   // the sensor's finder / semantic rows included
     int rc = sync_totals(h);
@@ -1938,15 +1784,11 @@ static int restored_reset(mbots_handle *h, bool sensed)
         HIP_TRY(hipMemset(h->S.big_cnt, 0, 4 * sizeof(uint32_t)));
         HIP_TRY(mbots::launch_build_lists(h->S, 1, nullptr));
     }
-    h->last_join = -1;
-    h->prev_join = -1;
-    h->waited_serial = h->sensor_serial;   // (the device is idle)
-    h->join_epoch = 0;
+    h->sched.idle_reset();   // (the device is idle; the next call is the first on its stream)
     h->defer.reset();   // (half 0, parity 0, nothing deferred)
     h->steps = 1;
     h->sensed = sensed;
     hipStream_t st = nullptr;
-    h->last_stream = st;
     h->totals_ok = false;
     int rc = record_totals(h, st);
     if (rc) return rc;
@@ -1983,7 +1825,7 @@ int mbots_load_checkpoint(mbots_handle *h, const void *src, uint64_t bytes)
     const uint32_t cap = h->cfg.agent_capacity, cap_src = hd.cap;
     if (hd.n_rows > (uint64_t)h->S.W * cap)
         return fail(MBOTS_E_INVALID, "checkpoint row count out of range");
-    if (int rc = capture_guard(h, h->last_stream)) return rc;
+    if (int rc = capture_guard(h)) return rc;
     auto segs = ckpt_segments(h, h->T[0], hd.n_rows);
     auto segs_src = ckpt_segments(h, h->T[0], hd.n_rows, cap_src);
     if (episodes)
@@ -2111,15 +1953,15 @@ int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
     HIP_TRY(hipSetDevice(h->device));
     if (capturing_now(h))
         return fail(MBOTS_E_INVALID, "grow_capacity moves the manager's storage and cannot be captured into a graph");
-    if (int rc = capture_guard(h, h->last_stream)) return rc;
+    if (int rc = capture_guard(h)) return rc;
     if (new_capacity == cap_old) return MBOTS_OK;
-    if (h->cap_seen != 0)
+    if (h->sched.graph_exists())
         return fail(MBOTS_E_INVALID, "captured graphs pin the capacity: a step of this manager was captured into a "
                                      "graph, whose replays write through the current storage's pointers; create "
                                      "a new manager (or load a checkpoint into one) to change agent_capacity");
     if ((uint64_t)h->S.W * new_capacity >= (1ull << 31))
         return fail(MBOTS_E_INVALID, "num_worlds * agent_capacity >= 2^31");
-    DeferExec ex{h, h->last_stream};
+    Exec ex{h, last_stream(h)};
     int rc = h->defer.require_all(ex, false);
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());   // the sensor's finder / semantic rows included
@@ -2194,9 +2036,10 @@ int mbots_grow_capacity(mbots_handle *h, uint32_t new_capacity)
         return fail(MBOTS_E_HIP, std::string("mbots_grow_capacity: ") + hipGetErrorString(e));
     }
     // what mbots_create derives from the capacity
-    h->k1_finder = h->S.W <= MB_K1_FINDER_MAX && h->S.cap <= 256;
-    h->S.k1_finder = h->k1_finder ? 1u : 0u;
-    h->S.mixed = (mixed_wanted() && h->S.cap > (uint32_t)mbots::kSmallCap && !h->k1_finder) ? 1u : 0u;
+    h->sched.mode = mbots::sched::choose(h->S.W, h->S.cap, h->sig[mbots::sched::kFork] != nullptr,
+                                         h->sig[mbots::sched::kJoin] != nullptr, h->sched.knobs);
+    h->S.k1_finder = h->sched.mode.k1_finder ? 1u : 0u;
+    h->S.mixed = (mixed_wanted() && h->S.cap > (uint32_t)mbots::kSmallCap && !h->sched.mode.k1_finder) ? 1u : 0u;
     h->retired.push_back(old_arena.base);
     const uint32_t reported = h->ovf_reported;
     const bool sensed = h->sensed;
@@ -2332,7 +2175,7 @@ int mbots_set_world_state(mbots_handle *h, uint32_t world, const float *xy_rwrz,
         return MBOTS_OK;
     }
     HIP_TRY(hipSetDevice(h->device));
-    if (int rc = capture_guard(h, h->last_stream)) return rc;
+    if (int rc = capture_guard(h)) return rc;
     if (capturing_now(h))
         return fail(MBOTS_E_INVALID, "set_world_state is a host-side write and cannot be captured into a graph");
     // the checkpoint path: save, patch the blob's segments (found by pointer
@@ -2391,14 +2234,14 @@ int mbots_reset_worlds(mbots_handle *h, const uint32_t *global_worlds, uint32_t 
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    if (capturing(st))
+    Exec ex{h, st};
+    if (ex.capturing())
         return fail(MBOTS_E_INVALID, "mbots_reset_worlds uploads its list from the host and cannot be captured into "
                                      "a graph: write the flags of MBOTS_EXPORT_RESET on the captured stream or "
                                      "between replays instead");
-    int rc = use_stream(h, st);
+    int rc = h->sched.enter(ex);
     if (rc) return rc;
     if ((rc = arm(h, st))) return rc;
-    DeferExec ex{h, st};
     if ((rc = h->defer.require_prev_action_storage(ex))) return rc;   // (an unusual call: the owed column made real)
     const uint32_t W = h->S.W;   // (the shard ghost is world W - 1: global index world_offset + num_worlds)
     if (!h->flag_stage) {
@@ -2431,13 +2274,13 @@ int mbots_set_episode_length(mbots_handle *h, uint32_t steps)
         return MBOTS_OK;
     }
     if (steps == h->ep_len) return MBOTS_OK;
-    if (h->cap_seen != 0)
+    if (h->sched.graph_exists())
         return fail(MBOTS_E_INVALID, "captured graphs pin the episode length: a step of this manager was captured "
                                      "into a graph, whose replays carry the length they recorded");
     if (steps != 0 && !h->armed) {
         HIP_TRY(hipSetDevice(h->device));
-        if (int rc = capture_guard(h, h->last_stream)) return rc;
-        if (int rc = arm(h, h->last_stream)) return rc;
+        if (int rc = capture_guard(h)) return rc;
+        if (int rc = arm(h, last_stream(h))) return rc;
     }
     h->ep_len = steps;
     return MBOTS_OK;
@@ -2483,16 +2326,17 @@ int mbots_render_worlds(mbots_handle *h, const uint32_t *worlds, uint32_t k, uin
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    if (capturing(st))
+    Exec ex{h, st};
+    if (ex.capturing())
         return fail(MBOTS_E_INVALID, "mbots_render_worlds cannot be captured into a graph (its world list is "
                                      "uploaded from the host, and a replay would read the state halves the capture "
                                      "recorded): render between replays");
-    if (int rc = use_stream(h, st)) return rc;
+    if (int rc = h->sched.enter(ex)) return rc;
     // In stream order the call follows the last step's K1 and K2 (on the
     // swapped schedule the caller's stream joined them after K2) and runs
     // beside its sensor, which writes nothing the kernel reads.  The next
     // step's K1 and reset pass, which overwrite what it reads, start after
-    // everything enqueued here (the same stream, or ev_caller): no wait of its
+    // everything enqueued here (the same stream, or the caller event): no wait of its
     // own is needed (DESIGN.md "Rasteriser").
     const uint32_t *list = nullptr;
     if (worlds) {
@@ -2543,11 +2387,10 @@ int mbots_schedule_info(mbots_handle *h, uint32_t out[4])
         out[3] = (uint32_t)h->steps;
         return MBOTS_OK;
     }
-    out[0] = (h->k1_finder ? 1u : 0u) | (h->sig_fork ? 2u : 0u) | (h->sig_join ? 4u : 0u) | (h->swap ? 8u : 0u) |
-             (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u) | (h->defer.hidden_lazy() ? 64u : 0u) |
+    out[0] = h->sched.info_bits() | (h->S.mixed ? 16u : 0u) | (h->armed ? 32u : 0u) | (h->defer.hidden_lazy() ? 64u : 0u) |
              (h->defer.prev_action_owed() ? 128u : 0u);
-    out[1] = h->epoch;
-    out[2] = h->epoch_wraps;
+    out[1] = h->sched.epoch;
+    out[2] = h->sched.epoch_wraps;
     out[3] = (uint32_t)h->steps;
     return MBOTS_OK;
 }
@@ -2716,10 +2559,11 @@ int mbots_traj_push(mbots_handle *h, const float *value, void *stream)
     } else {
         HIP_TRY(hipSetDevice(h->device));
         hipStream_t st = as_stream(stream);
-        if (capturing(st))
+        Exec ex{h, st};
+        if (ex.capturing())
             return fail(MBOTS_E_INVALID, "mbots_traj_push cannot be captured into a graph: the window's table count "
                                          "is host state");
-        if (int rc = use_stream(h, st)) return rc;
+        if (int rc = h->sched.enter(ex)) return rc;
         // after the step's K3a (this stream's order), which wrote the
         // provenance and the Reward column; not after its sensor
         HIP_TRY(mbots::launch_traj_push(h->S, tj.w, slot, h->T[h->defer.tb].reward, value, h->reset_mark, st));
@@ -2727,12 +2571,11 @@ int mbots_traj_push(mbots_handle *h, const float *value, void *stream)
         if (tj.w.hidden) {
             // Action / HiddenState where mbots_pack_learner reads them: the step's
             // deferred move of the two, then the sensor (and what it moved)
-            DeferExec ex{h, st};
             if ((rc = h->defer.require(ex, mbots::defer::kAction | mbots::defer::kHidden, mbots::defer::How::Rows)))
                 return rc;
         }
         if (tj.w.hidden || tj.w.rec) {
-            if ((rc = wait_sensor(h, st))) return rc;   // the semantic / depth rows come from K3b
+            if ((rc = h->sched.wait_sensor(ex))) return rc;   // the semantic / depth rows come from K3b
         }
         // (timed like mbots_pack_rollout / mbots_pack_learner: mbots_kernel_times sees them)
         if (tj.w.rec && (rc = timed(h, MBOTS_TK_OBS, st, [&] {
@@ -2762,10 +2605,11 @@ int mbots_traj_compute(mbots_handle *h, float gamma, float lambda, float death_r
     hipStream_t st = as_stream(stream);
     if (!h->cpu) {
         HIP_TRY(hipSetDevice(h->device));
-        if (capturing(st))
+        Exec ex{h, st};
+        if (ex.capturing())
             return fail(MBOTS_E_INVALID, "mbots_traj_compute returns the row counts to the host and cannot be "
                                          "captured into a graph");
-        if (int rc = use_stream(h, st)) return rc;
+        if (int rc = h->sched.enter(ex)) return rc;
         HIP_TRY(hipMemcpyAsync(tj.h_count, tj.w.count, (size_t)tj.w.horizon * sizeof(uint32_t), hipMemcpyDeviceToHost,
                                st));
         HIP_TRY(hipStreamSynchronize(st));
@@ -2878,10 +2722,11 @@ int mbots_traj_sequences(mbots_handle *h, uint64_t *S_out, void *stream)
     } else {
         HIP_TRY(hipSetDevice(h->device));
         hipStream_t st = as_stream(stream);
-        if (capturing(st))
+        Exec ex{h, st};
+        if (ex.capturing())
             return fail(MBOTS_E_INVALID, "mbots_traj_sequences returns the sequence count to the host and cannot be "
                                          "captured into a graph");
-        if (int rc = use_stream(h, st)) return rc;
+        if (int rc = h->sched.enter(ex)) return rc;
         HIP_TRY(mbots::launch_traj_sequences(tj.w, tj.n, tj.mx, st));
         const size_t tot = (size_t)tj.w.horizon * ((tj.w.max_rows + mbots::kTrajBlock - 1) / mbots::kTrajBlock);
         HIP_TRY(hipMemcpyAsync(tj.h_S, tj.w.blk + tot, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
@@ -2929,8 +2774,9 @@ int traj_batch_enter(mbots_handle *h, uint64_t lo, uint64_t hi, void *stream, hi
     *st_out = as_stream(stream);
     if (h->cpu) return MBOTS_OK;
     HIP_TRY(hipSetDevice(h->device));
-    if (capturing(*st_out)) return fail(MBOTS_E_INVALID, "a batch of the trajectory window cannot be captured into a graph");
-    return use_stream(h, *st_out);
+    Exec ex{h, *st_out};
+    if (ex.capturing()) return fail(MBOTS_E_INVALID, "a batch of the trajectory window cannot be captured into a graph");
+    return h->sched.enter(ex);
 }
 }  // namespace
 
@@ -3087,7 +2933,8 @@ int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_polic
     if (!h->cpu) {
         HIP_TRY(hipSetDevice(h->device));
         st = as_stream(stream);
-        if (int rc = use_stream(h, st)) return rc;
+        Exec ex{h, st};
+        if (int rc = h->sched.enter(ex)) return rc;
     }
     std::vector<PolLayer *> L = policy_layers(n);
     if (!policy_same_arch(cur, n)) {
@@ -3099,7 +2946,7 @@ int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_polic
             if (!mem) return fail(MBOTS_E_NOMEM, "policy net allocation failed");
             std::free(h->pol.mem[species - 1]);
         } else {
-            if (capturing(st))
+            if (capturing(h, st))
                 return fail(MBOTS_E_INVALID, "a policy net of a new architecture allocates: set it before the capture "
                                              "begins (a net of the same architecture is re-uploaded in place)");
             HIP_TRY(hipDeviceSynchronize());   // a queued act may still read the net in place
@@ -3178,15 +3025,15 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
     }
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = as_stream(stream);
-    int rc = use_stream(h, st);
+    Exec ex{h, st};
+    int rc = h->sched.enter(ex);
     if (rc) return rc;
     const int tb = h->defer.tb;
     namespace defer = mbots::defer;
-    DeferExec ex{h, st};
     // the inputs: the sensor's rows (mbots_construct_obs), and HiddenState where
     // its readers find it (the step's deferred move done; a column a fused shift
     // left aliased is read in its Prev storage, not copied)
-    if ((rc = wait_sensor(h, st))) return rc;
+    if ((rc = h->sched.wait_sensor(ex))) return rc;
     bool writes_hidden = false, reads_hidden = false, all_hidden = true;
     for (int s = 0; s < mbots::kNumSpecies; ++s) {
         writes_hidden |= h->pol.nets.net[s].has_memory != 0;
@@ -3233,11 +3080,11 @@ int mbots_policy_draw(mbots_handle *h, int32_t set, uint32_t *value)
         HIP_TRY(hipMemset(h->pol.draw, 0, 256));
     }
     if (set) {
-        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->pol.draw, (int)*value, 1, h->last_stream));
+        HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)h->pol.draw, (int)*value, 1, last_stream(h)));
         return MBOTS_OK;
     }
-    HIP_TRY(hipMemcpyAsync(value, h->pol.draw, sizeof(uint32_t), hipMemcpyDeviceToHost, h->last_stream));
-    HIP_TRY(hipStreamSynchronize(h->last_stream));
+    HIP_TRY(hipMemcpyAsync(value, h->pol.draw, sizeof(uint32_t), hipMemcpyDeviceToHost, last_stream(h)));
+    HIP_TRY(hipStreamSynchronize(last_stream(h)));
     return MBOTS_OK;
 }
 

@@ -211,3 +211,84 @@ def test_capture_guard_refuses_other_stream_without_poisoning():
         orc.step(); orc.shift_observations(); orc.write_synthetic_actions(1234, t)
     errs = compare(mgr, orc, "after the capture")
     assert not errs, errs[:5]
+
+
+_STREAM_OPS = ("step", "step", "shift", "write", "sem", "psem", "join")
+
+
+def _stream_switch_ops(W):
+    """The call sequence of test_caller_streams_switch_in_every_schedule: (op,
+    stream index) pairs up to the 12th step, the same for every manager of W
+    worlds."""
+    rng = np.random.default_rng(W)
+    ops, steps = [], 0
+    while steps < 12:
+        op = _STREAM_OPS[int(rng.integers(len(_STREAM_OPS)))]
+        ops.append((op, int(rng.integers(3)), bool(rng.integers(2))))
+        steps += op == "step"
+    return ops
+
+
+def _run_stream_switch_ops(mgr, ops, streams):
+    """Runs the calls, each on its stream, with no host synchronisation of the
+    test's own in between; returns what the reads saw and every column at the end."""
+    from simpair import COLUMNS, gpu_column
+    import contextlib
+    reads, t = [], 0
+    for op, k, wh in ops:
+        with (torch.cuda.stream(streams[k]) if streams else contextlib.nullcontext()):
+            if op == "step":
+                mgr.write_synthetic_actions(1234, t, wh)
+                mgr.step()
+                t += 1
+            elif op == "shift":
+                mgr.shift_observations()
+            elif op == "write":
+                mgr.write_synthetic_actions(4321, t, wh)
+            elif op == "join":
+                mgr.join()
+            else:
+                reads.append(mgr.semantic_tensor(op == "psem").to_torch().clone())
+    if streams:
+        torch.cuda.synchronize()
+    final = {(nm, p): gpu_column(mgr, nm, p) for nm, _ in COLUMNS for p in (False, True)}
+    return [r.cpu().numpy() for r in reads], final
+
+
+_stream_switch_reference = {}
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("W,swap_env,mode", [(64, None, "k1_finder"), (2304, None, "values"),
+                                             (8320, None, "swap"), (8320, "0", "events")])
+def test_caller_streams_switch_in_every_schedule(W, swap_env, mode, monkeypatch):
+    """Random interleavings of step, shift, a whole-table write, a semantic
+    read, a prev-semantic read and join, each call on one of three streams (the
+    default stream and two side streams), for 12 steps, against CPU mode bit for
+    bit: the hop between caller streams in each of the four schedules, at the
+    smallest world counts that choose them (K1-finder up to 2048 worlds, value
+    waits from 2049, the swapped schedule above 8192 and the forked one with
+    event waits there under MBOTS_SWAP=0).  schedule_info() pins the mode, so a
+    change of the thresholds cannot silently move a case to another schedule."""
+    import madrona_bots as mb
+    from simpair import bits
+    if swap_env is None:
+        monkeypatch.delenv("MBOTS_SWAP", raising=False)
+    else:
+        monkeypatch.setenv("MBOTS_SWAP", swap_env)
+    mgr = mb.SimManager(0, W, 69, 32)
+    info = mgr.schedule_info()
+    got = {"k1_finder": info["k1_finder"], "values": info["fork_by_value"] and info["join_by_value"], "swap": info["swap"]}
+    assert [k for k, v in got.items() if v] == ([mode] if mode != "events" else []), info
+    ops = _stream_switch_ops(W)
+    if W not in _stream_switch_reference:   # (the two 8320-world cases share one)
+        _stream_switch_reference[W] = _run_stream_switch_ops(mb.SimManager(0, W, 69, 32, exec_mode="cpu"), ops, None)
+    want_reads, want_final = _stream_switch_reference[W]
+    streams = [torch.cuda.current_stream(), torch.cuda.Stream(), torch.cuda.Stream()]
+    reads, final = _run_stream_switch_ops(mgr, ops, streams)
+    assert len(reads) == len(want_reads)
+    for i, (g, o) in enumerate(zip(reads, want_reads)):
+        assert g.shape == o.shape and np.array_equal(g, o), ("read", i)
+    for key, o in want_final.items():
+        g = final[key]
+        assert g.shape == o.shape and np.array_equal(bits(g), bits(o)), key

@@ -763,7 +763,8 @@ int mbots_policy_activation(int32_t act, const float *x, float *y, uint64_t n, i
  * threads (MBOTS_CPU_THREADS); both give the same bits, whatever the grid or
  * the thread count.  `net` is what mbots_policy_set takes, with the same
  * checks; its pointers are read in stream order during the call.  The memory
- * head takes no part and receives no gradient.
+ * head takes no part and receives no gradient here (mbots_policy_seq_grad
+ * below trains it).
  *
  * mbots_policy_eval: obs [n][69] f32 (mbots_construct_obs rows), hidden [n][16]
  * (MBOTS_POLICY_MEMORY_IN nets; else ignored, may be NULL), action int32 [n] in
@@ -793,7 +794,7 @@ struct mbots_policy_grad_layer {
 struct mbots_policy_grads {
     struct mbots_policy_grad_layer trunk[MBOTS_POLICY_MAX_TRUNK];
     struct mbots_policy_grad_layer actor[2], critic[2];
-    struct mbots_policy_grad_layer memory;   /* ignored: the memory head receives no gradient */
+    struct mbots_policy_grad_layer memory;   /* mbots_policy_seq_grad only; mbots_policy_grad ignores it */
 };
 int mbots_policy_grad_workspace(const struct mbots_policy_net *net, uint64_t n, uint64_t *bytes);
 int mbots_policy_eval(const struct mbots_policy_net *net, const float *obs, const float *hidden,
@@ -803,6 +804,51 @@ int mbots_policy_grad(const struct mbots_policy_net *net, const float *obs, cons
                       const int32_t *action, uint64_t n, const float *g_logp, const float *g_value,
                       const float *g_entropy, const struct mbots_policy_grads *out, void *workspace,
                       uint64_t workspace_bytes, int32_t device, void *stream);
+
+/* Training the memory head: the net run along padded sequences with the memory
+ * head's output carried from step to step, and backpropagation through time
+ * (DESIGN.md "Backpropagation through HiddenState" is the specification).  The
+ * conventions are mbots_policy_eval's (handle-free, `device` / `stream`, the
+ * same bits on both paths whatever the grid or the thread count).  `net` must
+ * have a memory head and MBOTS_POLICY_MEMORY_IN; any other net is refused (it
+ * has no state to carry: mbots_policy_eval).
+ *
+ * obs [L][B][69] f32, action int32 [L][B], length int32 [B] with 0 <=
+ * length[b] <= L, hidden0 [B][16] f32: what mbots_traj_batch hands out, for one
+ * species' columns.  Element (k, b) is present iff k < length[b].  Sequence b
+ * is evaluated for k ascending on obs[k][b] | h_k, h_0 = hidden0[b], h_{k+1}
+ * the memory head's output: on unchanged parameters logp[k][b], value[k][b]
+ * and h_k are bit for bit what mbots_policy_act produced along that lifeline.
+ *
+ * mbots_policy_seq_eval: logp, value, entropy [L][B] and hidden [L][B][16] (the
+ * h_k each present element was evaluated with); +0 at absent elements; any may
+ * be NULL.
+ *
+ * mbots_policy_seq_grad: g_* [L][B] as mbots_policy_grad's (absent elements
+ * are not read); every non-NULL pointer of `out`, out->memory included,
+ * receives its gradient, backpropagated through h (dh past a sequence's last
+ * step is +0).  obs and hidden0 receive none.  The sums run in a fixed order:
+ * sequences in tiles of 64, tile i into accumulator i mod 256, an accumulator
+ * over its tiles ascending, inside a tile k from the tile's largest length - 1
+ * down to 0, inside a (tile, k) the 64 sequences ascending, the accumulators
+ * added in ascending index.  With L == 1 and every length 1 the outputs and
+ * the trunk / actor / critic gradients are mbots_policy_grad's bits.  B == 0
+ * or L == 0 writes zeros.
+ *
+ * workspace: mbots_policy_seq_workspace(net, L, B, &bytes) bytes, as above.
+ * The calls allocate nothing and never wait for the host.  A length outside
+ * [0, L] or a present action outside 0..5 is refused on the host path
+ * (MBOTS_E_INVALID); on the device both are the caller's contract (a length is
+ * read as clamped to [0, L]). */
+int mbots_policy_seq_workspace(const struct mbots_policy_net *net, uint32_t L, uint64_t B, uint64_t *bytes);
+int mbots_policy_seq_eval(const struct mbots_policy_net *net, const float *obs, const int32_t *action,
+                          const int32_t *length, const float *hidden0, uint32_t L, uint64_t B, float *logp,
+                          float *value, float *entropy, float *hidden, void *workspace, uint64_t workspace_bytes,
+                          int32_t device, void *stream);
+int mbots_policy_seq_grad(const struct mbots_policy_net *net, const float *obs, const int32_t *action,
+                          const int32_t *length, const float *hidden0, uint32_t L, uint64_t B, const float *g_logp,
+                          const float *g_value, const float *g_entropy, const struct mbots_policy_grads *out,
+                          void *workspace, uint64_t workspace_bytes, int32_t device, void *stream);
 
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event

@@ -1005,14 +1005,13 @@ struct RowForward {
     float y[kPolMaxTrunk + 1][kPolMaxH + 4], ha[kPolMaxH], hc[kPolMaxH], z[16], v[1];
 };
 
-void row_forward(const PolNet &net, const PolEvalIO &io, uint64_t r, RowForward &f)
+void row_forward(const PolNet &net, const float *o, const float *hidden, RowForward &f)
 {
     float *x = f.y[0];
-    const float *o = io.obs + r * kPolObs;
     for (int k = 0; k < kPolObs; ++k) x[k] = o[k];
     uint32_t n = kPolObs;
     if (net.flags & kPolMemoryIn)
-        for (int k = 0; k < kHidden; ++k) x[n++] = io.hidden[r * kHidden + k];
+        for (int k = 0; k < kHidden; ++k) x[n++] = hidden[k];
     while (n < net.trunk[0].kp) x[n++] = 0.0f;
     for (uint32_t l = 0; l < net.n_trunk; ++l) policy_layer_host(net.trunk[l], (int)net.trunk[l].act, f.y[l], f.y[l + 1]);
     const float *top = f.y[net.n_trunk];
@@ -1020,6 +1019,10 @@ void row_forward(const PolNet &net, const PolEvalIO &io, uint64_t r, RowForward 
     policy_layer_host(net.actor[1], kActIdentity, f.ha, f.z);
     policy_layer_host(net.critic[0], kActRelu, top, f.hc);
     policy_layer_host(net.critic[1], kActIdentity, f.hc, f.v);
+}
+void row_forward(const PolNet &net, const PolEvalIO &io, uint64_t r, RowForward &f)
+{
+    row_forward(net, io.obs + r * kPolObs, io.hidden ? io.hidden + r * kHidden : nullptr, f);
 }
 
 // the layer's chains continued by one row: db[j] + d[j], fmaf(d[j], x[k], dW[j][k])
@@ -1043,6 +1046,21 @@ inline void grad_x_row(const PolLayer &L, const float *d, float *g)
     }
 }
 }  // namespace
+
+// the accumulators added in ascending index
+static void policy_grad_reduce(const PolGradSlabs &S, const PolGradOut &out)
+{
+    for (uint32_t l = 0; l < out.n; ++l) {
+        const uint64_t nw = out.w[l] ? (uint64_t)out.in[l] * out.out[l] : 0u, nb = out.b[l] ? out.out[l] : 0u;
+        par_for(nw + nb, 4096, [&](uint64_t i) {
+            const size_t off = i < nw ? S.w[l] + i : S.b[l] + (i - nw);
+            float acc = 0.0f;
+            for (uint32_t a = 0; a < S.nacc; ++a) acc = acc + S.base[(size_t)a * S.slab_floats + off];
+            if (i < nw) out.w[l][i] = acc;
+            else out.b[l][i - nw] = acc;
+        });
+    }
+}
 
 void policy_eval(const PolNet &net, const PolEvalIO &io)
 {
@@ -1102,17 +1120,130 @@ void policy_grad(const PolNet &net, const PolEvalIO &io, const PolGradSlabs &S, 
             }
         }
     });
-    // the accumulators in ascending index
-    for (uint32_t l = 0; l < out.n; ++l) {
-        const uint64_t nw = out.w[l] ? (uint64_t)out.in[l] * out.out[l] : 0u, nb = out.b[l] ? out.out[l] : 0u;
-        par_for(nw + nb, 4096, [&](uint64_t i) {
-            const size_t off = i < nw ? S.w[l] + i : S.b[l] + (i - nw);
-            float acc = 0.0f;
-            for (uint32_t a = 0; a < S.nacc; ++a) acc = acc + S.base[(size_t)a * S.slab_floats + off];
-            if (i < nw) out.w[l][i] = acc;
-            else out.b[l][i - nw] = acc;
-        });
-    }
+    policy_grad_reduce(S, out);
+}
+
+// ---- evaluate_sequences (DESIGN.md "Backpropagation through HiddenState") ----
+namespace {
+inline uint32_t seq_len(const PolSeqIO &io, uint64_t b)
+{
+    const int32_t n = io.length[b];
+    return n < 0 ? 0u : std::min((uint32_t)n, io.L);
+}
+}  // namespace
+
+void policy_seq_eval(const PolNet &net, const PolSeqIO &io)
+{
+    par_for(io.B, 16, [&](uint64_t b) {
+        RowForward f;
+        float h[kHidden], y[kHidden];
+        for (int c = 0; c < kHidden; ++c) h[c] = io.hidden0[b * kHidden + c];
+        const uint32_t n = seq_len(io, b);
+        for (uint32_t k = 0; k < io.L; ++k) {
+            const uint64_t e = (uint64_t)k * io.B + b;
+            if (k >= n) {
+                if (io.logp) io.logp[e] = 0.0f;
+                if (io.value) io.value[e] = 0.0f;
+                if (io.entropy) io.entropy[e] = 0.0f;
+                if (io.hidden)
+                    for (int c = 0; c < kHidden; ++c) io.hidden[e * kHidden + c] = 0.0f;
+                continue;
+            }
+            row_forward(net, io.obs + e * kPolObs, h, f);
+            policy_layer_host(net.memory, kActTanh, f.y[net.n_trunk], y);
+            float logp, ent, dz[kPolActions];
+            pol_head(f.z, io.action[e], 0.0f, 0.0f, &logp, &ent, dz);
+            if (io.logp) io.logp[e] = logp;
+            if (io.value) io.value[e] = f.v[0];
+            if (io.entropy) io.entropy[e] = ent;
+            if (io.hidden)
+                for (int c = 0; c < kHidden; ++c) io.hidden[e * kHidden + c] = h[c];
+            for (int c = 0; c < kHidden; ++c) h[c] = y[c];
+        }
+    });
+}
+
+void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &S, float *hws, const PolGradOut &out)
+{
+    const uint64_t tiles = (io.B + kPolGradRows - 1u) / kPolGradRows;
+    const uint32_t T = net.n_trunk;
+    constexpr int kM = kPolGradLayers;   // the memory head's slot
+    par_for(S.nacc, 1, [&](uint64_t a) {
+        float *slab = S.base + a * S.slab_floats;
+        std::fill(slab, slab + S.slab_floats, 0.0f);
+        float *hk = hws + a * (size_t)io.L * kPolGradRows * kHidden;   // [L][64][16]
+        RowForward f;
+        float d0[kPolMaxH], d1[kPolMaxH], ga[kPolMaxH], gc[kPolMaxH], gm[kPolMaxH], y[kHidden], dm[kHidden];
+        float dh[kPolGradRows][kHidden];
+        for (uint64_t tile = a; tile < tiles; tile += kPolGradAcc) {
+            const uint64_t b0 = tile * kPolGradRows;
+            const uint32_t nb = (uint32_t)std::min<uint64_t>(kPolGradRows, io.B - b0);
+            // the forward sweep: every present element's h_k
+            uint32_t maxlen = 0;
+            for (uint32_t r = 0; r < nb; ++r) {
+                const uint32_t n = seq_len(io, b0 + r);
+                maxlen = std::max(maxlen, n);
+                float h[kHidden];
+                for (int c = 0; c < kHidden; ++c) h[c] = io.hidden0[(b0 + r) * kHidden + c];
+                for (uint32_t k = 0; k < n; ++k) {
+                    float *o = hk + ((size_t)k * kPolGradRows + r) * kHidden;
+                    for (int c = 0; c < kHidden; ++c) o[c] = h[c];
+                    if (k + 1u == n) break;
+                    row_forward(net, io.obs + ((uint64_t)k * io.B + b0 + r) * kPolObs, h, f);
+                    policy_layer_host(net.memory, kActTanh, f.y[T], h);
+                }
+                for (int c = 0; c < kHidden; ++c) dh[r][c] = 0.0f;
+            }
+            // backward in time.  (An absent element is a row of +0 inputs and
+            // gradients: it leaves every chain as it is, and is skipped.)
+            for (uint32_t k = maxlen; k-- > 0u;)
+                for (uint32_t r = 0; r < nb; ++r) {
+                    if (k >= seq_len(io, b0 + r)) continue;
+                    const uint64_t e = (uint64_t)k * io.B + b0 + r;
+                    row_forward(net, io.obs + e * kPolObs, hk + ((size_t)k * kPolGradRows + r) * kHidden, f);
+                    const float *top = f.y[T];
+                    policy_layer_host(net.memory, kActTanh, top, y);
+                    float logp, ent, dz[kPolActions];
+                    pol_head(f.z, io.action[e], io.g_logp ? io.g_logp[e] : 0.0f, io.g_entropy ? io.g_entropy[e] : 0.0f,
+                             &logp, &ent, dz);
+                    const float dv[1] = {io.g_value ? io.g_value[e] : 0.0f};
+                    for (int c = 0; c < kHidden; ++c) dm[c] = dh[r][c] * pol_activation_grad(kActTanh, y[c]);
+                    grad_w_row(net.actor[1], dz, f.ha, slab + S.w[kPolMaxTrunk + 1], slab + S.b[kPolMaxTrunk + 1]);
+                    grad_w_row(net.critic[1], dv, f.hc, slab + S.w[kPolMaxTrunk + 3], slab + S.b[kPolMaxTrunk + 3]);
+                    grad_w_row(net.memory, dm, top, slab + S.w[kM], slab + S.b[kM]);
+                    grad_x_row(net.actor[1], dz, d0);
+                    grad_x_row(net.critic[1], dv, d1);
+                    for (uint32_t j = 0; j < net.H; ++j) {
+                        d0[j] = d0[j] * pol_activation_grad(kActRelu, f.ha[j]);
+                        d1[j] = d1[j] * pol_activation_grad(kActRelu, f.hc[j]);
+                    }
+                    grad_w_row(net.actor[0], d0, top, slab + S.w[kPolMaxTrunk], slab + S.b[kPolMaxTrunk]);
+                    grad_w_row(net.critic[0], d1, top, slab + S.w[kPolMaxTrunk + 2], slab + S.b[kPolMaxTrunk + 2]);
+                    grad_x_row(net.actor[0], d0, ga);
+                    grad_x_row(net.critic[0], d1, gc);
+                    grad_x_row(net.memory, dm, gm);
+                    float *d = d0, *g = d1;
+                    for (uint32_t j = 0; j < net.H; ++j)
+                        d[j] = ((ga[j] + gc[j]) + gm[j]) * pol_activation_grad((int)net.trunk[T - 1u].act, top[j]);
+                    for (uint32_t l = T; l-- > 0u;) {
+                        grad_w_row(net.trunk[l], d, f.y[l], slab + S.w[l], slab + S.b[l]);
+                        if (l == 0u) break;
+                        grad_x_row(net.trunk[l], d, g);
+                        for (uint32_t j = 0; j < net.H; ++j)
+                            g[j] = g[j] * pol_activation_grad((int)net.trunk[l - 1u].act, f.y[l][j]);
+                        std::swap(d, g);
+                    }
+                    // dh_k from the first layer's HiddenState columns
+                    for (int c = 0; c < kHidden; ++c) {
+                        float acc = 0.0f;
+                        for (uint32_t j = 0; j < net.H; ++j)
+                            acc = pol_fma(d[j], net.trunk[0].w[(size_t)j * net.trunk[0].kp + kPolObs + c], acc);
+                        dh[r][c] = acc;
+                    }
+                }
+        }
+    });
+    policy_grad_reduce(S, out);
 }
 
 void Sim::world_state(uint32_t w, float *xy_rwrz, int32_t *sp_hp_finder, uint64_t *food,

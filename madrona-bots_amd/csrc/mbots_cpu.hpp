@@ -155,6 +155,10 @@ private:
 // accumulators, then adds them in ascending index into `out`.
 void policy_eval(const PolNet &net, const PolEvalIO &io);
 void policy_grad(const PolNet &net, const PolEvalIO &io, const PolGradSlabs &slabs, const PolGradOut &out);
+// evaluate_sequences on the host threads; hws as the device's (mbots_kernels.hpp)
+void policy_seq_eval(const PolNet &net, const PolSeqIO &io);
+void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &slabs, float *hws,
+                     const PolGradOut &out);
 
 }  // namespace cpu
 }  // namespace mbots

@@ -302,5 +302,12 @@ hipError_t launch_policy_eval(const PolEvalIO &io, const PolNet &net, hipStream_
 size_t policy_grad_stash_floats(uint32_t nacc);
 hipError_t launch_policy_grad(const PolEvalIO &io, const PolNet &net, const PolNet &back, const PolGradSlabs &slabs,
                               float *stash, const PolGradOut &out, hipStream_t st);
+// evaluate_sequences and its backward pass through time (mbots_policy.hpp): as
+// above with the memory head in `net`, its transpose in back.memory, and in
+// back.trunk[0] the H -> 16 layer over the first layer's HiddenState columns;
+// hws: pol_seq_h_floats(slabs.nacc, io.L) floats, the h_k of a block's tile
+hipError_t launch_policy_seq_eval(const PolSeqIO &io, const PolNet &net, hipStream_t st);
+hipError_t launch_policy_seq_grad(const PolSeqIO &io, const PolNet &net, const PolNet &back, const PolGradSlabs &slabs,
+                                  float *stash, float *hws, const PolGradOut &out, hipStream_t st);
 
 }  // namespace mbots

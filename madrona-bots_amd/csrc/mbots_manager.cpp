@@ -3107,21 +3107,46 @@ namespace {
 // where a call's pieces lie in the caller's workspace
 struct EvalPlan {
     mbots::PolNet net, back;                  // w / b point into the workspace once bound
-    const mbots_policy_layer *src[mbots::kPolGradLayers];
-    mbots::PolLayer *fwd[mbots::kPolGradLayers], *bwd[mbots::kPolGradLayers];   // null: no such layer
+    const mbots_policy_layer *src[mbots::kPolSeqLayers];
+    mbots::PolLayer *fwd[mbots::kPolSeqLayers], *bwd[mbots::kPolSeqLayers];   // null: no such layer
     mbots::PolGradSlabs slabs;                // base bound; the device's layout, or the CPU mode's
     mbots::PolGradOut out;
-    size_t stash_off, floats;
+    // the slice of src's weight a back layer transposes: its row stride (0: the
+    // layer's own width) and first column
+    uint32_t bwd_ld[mbots::kPolSeqLayers], bwd_off[mbots::kPolSeqLayers];
+    size_t stash_off, h_off, floats;
 };
 
-int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, EvalPlan &P)
+// what a plan is laid out for: evaluate over n rows, or evaluate_sequences over
+// n sequences of L steps
+struct EvalMode {
+    bool seq;
+    uint32_t L;   // (seq only)
+};
+constexpr EvalMode kEvalRows{false, 0u};
+
+// With mode.seq the memory head takes part (slot kPolGradLayers), bwd[0] is the
+// H -> 16 layer over the first layer's HiddenState columns, and the workspace
+// ends with the accumulators' h_k store; without, the layout is evaluate's.
+int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, EvalPlan &P, EvalMode mode)
 {
     using namespace mbots;
+    const bool seq = mode.seq;
     if (int rc = policy_describe(src, P.net)) return rc;
-    P.net.has_memory = 0;
+    if (seq && !(P.net.has_memory && (P.net.flags & kPolMemoryIn)))
+        return fail(MBOTS_E_INVALID, "sequences are evaluated by a net with a memory head and MBOTS_POLICY_MEMORY_IN "
+                                     "(a net without them has no state to carry: mbots_policy_eval)");
+    if (!seq) P.net.has_memory = 0;
     P.back = PolNet{};
     const uint32_t T = P.net.n_trunk;
-    for (int i = 0; i < kPolGradLayers; ++i) P.src[i] = nullptr, P.fwd[i] = nullptr, P.bwd[i] = nullptr;
+    for (int i = 0; i < kPolSeqLayers; ++i)
+        P.src[i] = nullptr, P.fwd[i] = nullptr, P.bwd[i] = nullptr, P.bwd_ld[i] = 0u, P.bwd_off[i] = 0u;
+    if (seq) {
+        P.bwd[0] = &P.back.trunk[0];
+        P.src[kPolGradLayers] = &src->memory;
+        P.fwd[kPolGradLayers] = &P.net.memory;
+        P.bwd[kPolGradLayers] = &P.back.memory;
+    }
     for (uint32_t l = 0; l < T; ++l) {
         P.src[l] = &src->trunk[l];
         P.fwd[l] = &P.net.trunk[l];
@@ -3145,9 +3170,9 @@ int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, Eval
     P.slabs = PolGradSlabs{};
     P.slabs.nacc = (uint32_t)std::min<uint64_t>(tiles, kPolGradAcc);
     P.out = PolGradOut{};
-    P.out.n = kPolGradLayers;
+    P.out.n = seq ? kPolSeqLayers : kPolGradLayers;
     size_t slab = 0, slab_cpu = 0;
-    for (int i = 0; i < kPolGradLayers; ++i) {
+    for (int i = 0; i < (int)P.out.n; ++i) {
         if (!P.fwd[i]) continue;
         PolLayer &f = *P.fwd[i];
         f.w = take(pol_w_floats(f));
@@ -3156,6 +3181,11 @@ int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, Eval
             PolLayer &b = *P.bwd[i];
             b.in = f.out;
             b.out = f.in;
+            if (i == 0) {   // W0[:, 69:85] alone: dh_k
+                b.out = (uint32_t)kHidden;
+                P.bwd_ld[i] = f.in;
+                P.bwd_off[i] = (uint32_t)kPolObs;
+            }
             b.kp = (b.in + 7u) & ~7u;   // an even number of k-steps, as the layer kernel's paired loop takes
             b.nt = (b.out + 15u) / 16u;
             b.w = take(pol_w_floats(b));
@@ -3176,6 +3206,8 @@ int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, Eval
     P.slabs.base = take(slab * P.slabs.nacc);
     P.stash_off = off;
     take(policy_grad_stash_floats(P.slabs.nacc));
+    P.h_off = off;
+    if (seq) take(pol_seq_h_floats(P.slabs.nacc, mode.L));
     P.floats = off;
     return MBOTS_OK;
 }
@@ -3184,7 +3216,7 @@ int eval_check(const mbots_policy_net *net, const float *obs, const float *hidde
                void *ws, uint64_t ws_bytes, int32_t device, EvalPlan &P)
 {
     if (!net) return fail(MBOTS_E_INVALID, "null argument");
-    if (int rc = eval_plan(net, n, device < 0, static_cast<float *>(ws), P)) return rc;
+    if (int rc = eval_plan(net, n, device < 0, static_cast<float *>(ws), P, kEvalRows)) return rc;
     if (n && (!obs || !action)) return fail(MBOTS_E_INVALID, "null obs or action");
     if (n && (net->flags & MBOTS_POLICY_MEMORY_IN) && !hidden)
         return fail(MBOTS_E_INVALID, "a net with MBOTS_POLICY_MEMORY_IN needs the rows' hidden floats");
@@ -3206,7 +3238,7 @@ int eval_upload(const EvalPlan &P, bool back, int32_t device, hipStream_t st)
 {
     using namespace mbots;
     PolUploads U{}, B{};
-    for (int i = 0; i < kPolGradLayers; ++i) {
+    for (int i = 0; i < (int)P.out.n; ++i) {
         if (!P.fwd[i]) continue;
         const PolLayer &f = *P.fwd[i];
         if (device < 0) {
@@ -3216,7 +3248,8 @@ int eval_upload(const EvalPlan &P, bool back, int32_t device, hipStream_t st)
         U.l[U.n++] = PolUpload{P.src[i]->weight, P.src[i]->bias, f.w, f.b, f.in, f.out, f.kp, f.nt, 0u};
         if (back && P.bwd[i]) {
             const PolLayer &b = *P.bwd[i];
-            B.l[B.n++] = PolUpload{P.src[i]->weight, nullptr, b.w, b.b, b.in, b.out, b.kp, b.nt, 1u};
+            B.l[B.n++] = PolUpload{P.src[i]->weight, nullptr, b.w, b.b, b.in, b.out, b.kp, b.nt, 1u, P.bwd_ld[i],
+                                   P.bwd_off[i]};
         }
     }
     if (device < 0) return MBOTS_OK;
@@ -3230,7 +3263,7 @@ int mbots_policy_grad_workspace(const struct mbots_policy_net *net, uint64_t n, 
 {
     if (!net || !bytes) return fail(MBOTS_E_INVALID, "null argument");
     EvalPlan P;
-    if (int rc = eval_plan(net, n, false, nullptr, P)) return rc;
+    if (int rc = eval_plan(net, n, false, nullptr, P, kEvalRows)) return rc;
     *bytes = P.floats * sizeof(float);
     return MBOTS_OK;
 }
@@ -3277,6 +3310,92 @@ int mbots_policy_grad(const struct mbots_policy_net *net, const float *obs, cons
     }
     HIP_TRY(launch_policy_grad(io, P.net, P.back, P.slabs, static_cast<float *>(workspace) + P.stash_off, P.out,
                                as_stream(stream)));
+    return MBOTS_OK;
+}
+
+// ---- evaluate_sequences (include/mbots.h "Training the memory head") ----
+namespace {
+int seq_check(const mbots_policy_net *net, const float *obs, const int32_t *action, const int32_t *length,
+              const float *hidden0, uint32_t L, uint64_t B, void *ws, uint64_t ws_bytes, int32_t device, EvalPlan &P)
+{
+    if (!net) return fail(MBOTS_E_INVALID, "null argument");
+    if (int rc = eval_plan(net, B, device < 0, static_cast<float *>(ws), P, EvalMode{true, L})) return rc;
+    if (B && L && (!obs || !action)) return fail(MBOTS_E_INVALID, "null obs or action");
+    if (B && (!length || !hidden0)) return fail(MBOTS_E_INVALID, "null length or hidden0");
+    if (!ws || ((uintptr_t)ws & 15u)) return fail(MBOTS_E_INVALID, "the workspace must be 16-byte aligned memory");
+    if (ws_bytes < P.floats * sizeof(float))
+        return fail(MBOTS_E_INVALID, "workspace of " + std::to_string(ws_bytes) + " bytes, " +
+                                         std::to_string(P.floats * sizeof(float)) + " needed (mbots_policy_seq_workspace)");
+    if (device < 0)
+        for (uint64_t b = 0; b < B; ++b) {
+            if (length[b] < 0 || (uint32_t)length[b] > L)
+                return fail(MBOTS_E_INVALID, "length " + std::to_string(length[b]) + " of sequence " + std::to_string(b) +
+                                                 " is outside [0, " + std::to_string(L) + "]");
+            for (int32_t k = 0; k < length[b]; ++k) {
+                const int32_t a = action[(uint64_t)k * B + b];
+                if (a < 0 || a >= mbots::kPolActions)
+                    return fail(MBOTS_E_INVALID, "action " + std::to_string(a) + " of step " + std::to_string(k) +
+                                                     " of sequence " + std::to_string(b) + " is outside 0..5");
+            }
+        }
+    return MBOTS_OK;
+}
+}  // namespace
+
+int mbots_policy_seq_workspace(const struct mbots_policy_net *net, uint32_t L, uint64_t B, uint64_t *bytes)
+{
+    if (!net || !bytes) return fail(MBOTS_E_INVALID, "null argument");
+    EvalPlan P;
+    if (int rc = eval_plan(net, B, false, nullptr, P, EvalMode{true, L})) return rc;
+    *bytes = P.floats * sizeof(float);
+    return MBOTS_OK;
+}
+
+int mbots_policy_seq_eval(const struct mbots_policy_net *net, const float *obs, const int32_t *action,
+                          const int32_t *length, const float *hidden0, uint32_t L, uint64_t B, float *logp,
+                          float *value, float *entropy, float *hidden, void *workspace, uint64_t workspace_bytes,
+                          int32_t device, void *stream)
+{
+    EvalPlan P;
+    if (int rc = seq_check(net, obs, action, length, hidden0, L, B, workspace, workspace_bytes, device, P)) return rc;
+    const mbots::PolSeqIO io{obs, hidden0, action, length, nullptr, nullptr, nullptr, logp, value, entropy, hidden, L, B};
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    if (int rc = eval_upload(P, false, device, as_stream(stream))) return rc;
+    if (device < 0) {
+        mbots::cpu::policy_seq_eval(P.net, io);
+        return MBOTS_OK;
+    }
+    HIP_TRY(mbots::launch_policy_seq_eval(io, P.net, as_stream(stream)));
+    return MBOTS_OK;
+}
+
+int mbots_policy_seq_grad(const struct mbots_policy_net *net, const float *obs, const int32_t *action,
+                          const int32_t *length, const float *hidden0, uint32_t L, uint64_t B, const float *g_logp,
+                          const float *g_value, const float *g_entropy, const struct mbots_policy_grads *out,
+                          void *workspace, uint64_t workspace_bytes, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (!out) return fail(MBOTS_E_INVALID, "null argument");
+    EvalPlan P;
+    if (int rc = seq_check(net, obs, action, length, hidden0, L, B, workspace, workspace_bytes, device, P)) return rc;
+    for (uint32_t l = 0; l < P.net.n_trunk; ++l) P.out.w[l] = out->trunk[l].weight, P.out.b[l] = out->trunk[l].bias;
+    for (int i = 0; i < 2; ++i) {
+        P.out.w[kPolMaxTrunk + i] = out->actor[i].weight;
+        P.out.b[kPolMaxTrunk + i] = out->actor[i].bias;
+        P.out.w[kPolMaxTrunk + 2 + i] = out->critic[i].weight;
+        P.out.b[kPolMaxTrunk + 2 + i] = out->critic[i].bias;
+    }
+    P.out.w[kPolGradLayers] = out->memory.weight;
+    P.out.b[kPolGradLayers] = out->memory.bias;
+    const PolSeqIO io{obs, hidden0, action, length, g_logp, g_value, g_entropy, nullptr, nullptr, nullptr, nullptr, L, B};
+    float *ws = static_cast<float *>(workspace);
+    if (device >= 0) HIP_TRY(hipSetDevice(device));
+    if (int rc = eval_upload(P, true, device, as_stream(stream))) return rc;
+    if (device < 0) {
+        cpu::policy_seq_grad(P.net, io, P.slabs, ws + P.h_off, P.out);
+        return MBOTS_OK;
+    }
+    HIP_TRY(launch_policy_seq_grad(io, P.net, P.back, P.slabs, ws + P.stash_off, ws + P.h_off, P.out, as_stream(stream)));
     return MBOTS_OK;
 }
 

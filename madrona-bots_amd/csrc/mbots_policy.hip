@@ -31,8 +31,9 @@ constexpr size_t kPolLds =
 // kBack (the backward pass's input gradients, L the transposed layer with a +0
 // bias): the epilogue stores (add[r][j] +) acc times the derivative of
 // activation `act` at the value dst[r][j] holds -- the forward's output, which
-// the gradient replaces in place; act < 0: no derivative factor.
-template <bool kBack = false>
+// the gradient replaces in place; act < 0: no derivative factor.  kSrc: floats
+// per row of `src`.
+template <bool kBack = false, int kSrc = kPolStride>
 __device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const float *src, float *dst,
                                           uint32_t dst_stride, uint32_t wv, uint32_t woff, uint32_t lane,
                                           const float *add = nullptr)
@@ -53,7 +54,7 @@ __device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const floa
     }
     const float *wp0 = L.w + (size_t)j0 * 64u + lane, *wp1 = L.w + (size_t)j1 * 64u + lane;
     const size_t wstep = (size_t)nt * 64u;
-    const float *xa = src + c * kPolStride + q;
+    const float *xa = src + c * kSrc + q;
     // (a guarded register ring loading the B fragments four k-steps ahead
     // measured slower, 5.9 against 5.0 ms at 65536 worlds; the branch-free pair
     // below 4.85 against 4.90 for one k-step per pass)
@@ -70,13 +71,13 @@ __device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const floa
             n11 = wp1[kn + wstep];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
-                const float a = xa[mt * 16 * kPolStride + 4u * ks];
+                const float a = xa[mt * 16 * kSrc + 4u * ks];
                 acc0[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b00, acc0[mt], 0, 0, 0);
                 acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b10, acc1[mt], 0, 0, 0);
             }
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
-                const float a = xa[mt * 16 * kPolStride + 4u * ks + 4u];
+                const float a = xa[mt * 16 * kSrc + 4u * ks + 4u];
                 acc0[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b01, acc0[mt], 0, 0, 0);
                 acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b11, acc1[mt], 0, 0, 0);
             }
@@ -86,7 +87,7 @@ __device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const floa
             const float b0 = wp0[ks * wstep];
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
-                const float a = xa[mt * 16 * kPolStride + 4u * ks];
+                const float a = xa[mt * 16 * kSrc + 4u * ks];
                 acc0[mt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b0, acc0[mt], 0, 0, 0);
             }
         }
@@ -331,8 +332,10 @@ __global__ __launch_bounds__(256) void policy_repack_kernel(PolUploads U)
         if (i < nw) {
             const uint32_t l = i & 63u, f = i >> 6, jt = f % L.nt, ks = f / L.nt;
             const uint32_t j = jt * 16u + (l & 15u), k = 4u * ks + (l >> 4);
-            L.w_dst[i] = (j < L.out && k < L.in) ? (L.tr ? L.w_src[(size_t)k * L.out + j] : L.w_src[(size_t)j * L.in + k])
-                                                 : 0.0f;
+            const uint32_t ld = L.ld ? L.ld : L.out;
+            L.w_dst[i] = (j < L.out && k < L.in)
+                             ? (L.tr ? L.w_src[(size_t)k * ld + L.off + j] : L.w_src[(size_t)j * L.in + k])
+                             : 0.0f;
         } else {
             const uint32_t j = i - nw;
             L.b_dst[j] = (j < L.out && L.b_src) ? L.b_src[j] : 0.0f;
@@ -381,13 +384,15 @@ __device__ __forceinline__ void pol_copy_tile(float *dst, const float *src, uint
 // the C fragments of its 16 x 16 tiles) and start at +0 on the block's first
 // tile.  Wave w takes the out-feature tiles w and w + 4, four in-feature tiles
 // at a time; columns of x past kp and what they produce are never read back.
+// kD: floats per row of `d`.
+template <int kD = kPolStride>
 __device__ __forceinline__ void pol_grad_w(const PolLayer &L, const float *d, const float *x, float *sw, float *sb,
                                            bool first, uint32_t wv, uint32_t lane, uint32_t t)
 {
     const uint32_t nt = L.nt, nkt = pol_grad_nkt(L.kp);
     const uint32_t c = lane & 15u, q = lane >> 4;
     for (uint32_t jt = wv; jt < nt; jt += 4u) {
-        const float *da = d + q * kPolStride + jt * 16u + c;
+        const float *da = d + q * kD + jt * 16u + c;
         for (uint32_t kt0 = 0; kt0 < nkt; kt0 += 4u) {
             const uint32_t nk = min(4u, nkt - kt0);
             f32x4 acc[4];
@@ -403,14 +408,14 @@ __device__ __forceinline__ void pol_grad_w(const PolLayer &L, const float *d, co
             const float *xb = x + q * kPolStride + kt0 * 16u + c;
             if (nk == 4u) {
                 for (uint32_t s = 0; s < (uint32_t)kPolRows / 4u; ++s) {
-                    const float a = da[s * 4u * kPolStride];
+                    const float a = da[s * 4u * kD];
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
                         acc[u] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, xb[s * 4u * kPolStride + u * 16], acc[u], 0, 0, 0);
                 }
             } else {
                 for (uint32_t s = 0; s < (uint32_t)kPolRows / 4u; ++s) {
-                    const float a = da[s * 4u * kPolStride];
+                    const float a = da[s * 4u * kD];
 #pragma unroll
                     for (int u = 0; u < 4; ++u)
                         if ((uint32_t)u < nk)
@@ -429,7 +434,7 @@ __device__ __forceinline__ void pol_grad_w(const PolLayer &L, const float *d, co
     }
     if (t < nt * 16u) {
         float acc = first ? 0.0f : sb[t];
-        for (int r = 0; r < kPolRows; ++r) acc = acc + d[r * kPolStride + t];
+        for (int r = 0; r < kPolRows; ++r) acc = acc + d[r * kD + t];
         sb[t] = acc;
     }
 }
@@ -575,6 +580,278 @@ __global__ __launch_bounds__(256) void policy_grad_reduce_kernel(PolGradSlabs S,
     }
 }
 
+// ---- evaluate_sequences and its backward pass through time (mbots_policy.hpp;
+// DESIGN.md "Backpropagation through HiddenState") ----
+constexpr int kPolDmStride = 20;   // floats per row of the d mem_pre tile: 16 + 4, so the 16 rows x 4 k
+                                   // of its A fragments hit 64 banks as the big tiles' do
+constexpr int kPolHTile = kPolRows * kHidden;
+constexpr size_t kPolSeqEvalLds = (2 * kPolTile + kPolRows * (kPolLogitStride + 1) + kPolHTile + kPolRows) * sizeof(float);
+constexpr size_t kPolSeqGradLds =
+    (4 * kPolTile + kPolRows * (kPolLogitStride + 1) + kPolHTile + kPolRows * kPolDmStride + kPolRows) * sizeof(float);
+
+// the lengths of the tile's columns (clamped to [0, L]; 0 past B) into s_len, and the largest
+__device__ __forceinline__ uint32_t pol_seq_lengths(uint32_t *s_len, const PolSeqIO &A, uint64_t b0, uint32_t nb,
+                                                    uint32_t t)
+{
+    __syncthreads();   // the previous tile's readers
+    if (t < (uint32_t)kPolRows) {
+        const int32_t n = t < nb ? A.length[b0 + t] : 0;
+        s_len[t] = n < 0 ? 0u : min((uint32_t)n, A.L);
+    }
+    __syncthreads();
+    uint32_t m = 0;
+    for (int r = 0; r < kPolRows; ++r) m = max(m, s_len[r]);
+    return uniform(m);
+}
+
+// step k's inputs of the tile: X[64][kp] = obs[k, b0 + row] | h[row], +0 for the
+// pads and the absent elements (h: [64][16], LDS or the block's store)
+__device__ __forceinline__ void pol_stage_seq(float *x, const PolSeqIO &A, uint32_t k, uint64_t b0,
+                                              const uint32_t *s_len, const float *h, uint32_t kp, uint32_t t)
+{
+    const float *o = A.obs + ((uint64_t)k * A.B + b0) * kPolObs;
+    for (uint32_t i = t; i < (uint32_t)kPolRows * kp; i += 256u) {
+        const uint32_t row = i / kp, c = i - row * kp;
+        float v = 0.0f;
+        if (k < s_len[row]) {
+            if (c < (uint32_t)kPolObs) v = o[(size_t)row * kPolObs + c];
+            else if (c < (uint32_t)(kPolObs + kHidden)) v = h[row * kHidden + (c - kPolObs)];
+        }
+        x[row * kPolStride + c] = v;
+    }
+}
+
+// logp, value, entropy (and the h_k read) of every element, grid-stride over
+// the column tiles, k ascending inside a tile with h carried in LDS
+__global__ __launch_bounds__(256, 2) void policy_seq_eval_kernel(PolSeqIO A, PolNet net)
+{
+    extern __shared__ float s_pol[];
+    float *buf0 = s_pol, *buf1 = s_pol + kPolTile;
+    float *s_logit = s_pol + 2 * kPolTile, *s_val = s_logit + kPolRows * kPolLogitStride;
+    float *s_h = s_val + kPolRows;
+    uint32_t *s_len = reinterpret_cast<uint32_t *>(s_h + kPolHTile);
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    const uint64_t tiles = (A.B + kPolRows - 1u) / kPolRows;
+
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t b0 = tile * kPolRows;
+        const uint32_t nb = A.B - b0 < (uint64_t)kPolRows ? (uint32_t)(A.B - b0) : (uint32_t)kPolRows;
+        const uint32_t maxlen = pol_seq_lengths(s_len, A, b0, nb, t);
+        for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u)
+            s_h[i] = (i >> 4) < nb ? A.hidden0[b0 * kHidden + i] : 0.0f;
+        __syncthreads();
+        for (uint32_t k = 0; k < maxlen; ++k) {
+            const uint64_t e0 = (uint64_t)k * A.B + b0;
+            if (A.hidden)
+                for (uint32_t i = t; i < nb * (uint32_t)kHidden; i += 256u)
+                    A.hidden[e0 * kHidden + i] = k < s_len[i >> 4] ? s_h[i] : 0.0f;
+            pol_stage_seq(buf0, A, k, b0, s_len, s_h, net.trunk[0].kp, t);
+            __syncthreads();
+            float *cur = buf0, *oth = buf1;
+            for (uint32_t l = 0; l < net.n_trunk; ++l) {
+                pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
+                __syncthreads();
+                float *sw = cur;
+                cur = oth;
+                oth = sw;
+            }
+            pol_layer(net.actor[0], kActRelu, cur, oth, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            pol_layer(net.actor[1], kActIdentity, oth, s_logit, kPolLogitStride, wv, 0u, lane);
+            pol_layer(net.memory, kActTanh, cur, s_h, kHidden, wv, 1u, lane);   // h_{k+1}, as act() writes it
+            __syncthreads();
+            pol_layer(net.critic[0], kActRelu, cur, oth, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            pol_layer(net.critic[1], kActIdentity, oth, s_val, 1u, wv, 0u, lane);
+            __syncthreads();
+            if (t < nb) {
+                float logp = 0.0f, ent = 0.0f, val = 0.0f;
+                if (k < s_len[t]) {
+                    float z[kPolActions], dz[kPolActions];
+#pragma unroll
+                    for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
+                    pol_head(z, A.action[e0 + t], 0.0f, 0.0f, &logp, &ent, dz);
+                    val = s_val[t];
+                }
+                if (A.logp) A.logp[e0 + t] = logp;
+                if (A.value) A.value[e0 + t] = val;
+                if (A.entropy) A.entropy[e0 + t] = ent;
+            }
+        }
+        // the steps past the tile's largest length
+        for (uint32_t k = maxlen; k < A.L; ++k) {
+            const uint64_t e0 = (uint64_t)k * A.B + b0;
+            if (t < nb) {
+                if (A.logp) A.logp[e0 + t] = 0.0f;
+                if (A.value) A.value[e0 + t] = 0.0f;
+                if (A.entropy) A.entropy[e0 + t] = 0.0f;
+            }
+            if (A.hidden)
+                for (uint32_t i = t; i < nb * (uint32_t)kHidden; i += 256u) A.hidden[e0 * kHidden + i] = 0.0f;
+        }
+    }
+}
+
+struct PolSeqGradDev {
+    PolNet back;          // the transposed layers; memory the head's, trunk[0] the H -> 16 layer of dh
+    PolGradSlabs slabs;
+    float *stash;         // [blocks][kPolStashTiles][kPolTile]
+    float *hws;           // [blocks][L][64][16]
+};
+
+// Block b is accumulator b and takes the column tiles b, b + kPolGradAcc, ...
+// in order.  Per tile: a forward sweep that keeps only h_k (in the block's
+// store); then for k descending that step's forward again from (obs_k, h_k),
+// and policy_eval_kernel's backward with the memory head's gradients, d mem_pre
+// from the carried dh tile, and the next dh from the first layer's gradient.
+__global__ __launch_bounds__(256, 1) void policy_seq_grad_kernel(PolSeqIO A, PolNet net, PolSeqGradDev G)
+{
+    extern __shared__ float s_pol[];
+    float *buf0 = s_pol, *buf1 = s_pol + kPolTile, *ha = s_pol + 2 * kPolTile, *hc = s_pol + 3 * kPolTile;
+    float *s_logit = s_pol + 4 * kPolTile, *s_val = s_logit + kPolRows * kPolLogitStride;
+    float *s_hd = s_val + kPolRows;        // h during the sweep, dh on the way back
+    float *s_dm = s_hd + kPolHTile;        // the memory head's output y, then d mem_pre
+    uint32_t *s_len = reinterpret_cast<uint32_t *>(s_dm + kPolRows * kPolDmStride);
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    const uint64_t tiles = (A.B + kPolRows - 1u) / kPolRows;
+    const PolGradSlabs &S = G.slabs;
+    float *slab = S.base + (size_t)blockIdx.x * S.slab_floats;
+    float *stash = G.stash + (size_t)blockIdx.x * kPolStashTiles * kPolTile;
+    float *hk = G.hws + (size_t)blockIdx.x * A.L * kPolHTile;
+    const uint32_t T = net.n_trunk, kp0 = net.trunk[0].kp;
+    constexpr int kM = kPolGradLayers;   // the memory head's slot
+    bool started = false;                // the slab's chains have begun
+
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += (uint64_t)kPolGradAcc) {
+        const uint64_t b0 = tile * kPolRows;
+        const uint32_t nb = A.B - b0 < (uint64_t)kPolRows ? (uint32_t)(A.B - b0) : (uint32_t)kPolRows;
+        const uint32_t maxlen = pol_seq_lengths(s_len, A, b0, nb, t);
+        // ---- the forward sweep: h_k of every step ----
+        for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u)
+            s_hd[i] = (i >> 4) < nb ? A.hidden0[b0 * kHidden + i] : 0.0f;
+        __syncthreads();
+        for (uint32_t k = 0; k < maxlen; ++k) {
+            for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) hk[(size_t)k * kPolHTile + i] = s_hd[i];
+            if (k + 1u == maxlen) break;
+            pol_stage_seq(buf0, A, k, b0, s_len, s_hd, kp0, t);
+            __syncthreads();
+            float *cur = buf0, *oth = buf1;
+            for (uint32_t l = 0; l < T; ++l) {
+                pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
+                __syncthreads();
+                float *sw = cur;
+                cur = oth;
+                oth = sw;
+            }
+            pol_layer(net.memory, kActTanh, cur, s_hd, kHidden, wv, 0u, lane);
+            __syncthreads();
+        }
+        __syncthreads();
+        for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) s_hd[i] = 0.0f;   // dh past the last step
+        // ---- backward in time ----
+        for (uint32_t k = maxlen; k-- > 0u;) {
+            const float *h = hk + (size_t)k * kPolHTile;
+            const uint64_t e0 = (uint64_t)k * A.B + b0;
+            const bool first = !started;
+            pol_stage_seq(buf0, A, k, b0, s_len, h, kp0, t);
+            __syncthreads();
+            float *cur = buf0, *oth = buf1;
+            for (uint32_t l = 0; l < T; ++l) {
+                pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
+                __syncthreads();
+                float *sw = cur;
+                cur = oth;
+                oth = sw;
+                if (l + 1u < T) pol_copy_tile(stash + (size_t)l * kPolTile, cur, t);
+            }
+            pol_layer(net.actor[0], kActRelu, cur, ha, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            pol_layer(net.actor[1], kActIdentity, ha, s_logit, kPolLogitStride, wv, 0u, lane);
+            pol_layer(net.memory, kActTanh, cur, s_dm, kPolDmStride, wv, 1u, lane);
+            __syncthreads();
+            pol_layer(net.critic[0], kActRelu, cur, hc, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            pol_layer(net.critic[1], kActIdentity, hc, s_val, 1u, wv, 0u, lane);
+            __syncthreads();
+            // d loss / d logits | d value as in policy_eval_kernel, and d mem_pre = dh (1 - y^2)
+            if (t < (uint32_t)kPolRows) {
+                float dz[kPolActions] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, dv = 0.0f;
+                const bool present = k < s_len[t];
+                if (present) {
+                    const uint64_t e = e0 + t;
+                    float z[kPolActions];
+#pragma unroll
+                    for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
+                    const float gl = A.g_logp ? A.g_logp[e] : 0.0f, ge = A.g_entropy ? A.g_entropy[e] : 0.0f;
+                    float logp, ent;
+                    pol_head(z, A.action[e], gl, ge, &logp, &ent, dz);
+                    if (A.g_value) dv = A.g_value[e];
+                }
+                float *o = oth + t * kPolStride;
+#pragma unroll
+                for (int i = 0; i < 32; ++i) o[i] = 0.0f;
+                if (present) {
+#pragma unroll
+                    for (int i = 0; i < kPolActions; ++i) o[i] = dz[i];
+                    o[16] = dv;
+                }
+            }
+            {
+                const uint32_t row = t >> 2, c0 = (t & 3u) * 4u;
+                const bool present = k < s_len[row];
+#pragma unroll
+                for (uint32_t u = 0; u < 4u; ++u) {
+                    float *y = s_dm + row * kPolDmStride + c0 + u;
+                    *y = present ? s_hd[row * kHidden + c0 + u] * pol_activation_grad(kActTanh, *y) : 0.0f;
+                }
+            }
+            __syncthreads();
+            // heads' second layers, and the memory head
+            pol_grad_w(net.actor[1], oth, ha, slab + S.w[kPolMaxTrunk + 1], slab + S.b[kPolMaxTrunk + 1], first, wv, lane, t);
+            pol_grad_w(net.critic[1], oth + 16, hc, slab + S.w[kPolMaxTrunk + 3], slab + S.b[kPolMaxTrunk + 3], first, wv,
+                       lane, t);
+            pol_grad_w<kPolDmStride>(net.memory, s_dm, cur, slab + S.w[kM], slab + S.b[kM], first, wv, lane, t);
+            __syncthreads();
+            pol_layer<true>(G.back.actor[1], kActRelu, oth, ha, kPolStride, wv, 0u, lane);
+            pol_layer<true>(G.back.critic[1], kActRelu, oth + 16, hc, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            // heads' first layers; the trunk's last output receives the actor's input
+            // gradient, plus the critic's, plus the memory head's, times its
+            // activation's derivative
+            pol_grad_w(net.actor[0], ha, cur, slab + S.w[kPolMaxTrunk], slab + S.b[kPolMaxTrunk], first, wv, lane, t);
+            pol_grad_w(net.critic[0], hc, cur, slab + S.w[kPolMaxTrunk + 2], slab + S.b[kPolMaxTrunk + 2], first, wv, lane,
+                       t);
+            pol_layer<true>(G.back.actor[0], -1, ha, oth, kPolStride, wv, 0u, lane);
+            __syncthreads();
+            pol_layer<true>(G.back.critic[0], -1, hc, oth, kPolStride, wv, 0u, lane, oth);
+            __syncthreads();
+            pol_layer<true, kPolDmStride>(G.back.memory, (int)net.trunk[T - 1u].act, s_dm, cur, kPolStride, wv, 0u, lane,
+                                          oth);
+            __syncthreads();
+            // the trunk, last layer first: d in `cur`, the layer's input in `oth`
+            for (uint32_t l = T; l-- > 0u;) {
+                if (l == 0u) pol_stage_seq(oth, A, k, b0, s_len, h, kp0, t);
+                else pol_copy_tile(oth, stash + (size_t)(l - 1u) * kPolTile, t);
+                __syncthreads();
+                pol_grad_w(net.trunk[l], cur, oth, slab + S.w[l], slab + S.b[l], first, wv, lane, t);
+                __syncthreads();
+                if (l == 0u) break;
+                pol_layer<true>(G.back.trunk[l], (int)net.trunk[l - 1u].act, cur, oth, kPolStride, wv, 0u, lane);
+                __syncthreads();
+                float *sw = cur;
+                cur = oth;
+                oth = sw;
+            }
+            // dh_k[c] = sum_j d0[j] W0[j][69 + c]
+            pol_layer<true>(G.back.trunk[0], -1, cur, s_hd, kHidden, wv, 0u, lane);
+            __syncthreads();
+            started = true;
+        }
+    }
+    if (!started)   // no step at all: the chains are their +0 starts
+        for (size_t i = t; i < S.slab_floats; i += 256u) slab[i] = 0.0f;
+}
+
 template <bool kGrad> static hipError_t policy_eval_lds()
 {
     static bool set = false;
@@ -605,6 +882,42 @@ hipError_t launch_policy_grad(const PolEvalIO &io, const PolNet &net, const PolN
         if (const hipError_t e = policy_eval_lds<true>()) return e;
         PolGradDev G{back, slabs, stash};
         hipLaunchKernelGGL(policy_eval_kernel<true>, dim3(slabs.nacc), dim3(256), kPolGradLds, st, io, net, G);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3(16, out.n), dim3(256), 0, st, slabs, out);
+    return hipGetLastError();
+}
+
+static hipError_t policy_seq_lds(const void *fn, size_t bytes, bool &set)
+{
+    if (set) return hipSuccess;
+    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e == hipSuccess) set = true;
+    return e;
+}
+
+hipError_t launch_policy_seq_eval(const PolSeqIO &io, const PolNet &net, hipStream_t st)
+{
+    if (io.B == 0 || io.L == 0) return hipSuccess;
+    static bool set = false;
+    if (const hipError_t e = policy_seq_lds(reinterpret_cast<const void *>(policy_seq_eval_kernel), kPolSeqEvalLds, set))
+        return e;
+    const uint64_t tiles = (io.B + kPolRows - 1u) / kPolRows;
+    const unsigned blocks = (unsigned)std::min<uint64_t>(tiles, 512u);
+    hipLaunchKernelGGL(policy_seq_eval_kernel, dim3(blocks), dim3(256), kPolSeqEvalLds, st, io, net);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_seq_grad(const PolSeqIO &io, const PolNet &net, const PolNet &back, const PolGradSlabs &slabs,
+                                  float *stash, float *hws, const PolGradOut &out, hipStream_t st)
+{
+    if (slabs.nacc) {
+        static bool set = false;
+        if (const hipError_t e =
+                policy_seq_lds(reinterpret_cast<const void *>(policy_seq_grad_kernel), kPolSeqGradLds, set))
+            return e;
+        PolSeqGradDev G{back, slabs, stash, hws};
+        hipLaunchKernelGGL(policy_seq_grad_kernel, dim3(slabs.nacc), dim3(256), kPolSeqGradLds, st, io, net, G);
         if (const hipError_t e = hipGetLastError()) return e;
     }
     hipLaunchKernelGGL(policy_grad_reduce_kernel, dim3(16, out.n), dim3(256), 0, st, slabs, out);

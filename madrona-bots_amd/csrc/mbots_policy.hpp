@@ -247,10 +247,12 @@ MB_HD size_t pol_b_floats(const PolLayer &l) { return (size_t)l.nt * 16u; }
 
 // the repack / pad of one layer's weights at upload (src: [out][in] row-major;
 // tr: src is the [in][out] matrix this layer is the transpose of)
+// ld, off (tr only): src's row stride when not `out` (0: out), and the first of
+// the `out` columns of it the layer takes
 struct PolUpload {
     const float *w_src, *b_src;
     float *w_dst, *b_dst;
-    uint32_t in, out, kp, nt, tr;
+    uint32_t in, out, kp, nt, tr, ld, off;
 };
 struct PolUploads {
     PolUpload l[kPolLayers];
@@ -282,6 +284,8 @@ MB_HD void pol_row_input(float *x, const uint8_t *dep, const int8_t *sem, int32_
 // tile to tile), and the result is the accumulators added in ascending index.
 constexpr uint32_t kPolGradRows = 64, kPolGradAcc = 256;
 constexpr int kPolGradLayers = kPolMaxTrunk + 4;   // trunk, actor 2, critic 2 (the memory head takes no part)
+// evaluate_sequences' gradients: those, then the memory head (slot kPolGradLayers)
+constexpr int kPolSeqLayers = kPolGradLayers + 1;
 
 // d activation / d input, from the layer's output y
 MB_HD float pol_activation_grad(int code, float y)
@@ -346,16 +350,36 @@ struct PolEvalIO {
 struct PolGradSlabs {
     float *base;
     uint64_t slab_floats;
-    uint32_t w[kPolGradLayers], b[kPolGradLayers];
+    uint32_t w[kPolSeqLayers], b[kPolSeqLayers];
     uint32_t nacc;
 };
 // the gradients as the caller wants them ([out][in] / [out], null: not wanted), in
 // the order trunk, actor, critic
 struct PolGradOut {
-    float *w[kPolGradLayers], *b[kPolGradLayers];
-    uint32_t in[kPolGradLayers], out[kPolGradLayers], kp[kPolGradLayers];
-    uint32_t n;
+    float *w[kPolSeqLayers], *b[kPolSeqLayers];
+    uint32_t in[kPolSeqLayers], out[kPolSeqLayers], kp[kPolSeqLayers];
+    uint32_t n;   // slots in use: kPolGradLayers, or kPolSeqLayers
 };
 MB_HD uint32_t pol_grad_nkt(uint32_t kp) { return (kp + 15u) >> 4; }
+
+// ---- evaluate_sequences: the net along padded sequences with the memory
+// head's output carried from step to step, and backpropagation through time
+// (DESIGN.md "Backpropagation through HiddenState") ----
+// Element (k, b) of the [L][B] batch is present iff k < length[b].  The
+// parameter gradients' summation order: sequences in tiles of kPolGradRows
+// columns, tile i into accumulator i mod kPolGradAcc, an accumulator's chain
+// over its tiles ascending, inside a tile k from the tile's largest length - 1
+// down to 0, inside a (tile, k) the 64 columns ascending.
+struct PolSeqIO {
+    const float *obs, *hidden0;      // [L][B][69], [B][16]
+    const int32_t *action, *length;  // [L][B], [B]
+    const float *g_logp, *g_value, *g_entropy;   // [L][B] (null: zeros)
+    float *logp, *value, *entropy;   // [L][B], +0 where absent (null: not wanted)
+    float *hidden;                   // [L][B][16]: the h_k each present element read
+    uint32_t L;
+    uint64_t B;
+};
+// floats of the per-accumulator h_k store of the backward pass
+MB_HD size_t pol_seq_h_floats(uint32_t nacc, uint32_t L) { return (size_t)nacc * L * kPolGradRows * kHidden; }
 
 }  // namespace mbots

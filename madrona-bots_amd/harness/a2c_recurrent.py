@@ -1,0 +1,147 @@
+"""Recurrent A2C on the device's own arithmetic -- the learner loop of
+INTEGRATION.md "Training the memory head" as runnable code, beside a2c.py:
+
+    window.push() -> act() -> step() ... -> window.compute() -> sequences() ->
+    batch() / gather() -> PolicyNet.evaluate_sequences(obs, action, len, hidden0)
+    -> loss -> backward() -> optimizer.step() -> set_policy()
+
+The nets read HiddenState (memory_in) and write it (a memory head): act()
+carries the state from step to step through the species sort, the window
+records it, and evaluate_sequences() runs each net along its agents' padded
+lifelines -- logp, value and the carried state bit for bit what act() produced
+-- and backpropagates through time with the library's own kernels, so the
+memory head learns, with the same gradient bits in CPU mode and on the device.
+Losses and optimisers are plain torch.
+
+    python madrona-bots_amd/harness/a2c_recurrent.py --worlds 64 --iters 10 --exec-mode cpu
+    python madrona-bots_amd/harness/a2c_recurrent.py --worlds 4096 --iters 50
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+NUM_SPECIES = 4
+
+
+def make_modules(hidden=128, device="cpu", seed=0):
+    """Per species a2c.py's stacks with the 16 HiddenState floats after the 69
+    observation floats as the input, and the memory head Linear(H, 16), Tanh."""
+    nn = torch.nn
+    torch.manual_seed(seed)
+    mods = []
+    for _ in range(NUM_SPECIES):
+        feature = nn.Sequential(nn.Linear(85, hidden), nn.Linear(hidden, hidden), nn.Tanh(),
+                                nn.Linear(hidden, hidden), nn.ReLU())
+        actor = nn.Sequential(nn.Linear(hidden, hidden), nn.ReLU(), nn.Linear(hidden, 6))
+        critic = nn.Sequential(nn.Linear(hidden, hidden), nn.ReLU(), nn.Linear(hidden, 1))
+        memory = nn.Sequential(nn.Linear(hidden, 16), nn.Tanh())
+        with torch.no_grad():
+            feature[0].weight[:, :69].mul_(0.01)
+        mods.append(nn.ModuleDict({"feature": feature, "actor": actor, "critic": critic, "memory": memory}).to(device))
+    return mods
+
+
+def species_of_rows(sim):
+    """int32 [N, 1]: the species 0..3 of every row of the current (species-sorted) table."""
+    count = sim.species_count_tensor().to_torch().sum(dim=0).to(torch.int64)
+    return torch.repeat_interleave(torch.arange(NUM_SPECIES, device=count.device), count).to(torch.int32).reshape(-1, 1)
+
+
+def rollout(sim, win, horizon, gamma=0.99, lam=0.95, death_reward=-1.0):
+    """Fill the (empty) window with `horizon` tables of the manager's policy and
+    compute its advantages from act()'s own value estimates.  Returns
+    (compute()'s views, and per table in its row order: action, value, species).
+
+    push() comes before act(), so that the window records the HiddenState act()
+    is about to read; the critic's estimate of a table therefore exists only
+    after its push.  It goes into the window's value column -- a view of the
+    window's storage -- once a first compute() has told the host the row
+    counts, and a second compute() derives adv and ret from it."""
+    actions, values, species = [], [], []
+    for t in range(horizon):
+        last = t == horizon - 1                 # the last table only bootstraps
+        win.push()
+        o = sim.act(write=not last)
+        actions.append(o["action"])
+        values.append(o["value"])
+        species.append(species_of_rows(sim))
+        if not last:
+            sim.step()
+    out = win.compute(gamma=gamma, lam=lam, death_reward=death_reward)
+    for dst, v in zip(out["value"], values):
+        dst.copy_(v)
+    out = win.compute(gamma=gamma, lam=lam, death_reward=death_reward)
+    return out, actions, values, species
+
+
+def train(sim, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0, value_coef=0.5,
+          entropy_coef=0.01, log=None):
+    """`iters` updates of `horizon - 1` steps each.  Returns the losses (floats)."""
+    import madrona_bots as mb
+    nets = [mb.PolicyNet.from_torch(m["feature"], m["actor"], m["critic"], m["memory"], memory_in=True)
+            for m in modules]
+    sim.set_policy(nets)
+    win = sim.trajectory_window(horizon, max_rows=sim.num_worlds * sim.agent_capacity, record_obs=True,
+                                record_state=True)
+    losses = []
+    try:
+        for it in range(iters):
+            _, actions, _, species = rollout(sim, win, horizon, gamma, lam, death_reward)
+            win.sequences()
+            b = win.batch(keys=("rows", "t0", "len", "end", "obs", "adv", "ret", "hidden0"))
+            action = win.gather(actions)[:, :, 0]
+            sp = win.gather(species)[0, :, 0]           # a lifeline keeps its species
+            L = b["rows"].shape[0]
+            k = torch.arange(L, device=sim.device, dtype=torch.int32)[:, None]
+            keep = (b["rows"] >= 0) & (b["t0"][None, :] + k < horizon - 1)            # not the bootstrap table
+            keep &= ~((b["end"] == win.END_RESET)[None, :] & (k == b["len"][None, :] - 1))   # nor a reset's last row
+            total = max(int(keep.sum()), 1)
+            loss = torch.zeros((), device=sim.device)
+            for s, net in enumerate(nets):
+                cols = torch.nonzero(sp == s).reshape(-1)
+                if cols.numel() == 0:
+                    continue
+                take = lambda x: x.index_select(1, cols)
+                logp, value, entropy = net.evaluate_sequences(take(b["obs"]), take(action), b["len"][cols],
+                                                              b["hidden0"][cols])
+                per_row = -take(b["adv"]) * logp + value_coef * (value - take(b["ret"])) ** 2 - entropy_coef * entropy
+                loss = loss + (per_row * take(keep).to(torch.float32)).sum() / total
+            for opt in optimizers:
+                opt.zero_grad(set_to_none=True)
+            loss.backward()
+            for opt in optimizers:
+                opt.step()
+            sim.set_policy(nets)                        # same architecture: re-uploads, stream-ordered
+            win.clear()
+            losses.append(float(loss.detach()))
+            if log:
+                log(json.dumps({"iter": it, "loss": losses[-1], "rows": total}))
+    finally:
+        win.close()
+    return losses
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--worlds", type=int, default=64)
+    ap.add_argument("--agents", type=int, default=32)
+    ap.add_argument("--iters", type=int, default=10)
+    ap.add_argument("--horizon", type=int, default=8)
+    ap.add_argument("--hidden", type=int, default=128)
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--seed", type=int, default=69)
+    ap.add_argument("--exec-mode", choices=("hip", "cpu"), default="hip" if torch.cuda.is_available() else "cpu")
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    import madrona_bots as mb
+    sim = mb.SimManager(0, args.worlds, args.seed, args.agents, exec_mode=args.exec_mode)
+    modules = make_modules(args.hidden, sim.device, args.seed)
+    optimizers = [torch.optim.Adam(m.parameters(), lr=args.lr) for m in modules]
+    train(sim, modules, optimizers, args.iters, args.horizon, log=print)
+
+
+if __name__ == "__main__":
+    main()

@@ -155,6 +155,11 @@ def _load():
         "mbots_policy_eval": [P(_PolicyNet), vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, ctypes.c_uint64, i32, vp],
         "mbots_policy_grad": [P(_PolicyNet), vp, vp, vp, ctypes.c_uint64, vp, vp, vp, P(_PolicyGrads), vp,
                               ctypes.c_uint64, i32, vp],
+        "mbots_policy_seq_workspace": [P(_PolicyNet), u32, ctypes.c_uint64, P(ctypes.c_uint64)],
+        "mbots_policy_seq_eval": [P(_PolicyNet), vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp, vp, vp,
+                                  ctypes.c_uint64, i32, vp],
+        "mbots_policy_seq_grad": [P(_PolicyNet), vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp, P(_PolicyGrads), vp,
+                                  ctypes.c_uint64, i32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -1333,6 +1338,10 @@ class PolicyNet:
             w, b = params[2 * i], params[2 * i + 1]
             slot.in_, slot.out, slot.act = w.shape[1], w.shape[0], codes[i]
             slot.weight, slot.bias = w.data_ptr(), None if b is None else b.data_ptr()
+        if len(params) > 2 * len(slots):   # evaluate_sequences: the memory head follows
+            w, b = params[2 * len(slots)], params[2 * len(slots) + 1]
+            c.memory.in_, c.memory.out, c.memory.act = w.shape[1], w.shape[0], 0
+            c.memory.weight, c.memory.bias = w.data_ptr(), None if b is None else b.data_ptr()
         c.flags = 1 if self.memory_in else 0
         return c
 
@@ -1374,16 +1383,64 @@ class PolicyNet:
                                present, *[named[i][1] for i in present])
 
 
+    def evaluate_sequences(self, obs, action, length, hidden0, return_hidden=False):
+        """(logp, value, entropy), float32 [L, B] each on obs's device, of a
+        padded batch of sequences (TrajectoryWindow.batch(), one species'
+        columns): obs float32 [L, B, 69], action int32 [L, B] or [L, B, 1],
+        length int32 [B] in [0, L], hidden0 float32 [B, 16].  Element (k, b)
+        is present iff k < length[b]; absent elements are +0.  The net -- one
+        with a memory head and memory_in; evaluate() is for the others -- runs
+        along each sequence with the memory head's output carried from step to
+        step, so on unchanged parameters logp, value and the carried state are
+        bit for bit what act() produced along that lifeline.  backward()
+        backpropagates through time into every parameter, the memory head's
+        included; obs and hidden0 receive no gradient (the window boundary is
+        detached).  return_hidden: a fourth result, the non-differentiable
+        float32 [L, B, 16] state each present element was evaluated with.
+        Devices, bits and summation order as evaluate() (DESIGN.md
+        "Backpropagation through HiddenState")."""
+        self._validate()
+        if self.memory is None or not self.memory_in:
+            raise ValueError("evaluate_sequences needs a net with a memory head and memory_in=True (there is no state "
+                             "to carry otherwise): use evaluate()")
+        dev = obs.device
+        if obs.dtype != torch.float32 or obs.dim() != 3 or obs.shape[2] != 69:
+            raise ValueError(f"obs must be float32 [L, B, 69], not {obs.dtype} {list(obs.shape)}")
+        L, B = obs.shape[0], obs.shape[1]
+        if action.dtype != torch.int32 or action.device != dev or tuple(action.shape) not in ((L, B), (L, B, 1)):
+            raise ValueError(f"action must be int32 [L, B] or [L, B, 1] on {dev} with obs's steps and sequences, not "
+                             f"{action.dtype} {list(action.shape)} on {action.device}")
+        if length.dtype != torch.int32 or length.device != dev or tuple(length.shape) != (B,):
+            raise ValueError(f"length must be int32 [B] on {dev}, not {length.dtype} {list(length.shape)} on "
+                             f"{length.device}")
+        if hidden0.dtype != torch.float32 or hidden0.device != dev or tuple(hidden0.shape) != (B, 16):
+            raise ValueError(f"hidden0 must be float32 [B, 16] on {dev}, not {hidden0.dtype} {list(hidden0.shape)} on "
+                             f"{hidden0.device}")
+        named = self._named_params() + [("memory Linear weight", self.memory[0]), ("memory Linear bias", self.memory[1])]
+        for name, p in named:
+            if p is not None and (p.dtype != torch.float32 or p.device != dev):
+                raise ValueError(f"{name} must be float32 on {dev} (obs's device), not {p.dtype} on {p.device}")
+        present = [i for i, (_, p) in enumerate(named) if p is not None]
+        out = _EvaluateSequences.apply(self, obs.detach().contiguous(), action.detach().reshape(L, B).contiguous(),
+                                       length.detach().contiguous(), hidden0.detach().contiguous(), bool(return_hidden),
+                                       present, *[named[i][1] for i in present])
+        return out if return_hidden else out[:3]
+
+
 _workspaces = {}   # (device, bytes) -> uint8 buffer: evaluate()'s scratch
 
 
-def _eval_call(net, obs, hidden, action, params, fn):
-    """The workspace and the device / stream arguments for one of the two
-    handle-free calls; fn(c_net, workspace pointer, bytes, device index, stream)."""
+def _eval_call(net, obs, hidden, action, params, fn, seq=False):
+    """The workspace and the device / stream arguments for one of the
+    handle-free calls; fn(c_net, workspace pointer, bytes, device index, stream).
+    seq: obs is evaluate_sequences' [L, B, 69]."""
     dev = obs.device
     c = net._c_net(params)
     need = ctypes.c_uint64()
-    _check(_lib.mbots_policy_grad_workspace(ctypes.byref(c), obs.shape[0], ctypes.byref(need)))
+    if seq:
+        _check(_lib.mbots_policy_seq_workspace(ctypes.byref(c), obs.shape[0], obs.shape[1], ctypes.byref(need)))
+    else:
+        _check(_lib.mbots_policy_grad_workspace(ctypes.byref(c), obs.shape[0], ctypes.byref(need)))
     key = (dev, need.value)
     ws = _workspaces.get(key)
     if ws is None:
@@ -1434,6 +1491,49 @@ class _Evaluate(torch.autograd.Function):
             ctypes.byref(c), _ptr(obs), _ptr(hidden), _ptr(action), n, _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
             ctypes.byref(out), ws, nb, d, st))
         return (None, None, None, None, None) + tuple(grads[i] for i in present)
+
+
+class _EvaluateSequences(torch.autograd.Function):
+    """PolicyNet.evaluate_sequences: mbots_policy_seq_eval forward,
+    mbots_policy_seq_grad backward."""
+
+    @staticmethod
+    def forward(ctx, net, obs, action, length, hidden0, want_hidden, present, *params):
+        full = [None] * (2 * (len(net.trunk) + 5))
+        for i, p in zip(present, params):
+            full[i] = p.detach().contiguous()
+        L, B = obs.shape[0], obs.shape[1]
+        logp, value, entropy = (torch.empty(L, B, dtype=torch.float32, device=obs.device) for _ in range(3))
+        hidden = torch.empty(L, B, 16, dtype=torch.float32, device=obs.device) if want_hidden else None
+        _eval_call(net, obs, None, None, full, lambda c, ws, nb, d, st: _lib.mbots_policy_seq_eval(
+            ctypes.byref(c), _ptr(obs), _ptr(action), _ptr(length), _ptr(hidden0), L, B, _ptr(logp), _ptr(value),
+            _ptr(entropy), _ptr(hidden), ws, nb, d, st), seq=True)
+        ctx.net, ctx.rows, ctx.present, ctx.full = net, (obs, action, length, hidden0), present, full
+        ctx.set_materialize_grads(False)
+        if hidden is None:
+            hidden = torch.empty(0, dtype=torch.float32, device=obs.device)
+        ctx.mark_non_differentiable(hidden)
+        return logp, value, entropy, hidden
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logp, g_value, g_entropy, _g_hidden):
+        net, (obs, action, length, hidden0), present, full = ctx.net, ctx.rows, ctx.present, ctx.full
+        L, B = obs.shape[0], obs.shape[1]
+        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_logp, g_value, g_entropy)]
+        grads = [None] * len(full)
+        for k, i in enumerate(present):
+            if ctx.needs_input_grad[7 + k]:
+                grads[i] = torch.empty_like(full[i])
+        out = _PolicyGrads()
+        slots = [out.trunk[i] for i in range(len(net.trunk))] + [out.actor[0], out.actor[1], out.critic[0], out.critic[1],
+                                                                 out.memory]
+        for i, slot in enumerate(slots):
+            slot.weight, slot.bias = _ptr(grads[2 * i]).value, _ptr(grads[2 * i + 1]).value
+        _eval_call(net, obs, None, None, full, lambda c, ws, nb, d, st: _lib.mbots_policy_seq_grad(
+            ctypes.byref(c), _ptr(obs), _ptr(action), _ptr(length), _ptr(hidden0), L, B, _ptr(g[0]), _ptr(g[1]),
+            _ptr(g[2]), ctypes.byref(out), ws, nb, d, st), seq=True)
+        return (None,) * 7 + tuple(grads[i] for i in present)
 
 
 def policy_activation(act, x):

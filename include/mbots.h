@@ -731,7 +731,33 @@ int mbots_render_palette(uint8_t rgb[36]);
  * mbots_policy_activation(act, x, y, n, device, stream): learner side, no
  * manager: y[i] = the actor's own activation `act` of x[i] (codes 0..5; 6 the
  * actor's exp, 7 its log), device >= 0: device memory of that GPU on `stream`,
- * device == -1: host memory.  Both give the same bits. */
+ * device == -1: host memory.  Both give the same bits.
+ *
+ * Policy groups (DESIGN.md "Policy groups"): contiguous ranges of global world
+ * indices, each with four nets of its own, all acting in the one launch of
+ * mbots_policy_act.  mbots_policy_groups(h, starts, n): 1..MBOTS_POLICY_MAX_GROUPS
+ * ascending global world indices with starts[0] == 0; group g owns the worlds
+ * [starts[g], starts[g + 1]), the last group every world from its start on
+ * (n == 0 or NULL: back to the one group a manager starts with).  The indices
+ * are global: a shard's worlds (world_offset) and its ghost world fall into
+ * groups by their global index, and a group without a world in this manager
+ * is legal.  New starts wait for the device, remove every net and are refused
+ * under capture; the starts in place again change nothing.  Groups and nets
+ * are not part of a checkpoint; growths, resets and loads leave them alone.
+ * mbots_policy_num_groups(h, n, starts_out): *n the groups, starts_out (may
+ * be NULL) their *n starts.  mbots_policy_set_group / mbots_policy_clear_group
+ * are mbots_policy_set / mbots_policy_clear for one group's species (nets of
+ * different groups may differ in every part of the architecture);
+ * mbots_policy_set and mbots_policy_clear apply to every group.  A row's result
+ * is bit for bit what a one-group manager holding the net of the row's (group,
+ * species) computes for it -- the draw's key has no group in it -- and
+ * mbots_policy_act asks for a net of every (group, species) whose range holds
+ * one of the manager's worlds, the ghost included.  mbots_policy_segments(h,
+ * out, stream): out (device memory; host memory in CPU mode) receives
+ * [groups][4][2] int32, the rows [lo, hi) of every (group, species) among the
+ * exported rows of the current table -- one contiguous range each, lo == hi
+ * where there is none --, stream-ordered, no host wait, capturable. */
+#define MBOTS_POLICY_MAX_GROUPS 64
 #define MBOTS_POLICY_MEMORY_IN  1u
 #define MBOTS_ACT_GREEDY    1u
 #define MBOTS_ACT_NO_WRITE  2u
@@ -755,6 +781,12 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
                      uint64_t out_rows, void *stream);
 int mbots_policy_draw(mbots_handle *h, int32_t set, uint32_t *value);
 int mbots_policy_activation(int32_t act, const float *x, float *y, uint64_t n, int32_t device, void *stream);
+int mbots_policy_groups(mbots_handle *h, const uint32_t *starts, uint32_t n);      /* n == 0 / NULL: back to one group */
+int mbots_policy_num_groups(mbots_handle *h, uint32_t *n, uint32_t *starts_out /* may be NULL */);
+int mbots_policy_set_group(mbots_handle *h, uint32_t group, uint32_t species, const struct mbots_policy_net *net,
+                           void *stream);
+int mbots_policy_clear_group(mbots_handle *h, uint32_t group, uint32_t species);
+int mbots_policy_segments(mbots_handle *h, int32_t *out /* [groups][4][2] */, void *stream);
 
 /* Learning from what the actor did: a net evaluated on recorded (obs, action)
  * rows, and the gradients of its parameters (DESIGN.md "Differentiable

@@ -926,7 +926,20 @@ inline void policy_layer_host(const PolLayer &L, int act, const float *in, float
 }
 }  // namespace
 
-void Sim::policy_act(const PolNets &nets, uint32_t flags, uint32_t draw, int32_t *action_out, float *logp_out,
+void Sim::policy_segments(const PolGroups &groups, int32_t *out) const
+{
+    uint32_t end = 0;
+    for (uint32_t s = 0; s < (uint32_t)kNumSpecies; ++s) {
+        end += totals_[1 + s];
+        for (uint32_t g = 0; g < groups.G; ++g) {
+            int32_t *o = out + 2u * (4u * g + s);
+            o[0] = (int32_t)pol_group_edge(row_base_.data(), Wx_, groups.first[g], s, end);
+            o[1] = (int32_t)pol_group_edge(row_base_.data(), Wx_, groups.first[g + 1u], s, end);
+        }
+    }
+}
+
+void Sim::policy_act(const PolGroups &groups, uint32_t flags, uint32_t draw, int32_t *action_out, float *logp_out,
                      float *value_out, uint64_t out_rows)
 {
     Table &t = T_[tb_];
@@ -935,8 +948,11 @@ void Sim::policy_act(const PolNets &nets, uint32_t flags, uint32_t draw, int32_t
     const bool write = !(flags & kActNoWrite), greedy = (flags & kActGreedy) != 0;
     for_worlds([&](uint32_t w) {
         float a[kPolMaxH + 4], b[kPolMaxH + 4], hid[kPolMaxH], z[16], v[1], mem[kHidden];
+        uint32_t g = groups.ghost;   // the world's group: the ghost's, or the one whose local range holds w
+        if (w < Wx_)
+            for (g = 0; groups.first[g + 1u] <= w; ++g) {}
         for (int s = 0; s < kNumSpecies; ++s) {
-            const PolNet &net = nets.net[s];
+            const PolNet &net = groups.table[4u * g + (uint32_t)s];
             const int32_t base = row_base_[(size_t)w * kNumSpecies + s], cnt = scount_[(size_t)w * kNumSpecies + s];
             for (int32_t k = 0; k < cnt; ++k) {
                 const size_t r = (size_t)(base + k);

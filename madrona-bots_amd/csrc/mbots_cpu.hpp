@@ -99,12 +99,14 @@ public:
     // split over the host threads
     void render(const uint32_t *worlds, uint32_t k, uint32_t scale, const RenderOut &out) const;
     // device actor (mbots_policy.hpp), the HIP kernel as loops over the host
-    // threads: every table row (the shard ghost's included) through its
-    // species' net -- layers held as [nt * 16][kp] rows --, sampled with the
-    // draw counter's value `draw`; writes Action / HiddenState unless
-    // kActNoWrite, and rows [0, out_rows) of the non-null outputs
-    void policy_act(const PolNets &nets, uint32_t flags, uint32_t draw, int32_t *action_out, float *logp_out,
+    // threads: every table row (the shard ghost's included) through the net
+    // of its (group, species) -- layers held as [nt * 16][kp] rows --, sampled
+    // with the draw counter's value `draw`; writes Action / HiddenState unless
+    // kActNoWrite, and rows [0, out_rows) of the non-null outputs.
+    // policy_segments: out [G][4][2], the exported rows of every (group, species)
+    void policy_act(const PolGroups &groups, uint32_t flags, uint32_t draw, int32_t *action_out, float *logp_out,
                     float *value_out, uint64_t out_rows);
+    void policy_segments(const PolGroups &groups, int32_t *out) const;
     const mbots_config &config() const { return cfg_; }
 
 private:

@@ -159,12 +159,16 @@ struct mbots_handle {
         const void **h_tabs = nullptr;   // ([horizon]), its pinned staging and the event after the
         hipEvent_t ev_tabs = nullptr;    // last upload
     } traj;
-    // the device actor (include/mbots.h "Acting on the device"): per species one
-    // allocation of its own holding the uploaded layers (fragment order in HIP
-    // mode, padded rows in CPU mode), so growths leave it alone
+    // the device actor (include/mbots.h "Acting on the device"): per (group,
+    // species) one allocation of its own holding the uploaded layers (fragment
+    // order in HIP mode, padded rows in CPU mode), so growths leave it alone
     struct Policy {
-        mbots::PolNets nets{};
-        float *mem[mbots::kNumSpecies] = {};
+        std::vector<uint32_t> starts = std::vector<uint32_t>(1, 0u);   // the groups' first global worlds
+        std::vector<mbots::PolNet> nets = std::vector<mbots::PolNet>(mbots::kNumSpecies);   // [G][4]
+        std::vector<float *> mem = std::vector<float *>(mbots::kNumSpecies, nullptr);      // [G][4]
+        mbots::PolNet *table = nullptr;   // HIP mode, once there were groups: the device's copy of
+                                          // `nets`, [MBOTS_POLICY_MAX_GROUPS][4] (a captured act reads it in place)
+        uint32_t groups() const { return (uint32_t)starts.size(); }
         uint32_t *draw = nullptr;     // the device's draw counter (HIP mode)
         uint32_t draw_host = 0;       // CPU mode's
     } pol;
@@ -981,6 +985,7 @@ int mbots_destroy(mbots_handle *h)
     (void)hipSetDevice(h->device);
     (void)hipDeviceSynchronize();
     for (float *p : h->pol.mem) if (p) (void)hipFree(p);
+    if (h->pol.table) (void)hipFree(h->pol.table);
     if (h->pol.draw) (void)hipFree(h->pol.draw);
     if (h->traj.mem) (void)hipFree(h->traj.mem);
     if (h->traj.h_count) (void)hipHostFree(h->traj.h_count);
@@ -2921,14 +2926,37 @@ static bool policy_same_arch(mbots::PolNet &a, mbots::PolNet &b)
     return true;
 }
 
-int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_policy_net *net, void *stream)
+// the groups as the kernels and the CPU loops take them (mbots_policy.hpp)
+static mbots::PolGroups policy_groups_view(const mbots_handle *h)
+{
+    mbots::PolGroups g{};
+    const std::vector<uint32_t> &st = h->pol.starts;
+    const uint32_t G = h->pol.groups(), off = h->cfg.world_offset, Wx = h->cfg.num_worlds;
+    g.table = h->cpu ? h->pol.nets.data() : h->pol.table;
+    g.G = G;
+    for (uint32_t i = 0; i < G; ++i) g.first[i] = st[i] <= off ? 0u : std::min(st[i] - off, Wx);
+    g.first[G] = Wx;
+    g.ghost = mbots::pol_group_of(st.data(), G, off + Wx);
+    return g;
+}
+
+// does group g own one of the manager's worlds (the shard ghost's included)?
+static bool policy_group_needed(const mbots_handle *h, uint32_t g)
+{
+    const std::vector<uint32_t> &st = h->pol.starts;
+    const uint64_t lo = h->cfg.world_offset;
+    const uint64_t hi = lo + h->cfg.num_worlds + ((h->cfg.flags & MBOTS_FLAG_SHARD_GHOST) ? 1u : 0u);
+    return st[g] < hi && (g + 1u == st.size() || st[g + 1u] > lo);
+}
+
+static int policy_set_one(mbots_handle *h, uint32_t group, uint32_t species, const struct mbots_policy_net *net,
+                          void *stream)
 {
     using namespace mbots;
-    if (!h || !net) return fail(MBOTS_E_INVALID, "null argument");
-    if (species < 1 || species > (uint32_t)kNumSpecies) return fail(MBOTS_E_INVALID, "species must be 1..4");
     PolNet n;
     if (int rc = policy_describe(net, n)) return rc;
-    PolNet &cur = h->pol.nets.net[species - 1];
+    const size_t slot = (size_t)group * kNumSpecies + (species - 1);
+    PolNet &cur = h->pol.nets[slot];
     hipStream_t st = nullptr;
     if (!h->cpu) {
         HIP_TRY(hipSetDevice(h->device));
@@ -2944,7 +2972,7 @@ int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_polic
         if (h->cpu) {
             mem = static_cast<float *>(std::malloc(floats * sizeof(float)));
             if (!mem) return fail(MBOTS_E_NOMEM, "policy net allocation failed");
-            std::free(h->pol.mem[species - 1]);
+            std::free(h->pol.mem[slot]);
         } else {
             if (capturing(h, st))
                 return fail(MBOTS_E_INVALID, "a policy net of a new architecture allocates: set it before the capture "
@@ -2958,9 +2986,9 @@ int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_polic
                 (void)hipGetLastError();
                 return fail(MBOTS_E_NOMEM, "policy net allocation failed");
             }
-            if (h->pol.mem[species - 1]) (void)hipFree(h->pol.mem[species - 1]);
+            if (h->pol.mem[slot]) (void)hipFree(h->pol.mem[slot]);
         }
-        h->pol.mem[species - 1] = mem;
+        h->pol.mem[slot] = mem;
         for (PolLayer *l : L) {
             l->w = mem;
             mem += (pol_w_floats(*l) + 63u) & ~size_t(63);
@@ -2968,6 +2996,9 @@ int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_polic
             mem += (pol_b_floats(*l) + 63u) & ~size_t(63);
         }
         cur = n;
+        // (the device has drained: the table's entry changes only here and in a
+        // clear, never under a capture; a re-upload leaves it as it is)
+        if (h->pol.table) HIP_TRY(hipMemcpy(h->pol.table + slot, &cur, sizeof(PolNet), hipMemcpyHostToDevice));
     }
     // the weights into the storage in place
     std::vector<PolLayer *> D = policy_layers(cur);
@@ -2992,20 +3023,135 @@ int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_polic
     return MBOTS_OK;
 }
 
+static int policy_clear_one(mbots_handle *h, uint32_t group, uint32_t species)
+{
+    const size_t slot = (size_t)group * mbots::kNumSpecies + (species - 1);
+    if (!h->pol.mem[slot]) return MBOTS_OK;   // no net there: nothing to wait for, nothing to write
+    if (h->cpu) {
+        std::free(h->pol.mem[slot]);
+    } else {
+        HIP_TRY(hipSetDevice(h->device));
+        if (capturing_now(h)) return fail(MBOTS_E_INVALID, "a policy net cannot be cleared during a graph capture");
+        HIP_TRY(hipDeviceSynchronize());
+        (void)hipFree(h->pol.mem[slot]);
+    }
+    h->pol.mem[slot] = nullptr;
+    h->pol.nets[slot] = mbots::PolNet{};
+    if (h->pol.table)
+        HIP_TRY(hipMemcpy(h->pol.table + slot, &h->pol.nets[slot], sizeof(mbots::PolNet), hipMemcpyHostToDevice));
+    return MBOTS_OK;
+}
+
+static int policy_check_group(mbots_handle *h, uint32_t group, uint32_t species)
+{
+    if (species < 1 || species > (uint32_t)mbots::kNumSpecies) return fail(MBOTS_E_INVALID, "species must be 1..4");
+    if (group >= h->pol.groups())
+        return fail(MBOTS_E_INVALID, "policy group " + std::to_string(group) + " out of range: the manager has " +
+                                         std::to_string(h->pol.groups()) + " (mbots_policy_groups)");
+    return MBOTS_OK;
+}
+
+int mbots_policy_set(mbots_handle *h, uint32_t species, const struct mbots_policy_net *net, void *stream)
+{
+    if (!h || !net) return fail(MBOTS_E_INVALID, "null argument");
+    if (species < 1 || species > (uint32_t)mbots::kNumSpecies) return fail(MBOTS_E_INVALID, "species must be 1..4");
+    for (uint32_t g = 0; g < h->pol.groups(); ++g)
+        if (int rc = policy_set_one(h, g, species, net, stream)) return rc;
+    return MBOTS_OK;
+}
+
+int mbots_policy_set_group(mbots_handle *h, uint32_t group, uint32_t species, const struct mbots_policy_net *net,
+                           void *stream)
+{
+    if (!h || !net) return fail(MBOTS_E_INVALID, "null argument");
+    if (int rc = policy_check_group(h, group, species)) return rc;
+    return policy_set_one(h, group, species, net, stream);
+}
+
 int mbots_policy_clear(mbots_handle *h, uint32_t species)
 {
     if (!h) return fail(MBOTS_E_INVALID, "null handle");
     if (species < 1 || species > (uint32_t)mbots::kNumSpecies) return fail(MBOTS_E_INVALID, "species must be 1..4");
-    if (h->cpu) {
-        std::free(h->pol.mem[species - 1]);
-    } else if (h->pol.mem[species - 1]) {
-        HIP_TRY(hipSetDevice(h->device));
-        if (capturing_now(h)) return fail(MBOTS_E_INVALID, "a policy net cannot be cleared during a graph capture");
-        HIP_TRY(hipDeviceSynchronize());
-        (void)hipFree(h->pol.mem[species - 1]);
+    for (uint32_t g = 0; g < h->pol.groups(); ++g)
+        if (int rc = policy_clear_one(h, g, species)) return rc;
+    return MBOTS_OK;
+}
+
+int mbots_policy_clear_group(mbots_handle *h, uint32_t group, uint32_t species)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    if (int rc = policy_check_group(h, group, species)) return rc;
+    return policy_clear_one(h, group, species);
+}
+
+int mbots_policy_groups(mbots_handle *h, const uint32_t *starts, uint32_t n)
+{
+    if (!h) return fail(MBOTS_E_INVALID, "null handle");
+    static const uint32_t kOne[1] = {0u};
+    if (!starts || n == 0) {
+        starts = kOne;
+        n = 1;
     }
-    h->pol.mem[species - 1] = nullptr;
-    h->pol.nets.net[species - 1] = mbots::PolNet{};
+    if (n > (uint32_t)MBOTS_POLICY_MAX_GROUPS)
+        return fail(MBOTS_E_INVALID, std::to_string(n) + " policy groups: at most " +
+                                         std::to_string(MBOTS_POLICY_MAX_GROUPS) + " (MBOTS_POLICY_MAX_GROUPS)");
+    if (starts[0] != 0u)
+        return fail(MBOTS_E_INVALID, "policy group starts begin at world 0, not " + std::to_string(starts[0]));
+    for (uint32_t i = 1; i < n; ++i)
+        if (starts[i] <= starts[i - 1])
+            return fail(MBOTS_E_INVALID, "policy group starts must be ascending: starts[" + std::to_string(i) + "] = " +
+                                             std::to_string(starts[i]) + " after " + std::to_string(starts[i - 1]));
+    if (std::vector<uint32_t>(starts, starts + n) == h->pol.starts) return MBOTS_OK;
+    if (!h->cpu) {
+        HIP_TRY(hipSetDevice(h->device));
+        if (capturing_now(h))
+            return fail(MBOTS_E_INVALID, "policy groups cannot be changed during a graph capture");
+        HIP_TRY(hipDeviceSynchronize());   // a queued act may still read the nets and the table in place
+        if (n > 1 && !h->pol.table) {
+            const size_t bytes = (size_t)MBOTS_POLICY_MAX_GROUPS * mbots::kNumSpecies * sizeof(mbots::PolNet);
+            if (hipMalloc((void **)&h->pol.table, bytes) != hipSuccess) {
+                (void)hipGetLastError();
+                h->pol.table = nullptr;
+                return fail(MBOTS_E_NOMEM, "policy net table allocation failed");
+            }
+        }
+        if (h->pol.table)
+            HIP_TRY(hipMemset(h->pol.table, 0,
+                              (size_t)MBOTS_POLICY_MAX_GROUPS * mbots::kNumSpecies * sizeof(mbots::PolNet)));
+    }
+    // every net goes with the old groups
+    for (float *&p : h->pol.mem) {
+        if (h->cpu) std::free(p);
+        else if (p) (void)hipFree(p);
+        p = nullptr;
+    }
+    h->pol.starts.assign(starts, starts + n);
+    h->pol.nets.assign((size_t)n * mbots::kNumSpecies, mbots::PolNet{});
+    h->pol.mem.assign((size_t)n * mbots::kNumSpecies, nullptr);
+    return MBOTS_OK;
+}
+
+int mbots_policy_num_groups(mbots_handle *h, uint32_t *n, uint32_t *starts_out)
+{
+    if (!h || !n) return fail(MBOTS_E_INVALID, "null argument");
+    *n = h->pol.groups();
+    if (starts_out) std::copy(h->pol.starts.begin(), h->pol.starts.end(), starts_out);
+    return MBOTS_OK;
+}
+
+int mbots_policy_segments(mbots_handle *h, int32_t *out, void *stream)
+{
+    if (!h || !out) return fail(MBOTS_E_INVALID, "null argument");
+    const mbots::PolGroups G = policy_groups_view(h);
+    if (h->cpu) {
+        h->cpu->policy_segments(G, out);
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = as_stream(stream);
+    Exec ex{h, st};
+    if (int rc = h->sched.enter(ex)) return rc;
+    HIP_TRY(mbots::launch_policy_segments(h->S, G, out, st));
     return MBOTS_OK;
 }
 
@@ -3014,12 +3160,26 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
 {
     if (!h) return fail(MBOTS_E_INVALID, "null handle");
     if (flags & ~(MBOTS_ACT_GREEDY | MBOTS_ACT_NO_WRITE)) return fail(MBOTS_E_INVALID, "unknown act flags");
-    for (int s = 0; s < mbots::kNumSpecies; ++s)
-        if (!h->pol.nets.net[s].set)
-            return fail(MBOTS_E_INVALID, "species " + std::to_string(s + 1) + " has no policy net (mbots_policy_set)");
+    // the nets of every (group, species) that owns one of the manager's worlds,
+    // and what they do with HiddenState
+    const uint32_t nG = h->pol.groups();
+    bool writes_hidden = false, reads_hidden = false, all_hidden = true;
+    for (uint32_t g = 0; g < nG; ++g) {
+        if (!policy_group_needed(h, g)) continue;
+        for (int s = 0; s < mbots::kNumSpecies; ++s) {
+            const mbots::PolNet &n = h->pol.nets[(size_t)g * mbots::kNumSpecies + s];
+            if (!n.set)
+                return fail(MBOTS_E_INVALID, (nG > 1 ? "group " + std::to_string(g) + " species " : std::string("species ")) +
+                                                 std::to_string(s + 1) + " has no policy net (mbots_policy_set)");
+            writes_hidden |= n.has_memory != 0;
+            all_hidden &= n.has_memory != 0;
+            reads_hidden |= (n.flags & mbots::kPolMemoryIn) != 0u;
+        }
+    }
     if (out_rows > 0xFFFFFFFFull) out_rows = 0xFFFFFFFFull;
+    const mbots::PolGroups G = policy_groups_view(h);
     if (h->cpu) {
-        h->cpu->policy_act(h->pol.nets, flags, h->pol.draw_host, action_out, logp_out, value_out, out_rows);
+        h->cpu->policy_act(G, flags, h->pol.draw_host, action_out, logp_out, value_out, out_rows);
         h->pol.draw_host += 1u;
         return MBOTS_OK;
     }
@@ -3034,12 +3194,6 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
     // its readers find it (the step's deferred move done; a column a fused shift
     // left aliased is read in its Prev storage, not copied)
     if ((rc = h->sched.wait_sensor(ex))) return rc;
-    bool writes_hidden = false, reads_hidden = false, all_hidden = true;
-    for (int s = 0; s < mbots::kNumSpecies; ++s) {
-        writes_hidden |= h->pol.nets.net[s].has_memory != 0;
-        all_hidden &= h->pol.nets.net[s].has_memory != 0;
-        reads_hidden |= (h->pol.nets.net[s].flags & mbots::kPolMemoryIn) != 0u;
-    }
     // (a lazy HiddenState column a net reads, or keeps rows of: real rows first;
     // memoryless nets leave it lazy)
     if ((rc = h->defer.require(ex, defer::kAction | (reads_hidden || writes_hidden ? defer::kHidden : 0),
@@ -3047,7 +3201,7 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
         return rc;
     const bool write = !(flags & MBOTS_ACT_NO_WRITE);
     // a net without a memory head leaves its rows' HiddenState as it is: if the
-    // column is written at all (another species' head) while still aliased, the
+    // column is written at all (another net's head) while still aliased, the
     // rows it keeps are copied out first, as mbots_write_actions does for a part
     if (write && writes_hidden && !all_hidden && (rc = h->defer.require(ex, defer::kHidden, defer::How::WritePart)))
         return rc;
@@ -3055,9 +3209,13 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
     // (the columns the nets write whole are simply written)
     if (write && (rc = h->defer.require(ex, defer::kAction | (writes_hidden ? defer::kHidden : 0), defer::How::WriteAll)))
         return rc;
+    // one group: its four nets by value, as ever; more: the table in device memory
+    mbots::PolNets four{};
+    if (nG == 1)
+        for (int s = 0; s < mbots::kNumSpecies; ++s) four.net[s] = h->pol.nets[s];
     rc = timed(h, MBOTS_TK_ACTIONS, st, [&] {
-        return mbots::launch_policy_act(h->S, h->T[tb], hidden_in, h->pol.nets, flags, h->pol.draw, action_out,
-                                        logp_out, value_out, (uint32_t)out_rows,
+        return mbots::launch_policy_act(h->S, h->T[tb], hidden_in, four, nG > 1 ? &G : nullptr, flags, h->pol.draw,
+                                        action_out, logp_out, value_out, (uint32_t)out_rows,
                                         (uint32_t)((uint64_t)h->S.W * h->S.cap), st);
     });
     if (rc) return rc;

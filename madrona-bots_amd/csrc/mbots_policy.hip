@@ -137,9 +137,45 @@ struct PolActArgs {
     uint32_t out_rows, W, Wx, world_offset, seed, greedy;
 };
 
-__global__ __launch_bounds__(256, 2) void policy_act_kernel(PolActArgs A, PolNets P)
+// A net's scalars and layers as the tile body reads them.  The four nets of a
+// one-group launch are kernel arguments and read where they lie (scalar
+// loads); an entry of the groups' table lies in device memory, whose loads the
+// compiler cannot prove uniform, so each value goes through an SGPR.
+template <bool kTable> __device__ __forceinline__ uint32_t pol_u(uint32_t v)
 {
-    extern __shared__ float s_pol[];
+    if constexpr (kTable) return uniform(v);
+    else return v;
+}
+__device__ __forceinline__ float *pol_uniform_ptr(float *p)
+{
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint64_t lo = uniform((uint32_t)v), hi = uniform((uint32_t)(v >> 32));
+    return reinterpret_cast<float *>((hi << 32) | lo);
+}
+template <bool kTable> __device__ __forceinline__ decltype(auto) pol_pick(const PolLayer &l)
+{
+    if constexpr (kTable) {
+        PolLayer u;
+        u.w = pol_uniform_ptr(l.w);
+        u.b = pol_uniform_ptr(l.b);
+        u.in = uniform(l.in);
+        u.out = uniform(l.out);
+        u.kp = uniform(l.kp);
+        u.nt = uniform(l.nt);
+        u.act = uniform(l.act);
+        return u;
+    } else {
+        return (l);   // the kernel argument itself, by reference
+    }
+}
+
+// One tile of policy_act: rows [r0, r0 + nr) of species sp + 1 (one (group,
+// species) segment, `ghost`: the shard ghost's) through `net`, sampled and
+// written.  kTable: `net` is an entry of the groups' table.
+template <bool kTable>
+__device__ __forceinline__ void pol_act_tile(const PolActArgs &A, const PolNet &net, bool ghost, uint32_t sp,
+                                             uint32_t r0, uint32_t nr, uint32_t draw, float *s_pol)
+{
     float *buf0 = s_pol, *buf1 = s_pol + kPolRows * kPolStride;
     float *s_logit = buf1 + kPolRows * kPolStride;
     float *s_val = s_logit + kPolRows * kPolLogitStride;
@@ -147,6 +183,153 @@ __global__ __launch_bounds__(256, 2) void policy_act_kernel(PolActArgs A, PolNet
     uint32_t *s_win = reinterpret_cast<uint32_t *>(s_mem + kPolRows * kPolMemStride);
     uint32_t *s_w = s_win + kPolRows, *s_k = s_w + kPolRows;
     const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    const bool mem_in = (pol_u<kTable>(net.flags) & kPolMemoryIn) != 0u;
+    const uint32_t n_trunk = pol_u<kTable>(net.n_trunk);
+    const bool has_memory = pol_u<kTable>(net.has_memory) != 0u;
+
+    // ---- stage the tile's inputs, coalesced, as the f32 tile X[64][Kp] ----
+    {
+        const uint32_t row = (t & 127u) >> 1, half = t & 1u;
+        float *x = buf0 + row * kPolStride + (t < 128u ? 0u : 35u) + half * 16u;
+        if (row < nr) {
+            const uint4 g = t < 128u ? reinterpret_cast<const uint4 *>(A.depth + (size_t)r0 * kSensor)[t]
+                                     : reinterpret_cast<const uint4 *>(A.sem + (size_t)r0 * kSensor)[t - 128u];
+            const uint32_t wds[4] = {g.x, g.y, g.z, g.w};
+#pragma unroll
+            for (int i = 0; i < 16; ++i) {
+                const uint32_t b = (wds[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+                x[i] = t < 128u ? (float)b : (float)(int8_t)b;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 16; ++i) x[i] = 0.0f;
+        }
+    }
+    if (t < (uint32_t)kPolRows) {
+        float *x = buf0 + t * kPolStride;
+        int32_t hp = 0;
+        float2 ps = make_float2(0.0f, 0.0f), su = ps;
+        if (t < nr) {
+            hp = A.health[r0 + t];
+            ps = reinterpret_cast<const float2 *>(A.pos)[r0 + t];
+            su = reinterpret_cast<const float2 *>(A.sur)[r0 + t];
+        }
+        x[32] = __int_as_float(hp);
+        x[33] = ps.x;
+        x[34] = ps.y;
+        x[67] = su.x;
+        x[68] = su.y;
+        if (!mem_in) x[69] = x[70] = x[71] = 0.0f;
+        else x[85] = x[86] = x[87] = 0.0f;
+    }
+    if (mem_in) {
+        const uint32_t row = t >> 2, g = t & 3u;
+        float4 h = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+        if (row < nr) h = reinterpret_cast<const float4 *>(A.hidden_in + (size_t)r0 * kHidden)[t];
+        float *x = buf0 + row * kPolStride + kPolObs + 4u * g;
+        x[0] = h.x;
+        x[1] = h.y;
+        x[2] = h.z;
+        x[3] = h.w;
+    }
+    // ---- wave 3: each row's world and its index k inside the (world, species)
+    // segment, for the epilogue's RNG key.  The first row's world by a 64-ary
+    // search of row_base (three rounds at 65536 worlds), then the next 64
+    // worlds' bases as a window in LDS that the rows bisect ----
+    if (wv == 3u) {
+        const uint32_t r = r0 + lane;
+        uint32_t w = A.Wx, k = 0;
+        if (ghost) {
+            k = r - (uint32_t)A.row_base[4u * A.Wx + sp];
+        } else {
+            uint32_t lo = 0, n = A.Wx;   // the world lies in [lo, lo + n), row_base[lo] <= r0
+            while (n > 1u) {
+                const uint32_t step = (n + 63u) >> 6, end = lo + n, p = lo + (lane + 1u) * step;
+                const bool ok = p < end && (uint32_t)A.row_base[4u * p + sp] <= r0;
+                lo += (uint32_t)__popcll(ballot64(ok)) * step;
+                n = min(step, end - lo);
+            }
+            const uint32_t w0 = lo, pw = w0 + 1u + lane;
+            s_win[lane] = pw < A.Wx ? (uint32_t)A.row_base[4u * pw + sp] : 0xFFFFFFFFu;
+            wave_sync();
+            if (lane < nr) {
+                uint32_t c = 0;   // window entries <= r: the row's world is w0 + c
+                for (uint32_t s = 32u; s; s >>= 1)
+                    if (s_win[c + s - 1u] <= r) c += s;
+                if (c == 63u && s_win[63] <= r) c = 64u;
+                w = w0 + c;
+                if (c == 64u) {   // past the window (a long run of worlds without the species)
+                    uint32_t hi = A.Wx;
+                    while (hi - w > 1u) {
+                        const uint32_t mid = (w + hi) >> 1;
+                        if ((uint32_t)A.row_base[4u * mid + sp] <= r) w = mid;
+                        else hi = mid;
+                    }
+                }
+                k = r - (uint32_t)A.row_base[4u * w + sp];
+            }
+        }
+        s_w[lane] = w;
+        s_k[lane] = k;
+    }
+    __syncthreads();
+
+    // ---- trunk: ping-pong between the two tiles ----
+    float *cur = buf0, *oth = buf1;
+    for (uint32_t l = 0; l < n_trunk; ++l) {
+        pol_layer(pol_pick<kTable>(net.trunk[l]), (int)pol_u<kTable>(net.trunk[l].act), cur, oth, kPolStride, wv, 0u,
+                  lane);
+        __syncthreads();
+        float *sw = cur;
+        cur = oth;
+        oth = sw;
+    }
+    // ---- heads, all reading the trunk's last tile `cur` ----
+    pol_layer(pol_pick<kTable>(net.actor[0]), kActRelu, cur, oth, kPolStride, wv, 0u, lane);
+    __syncthreads();
+    pol_layer(pol_pick<kTable>(net.actor[1]), kActIdentity, oth, s_logit, kPolLogitStride, wv, 0u, lane);
+    if (has_memory) pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_mem, kPolMemStride, wv, 1u, lane);
+    __syncthreads();
+    pol_layer(pol_pick<kTable>(net.critic[0]), kActRelu, cur, oth, kPolStride, wv, 0u, lane);
+    __syncthreads();
+    pol_layer(pol_pick<kTable>(net.critic[1]), kActIdentity, oth, s_val, 1u, wv, 0u, lane);
+    __syncthreads();
+
+    // ---- epilogue: sample, log-probability, the table's writes ----
+    if (t < nr) {
+        const uint32_t r = r0 + t;
+        const uint32_t w = s_w[t], k = s_k[t];
+        float z[kPolActions];
+#pragma unroll
+        for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
+        const float u = pol_uniform(A.seed, draw, A.world_offset + w, sp + 1u, k);
+        float logp;
+        const int32_t a = pol_sample(z, u, A.greedy != 0u, &logp);
+        if (A.action) {
+            int2 *o = reinterpret_cast<int2 *>(A.action + (size_t)r * 6u);
+            o[0] = make_int2(a == 0, a == 1);
+            o[1] = make_int2(a == 2, a == 3);
+            o[2] = make_int2(a == 4, a == 5);
+        }
+        if (r < A.out_rows) {
+            if (A.action_out) A.action_out[r] = a;
+            if (A.logp_out) A.logp_out[r] = logp;
+            if (A.value_out) A.value_out[r] = s_val[t];
+        }
+    }
+    if (has_memory && A.hidden_out) {
+        const uint32_t row = t >> 2, g = t & 3u;
+        if (row < nr) {
+            const float *m = s_mem + row * kPolMemStride + 4u * g;
+            reinterpret_cast<float4 *>(A.hidden_out + (size_t)r0 * kHidden)[t] = make_float4(m[0], m[1], m[2], m[3]);
+        }
+    }
+    __syncthreads();
+}
+
+__global__ __launch_bounds__(256, 2) void policy_act_kernel(PolActArgs A, PolNets P)
+{
+    extern __shared__ float s_pol[];
 
     // the table's eight species segments: the exported rows of species 1..4,
     // then the shard ghost's (after row N); a tile never straddles two
@@ -178,147 +361,105 @@ __global__ __launch_bounds__(256, 2) void policy_act_kernel(PolActArgs A, PolNet
         const uint32_t sp = seg & 3u;   // species - 1
         const uint32_t r0 = seg_start[seg] + rest * kPolRows;
         const uint32_t nr = min((uint32_t)kPolRows, seg_len[seg] - rest * kPolRows);
-        const PolNet &net = P.net[sp];
-        const bool mem_in = (net.flags & kPolMemoryIn) != 0u;
+        pol_act_tile<false>(A, P.net[sp], seg >= 4u, sp, r0, nr, draw, s_pol);
+    }
+}
 
-        // ---- stage the tile's inputs, coalesced, as the f32 tile X[64][Kp] ----
-        {
-            const uint32_t row = (t & 127u) >> 1, half = t & 1u;
-            float *x = buf0 + row * kPolStride + (t < 128u ? 0u : 35u) + half * 16u;
-            if (row < nr) {
-                const uint4 g = t < 128u ? reinterpret_cast<const uint4 *>(A.depth + (size_t)r0 * kSensor)[t]
-                                         : reinterpret_cast<const uint4 *>(A.sem + (size_t)r0 * kSensor)[t - 128u];
-                const uint32_t wds[4] = {g.x, g.y, g.z, g.w};
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const uint32_t b = (wds[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-                    x[i] = t < 128u ? (float)b : (float)(int8_t)b;
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < 16; ++i) x[i] = 0.0f;
-            }
-        }
-        if (t < (uint32_t)kPolRows) {
-            float *x = buf0 + t * kPolStride;
-            int32_t hp = 0;
-            float2 ps = make_float2(0.0f, 0.0f), su = ps;
-            if (t < nr) {
-                hp = A.health[r0 + t];
-                ps = reinterpret_cast<const float2 *>(A.pos)[r0 + t];
-                su = reinterpret_cast<const float2 *>(A.sur)[r0 + t];
-            }
-            x[32] = __int_as_float(hp);
-            x[33] = ps.x;
-            x[34] = ps.y;
-            x[67] = su.x;
-            x[68] = su.y;
-            if (!mem_in) x[69] = x[70] = x[71] = 0.0f;
-            else x[85] = x[86] = x[87] = 0.0f;
-        }
-        if (mem_in) {
-            const uint32_t row = t >> 2, g = t & 3u;
-            float4 h = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (row < nr) h = reinterpret_cast<const float4 *>(A.hidden_in + (size_t)r0 * kHidden)[t];
-            float *x = buf0 + row * kPolStride + kPolObs + 4u * g;
-            x[0] = h.x;
-            x[1] = h.y;
-            x[2] = h.z;
-            x[3] = h.w;
-        }
-        // ---- wave 3: each row's world and its index k inside the (world, species)
-        // segment, for the epilogue's RNG key.  The first row's world by a 64-ary
-        // search of row_base (three rounds at 65536 worlds), then the next 64
-        // worlds' bases as a window in LDS that the rows bisect ----
-        if (wv == 3u) {
-            const uint32_t r = r0 + lane;
-            uint32_t w = A.Wx, k = 0;
-            if (seg >= 4u) {
-                k = r - (uint32_t)A.row_base[4u * A.Wx + sp];
-            } else {
-                uint32_t lo = 0, n = A.Wx;   // the world lies in [lo, lo + n), row_base[lo] <= r0
-                while (n > 1u) {
-                    const uint32_t step = (n + 63u) >> 6, end = lo + n, p = lo + (lane + 1u) * step;
-                    const bool ok = p < end && (uint32_t)A.row_base[4u * p + sp] <= r0;
-                    lo += (uint32_t)__popcll(ballot64(ok)) * step;
-                    n = min(step, end - lo);
-                }
-                const uint32_t w0 = lo, pw = w0 + 1u + lane;
-                s_win[lane] = pw < A.Wx ? (uint32_t)A.row_base[4u * pw + sp] : 0xFFFFFFFFu;
-                wave_sync();
-                if (lane < nr) {
-                    uint32_t c = 0;   // window entries <= r: the row's world is w0 + c
-                    for (uint32_t s = 32u; s; s >>= 1)
-                        if (s_win[c + s - 1u] <= r) c += s;
-                    if (c == 63u && s_win[63] <= r) c = 64u;
-                    w = w0 + c;
-                    if (c == 64u) {   // past the window (a long run of worlds without the species)
-                        uint32_t hi = A.Wx;
-                        while (hi - w > 1u) {
-                            const uint32_t mid = (w + hi) >> 1;
-                            if ((uint32_t)A.row_base[4u * mid + sp] <= r) w = mid;
-                            else hi = mid;
-                        }
-                    }
-                    k = r - (uint32_t)A.row_base[4u * w + sp];
-                }
-            }
-            s_w[lane] = w;
-            s_k[lane] = k;
-        }
-        __syncthreads();
+// ---- policy groups (mbots_policy.hpp; DESIGN.md "Policy groups") ----
+// The segments of a grouped table in row order: entry s * G + g the exported
+// rows of (group g, species s + 1), then the shard ghost's four.  Each block
+// builds the table in its prologue -- first row, length, and the inclusive scan
+// of the tile counts, which every tile then bisects -- behind the tile's LDS.
+// (A copy of the tile's net descriptor in LDS, so that a layer starts from LDS
+// and not from a load of the table, measured no faster: 6.14 against 6.09 ms
+// with 32 groups at 65536 worlds.)
+constexpr uint32_t kPolMaxSegs = 4u * kPolMaxGroups + 4u;
+constexpr size_t kPolGroupLds = kPolLds + (3u * kPolMaxSegs + 4u) * sizeof(uint32_t);
+static_assert(kPolGroupLds <= 80u * 1024u, "two blocks of policy_act_groups_kernel share a compute unit's LDS");
+static_assert(kPolMaxSegs <= 2u * 256u, "two segment entries per thread");
 
-        // ---- trunk: ping-pong between the two tiles ----
-        float *cur = buf0, *oth = buf1;
-        for (uint32_t l = 0; l < net.n_trunk; ++l) {
-            pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            float *sw = cur;
-            cur = oth;
-            oth = sw;
+__global__ __launch_bounds__(256, 2) void policy_act_groups_kernel(PolActArgs A, PolGroups G)
+{
+    extern __shared__ float s_pol[];
+    uint32_t *s_start = reinterpret_cast<uint32_t *>(s_pol) + kPolLds / sizeof(uint32_t);
+    uint32_t *s_len = s_start + kPolMaxSegs, *s_scan = s_len + kPolMaxSegs, *s_wsum = s_scan + kPolMaxSegs;
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    const uint32_t nG = G.G, nseg = 4u * nG + 4u;
+    {
+        uint32_t sp_end[4], run = 0;
+        for (int s = 0; s < 4; ++s) {
+            run += uniform(A.totals[1 + s]);
+            sp_end[s] = run;
         }
-        // ---- heads, all reading the trunk's last tile `cur` ----
-        pol_layer(net.actor[0], kActRelu, cur, oth, kPolStride, wv, 0u, lane);
-        __syncthreads();
-        pol_layer(net.actor[1], kActIdentity, oth, s_logit, kPolLogitStride, wv, 0u, lane);
-        if (net.has_memory) pol_layer(net.memory, kActTanh, cur, s_mem, kPolMemStride, wv, 1u, lane);
-        __syncthreads();
-        pol_layer(net.critic[0], kActRelu, cur, oth, kPolStride, wv, 0u, lane);
-        __syncthreads();
-        pol_layer(net.critic[1], kActIdentity, oth, s_val, 1u, wv, 0u, lane);
-        __syncthreads();
-
-        // ---- epilogue: sample, log-probability, the table's writes ----
-        if (t < nr) {
-            const uint32_t r = r0 + t;
-            const uint32_t w = s_w[t], k = s_k[t];
-            float z[kPolActions];
-#pragma unroll
-            for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
-            const float u = pol_uniform(A.seed, draw, A.world_offset + w, sp + 1u, k);
-            float logp;
-            const int32_t a = pol_sample(z, u, A.greedy != 0u, &logp);
-            if (A.action) {
-                int2 *o = reinterpret_cast<int2 *>(A.action + (size_t)r * 6u);
-                o[0] = make_int2(a == 0, a == 1);
-                o[1] = make_int2(a == 2, a == 3);
-                o[2] = make_int2(a == 4, a == 5);
+        uint32_t c[2];
+        for (uint32_t i = 0; i < 2u; ++i) {
+            const uint32_t e = 2u * t + i;
+            uint32_t start = 0, len = 0;
+            if (e < 4u * nG) {
+                const uint32_t s = e / nG, g = e - s * nG;
+                const uint32_t end = s == 0u ? sp_end[0] : s == 1u ? sp_end[1] : s == 2u ? sp_end[2] : sp_end[3];
+                start = pol_group_edge(A.row_base, A.Wx, G.first[g], s, end);
+                len = pol_group_edge(A.row_base, A.Wx, G.first[g + 1u], s, end) - start;
+            } else if (e < nseg && A.W > A.Wx) {
+                const uint32_t s = e - 4u * nG;
+                start = A.totals[0];
+                for (uint32_t q = 0; q < s; ++q) start += (uint32_t)A.scount[4u * A.Wx + q];
+                len = (uint32_t)A.scount[4u * A.Wx + s];
             }
-            if (r < A.out_rows) {
-                if (A.action_out) A.action_out[r] = a;
-                if (A.logp_out) A.logp_out[r] = logp;
-                if (A.value_out) A.value_out[r] = s_val[t];
+            if (e < kPolMaxSegs) {
+                s_start[e] = start;
+                s_len[e] = len;
             }
+            c[i] = (len + kPolRows - 1u) / kPolRows;
         }
-        if (net.has_memory && A.hidden_out) {
-            const uint32_t row = t >> 2, g = t & 3u;
-            if (row < nr) {
-                const float *m = s_mem + row * kPolMemStride + 4u * g;
-                reinterpret_cast<float4 *>(A.hidden_out + (size_t)r0 * kHidden)[t] = make_float4(m[0], m[1], m[2], m[3]);
-            }
+        // the block-wide inclusive scan of the tile counts: pairs, waves, the four wave sums
+        uint32_t incl = c[0] + c[1];
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
         }
+        if (lane == 63u) s_wsum[wv] = incl;
+        __syncthreads();
+        for (uint32_t q = 0; q < wv; ++q) incl += s_wsum[q];
+        if (2u * t < kPolMaxSegs) s_scan[2u * t] = incl - c[1];
+        if (2u * t + 1u < kPolMaxSegs) s_scan[2u * t + 1u] = incl;
         __syncthreads();
     }
+    const uint32_t tiles = uniform(s_scan[nseg - 1u]);
+    const uint32_t draw = uniform(*A.draw);
+
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        // the first entry whose scan exceeds the tile (entries without rows are passed over)
+        uint32_t lo = 0, hi = nseg - 1u;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s_scan[mid] > tile) hi = mid;
+            else lo = mid + 1u;
+        }
+        const uint32_t e = uniform(lo);
+        const uint32_t rest = tile - (e ? uniform(s_scan[e - 1u]) : 0u);
+        const bool ghost = e >= 4u * nG;
+        const uint32_t sp = ghost ? e - 4u * nG : e / nG;   // species - 1
+        const uint32_t g = ghost ? G.ghost : e - sp * nG;
+        const uint32_t len = uniform(s_len[e]);
+        const uint32_t r0 = uniform(s_start[e]) + rest * kPolRows;
+        const uint32_t nr = min((uint32_t)kPolRows, len - rest * kPolRows);
+        pol_act_tile<true>(A, G.table[4u * g + sp], ghost, sp, r0, nr, draw, s_pol);
+    }
+}
+
+// [lo, hi) of every (group, species) among the exported rows of the current table
+static_assert(4u * kPolMaxGroups <= 256u, "policy_segments_kernel: one thread per (group, species) in its one block");
+__global__ __launch_bounds__(256) void policy_segments_kernel(const uint32_t *totals, const int32_t *row_base,
+                                                              uint32_t Wx, PolGroups G, int32_t *out)
+{
+    const uint32_t e = threadIdx.x;
+    if (e >= 4u * G.G) return;
+    const uint32_t g = e >> 2, s = e & 3u;
+    uint32_t end = 0;
+    for (uint32_t q = 0; q <= s; ++q) end += totals[1u + q];
+    out[2u * e] = (int32_t)pol_group_edge(row_base, Wx, G.first[g], s, end);
+    out[2u * e + 1u] = (int32_t)pol_group_edge(row_base, Wx, G.first[g + 1u], s, end);
 }
 
 __global__ void policy_draw_next_kernel(uint32_t *draw) { *draw += 1u; }
@@ -925,15 +1066,18 @@ hipError_t launch_policy_seq_grad(const PolSeqIO &io, const PolNet &net, const P
 }
 
 hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *hidden_in, const PolNets &nets,
-                             uint32_t flags, const uint32_t *draw, int32_t *action_out, float *logp_out,
-                             float *value_out, uint32_t out_rows, uint32_t max_rows, hipStream_t st)
+                             const PolGroups *groups, uint32_t flags, const uint32_t *draw, int32_t *action_out,
+                             float *logp_out, float *value_out, uint32_t out_rows, uint32_t max_rows, hipStream_t st)
 {
-    static bool lds_set = false;
-    if (!lds_set) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolLds);
+    static bool lds_set[2] = {false, false};
+    if (!lds_set[groups ? 1 : 0]) {
+        const hipError_t e =
+            groups ? hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_groups_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolGroupLds)
+                   : hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolLds);
         if (e != hipSuccess) return e;
-        lds_set = true;
+        lds_set[groups ? 1 : 0] = true;
     }
     PolActArgs A{};
     A.totals = S.totals;
@@ -960,9 +1104,17 @@ hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *
     A.greedy = (flags & kActGreedy) ? 1u : 0u;
     // persistent: two blocks per compute unit at most (the LDS tile), never more
     // blocks than the table can hold tiles (8 segments, each with a ragged one)
-    const uint64_t tiles = (uint64_t)max_rows / kPolRows + 8u;
+    // (with groups: 4 G + 4 segments)
+    const uint64_t tiles = (uint64_t)max_rows / kPolRows + (groups ? 4u * groups->G + 4u : 8u);
     const unsigned blocks = (unsigned)std::min<uint64_t>(tiles, 512u);
-    hipLaunchKernelGGL(policy_act_kernel, dim3(blocks), dim3(256), kPolLds, st, A, nets);
+    if (groups) hipLaunchKernelGGL(policy_act_groups_kernel, dim3(blocks), dim3(256), kPolGroupLds, st, A, *groups);
+    else hipLaunchKernelGGL(policy_act_kernel, dim3(blocks), dim3(256), kPolLds, st, A, nets);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_segments(const SimState &S, const PolGroups &groups, int32_t *out, hipStream_t st)
+{
+    hipLaunchKernelGGL(policy_segments_kernel, dim3(1), dim3(256), 0, st, S.totals, S.row_base, S.Wx, groups, out);
     return hipGetLastError();
 }
 

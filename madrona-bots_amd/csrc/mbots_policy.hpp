@@ -242,6 +242,34 @@ struct PolNet {
 struct PolNets {
     PolNet net[kNumSpecies];
 };
+// ---- policy groups (DESIGN.md "Device actor", "Policy groups"): contiguous
+// ranges of global worlds, each with its own four nets ----
+constexpr uint32_t kPolMaxGroups = 64;   // MBOTS_POLICY_MAX_GROUPS
+// The groups as one manager sees them: the net table [G][4] (device memory in
+// HIP mode; an entry with set == 0 has no net), each group's first local world
+// clamped into [0, Wx] (first[G] = Wx, so group g owns the local worlds
+// [first[g], first[g + 1])), and the group of the shard ghost's global world.
+struct PolGroups {
+    const PolNet *table;
+    uint32_t G, ghost;
+    uint32_t first[kPolMaxGroups + 1];
+};
+// the group of global world gw: the last g with starts[g] <= gw (starts[0] == 0)
+MB_HD uint32_t pol_group_of(const uint32_t *starts, uint32_t G, uint32_t gw)
+{
+    uint32_t g = 0;
+    while (g + 1u < G && starts[g + 1u] <= gw) ++g;
+    return g;
+}
+// The table row at which local world lw's rows of species s (0..3) begin among
+// the exported rows: row_base's entry, or past the last exported world the
+// species' end.  Rows are ordered (species, world, slot), so [edge(first[g]),
+// edge(first[g + 1])) is the one segment of (group g, species s).
+MB_HD uint32_t pol_group_edge(const int32_t *row_base, uint32_t Wx, uint32_t lw, uint32_t s, uint32_t species_end)
+{
+    return lw < Wx ? (uint32_t)row_base[4u * lw + s] : species_end;
+}
+
 MB_HD size_t pol_w_floats(const PolLayer &l) { return (size_t)l.kp * l.nt * 16u; }
 MB_HD size_t pol_b_floats(const PolLayer &l) { return (size_t)l.nt * 16u; }
 

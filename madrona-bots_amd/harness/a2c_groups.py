@@ -1,0 +1,115 @@
+"""G independent A2C learners on one manager -- policy groups (INTEGRATION.md
+"Policy groups") as runnable code, beside a2c.py, whose pieces it builds on:
+
+    set_policy_groups(starts); per group u: set_policy(nets_u, group=u)
+    act() -> window.push(value) -> step() ... -> window.compute() ->
+    per group and species: PolicyNet.evaluate(obs[lo:hi], action[lo:hi]) ->
+    the group's loss -> backward() -> the group's optimizers -> set_policy(group=u)
+
+Every universe -- a contiguous range of worlds with four nets of its own, of
+its own width -- rolls out in the one act() launch of the manager; the flat
+[N, ...] tensors of a table are sliced per (group, species) by one
+policy_segments().tolist(); each group has a loss, a backward() and optimizers
+of its own, over its own rows and parameters.  With reward_fixed managers no
+group's update depends on another group's nets; the reference's faithful
+reward pays species 4 of a group's last world from the next group's first
+world (INTEGRATION.md "Policy groups", "Where groups meet").
+
+    python madrona-bots_amd/harness/a2c_groups.py --worlds 64 --groups 4 --iters 5 --exec-mode cpu
+    python madrona-bots_amd/harness/a2c_groups.py --worlds 65536 --groups 32 --iters 20
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from a2c import make_modules  # noqa: E402
+
+
+def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0,
+          value_coef=0.5, entropy_coef=0.01, log=None):
+    """`iters` updates of `horizon - 1` steps each of every group.  modules[u],
+    optimizers[u]: a2c.make_modules' four ModuleDicts and their optimizers for
+    group u.  Returns the losses, [iters][groups] floats."""
+    import madrona_bots as mb
+    G = len(starts)
+    sim.set_policy_groups(starts)
+    nets = [[mb.PolicyNet.from_torch(m["feature"], m["actor"], m["critic"]) for m in modules[u]] for u in range(G)]
+    for u in range(G):
+        sim.set_policy(nets[u], group=u)
+    win = sim.trajectory_window(horizon, max_rows=sim.num_worlds * sim.agent_capacity)
+    seg = torch.empty((G, 4, 2), dtype=torch.int32, device=sim.device)
+    losses = []
+    try:
+        for it in range(iters):
+            rows = []                                   # per table: (obs, action, [G][4] (lo, hi))
+            for t in range(horizon):
+                last = t == horizon - 1                 # the last table only bootstraps
+                obs = None if last else sim.construct_obs().clone()
+                o = sim.act(write=not last)
+                win.push(o["value"])
+                if not last:
+                    rows.append((obs, o["action"], sim.policy_segments(out=seg).tolist()))
+                    sim.step()
+            out = win.compute(gamma=gamma, lam=lam, death_reward=death_reward)
+            loss = [torch.zeros((), device=sim.device) for _ in range(G)]
+            total = [sum(hi - lo for _, _, sg in rows for lo, hi in sg[u]) for u in range(G)]
+            for t, (obs, action, sg) in enumerate(rows):
+                keep = (out["end"][t].reshape(-1) != win.END_RESET).to(torch.float32)
+                for u in range(G):
+                    for net, (lo, hi) in zip(nets[u], sg[u]):
+                        if hi == lo:
+                            continue
+                        logp, value, entropy = net.evaluate(obs[lo:hi], action[lo:hi])
+                        adv, ret = out["adv"][t][lo:hi, 0], out["ret"][t][lo:hi, 0]
+                        per_row = -adv * logp + value_coef * (value - ret) ** 2 - entropy_coef * entropy
+                        loss[u] = loss[u] + (per_row * keep[lo:hi]).sum() / total[u]
+            for u in range(G):
+                if not total[u]:
+                    continue
+                for opt in optimizers[u]:
+                    opt.zero_grad(set_to_none=True)
+                loss[u].backward()
+                for opt in optimizers[u]:
+                    opt.step()
+                sim.set_policy(nets[u], group=u)        # same architecture: re-uploads, stream-ordered
+            win.clear()
+            losses.append([float(x.detach()) for x in loss])
+            if log:
+                log(json.dumps({"iter": it, "loss": losses[-1], "rows": total}))
+    finally:
+        win.close()
+    return losses
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--worlds", type=int, default=64)
+    ap.add_argument("--groups", type=int, default=4)
+    ap.add_argument("--agents", type=int, default=32)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--horizon", type=int, default=8)
+    ap.add_argument("--hidden", type=int, nargs="+", default=[128, 64],
+                    help="trunk widths, cycled over the groups (universes differ in architecture)")
+    ap.add_argument("--lr", type=float, default=3e-4)
+    ap.add_argument("--seed", type=int, default=69)
+    ap.add_argument("--exec-mode", choices=("hip", "cpu"), default="hip" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--reward-fixed", action="store_true", help="rewards[speciesID - 1]: universes fully apart")
+    args = ap.parse_args()
+    if not 1 <= args.groups <= 64 or args.worlds < args.groups:
+        ap.error("--groups must be in [1, 64] and at most --worlds")
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+    import madrona_bots as mb
+    sim = mb.SimManager(0, args.worlds, args.seed, args.agents, exec_mode=args.exec_mode,
+                        reward_fixed=args.reward_fixed)
+    starts = [u * args.worlds // args.groups for u in range(args.groups)]
+    modules = [make_modules(args.hidden[u % len(args.hidden)], sim.device, args.seed + u) for u in range(args.groups)]
+    optimizers = [[torch.optim.Adam(m.parameters(), lr=args.lr) for m in four] for four in modules]
+    train(sim, starts, modules, optimizers, args.iters, args.horizon, log=print)
+
+
+if __name__ == "__main__":
+    main()

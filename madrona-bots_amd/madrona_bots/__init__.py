@@ -148,6 +148,11 @@ def _load():
         "mbots_render_palette": [P(ctypes.c_uint8)],
         "mbots_policy_set": [vp, u32, P(_PolicyNet), vp],
         "mbots_policy_clear": [vp, u32],
+        "mbots_policy_groups": [vp, P(u32), u32],
+        "mbots_policy_num_groups": [vp, P(u32), P(u32)],
+        "mbots_policy_set_group": [vp, u32, u32, P(_PolicyNet), vp],
+        "mbots_policy_clear_group": [vp, u32, u32],
+        "mbots_policy_segments": [vp, vp, vp],
         "mbots_policy_act": [vp, u32, vp, vp, vp, ctypes.c_uint64, vp],
         "mbots_policy_draw": [vp, i32, P(u32)],
         "mbots_policy_activation": [i32, vp, vp, ctypes.c_uint64, i32, vp],
@@ -542,7 +547,7 @@ class SimManager:
         self._ktiming = False
         self._gen = 0                # bumped when the columns' storage moves (a growth)
         self._traj = None            # the open TrajectoryWindow, if any
-        self._policy = [None] * 4    # the PolicyNet set per species (set_policy)
+        self._policy = [[None] * 4]  # the PolicyNet set per (group, species) (set_policy)
         self._episode_length = int(episode_length)
         if not 0 <= self._episode_length < 2 ** 32:
             raise ValueError("episode_length must be in [0, 2^32)")
@@ -620,12 +625,19 @@ class SimManager:
             raise
         if self._ktiming:
             self.enable_kernel_timing(True)
-        if any(n is not None for n in self._policy):   # the nets and the draw counter follow the hand-over
+        # the groups, the nets and the draw counter follow the hand-over
+        if len(self._policy) > 1 or any(n is not None for n in self._policy[0]):
             draw = ctypes.c_uint32()
             _check(_lib.mbots_policy_draw(old[1], 0, ctypes.byref(draw)))
-            for sp, n in enumerate(self._policy):
-                if n is not None:
-                    self._set_policy_one(sp + 1, n)
+            nets, self._policy = self._policy, [[None] * 4]
+            starts = (ctypes.c_uint32 * 64)()
+            n = ctypes.c_uint32()
+            _check(_lib.mbots_policy_num_groups(old[1], ctypes.byref(n), starts))
+            self.set_policy_groups(list(starts[:n.value]))
+            for g, four in enumerate(nets):
+                for sp, net in enumerate(four):
+                    if net is not None:
+                        self._set_policy_one(sp + 1, net, g)
             _check(_lib.mbots_policy_draw(self._h, 1, ctypes.byref(draw)))
         del old                      # (freed now unless a view still holds it)
 
@@ -911,7 +923,50 @@ class SimManager:
                                         self._stream()))
 
     # -- acting on the device -------------------------------------------------
-    def _set_policy_one(self, species, net):
+    @property
+    def policy_groups(self):
+        """The policy groups' starts (set_policy_groups); [0]: one group."""
+        n = ctypes.c_uint32()
+        starts = (ctypes.c_uint32 * 64)()
+        _check(_lib.mbots_policy_num_groups(self._h, ctypes.byref(n), starts))
+        return list(starts[:n.value])
+
+    def set_policy_groups(self, starts=None):
+        """Policy groups: `starts`, 1..64 ascending global world indices with
+        starts[0] == 0; group g owns the worlds [starts[g], starts[g + 1]) (the
+        last every world from its start on) and acts through four nets of its
+        own (set_policy(..., group=g)), all in the one launch of act().  The
+        indices are global, so the shards of one run take the same starts.  New
+        starts wait for the device and remove every net; the starts in place
+        change nothing; None or []: back to one group (mbots_policy_groups)."""
+        starts = [int(v) for v in starts] if starts is not None and len(starts) else [0]
+        if any(not 0 <= v < 2 ** 32 for v in starts):
+            raise ValueError("policy group starts are world indices in [0, 2^32)")
+        if starts == self.policy_groups:
+            return
+        if self.exec_mode == ExecMode.HIP and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("madrona_bots: policy groups cannot be changed during a graph capture")
+        arr = (ctypes.c_uint32 * max(len(starts), 1))(*starts)
+        _check(_lib.mbots_policy_groups(self._h, arr, len(starts)))
+        self._policy = [[None] * 4 for _ in starts]
+
+    def policy_segments(self, out=None):
+        """int32 [G, 4, 2] on `device`: the rows [lo, hi) of every (group,
+        species) among the N exported rows of the current table -- rows are
+        ordered (species, world, slot), so each is one contiguous range, lo ==
+        hi where a group has no such row.  Stream-ordered, no host wait,
+        capturable (mbots_policy_segments); one .tolist() gives a learner the
+        slices of every flat [N, ...] tensor."""
+        G = len(self._policy)
+        if out is None:
+            out = torch.empty((G, 4, 2), dtype=torch.int32, device=self.device)
+        if out.dtype != torch.int32 or out.device != self.device or not out.is_contiguous() \
+                or tuple(out.shape) != (G, 4, 2):
+            raise ValueError(f"out must be a contiguous int32 [{G}, 4, 2] tensor on {self.device}")
+        _check(_lib.mbots_policy_segments(self._h, ctypes.c_void_p(out.data_ptr()), self._stream()))
+        return out
+
+    def _set_policy_one(self, species, net, group=None):
         dev = self.device
 
         def layer(spec):
@@ -934,15 +989,27 @@ class SimManager:
         c.flags = 1 if net.memory_in else 0
         # (the upload reads the tensors in stream order on torch's current
         # stream, where the caching allocator also orders their release)
-        _check(_lib.mbots_policy_set(self._h, int(species), ctypes.byref(c), self._stream()))
-        self._policy[species - 1] = net
+        if group is None:
+            _check(_lib.mbots_policy_set(self._h, int(species), ctypes.byref(c), self._stream()))
+        else:
+            _check(_lib.mbots_policy_set_group(self._h, int(group), int(species), ctypes.byref(c), self._stream()))
+        for g in (range(len(self._policy)) if group is None else [int(group)]):
+            self._policy[g][species - 1] = net
 
-    def set_policy(self, net, species=None):
+    def _check_group(self, group):
+        if group is not None and not 0 <= int(group) < len(self._policy):
+            raise ValueError(f"policy group {group} out of range: the manager has {len(self._policy)} "
+                             "(set_policy_groups)")
+
+    def set_policy(self, net, species=None, group=None):
         """Give species 1..4 their policy nets (PolicyNet): one net for every
         species, a list of four, or one net for `species`.  The first call, or
         a net of another architecture, allocates; calling again with the same
         architecture -- after every optimiser step -- only re-uploads the
-        weights, stream-ordered on torch's current stream (mbots_policy_set)."""
+        weights, stream-ordered on torch's current stream (mbots_policy_set).
+        group: the policy group (set_policy_groups) the nets are for; None:
+        every group."""
+        self._check_group(group)
         if species is not None:
             if isinstance(net, (list, tuple)):
                 raise ValueError("one PolicyNet for one species")
@@ -959,17 +1026,22 @@ class SimManager:
             if not 1 <= sp <= 4:
                 raise ValueError("species must be 1..4")
         for sp, n in nets.items():
-            self._set_policy_one(sp, n)
+            self._set_policy_one(sp, n, group)
 
-    def clear_policy(self, species=None):
+    def clear_policy(self, species=None, group=None):
+        self._check_group(group)
         for sp in ([int(species)] if species is not None else [1, 2, 3, 4]):
-            _check(_lib.mbots_policy_clear(self._h, sp))
-            self._policy[sp - 1] = None
+            if group is None:
+                _check(_lib.mbots_policy_clear(self._h, sp))
+            else:
+                _check(_lib.mbots_policy_clear_group(self._h, int(group), sp))
+            for g in (range(len(self._policy)) if group is None else [int(group)]):
+                self._policy[g][sp - 1] = None
 
     def act(self, greedy=False, write=True, out=None):
         """One stream-ordered call for policy(construct_obs()) -> sample ->
-        write_actions(): every table row (the shard ghost's too) runs its
-        species' net, an action is sampled from the manager's counter RNG
+        write_actions(): every table row (the shard ghost's too) runs the net
+        of its species (with policy groups: of its world's group), an action is sampled from the manager's counter RNG
         (greedy: the first maximal logit), and -- unless write=False -- Action
         receives the one-hot and HiddenState the memory head's output.  Returns
         {"action": int32 [N, 1], "logp": float32 [N, 1], "value": float32

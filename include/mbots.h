@@ -837,6 +837,50 @@ int mbots_policy_grad(const struct mbots_policy_net *net, const float *obs, cons
                       const float *g_entropy, const struct mbots_policy_grads *out, void *workspace,
                       uint64_t workspace_bytes, int32_t device, void *stream);
 
+/* Every group's nets in one call: the learner's half of policy groups
+ * (DESIGN.md "Grouped evaluate" is the specification).  nets[groups][4] (1 <=
+ * groups <= MBOTS_POLICY_MAX_GROUPS) holds the net of every (group, species);
+ * an entry with n_trunk == 0 means the pair has no net.  segments
+ * [groups][4][2] int32 is what mbots_policy_segments wrote -- the rows [lo, hi)
+ * of every pair -- in the memory of the rows: on the device it is read by the
+ * kernels only, never by the host, so a call does not wait for it.  obs,
+ * hidden (needed iff any net has MBOTS_POLICY_MEMORY_IN), action and the
+ * outputs are mbots_policy_eval's, [n] rows each.
+ *
+ * mbots_policy_eval_groups: a row inside the segment of (g, s) receives, bit
+ * for bit, what mbots_policy_eval of nets[g][s] on the rows [lo, hi) alone
+ * gives it; a row in no segment, or in the segment of a pair without a net,
+ * receives +0.
+ *
+ * mbots_policy_grad_groups: out[groups][4]; every non-NULL pointer of out[g][s]
+ * receives, bit for bit, what mbots_policy_grad of nets[g][s] on the rows
+ * [lo, hi) and the g_* of those rows leaves there (the sums in that call's
+ * order, counted from lo; zeros for an empty segment).  Entries of pairs
+ * without a net are ignored; rows outside every segment take no part.
+ *
+ * Contract on segments: 0 <= lo <= hi <= n, pairwise disjoint.  The host path
+ * refuses a violation (MBOTS_E_INVALID, naming the pair); the device reads hi
+ * as min(hi, n) and lo as min(lo, hi), and disjointness is the caller's
+ * contract there.  Actions as mbots_policy_eval's.
+ *
+ * workspace: mbots_policy_groups_workspace(nets, groups, n, &bytes) bytes,
+ * 16-byte aligned, of the same memory kind as the rows; it grows with the
+ * nets' weights and with 8 x min(256, ceil(n / 64)) slabs of the largest net,
+ * not with 256 slabs per net.  The calls allocate nothing and never wait for
+ * the host: they can be captured into a graph, and a replay reads the
+ * segments then in place. */
+int mbots_policy_groups_workspace(const struct mbots_policy_net *nets /* [groups][4] */, uint32_t groups, uint64_t n,
+                                  uint64_t *bytes);
+int mbots_policy_eval_groups(const struct mbots_policy_net *nets, uint32_t groups, const int32_t *segments,
+                             const float *obs, const float *hidden, const int32_t *action, uint64_t n, float *logp,
+                             float *value, float *entropy, void *workspace, uint64_t workspace_bytes, int32_t device,
+                             void *stream);
+int mbots_policy_grad_groups(const struct mbots_policy_net *nets, uint32_t groups, const int32_t *segments,
+                             const float *obs, const float *hidden, const int32_t *action, uint64_t n,
+                             const float *g_logp, const float *g_value, const float *g_entropy,
+                             const struct mbots_policy_grads *out /* [groups][4] */, void *workspace,
+                             uint64_t workspace_bytes, int32_t device, void *stream);
+
 /* Training the memory head: the net run along padded sequences with the memory
  * head's output carried from step to step, and backpropagation through time
  * (DESIGN.md "Backpropagation through HiddenState" is the specification).  The

@@ -306,6 +306,19 @@ hipError_t launch_policy_eval(const PolEvalIO &io, const PolNet &net, hipStream_
 size_t policy_grad_stash_floats(uint32_t nacc);
 hipError_t launch_policy_grad(const PolEvalIO &io, const PolNet &net, const PolNet &back, const PolGradSlabs &slabs,
                               float *stash, const PolGradOut &out, hipStream_t st);
+// grouped evaluate (mbots_policy.hpp): the 4 G nets of `specs` (host memory; the
+// specs travel as kernel arguments) described into `table` and repacked into
+// `ws` by way of `uploads` (nseg * kPolGroupUploads entries), then one forward
+// launch over the segments' tiles; or the backward in `nwaves` waves, wave w
+// the segments waves[w] with a grid of (wave_acc, waves[w].n) blocks -- block
+// (a, c) on slab and stash c * wave_acc + a -- followed by its reduce into
+// grads[w].  `segments` [nseg][2] is read on the device only.
+hipError_t launch_policy_eval_groups(const PolEvalIO &io, const int32_t *segments, const PolGroupSpec *specs,
+                                     uint32_t nseg, float *ws, PolGroupEntry *table, PolUpload *uploads, hipStream_t st);
+hipError_t launch_policy_grad_groups(const PolEvalIO &io, const int32_t *segments, const PolGroupSpec *specs,
+                                     uint32_t nseg, const PolGroupWave *waves, const PolGroupGrads *grads,
+                                     uint32_t nwaves, float *ws, PolGroupEntry *table, PolUpload *uploads, float *slabs,
+                                     uint64_t slab_stride, float *stash, uint32_t wave_acc, hipStream_t st);
 // evaluate_sequences and its backward pass through time (mbots_policy.hpp): as
 // above with the memory head in `net`, its transpose in back.memory, and in
 // back.trunk[0] the H -> 16 layer over the first layer's HiddenState columns;

@@ -3471,6 +3471,203 @@ int mbots_policy_grad(const struct mbots_policy_net *net, const float *obs, cons
     return MBOTS_OK;
 }
 
+// ---- grouped evaluate (include/mbots.h "Every group's nets in one call") ----
+namespace {
+// where a grouped call's pieces lie in the caller's workspace (floats): the
+// descriptor table, the repack list, every net's packed weights, and one
+// wave's slabs and stash
+struct GroupsPlan {
+    std::vector<mbots::PolGroupSpec> spec;   // [4 groups]; n_trunk == 0: no net
+    std::vector<uint32_t> present;           // the segments that have one
+    bool memory_in = false;
+    size_t table_off = 0, upload_off = 0, slab_off = 0, stash_off = 0, floats = 0;
+    uint64_t slab_stride = 0;
+    uint32_t wave_acc = 0;                   // accumulators of a segment at most: min(256, tiles of n rows)
+};
+
+// "group g species s" of segment e, as mbots_policy_act names a pair
+const auto pair_name = [](uint32_t e) {
+    return "group " + std::to_string(e >> 2) + " species " + std::to_string((e & 3u) + 1u);
+};
+int fail_pair(int rc, uint32_t e) { return fail(rc, pair_name(e) + ": " + g_err); }
+
+int groups_plan(const mbots_policy_net *nets, uint32_t groups, uint64_t n, GroupsPlan &P)
+{
+    using namespace mbots;
+    if (!nets) return fail(MBOTS_E_INVALID, "null nets");
+    if (groups < 1 || groups > kPolMaxGroups)
+        return fail(MBOTS_E_INVALID, "1.." + std::to_string(kPolMaxGroups) + " groups, not " + std::to_string(groups));
+    if (n > 0x7FFFFFFFull) return fail(MBOTS_E_INVALID, "segments address rows as int32: at most 2^31 - 1 rows");
+    const uint32_t nseg = 4u * groups;
+    P.spec.assign(nseg, PolGroupSpec{});
+    size_t off = 0, cpu_floats = 0;
+    auto take = [&](size_t floats) {
+        const size_t at = off;
+        off += (floats + 63u) & ~size_t(63);
+        return at;
+    };
+    P.table_off = take((size_t)nseg * sizeof(PolGroupEntry) / sizeof(float));
+    P.upload_off = take((size_t)nseg * kPolGroupUploads * sizeof(PolUpload) / sizeof(float));
+    for (uint32_t e = 0; e < nseg; ++e) {
+        const mbots_policy_net &src = nets[e];
+        if (src.n_trunk == 0) continue;
+        PolNet d;
+        if (int rc = policy_describe(&src, d)) return fail_pair(rc, e);
+        PolGroupSpec &s = P.spec[e];
+        s.w_off = off;
+        s.n_trunk = d.n_trunk;
+        s.H = d.H;
+        s.flags = d.flags;
+        for (uint32_t l = 0; l < d.n_trunk; ++l) {
+            s.act |= d.trunk[l].act << (8u * l);
+            s.w[l] = src.trunk[l].weight, s.b[l] = src.trunk[l].bias;
+        }
+        for (int i = 0; i < 2; ++i) {
+            s.w[kPolMaxTrunk + i] = src.actor[i].weight, s.b[kPolMaxTrunk + i] = src.actor[i].bias;
+            s.w[kPolMaxTrunk + 2 + i] = src.critic[i].weight, s.b[kPolMaxTrunk + 2 + i] = src.critic[i].bias;
+        }
+        PolGroupEntry E;
+        off += pol_group_entry(s, nullptr, E, nullptr);
+        P.slab_stride = std::max<uint64_t>(P.slab_stride, E.slab_floats);
+        P.memory_in |= (d.flags & kPolMemoryIn) != 0u;
+        P.present.push_back(e);
+        // (the host path runs evaluate's own plan, one net at a time, in the same memory)
+        EvalPlan one;
+        if (int rc = eval_plan(&src, n, true, nullptr, one, kEvalRows)) return fail_pair(rc, e);
+        cpu_floats = std::max(cpu_floats, one.floats);
+    }
+    P.wave_acc = (uint32_t)std::min<uint64_t>((n + kPolGradRows - 1u) / kPolGradRows, kPolGradAcc);
+    const size_t wave_blocks = (size_t)kPolGroupWave * P.wave_acc;
+    P.slab_off = take(wave_blocks * P.slab_stride);
+    P.stash_off = take(policy_grad_stash_floats((uint32_t)wave_blocks));
+    P.floats = std::max(off, cpu_floats);
+    return MBOTS_OK;
+}
+
+int groups_check(const mbots_policy_net *nets, uint32_t groups, const int32_t *segments, const float *obs,
+                 const float *hidden, const int32_t *action, uint64_t n, void *ws, uint64_t ws_bytes, int32_t device,
+                 GroupsPlan &P)
+{
+    if (int rc = groups_plan(nets, groups, n, P)) return rc;
+    if (!segments) return fail(MBOTS_E_INVALID, "null segments");
+    if (n && (!obs || !action)) return fail(MBOTS_E_INVALID, "null obs or action");
+    if (n && P.memory_in && !hidden)
+        return fail(MBOTS_E_INVALID, "a net with MBOTS_POLICY_MEMORY_IN needs the rows' hidden floats");
+    if (!ws || ((uintptr_t)ws & 15u)) return fail(MBOTS_E_INVALID, "the workspace must be 16-byte aligned memory");
+    if (ws_bytes < P.floats * sizeof(float))
+        return fail(MBOTS_E_INVALID, "workspace of " + std::to_string(ws_bytes) + " bytes, " +
+                                         std::to_string(P.floats * sizeof(float)) +
+                                         " needed (mbots_policy_groups_workspace)");
+    if (device >= 0) return MBOTS_OK;
+    // the host path reads the segments: 0 <= lo <= hi <= n, pairwise disjoint
+    std::vector<std::pair<int64_t, uint32_t>> by_lo;
+    for (uint32_t e = 0; e < 4u * groups; ++e) {
+        const int64_t lo = segments[2u * e], hi = segments[2u * e + 1u];
+        if (lo < 0 || lo > hi || hi > (int64_t)n)
+            return fail(MBOTS_E_INVALID, "the segment [" + std::to_string(lo) + ", " + std::to_string(hi) + ") of " +
+                                             pair_name(e) + " is not inside the " + std::to_string(n) + " rows");
+        if (hi > lo) by_lo.emplace_back(lo, e);
+    }
+    std::sort(by_lo.begin(), by_lo.end());
+    for (size_t i = 1; i < by_lo.size(); ++i) {
+        const uint32_t a = by_lo[i - 1].second, b = by_lo[i].second;
+        if (segments[2u * a + 1u] > segments[2u * b])
+            return fail(MBOTS_E_INVALID, "the segments of " + pair_name(a) + " and " + pair_name(b) + " overlap");
+    }
+    return MBOTS_OK;
+}
+}  // namespace
+
+int mbots_policy_groups_workspace(const struct mbots_policy_net *nets, uint32_t groups, uint64_t n, uint64_t *bytes)
+{
+    if (!bytes) return fail(MBOTS_E_INVALID, "null argument");
+    GroupsPlan P;
+    if (int rc = groups_plan(nets, groups, n, P)) return rc;
+    *bytes = P.floats * sizeof(float);
+    return MBOTS_OK;
+}
+
+int mbots_policy_eval_groups(const struct mbots_policy_net *nets, uint32_t groups, const int32_t *segments,
+                             const float *obs, const float *hidden, const int32_t *action, uint64_t n, float *logp,
+                             float *value, float *entropy, void *workspace, uint64_t workspace_bytes, int32_t device,
+                             void *stream)
+{
+    using namespace mbots;
+    GroupsPlan P;
+    if (int rc = groups_check(nets, groups, segments, obs, hidden, action, n, workspace, workspace_bytes, device, P))
+        return rc;
+    if (device < 0) {
+        // rows of no segment, or of a pair without a net: +0
+        for (float *o : {logp, value, entropy})
+            if (o) std::fill(o, o + n, 0.0f);
+        for (uint32_t e : P.present) {
+            const uint64_t lo = (uint64_t)segments[2u * e], len = (uint64_t)segments[2u * e + 1u] - lo;
+            if (!len) continue;
+            if (int rc = mbots_policy_eval(&nets[e], obs + lo * kPolObs, hidden ? hidden + lo * kHidden : nullptr,
+                                           action + lo, len, logp ? logp + lo : nullptr, value ? value + lo : nullptr,
+                                           entropy ? entropy + lo : nullptr, workspace, workspace_bytes, -1, nullptr))
+                return fail_pair(rc, e);
+        }
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(device));
+    float *ws = static_cast<float *>(workspace);
+    const PolEvalIO io{obs, hidden, action, nullptr, nullptr, nullptr, logp, value, entropy, n};
+    HIP_TRY(launch_policy_eval_groups(io, segments, P.spec.data(), 4u * groups, ws,
+                                      reinterpret_cast<PolGroupEntry *>(ws + P.table_off),
+                                      reinterpret_cast<PolUpload *>(ws + P.upload_off), as_stream(stream)));
+    return MBOTS_OK;
+}
+
+int mbots_policy_grad_groups(const struct mbots_policy_net *nets, uint32_t groups, const int32_t *segments,
+                             const float *obs, const float *hidden, const int32_t *action, uint64_t n,
+                             const float *g_logp, const float *g_value, const float *g_entropy,
+                             const struct mbots_policy_grads *out, void *workspace, uint64_t workspace_bytes,
+                             int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (!out) return fail(MBOTS_E_INVALID, "null argument");
+    GroupsPlan P;
+    if (int rc = groups_check(nets, groups, segments, obs, hidden, action, n, workspace, workspace_bytes, device, P))
+        return rc;
+    if (device < 0) {
+        for (uint32_t e : P.present) {
+            const uint64_t lo = (uint64_t)segments[2u * e], len = (uint64_t)segments[2u * e + 1u] - lo;
+            if (int rc = mbots_policy_grad(&nets[e], obs + lo * kPolObs, hidden ? hidden + lo * kHidden : nullptr,
+                                           action + lo, len, g_logp ? g_logp + lo : nullptr,
+                                           g_value ? g_value + lo : nullptr, g_entropy ? g_entropy + lo : nullptr,
+                                           &out[e], workspace, workspace_bytes, -1, nullptr))
+                return fail_pair(rc, e);
+        }
+        return MBOTS_OK;
+    }
+    // the present segments in waves, each with the pointers its reduce writes
+    std::vector<PolGroupWave> waves((P.present.size() + kPolGroupWave - 1u) / kPolGroupWave);
+    std::vector<PolGroupGrads> grads(waves.size());
+    for (size_t i = 0; i < P.present.size(); ++i) {
+        const uint32_t e = P.present[i], c = (uint32_t)(i % kPolGroupWave);
+        PolGroupWave &W = waves[i / kPolGroupWave];
+        PolGroupGrads &O = grads[i / kPolGroupWave];
+        if (c == 0) W = PolGroupWave{}, O = PolGroupGrads{};
+        W.seg[c] = e;
+        W.n = c + 1u;
+        for (uint32_t l = 0; l < P.spec[e].n_trunk; ++l)
+            O.w[c][l] = out[e].trunk[l].weight, O.b[c][l] = out[e].trunk[l].bias;
+        for (int k = 0; k < 2; ++k) {
+            O.w[c][kPolMaxTrunk + k] = out[e].actor[k].weight, O.b[c][kPolMaxTrunk + k] = out[e].actor[k].bias;
+            O.w[c][kPolMaxTrunk + 2 + k] = out[e].critic[k].weight, O.b[c][kPolMaxTrunk + 2 + k] = out[e].critic[k].bias;
+        }
+    }
+    HIP_TRY(hipSetDevice(device));
+    float *ws = static_cast<float *>(workspace);
+    const PolEvalIO io{obs, hidden, action, g_logp, g_value, g_entropy, nullptr, nullptr, nullptr, n};
+    HIP_TRY(launch_policy_grad_groups(io, segments, P.spec.data(), 4u * groups, waves.data(), grads.data(),
+                                      (uint32_t)waves.size(), ws, reinterpret_cast<PolGroupEntry *>(ws + P.table_off),
+                                      reinterpret_cast<PolUpload *>(ws + P.upload_off), ws + P.slab_off, P.slab_stride,
+                                      ws + P.stash_off, P.wave_acc, as_stream(stream)));
+    return MBOTS_OK;
+}
+
 // ---- evaluate_sequences (include/mbots.h "Training the memory head") ----
 namespace {
 int seq_check(const mbots_policy_net *net, const float *obs, const int32_t *action, const int32_t *length,

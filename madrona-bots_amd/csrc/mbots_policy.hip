@@ -464,10 +464,9 @@ __global__ __launch_bounds__(256) void policy_segments_kernel(const uint32_t *to
 
 __global__ void policy_draw_next_kernel(uint32_t *draw) { *draw += 1u; }
 
-// weights into the fragment order / the padded bias, one block column per layer
-__global__ __launch_bounds__(256) void policy_repack_kernel(PolUploads U)
+// one layer's weights into the fragment order / the padded bias, over the blocks of a grid row
+__device__ __forceinline__ void pol_repack_layer(const PolUpload &L)
 {
-    const PolUpload &L = U.l[blockIdx.y];
     const uint32_t nw = L.kp * L.nt * 16u, nb = L.nt * 16u;
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nw + nb; i += gridDim.x * 256u) {
         if (i < nw) {
@@ -483,6 +482,9 @@ __global__ __launch_bounds__(256) void policy_repack_kernel(PolUploads U)
         }
     }
 }
+
+// one block column per layer
+__global__ __launch_bounds__(256) void policy_repack_kernel(PolUploads U) { pol_repack_layer(U.l[blockIdx.y]); }
 
 __global__ __launch_bounds__(256) void policy_activation_kernel(int act, const float *x, float *y, uint64_t n)
 {
@@ -586,21 +588,125 @@ struct PolGradDev {
     float *stash;         // [blocks][kPolStashTiles][kPolTile]
 };
 
-// kGrad false: logp, value and entropy of every row, grid-stride over the
-// tiles.  kGrad true: block b is accumulator b and takes the tiles b, b +
-// kPolGradAcc, ... in order: the forward again (outputs of the inner trunk
-// layers to the block's stash), d loss / d logits, then layer by layer from
-// the heads down the parameter gradients into the block's slab and the input
-// gradients in place of the layer outputs.
+// One tile of evaluate: rows [r0, r0 + nr) through `net`.  kGrad false: their
+// logp, value and entropy.  kGrad true: the forward again (outputs of the inner
+// trunk layers to the block's stash), d loss / d logits, then layer by layer
+// from the heads down the parameter gradients into the block's slab (layer
+// l's dW at sw[l], db at sb[l]; `first`: the chains start here) and the input
+// gradients in place of the layer outputs.  kTable: `net`, `back`, sw and sb
+// lie in device memory (the grouped calls' descriptor table).  t, wv, lane: the
+// thread, its wave (uniform) and its lane, which the kernel works out once.
+template <bool kGrad, bool kTable>
+__device__ __forceinline__ void pol_eval_tile(const PolEvalIO &A, const PolNet &net, const PolNet &back,
+                                              const uint32_t *sw, const uint32_t *sb, float *slab, float *stash,
+                                              uint64_t r0, uint32_t nr, bool first, float *s_pol, uint32_t t, uint32_t wv,
+                                              uint32_t lane)
+{
+    float *buf0 = s_pol, *buf1 = s_pol + kPolTile;
+    float *tail = s_pol + (kGrad ? 4 : 2) * kPolTile;
+    float *s_logit = tail, *s_val = tail + kPolRows * kPolLogitStride;
+    const bool mem_in = (pol_u<kTable>(net.flags) & kPolMemoryIn) != 0u;
+
+    pol_stage_dense(buf0, A, r0, nr, pol_u<kTable>(net.trunk[0].kp), mem_in, t);
+    __syncthreads();
+    float *cur = buf0, *oth = buf1;
+    for (uint32_t l = 0; l < pol_u<kTable>(net.n_trunk); ++l) {
+        pol_layer(pol_pick<kTable>(net.trunk[l]), (int)pol_u<kTable>(net.trunk[l].act), cur, oth, kPolStride, wv, 0u,
+                  lane);
+        __syncthreads();
+        float *sw_ = cur;
+        cur = oth;
+        oth = sw_;
+        if (kGrad && l + 1u < pol_u<kTable>(net.n_trunk)) pol_copy_tile(stash + (size_t)l * kPolTile, cur, t);
+    }
+    // the heads' hidden layers: each in a tile of its own when the backward pass needs them
+    float *ha = kGrad ? s_pol + 2 * kPolTile : oth, *hc = kGrad ? s_pol + 3 * kPolTile : oth;
+    pol_layer(pol_pick<kTable>(net.actor[0]), kActRelu, cur, ha, kPolStride, wv, 0u, lane);
+    __syncthreads();
+    pol_layer(pol_pick<kTable>(net.actor[1]), kActIdentity, ha, s_logit, kPolLogitStride, wv, 0u, lane);
+    __syncthreads();
+    pol_layer(pol_pick<kTable>(net.critic[0]), kActRelu, cur, hc, kPolStride, wv, 0u, lane);
+    __syncthreads();
+    pol_layer(pol_pick<kTable>(net.critic[1]), kActIdentity, hc, s_val, 1u, wv, 0u, lane);
+    __syncthreads();
+
+    // ---- one row per thread: logp, entropy, and d loss / d logits | d value
+    // as the 16-column operands oth[:, 0:16] and oth[:, 16:32] (+0 pads) ----
+    if (t < (uint32_t)kPolRows) {
+        float dz[kPolActions] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, dv = 0.0f;
+        if (t < nr) {
+            const uint64_t r = r0 + t;
+            float z[kPolActions];
+#pragma unroll
+            for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
+            const float gl = kGrad && A.g_logp ? A.g_logp[r] : 0.0f, ge = kGrad && A.g_entropy ? A.g_entropy[r] : 0.0f;
+            float logp, ent;
+            pol_head(z, A.action[r], gl, ge, &logp, &ent, dz);
+            if (A.logp) A.logp[r] = logp;
+            if (A.value) A.value[r] = s_val[t];
+            if (A.entropy) A.entropy[r] = ent;
+            if (kGrad && A.g_value) dv = A.g_value[r];
+        }
+        if (kGrad) {
+            float *o = oth + t * kPolStride;
+#pragma unroll
+            for (int i = 0; i < 32; ++i) o[i] = 0.0f;
+            if (t < nr) {
+#pragma unroll
+                for (int i = 0; i < kPolActions; ++i) o[i] = dz[i];
+                o[16] = dv;
+            }
+        }
+    }
+    __syncthreads();
+    if constexpr (kGrad) {
+        const uint32_t T = pol_u<kTable>(net.n_trunk);
+        // layer l's dW and db chains in the block's slab
+        auto dw = [&](int l) { return slab + pol_u<kTable>(sw[l]); };
+        auto db = [&](int l) { return slab + pol_u<kTable>(sb[l]); };
+        // heads' second layers
+        pol_grad_w(pol_pick<kTable>(net.actor[1]), oth, ha, dw(kPolMaxTrunk + 1), db(kPolMaxTrunk + 1), first, wv, lane, t);
+        pol_grad_w(pol_pick<kTable>(net.critic[1]), oth + 16, hc, dw(kPolMaxTrunk + 3), db(kPolMaxTrunk + 3), first, wv,
+                   lane, t);
+        __syncthreads();
+        pol_layer<true>(pol_pick<kTable>(back.actor[1]), kActRelu, oth, ha, kPolStride, wv, 0u, lane);
+        pol_layer<true>(pol_pick<kTable>(back.critic[1]), kActRelu, oth + 16, hc, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        // heads' first layers; the trunk's last output receives the actor's input
+        // gradient plus the critic's, times its activation's derivative
+        pol_grad_w(pol_pick<kTable>(net.actor[0]), ha, cur, dw(kPolMaxTrunk), db(kPolMaxTrunk), first, wv, lane, t);
+        pol_grad_w(pol_pick<kTable>(net.critic[0]), hc, cur, dw(kPolMaxTrunk + 2), db(kPolMaxTrunk + 2), first, wv, lane,
+                   t);
+        pol_layer<true>(pol_pick<kTable>(back.actor[0]), -1, ha, oth, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer<true>(pol_pick<kTable>(back.critic[0]), (int)pol_u<kTable>(net.trunk[T - 1u].act), hc, cur, kPolStride,
+                        wv, 0u, lane, oth);
+        __syncthreads();
+        // the trunk, last layer first: d in `cur`, the layer's input in `oth`
+        for (uint32_t l = T; l-- > 0u;) {
+            if (l == 0u) pol_stage_dense(oth, A, r0, nr, pol_u<kTable>(net.trunk[0].kp), mem_in, t);
+            else pol_copy_tile(oth, stash + (size_t)(l - 1u) * kPolTile, t);
+            __syncthreads();
+            pol_grad_w(pol_pick<kTable>(net.trunk[l]), cur, oth, dw((int)l), db((int)l), first, wv, lane, t);
+            __syncthreads();
+            if (l == 0u) break;
+            pol_layer<true>(pol_pick<kTable>(back.trunk[l]), (int)pol_u<kTable>(net.trunk[l - 1u].act), cur, oth,
+                            kPolStride, wv, 0u, lane);
+            __syncthreads();
+            float *sw_ = cur;
+            cur = oth;
+            oth = sw_;
+        }
+    }
+}
+
+// kGrad false: every row, grid-stride over the tiles.  kGrad true: block b is
+// accumulator b and takes the tiles b, b + kPolGradAcc, ... in order.
 template <bool kGrad>
 __global__ __launch_bounds__(256, kGrad ? 1 : 2) void policy_eval_kernel(PolEvalIO A, PolNet net, PolGradDev G)
 {
     extern __shared__ float s_pol[];
-    float *buf0 = s_pol, *buf1 = s_pol + kPolTile;
-    float *tail = s_pol + (kGrad ? 4 : 2) * kPolTile;
-    float *s_logit = tail, *s_val = tail + kPolRows * kPolLogitStride;
     const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
-    const bool mem_in = (net.flags & kPolMemoryIn) != 0u;
     const uint64_t tiles = (A.n + kPolRows - 1u) / kPolRows;
     const uint64_t stride = kGrad ? (uint64_t)kPolGradAcc : (uint64_t)gridDim.x;
     float *slab = kGrad ? G.slabs.base + (size_t)blockIdx.x * G.slabs.slab_floats : nullptr;
@@ -609,93 +715,32 @@ __global__ __launch_bounds__(256, kGrad ? 1 : 2) void policy_eval_kernel(PolEval
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += stride) {
         const uint64_t r0 = tile * kPolRows;
         const uint32_t nr = A.n - r0 < (uint64_t)kPolRows ? (uint32_t)(A.n - r0) : (uint32_t)kPolRows;
-        const bool first = tile == (uint64_t)blockIdx.x;
-        pol_stage_dense(buf0, A, r0, nr, net.trunk[0].kp, mem_in, t);
-        __syncthreads();
-        float *cur = buf0, *oth = buf1;
-        for (uint32_t l = 0; l < net.n_trunk; ++l) {
-            pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            float *sw = cur;
-            cur = oth;
-            oth = sw;
-            if (kGrad && l + 1u < net.n_trunk) pol_copy_tile(stash + (size_t)l * kPolTile, cur, t);
-        }
-        // the heads' hidden layers: each in a tile of its own when the backward pass needs them
-        float *ha = kGrad ? s_pol + 2 * kPolTile : oth, *hc = kGrad ? s_pol + 3 * kPolTile : oth;
-        pol_layer(net.actor[0], kActRelu, cur, ha, kPolStride, wv, 0u, lane);
-        __syncthreads();
-        pol_layer(net.actor[1], kActIdentity, ha, s_logit, kPolLogitStride, wv, 0u, lane);
-        __syncthreads();
-        pol_layer(net.critic[0], kActRelu, cur, hc, kPolStride, wv, 0u, lane);
-        __syncthreads();
-        pol_layer(net.critic[1], kActIdentity, hc, s_val, 1u, wv, 0u, lane);
-        __syncthreads();
+        pol_eval_tile<kGrad, false>(A, net, G.back, G.slabs.w, G.slabs.b, slab, stash, r0, nr,
+                                    tile == (uint64_t)blockIdx.x, s_pol, t, wv, lane);
+    }
+}
 
-        // ---- one row per thread: logp, entropy, and d loss / d logits | d value
-        // as the 16-column operands oth[:, 0:16] and oth[:, 16:32] (+0 pads) ----
-        if (t < (uint32_t)kPolRows) {
-            float dz[kPolActions] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, dv = 0.0f;
-            if (t < nr) {
-                const uint64_t r = r0 + t;
-                float z[kPolActions];
-#pragma unroll
-                for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
-                const float gl = kGrad && A.g_logp ? A.g_logp[r] : 0.0f, ge = kGrad && A.g_entropy ? A.g_entropy[r] : 0.0f;
-                float logp, ent;
-                pol_head(z, A.action[r], gl, ge, &logp, &ent, dz);
-                if (A.logp) A.logp[r] = logp;
-                if (A.value) A.value[r] = s_val[t];
-                if (A.entropy) A.entropy[r] = ent;
-                if (kGrad && A.g_value) dv = A.g_value[r];
-            }
-            if (kGrad) {
-                float *o = oth + t * kPolStride;
-#pragma unroll
-                for (int i = 0; i < 32; ++i) o[i] = 0.0f;
-                if (t < nr) {
-#pragma unroll
-                    for (int i = 0; i < kPolActions; ++i) o[i] = dz[i];
-                    o[16] = dv;
-                }
-            }
+// layer `l`'s accumulators -- slabs [0, nacc) of `base`, `stride` floats apart,
+// dW at `woff` in the C-fragment order, db at `boff` -- added in ascending index
+// from +0 into the gradient's [out][in] / [out] layout (null: not wanted)
+__device__ __forceinline__ void pol_reduce_layer(const float *base, uint64_t stride, uint32_t nacc, uint32_t woff,
+                                                 uint32_t boff, uint32_t in, uint32_t out, uint32_t nkt, float *ow,
+                                                 float *ob)
+{
+    const uint32_t nw = ow ? in * out : 0u, nb = ob ? out : 0u;
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nw + nb; i += gridDim.x * 256u) {
+        size_t off;
+        if (i < nw) {
+            const uint32_t j = i / in, k = i - j * in;
+            const uint32_t jt = j >> 4, q = (j & 15u) >> 2, r = j & 3u, kt = k >> 4, c = k & 15u;
+            off = woff + ((size_t)(jt * nkt + kt) * 4u + r) * 64u + q * 16u + c;
+        } else {
+            off = boff + (i - nw);
         }
-        __syncthreads();
-        if constexpr (kGrad) {
-            const PolGradSlabs &S = G.slabs;
-            const uint32_t T = net.n_trunk;
-            // heads' second layers
-            pol_grad_w(net.actor[1], oth, ha, slab + S.w[kPolMaxTrunk + 1], slab + S.b[kPolMaxTrunk + 1], first, wv, lane, t);
-            pol_grad_w(net.critic[1], oth + 16, hc, slab + S.w[kPolMaxTrunk + 3], slab + S.b[kPolMaxTrunk + 3], first, wv,
-                       lane, t);
-            __syncthreads();
-            pol_layer<true>(G.back.actor[1], kActRelu, oth, ha, kPolStride, wv, 0u, lane);
-            pol_layer<true>(G.back.critic[1], kActRelu, oth + 16, hc, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            // heads' first layers; the trunk's last output receives the actor's input
-            // gradient plus the critic's, times its activation's derivative
-            pol_grad_w(net.actor[0], ha, cur, slab + S.w[kPolMaxTrunk], slab + S.b[kPolMaxTrunk], first, wv, lane, t);
-            pol_grad_w(net.critic[0], hc, cur, slab + S.w[kPolMaxTrunk + 2], slab + S.b[kPolMaxTrunk + 2], first, wv, lane,
-                       t);
-            pol_layer<true>(G.back.actor[0], -1, ha, oth, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            pol_layer<true>(G.back.critic[0], (int)net.trunk[T - 1u].act, hc, cur, kPolStride, wv, 0u, lane, oth);
-            __syncthreads();
-            // the trunk, last layer first: d in `cur`, the layer's input in `oth`
-            for (uint32_t l = T; l-- > 0u;) {
-                if (l == 0u) pol_stage_dense(oth, A, r0, nr, net.trunk[0].kp, mem_in, t);
-                else pol_copy_tile(oth, stash + (size_t)(l - 1u) * kPolTile, t);
-                __syncthreads();
-                pol_grad_w(net.trunk[l], cur, oth, slab + S.w[l], slab + S.b[l], first, wv, lane, t);
-                __syncthreads();
-                if (l == 0u) break;
-                pol_layer<true>(G.back.trunk[l], (int)net.trunk[l - 1u].act, cur, oth, kPolStride, wv, 0u, lane);
-                __syncthreads();
-                float *sw = cur;
-                cur = oth;
-                oth = sw;
-            }
-        }
+        float acc = 0.0f;
+        for (uint32_t a = 0; a < nacc; ++a) acc = acc + base[(size_t)a * stride + off];
+        if (i < nw) ow[i] = acc;
+        else ob[i - nw] = acc;
     }
 }
 
@@ -703,22 +748,148 @@ __global__ __launch_bounds__(256, kGrad ? 1 : 2) void policy_eval_kernel(PolEval
 __global__ __launch_bounds__(256) void policy_grad_reduce_kernel(PolGradSlabs S, PolGradOut O)
 {
     const uint32_t l = blockIdx.y;
-    const uint32_t in = O.in[l], out = O.out[l], nkt = pol_grad_nkt(O.kp[l]);
-    const uint32_t nw = O.w[l] ? in * out : 0u, nb = O.b[l] ? out : 0u;
-    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < nw + nb; i += gridDim.x * 256u) {
-        size_t off;
-        if (i < nw) {
-            const uint32_t j = i / in, k = i - j * in;
-            const uint32_t jt = j >> 4, q = (j & 15u) >> 2, r = j & 3u, kt = k >> 4, c = k & 15u;
-            off = S.w[l] + ((size_t)(jt * nkt + kt) * 4u + r) * 64u + q * 16u + c;
-        } else {
-            off = S.b[l] + (i - nw);
-        }
-        float acc = 0.0f;
-        for (uint32_t a = 0; a < S.nacc; ++a) acc = acc + S.base[(size_t)a * S.slab_floats + off];
-        if (i < nw) O.w[l][i] = acc;
-        else O.b[l][i - nw] = acc;
+    pol_reduce_layer(S.base, S.slab_floats, S.nacc, S.w[l], S.b[l], O.in[l], O.out[l], pol_grad_nkt(O.kp[l]), O.w[l],
+                     O.b[l]);
+}
+
+// ---- grouped evaluate (mbots_policy.hpp; DESIGN.md "Grouped evaluate") ----
+// The descriptor table and the repack list of the nets [S.first, S.first +
+// S.n), written from the launch's arguments: one thread per net.
+__global__ __launch_bounds__(64) void policy_groups_setup_kernel(PolGroupSpecs S, float *ws, PolGroupEntry *table,
+                                                                 PolUpload *uploads)
+{
+    const uint32_t i = threadIdx.x;
+    if (i >= S.n) return;
+    const uint32_t e = S.first + i;
+    PolGroupEntry E;
+    pol_group_entry(S.s[i], ws, E, uploads + (size_t)e * kPolGroupUploads);
+    table[e] = E;
+}
+
+// every net's weights into the fragment orders: block (x, layer, net) of the
+// repack list (fwd_only: the transposed layers are not wanted)
+__global__ __launch_bounds__(256) void policy_repack_groups_kernel(const PolUpload *uploads, uint32_t fwd_only)
+{
+    const PolUpload L = uploads[(size_t)blockIdx.z * kPolGroupUploads + blockIdx.y];
+    if (L.w_dst == nullptr || (fwd_only && L.tr)) return;
+    pol_repack_layer(L);
+}
+
+__global__ __launch_bounds__(256) void policy_zero_rows_kernel(float *a, float *b, float *c, uint64_t n)
+{
+    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u) {
+        if (a) a[i] = 0.0f;
+        if (b) b[i] = 0.0f;
+        if (c) c[i] = 0.0f;
     }
+}
+
+// segment e's rows as the device reads them: hi as min(hi, n), lo as min(lo, hi)
+// (and neither below 0)
+__device__ __forceinline__ void pol_segment(const int32_t *segments, uint32_t e, uint64_t n, uint32_t &lo,
+                                            uint32_t &len)
+{
+    const int32_t a = segments[2u * e], b = segments[2u * e + 1u];
+    const uint32_t hi = (uint32_t)min((uint64_t)(b < 0 ? 0 : b), n);
+    lo = min((uint32_t)(a < 0 ? 0 : a), hi);
+    len = hi - lo;
+}
+
+// policy_act_groups_kernel's table behind evaluate's tile: first row, length and
+// the inclusive scan of the tile counts of the (group, species) segments
+constexpr size_t kPolEvalGroupLds = kPolEvalLds + (3u * kPolEvalMaxSegs + 4u) * sizeof(uint32_t);
+static_assert(kPolEvalGroupLds <= 80u * 1024u, "two blocks of policy_eval_groups_kernel share a compute unit's LDS");
+static_assert(kPolEvalMaxSegs == 256u, "policy_eval_groups_kernel: one segment entry per thread");
+
+// logp, value and entropy of every row of every segment that has a net, grid-
+// stride over the segments' tiles (a tile never straddles two segments)
+__global__ __launch_bounds__(256, 2) void policy_eval_groups_kernel(PolEvalIO A, const int32_t *segments,
+                                                                    const PolGroupEntry *table, uint32_t nseg)
+{
+    extern __shared__ float s_pol[];
+    uint32_t *s_start = reinterpret_cast<uint32_t *>(s_pol) + kPolEvalLds / sizeof(uint32_t);
+    uint32_t *s_len = s_start + kPolEvalMaxSegs, *s_scan = s_len + kPolEvalMaxSegs, *s_wsum = s_scan + kPolEvalMaxSegs;
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    {
+        uint32_t lo = 0, len = 0;
+        if (t < nseg && table[t].net.set) pol_segment(segments, t, A.n, lo, len);
+        s_start[t] = lo;
+        s_len[t] = len;
+        uint32_t incl = (len + kPolRows - 1u) / kPolRows;
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63u) s_wsum[wv] = incl;
+        __syncthreads();
+        for (uint32_t q = 0; q < wv; ++q) incl += s_wsum[q];
+        s_scan[t] = incl;
+        __syncthreads();
+    }
+    const uint32_t tiles = uniform(s_scan[kPolEvalMaxSegs - 1u]);
+
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        // the first entry whose scan exceeds the tile (entries without rows are passed over)
+        uint32_t lo = 0, hi = nseg - 1u;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s_scan[mid] > tile) hi = mid;
+            else lo = mid + 1u;
+        }
+        const uint32_t e = uniform(lo);
+        const uint32_t rest = tile - (e ? uniform(s_scan[e - 1u]) : 0u);
+        const uint32_t len = uniform(s_len[e]);
+        const uint64_t r0 = (uint64_t)uniform(s_start[e]) + (uint64_t)rest * kPolRows;
+        const uint32_t nr = min((uint32_t)kPolRows, len - rest * kPolRows);
+        const PolGroupEntry &E = table[e];
+        pol_eval_tile<false, true>(A, E.net, E.back, E.sw, E.sb, nullptr, nullptr, r0, nr, false, s_pol, t, wv, lane);
+    }
+}
+
+// Block (a, c) is accumulator a of the wave's segment c: the tiles a, a +
+// kPolGradAcc, ... counted from the segment's lo, into slab and stash (c, a).  A
+// block without a tile leaves its slab alone: the reduce never reads it.
+__global__ __launch_bounds__(256, 1) void policy_grad_groups_kernel(PolEvalIO A, const int32_t *segments,
+                                                                    const PolGroupEntry *table, PolGroupWave Wv,
+                                                                    float *slabs, uint64_t slab_stride, float *stash)
+{
+    extern __shared__ float s_pol[];
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    const uint32_t a = blockIdx.x, c = blockIdx.y, e = Wv.seg[c];
+    uint32_t lo, len;
+    pol_segment(segments, e, A.n, lo, len);
+    lo = uniform(lo);
+    len = uniform(len);
+    const uint32_t tiles = (len + kPolRows - 1u) / kPolRows;
+    if (a >= tiles) return;
+    const size_t blk = (size_t)c * gridDim.x + a;
+    float *slab = slabs + blk * slab_stride;
+    float *st = stash + blk * kPolStashTiles * kPolTile;
+    const PolGroupEntry &E = table[e];
+    for (uint32_t tile = a; tile < tiles; tile += kPolGradAcc) {
+        const uint64_t r0 = (uint64_t)lo + (uint64_t)tile * kPolRows;
+        const uint32_t nr = min((uint32_t)kPolRows, len - tile * kPolRows);
+        pol_eval_tile<true, true>(A, E.net, E.back, E.sw, E.sb, slab, st, r0, nr, tile == a, s_pol, t, wv, lane);
+    }
+}
+
+// block (x, layer, c): the wave's segment c adds the slabs its tiles reached,
+// the first min(kPolGradAcc, tiles) -- none for an empty segment: zeros
+__global__ __launch_bounds__(256) void policy_grad_groups_reduce_kernel(const int32_t *segments, uint64_t n,
+                                                                        const PolGroupEntry *table, PolGroupWave Wv,
+                                                                        PolGroupGrads O, const float *slabs,
+                                                                        uint64_t slab_stride, uint32_t wave_acc)
+{
+    const uint32_t l = blockIdx.y, c = blockIdx.z, e = Wv.seg[c];
+    const PolGroupEntry &E = table[e];
+    if (l < (uint32_t)kPolMaxTrunk && l >= E.net.n_trunk) return;
+    const uint32_t h = l - (uint32_t)kPolMaxTrunk;
+    const PolLayer &f = l < (uint32_t)kPolMaxTrunk ? E.net.trunk[l] : h < 2u ? E.net.actor[h] : E.net.critic[h - 2u];
+    uint32_t lo, len;
+    pol_segment(segments, e, n, lo, len);
+    const uint32_t nacc = min(min((len + kPolRows - 1u) / kPolRows, kPolGradAcc), wave_acc);
+    pol_reduce_layer(slabs + (size_t)c * wave_acc * slab_stride, slab_stride, nacc, E.sw[l], E.sb[l], f.in, f.out,
+                     pol_grad_nkt(f.kp), O.w[c][l], O.b[c][l]);
 }
 
 // ---- evaluate_sequences and its backward pass through time (mbots_policy.hpp;
@@ -1035,6 +1206,67 @@ static hipError_t policy_seq_lds(const void *fn, size_t bytes, bool &set)
     const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
     if (e == hipSuccess) set = true;
     return e;
+}
+
+// ---- grouped evaluate: the descriptor table and the repacked weights of the
+// 4 G nets of `specs` (host memory: they travel as kernel arguments), then the
+// forward, or the backward in waves of kPolGroupWave segments ----
+static hipError_t policy_groups_prepare(const PolGroupSpec *specs, uint32_t nseg, float *ws, PolGroupEntry *table,
+                                        PolUpload *uploads, bool fwd_only, hipStream_t st)
+{
+    for (uint32_t first = 0; first < nseg; first += kPolGroupChunk) {
+        PolGroupSpecs S{};
+        S.first = first;
+        S.n = std::min(kPolGroupChunk, nseg - first);
+        std::copy(specs + first, specs + first + S.n, S.s);
+        hipLaunchKernelGGL(policy_groups_setup_kernel, dim3(1), dim3(64), 0, st, S, ws, table, uploads);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(policy_repack_groups_kernel, dim3(8, kPolGroupUploads, nseg), dim3(256), 0, st, uploads,
+                       fwd_only ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_eval_groups(const PolEvalIO &io, const int32_t *segments, const PolGroupSpec *specs,
+                                     uint32_t nseg, float *ws, PolGroupEntry *table, PolUpload *uploads, hipStream_t st)
+{
+    if (io.n == 0) return hipSuccess;
+    static bool set = false;
+    if (const hipError_t e =
+            policy_seq_lds(reinterpret_cast<const void *>(policy_eval_groups_kernel), kPolEvalGroupLds, set))
+        return e;
+    if (const hipError_t e = policy_groups_prepare(specs, nseg, ws, table, uploads, true, st)) return e;
+    const unsigned zb = (unsigned)std::min<uint64_t>((io.n + 255u) / 256u, 2048u);
+    hipLaunchKernelGGL(policy_zero_rows_kernel, dim3(zb), dim3(256), 0, st, io.logp, io.value, io.entropy, io.n);
+    if (const hipError_t e = hipGetLastError()) return e;
+    // never more blocks than the rows can hold tiles (each segment with a ragged one)
+    const unsigned blocks = (unsigned)std::min<uint64_t>(io.n / kPolRows + nseg, 512u);
+    hipLaunchKernelGGL(policy_eval_groups_kernel, dim3(blocks), dim3(256), kPolEvalGroupLds, st, io, segments, table,
+                       nseg);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_grad_groups(const PolEvalIO &io, const int32_t *segments, const PolGroupSpec *specs,
+                                     uint32_t nseg, const PolGroupWave *waves, const PolGroupGrads *grads,
+                                     uint32_t nwaves, float *ws, PolGroupEntry *table, PolUpload *uploads, float *slabs,
+                                     uint64_t slab_stride, float *stash, uint32_t wave_acc, hipStream_t st)
+{
+    static bool set = false;
+    if (const hipError_t e =
+            policy_seq_lds(reinterpret_cast<const void *>(policy_grad_groups_kernel), kPolGradLds, set))
+        return e;
+    if (const hipError_t e = policy_groups_prepare(specs, nseg, ws, table, uploads, false, st)) return e;
+    for (uint32_t w = 0; w < nwaves; ++w) {
+        if (wave_acc) {
+            hipLaunchKernelGGL(policy_grad_groups_kernel, dim3(wave_acc, waves[w].n), dim3(256), kPolGradLds, st, io,
+                               segments, table, waves[w], slabs, slab_stride, stash);
+            if (const hipError_t e = hipGetLastError()) return e;
+        }
+        hipLaunchKernelGGL(policy_grad_groups_reduce_kernel, dim3(16, kPolGradLayers, waves[w].n), dim3(256), 0, st,
+                           segments, io.n, table, waves[w], grads[w], slabs, slab_stride, wave_acc);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_policy_seq_eval(const PolSeqIO &io, const PolNet &net, hipStream_t st)

@@ -390,6 +390,107 @@ struct PolGradOut {
 };
 MB_HD uint32_t pol_grad_nkt(uint32_t kp) { return (kp + 15u) >> 4; }
 
+// ---- grouped evaluate: every (group, species) segment of a table through its
+// own net in one forward and one backward call (DESIGN.md "Grouped evaluate") ----
+// Segment e = 4 g + s is the rows [lo, hi) of `segments` [G][4][2], read on the
+// device; its tiles, accumulators and chains are evaluate's, counted from lo.
+constexpr uint32_t kPolEvalMaxSegs = 4u * kPolMaxGroups;
+constexpr uint32_t kPolGroupWave = 8;    // segments whose backward shares a launch, its slabs and its stash
+constexpr int kPolGroupUploads = 16;     // a net's 8 forward and 7 transposed layers, rounded up
+// One net as a kernel argument carries it: every width follows from (n_trunk,
+// H, flags), so the descriptors themselves are built on the device.
+struct PolGroupSpec {
+    uint64_t w_off;                     // floats from the workspace's start to the net's packed weights
+    uint32_t n_trunk, H, flags, act;    // n_trunk == 0: the pair has no net; act: trunk layer l's code in byte l
+    const float *w[kPolGradLayers], *b[kPolGradLayers];   // the caller's parameters (slots as PolGradOut's)
+};
+// The net's descriptors in the workspace: forward and transposed layers (as
+// evaluate's plan lays them out) and where each layer's dW / db lie in a slab.
+struct PolGroupEntry {
+    PolNet net, back;
+    uint32_t sw[kPolGradLayers], sb[kPolGradLayers];
+    uint32_t slab_floats, pad;
+};
+MB_HD float *pol_group_take(float *ws, uint64_t base, size_t &off, size_t floats)
+{
+    float *p = ws ? ws + base + off : nullptr;
+    off += (floats + 63u) & ~size_t(63);
+    return p;
+}
+// `e` (and, `up` not null, the kPolGroupUploads repacks that fill its weights)
+// from `s`; returns the floats the weights take from ws + s.w_off on.
+MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e, PolUpload *up)
+{
+    e = PolGroupEntry{};
+    size_t off = 0;
+    int nu = 0;
+    if (s.n_trunk) {
+        const uint32_t H = s.H, in0 = (s.flags & kPolMemoryIn) ? (uint32_t)(kPolObs + kHidden) : (uint32_t)kPolObs;
+        e.net.set = 1;
+        e.net.n_trunk = s.n_trunk;
+        e.net.H = H;
+        e.net.flags = s.flags;
+        uint32_t slab = 0;
+        for (int i = 0; i < kPolGradLayers; ++i) {
+            PolLayer *f, *b;
+            uint32_t in = H, out = H, act = 0;
+            if (i < kPolMaxTrunk) {
+                if ((uint32_t)i >= s.n_trunk) continue;
+                f = &e.net.trunk[i];
+                b = i ? &e.back.trunk[i] : nullptr;
+                if (i == 0) in = in0;
+                act = (s.act >> (8 * i)) & 0xFFu;
+            } else {
+                const int h = i - kPolMaxTrunk;
+                f = h < 2 ? &e.net.actor[h] : &e.net.critic[h - 2];
+                b = h < 2 ? &e.back.actor[h] : &e.back.critic[h - 2];
+                if (h == 1) out = (uint32_t)kPolActions;
+                if (h == 3) out = 1u;
+            }
+            f->in = in;
+            f->out = out;
+            f->kp = pol_kp(in);
+            f->nt = (out + 15u) / 16u;
+            f->act = act;
+            f->w = pol_group_take(ws, s.w_off, off, pol_w_floats(*f));
+            f->b = pol_group_take(ws, s.w_off, off, pol_b_floats(*f));
+            if (up) up[nu++] = PolUpload{s.w[i], s.b[i], f->w, f->b, in, out, f->kp, f->nt, 0u, 0u, 0u};
+            if (b) {
+                b->in = out;
+                b->out = in;
+                b->kp = (out + 7u) & ~7u;   // an even number of k-steps, as the layer kernel's paired loop takes
+                b->nt = (in + 15u) / 16u;
+                b->w = pol_group_take(ws, s.w_off, off, pol_w_floats(*b));
+                b->b = pol_group_take(ws, s.w_off, off, pol_b_floats(*b));
+                if (up) up[nu++] = PolUpload{s.w[i], nullptr, b->w, b->b, b->in, b->out, b->kp, b->nt, 1u, 0u, 0u};
+            }
+            e.sw[i] = slab;
+            slab += f->nt * pol_grad_nkt(f->kp) * 256u;
+            e.sb[i] = slab;
+            slab += f->nt * 16u;
+        }
+        e.slab_floats = slab;
+    }
+    if (up)
+        for (; nu < kPolGroupUploads; ++nu) up[nu] = PolUpload{};
+    return off;
+}
+// the segments of one backward wave, and where their gradients go ([out][in] /
+// [out], null: not wanted)
+struct PolGroupWave {
+    uint32_t seg[kPolGroupWave], n;
+};
+struct PolGroupGrads {
+    float *w[kPolGroupWave][kPolGradLayers], *b[kPolGroupWave][kPolGradLayers];
+};
+// the specs a setup launch carries in its arguments
+constexpr uint32_t kPolGroupChunk = 24;
+struct PolGroupSpecs {
+    PolGroupSpec s[kPolGroupChunk];
+    uint32_t first, n;
+};
+static_assert(sizeof(PolGroupSpecs) + 64u <= 4096u, "a setup launch's specs travel as kernel arguments");
+
 // ---- evaluate_sequences: the net along padded sequences with the memory
 // head's output carried from step to step, and backpropagation through time
 // (DESIGN.md "Backpropagation through HiddenState") ----

@@ -15,6 +15,15 @@ group's update depends on another group's nets; the reference's faithful
 reward pays species 4 of a group's last world from the next group's first
 world (INTEGRATION.md "Policy groups", "Where groups meet").
 
+--grouped-evaluate: the learner's half in one call per table instead --
+
+    madrona_bots.evaluate_groups(nets, obs, action, segments) -> one loss over
+    per-row group weights built on the device from `segments` -> one backward()
+
+-- with no .tolist(): the host never reads the segments, so the update neither
+waits for the device nor depends on where the groups' rows lie.  With nets that
+own their parameters it leaves the same bits in every parameter as the loop.
+
     python madrona-bots_amd/harness/a2c_groups.py --worlds 64 --groups 4 --iters 5 --exec-mode cpu
     python madrona-bots_amd/harness/a2c_groups.py --worlds 65536 --groups 32 --iters 20
 """
@@ -30,10 +39,12 @@ from a2c import make_modules  # noqa: E402
 
 
 def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0,
-          value_coef=0.5, entropy_coef=0.01, log=None):
+          value_coef=0.5, entropy_coef=0.01, log=None, grouped_evaluate=False):
     """`iters` updates of `horizon - 1` steps each of every group.  modules[u],
     optimizers[u]: a2c.make_modules' four ModuleDicts and their optimizers for
-    group u.  Returns the losses, [iters][groups] floats."""
+    group u.  grouped_evaluate: one evaluate_groups per table and one
+    backward() (train_grouped_update) in place of the per-net loop.  Returns
+    the losses, [iters][groups] floats."""
     import madrona_bots as mb
     G = len(starts)
     sim.set_policy_groups(starts)
@@ -52,9 +63,19 @@ def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.
                 o = sim.act(write=not last)
                 win.push(o["value"])
                 if not last:
-                    rows.append((obs, o["action"], sim.policy_segments(out=seg).tolist()))
+                    sg = sim.policy_segments(out=seg)
+                    rows.append((obs, o["action"], sg.clone() if grouped_evaluate else sg.tolist()))
                     sim.step()
             out = win.compute(gamma=gamma, lam=lam, death_reward=death_reward)
+            if grouped_evaluate:
+                loss, total = grouped_update(mb, nets, optimizers, rows, out, win.END_RESET, value_coef, entropy_coef)
+                for u in range(G):
+                    sim.set_policy(nets[u], group=u)
+                win.clear()
+                losses.append(loss)
+                if log:
+                    log(json.dumps({"iter": it, "loss": loss, "rows": total}))
+                continue
             loss = [torch.zeros((), device=sim.device) for _ in range(G)]
             total = [sum(hi - lo for _, _, sg in rows for lo, hi in sg[u]) for u in range(G)]
             for t, (obs, action, sg) in enumerate(rows):
@@ -85,6 +106,48 @@ def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.
     return losses
 
 
+def grouped_update(mb, nets, optimizers, rows, out, end_reset, value_coef, entropy_coef):
+    """One update of every group from the recorded tables `rows` -- (obs,
+    action, segments [G, 4, 2] on the device) -- and the window's `out`: one
+    evaluate_groups per table, the groups' losses summed into one scalar, one
+    backward().  Row r of group u weighs keep[r] / total[u], total[u] the
+    group's rows over all tables: what the loop's `.sum() / total[u]` hands
+    every row's gradient, so the parameters receive the loop's bits.  (A group
+    without a row receives zero gradients here, where the loop skips its
+    optimizers.)  Returns ([G] losses, [G] rows) as Python numbers, read from
+    the device once, after the optimizers' steps."""
+    G = len(nets)
+    dev = rows[0][0].device
+    spans = torch.stack([sg for _, _, sg in rows]).to(torch.int64)             # [T, G, 4, 2]
+    total = (spans[..., 1] - spans[..., 0]).sum(dim=(0, 2))                    # [G]
+    weight = torch.cat([torch.zeros(1, device=dev), torch.where(total > 0, 1.0 / total.to(torch.float32), 0.0)])
+    ids = torch.arange(1, G + 1, device=dev).repeat_interleave(4)              # the group of every segment, from 1
+    loss = torch.zeros((), device=dev)
+    per_group = torch.zeros(G + 1, device=dev)
+    for t, (obs, action, sg) in enumerate(rows):
+        n = obs.shape[0]
+        # the row's group (0: none): +id at lo, -id at hi, summed along the rows -- integers, exact
+        edge = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+        edge.index_add_(0, spans[t, :, :, 0].reshape(-1), ids)
+        edge.index_add_(0, spans[t, :, :, 1].reshape(-1), -ids)
+        group = edge.cumsum(0)[:n]
+        keep = (out["end"][t].reshape(-1) != end_reset).to(torch.float32)
+        logp, value, entropy = mb.evaluate_groups(nets, obs, action, sg)
+        adv, ret = out["adv"][t][:, 0], out["ret"][t][:, 0]
+        per_row = (-adv * logp + value_coef * (value - ret) ** 2 - entropy_coef * entropy) * (keep * weight[group])
+        loss = loss + per_row.sum()
+        per_group.index_add_(0, group, per_row.detach())
+    for opts in optimizers:
+        for opt in opts:
+            opt.zero_grad(set_to_none=True)
+    loss.backward()
+    for opts in optimizers:
+        for opt in opts:
+            opt.step()
+    host = torch.cat([per_group[1:].to(torch.float64), total.to(torch.float64)]).cpu()
+    return [float(x) for x in host[:G]], [int(x) for x in host[G:]]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worlds", type=int, default=64)
@@ -98,6 +161,8 @@ def main():
     ap.add_argument("--seed", type=int, default=69)
     ap.add_argument("--exec-mode", choices=("hip", "cpu"), default="hip" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--reward-fixed", action="store_true", help="rewards[speciesID - 1]: universes fully apart")
+    ap.add_argument("--grouped-evaluate", action="store_true",
+                    help="one evaluate_groups and one backward() per update instead of one evaluate per (group, species)")
     args = ap.parse_args()
     if not 1 <= args.groups <= 64 or args.worlds < args.groups:
         ap.error("--groups must be in [1, 64] and at most --worlds")
@@ -108,7 +173,8 @@ def main():
     starts = [u * args.worlds // args.groups for u in range(args.groups)]
     modules = [make_modules(args.hidden[u % len(args.hidden)], sim.device, args.seed + u) for u in range(args.groups)]
     optimizers = [[torch.optim.Adam(m.parameters(), lr=args.lr) for m in four] for four in modules]
-    train(sim, starts, modules, optimizers, args.iters, args.horizon, log=print)
+    train(sim, starts, modules, optimizers, args.iters, args.horizon, log=print,
+          grouped_evaluate=args.grouped_evaluate)
 
 
 if __name__ == "__main__":

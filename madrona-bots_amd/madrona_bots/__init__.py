@@ -29,7 +29,7 @@ import torch  # loads the HIP runtime libmbots.so links against (same soname)
 __all__ = ["SimManager", "ScriptBotsViewer", "Tensor", "madrona", "ExportID", "ExecMode", "unpack_rollout",
            "unpack_learner", "rebuild_learner", "CapacityWarning", "CapacityError", "MAX_CAPACITY",
            "CAPACITY_CLASSES", "TrajectoryWindow", "RENDER_PALETTE", "RENDER_SCALES", "CLS_FLOOR", "CLS_WALL",
-           "CLS_FOOD", "CLS_BODY", "CLS_MARK", "PolicyNet", "policy_activation", "ACTIVATIONS"]
+           "CLS_FOOD", "CLS_BODY", "CLS_MARK", "PolicyNet", "policy_activation", "ACTIVATIONS", "evaluate_groups"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmbots.so")
@@ -160,6 +160,11 @@ def _load():
         "mbots_policy_eval": [P(_PolicyNet), vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp, ctypes.c_uint64, i32, vp],
         "mbots_policy_grad": [P(_PolicyNet), vp, vp, vp, ctypes.c_uint64, vp, vp, vp, P(_PolicyGrads), vp,
                               ctypes.c_uint64, i32, vp],
+        "mbots_policy_groups_workspace": [P(_PolicyNet), u32, ctypes.c_uint64, P(ctypes.c_uint64)],
+        "mbots_policy_eval_groups": [P(_PolicyNet), u32, vp, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, vp,
+                                     ctypes.c_uint64, i32, vp],
+        "mbots_policy_grad_groups": [P(_PolicyNet), u32, vp, vp, vp, vp, ctypes.c_uint64, vp, vp, vp, P(_PolicyGrads), vp,
+                                     ctypes.c_uint64, i32, vp],
         "mbots_policy_seq_workspace": [P(_PolicyNet), u32, ctypes.c_uint64, P(ctypes.c_uint64)],
         "mbots_policy_seq_eval": [P(_PolicyNet), vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp, vp, vp,
                                   ctypes.c_uint64, i32, vp],
@@ -1606,6 +1611,155 @@ class _EvaluateSequences(torch.autograd.Function):
             ctypes.byref(c), _ptr(obs), _ptr(action), _ptr(length), _ptr(hidden0), L, B, _ptr(g[0]), _ptr(g[1]),
             _ptr(g[2]), ctypes.byref(out), ws, nb, d, st), seq=True)
         return (None,) * 7 + tuple(grads[i] for i in present)
+
+
+def _species_name(g, s):
+    return f"nets[{g}][{s}] (group {g}, species {s + 1})"
+
+
+def evaluate_groups(nets, obs, action, segments, hidden=None):
+    """(logp, value, entropy), float32 [n] each on obs's device: every (group,
+    species) segment of a table through its own net, in one forward call and
+    one backward call (the learner's half of policy groups; DESIGN.md "Grouped
+    evaluate").  nets: a list of 1..64 groups, each a list of four PolicyNet
+    (species 1..4) or one PolicyNet for all four; None where a pair has no
+    net; the nets may differ in every part of the architecture.  obs float32
+    [n, 69], action int32 [n] or [n, 1], hidden float32 [n, 16] iff any net
+    is memory_in; segments int32 [G, 4, 2] on obs's device, exactly what
+    SimManager.policy_segments() returns: on a GPU it is read by the kernels
+    only, never by the host.
+
+    A row inside segment (g, s) gets, bit for bit, what
+    nets[g][s].evaluate(obs[lo:hi], action[lo:hi], hidden[lo:hi]) gives it; a
+    row in no segment, or in the segment of a None, gets +0 and takes no part
+    in any gradient.  backward() leaves in every parameter that one net owns,
+    bit for bit, the gradient the per-net call's backward leaves (sums in
+    evaluate's order counted from the segment's lo; zeros for an empty
+    segment).  A parameter tensor shared by several segments receives the sum
+    of its segments' gradients, added by autograd in torch's order: the
+    bitwise claim covers unshared parameters only.  obs and hidden receive no
+    gradient; the memory head takes no part.
+
+    segments must hold 0 <= lo <= hi <= n, pairwise disjoint: CPU tensors are
+    checked (a violation names the pair); on a GPU hi is read as min(hi, n),
+    lo as min(lo, hi), and disjointness is the caller's contract.  Forward
+    and backward allocate no workspace after the first call of a shape and
+    never wait for the host, so both can be recorded into a graph and
+    replayed on other contents of `segments`."""
+    groups = [list(g) if isinstance(g, (list, tuple)) else [g] * 4 for g in nets]
+    G = len(groups)
+    if not 1 <= G <= 64:
+        raise ValueError(f"nets must hold 1..64 groups, not {G}")
+    for g, four in enumerate(groups):
+        if len(four) != 4 or any(x is not None and not isinstance(x, PolicyNet) for x in four):
+            raise ValueError(f"nets[{g}] must be four PolicyNet (or None), or one PolicyNet for all species")
+    dev = obs.device
+    if obs.dtype != torch.float32 or obs.dim() != 2 or obs.shape[1] != 69:
+        raise ValueError(f"obs must be float32 [n, 69], not {obs.dtype} {list(obs.shape)}")
+    n = obs.shape[0]
+    if action.dtype != torch.int32 or action.device != dev or action.numel() != n \
+            or action.dim() not in (1, 2) or action.shape[0] != n:
+        raise ValueError(f"action must be int32 [n] or [n, 1] on {dev} with obs's rows, not {action.dtype} "
+                         f"{list(action.shape)} on {action.device}")
+    if segments.dtype != torch.int32 or segments.device != dev or tuple(segments.shape) != (G, 4, 2):
+        raise ValueError(f"segments must be int32 [{G}, 4, 2] on {dev} (policy_segments() of the nets' {G} groups), "
+                         f"not {segments.dtype} {list(segments.shape)} on {segments.device}")
+    flat = [x for four in groups for x in four]
+    if any(x is not None and x.memory_in for x in flat):
+        if hidden is None:
+            raise ValueError("hidden (float32 [n, 16]) is needed: a net is memory_in")
+        if hidden.dtype != torch.float32 or hidden.device != dev or tuple(hidden.shape) != (n, 16):
+            raise ValueError(f"hidden must be float32 [n, 16] on {dev}, not {hidden.dtype} {list(hidden.shape)} "
+                             f"on {hidden.device}")
+        hidden = hidden.detach().contiguous()
+    else:
+        hidden = None
+    index, params = [], []       # (segment, slot of _named_params) of every parameter passed on
+    for e, x in enumerate(flat):
+        if x is None:
+            continue
+        try:
+            x._validate()
+        except ValueError as err:
+            raise ValueError(f"{_species_name(e // 4, e % 4)}: {err}") from None
+        for i, (name, p) in enumerate(x._named_params()):
+            if p is None:
+                continue
+            if p.dtype != torch.float32 or p.device != dev:
+                raise ValueError(f"{_species_name(e // 4, e % 4)}: {name} must be float32 on {dev} (obs's device), "
+                                 f"not {p.dtype} on {p.device}")
+            index.append((e, i))
+            params.append(p)
+    return _EvaluateGroups.apply(flat, obs.detach().contiguous(), action.detach().reshape(n).contiguous(), hidden,
+                                 segments.detach().contiguous(), index, *params)
+
+
+def _groups_call(flat, full, obs, fn):
+    """The C net table [G][4] over `full` (per segment the tensors of
+    _named_params(), None: no net), the workspace, and the device / stream
+    arguments; fn(nets, groups, workspace pointer, bytes, device index, stream)."""
+    dev = obs.device
+    c = (_PolicyNet * len(flat))()
+    for e, x in enumerate(flat):
+        if x is not None:
+            c[e] = x._c_net(full[e])
+    G = len(flat) // 4
+    need = ctypes.c_uint64()
+    _check(_lib.mbots_policy_groups_workspace(c, G, obs.shape[0], ctypes.byref(need)))
+    key = (dev, need.value)
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.empty(max(need.value, 64), dtype=torch.uint8, device=dev)
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            _check(fn(c, G, ctypes.c_void_p(ws.data_ptr()), need.value, dev.index,
+                      ctypes.c_void_p(_raw_stream(dev.index))))
+    else:
+        _check(fn(c, G, ctypes.c_void_p(ws.data_ptr()), need.value, -1, None))
+
+
+class _EvaluateGroups(torch.autograd.Function):
+    """evaluate_groups: mbots_policy_eval_groups forward, mbots_policy_grad_groups
+    backward, one node over the parameters of every net."""
+
+    @staticmethod
+    def forward(ctx, flat, obs, action, hidden, segments, index, *params):
+        full = [None if x is None else [None] * (2 * (len(x.trunk) + 4)) for x in flat]
+        for (e, i), p in zip(index, params):
+            full[e][i] = p.detach().contiguous()
+        n = obs.shape[0]
+        logp, value, entropy = (torch.empty(n, dtype=torch.float32, device=obs.device) for _ in range(3))
+        _groups_call(flat, full, obs, lambda c, G, ws, nb, d, st: _lib.mbots_policy_eval_groups(
+            c, G, _ptr(segments), _ptr(obs), _ptr(hidden), _ptr(action), n, _ptr(logp), _ptr(value), _ptr(entropy),
+            ws, nb, d, st))
+        ctx.flat, ctx.rows, ctx.index, ctx.full = flat, (obs, action, hidden, segments), index, full
+        ctx.set_materialize_grads(False)   # an output the loss does not use: no g_* (zeros)
+        return logp, value, entropy
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logp, g_value, g_entropy):
+        flat, (obs, action, hidden, segments), index, full = ctx.flat, ctx.rows, ctx.index, ctx.full
+        n = obs.shape[0]
+        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_logp, g_value, g_entropy)]
+        out = (_PolicyGrads * len(flat))()
+        grads = []
+        for k, (e, i) in enumerate(index):
+            if not ctx.needs_input_grad[6 + k]:
+                grads.append(None)
+                continue
+            grads.append(torch.empty_like(full[e][i]))
+            T = len(flat[e].trunk)
+            layer, slots = i // 2, out[e]
+            slot = slots.trunk[layer] if layer < T else (slots.actor, slots.critic)[(layer - T) // 2][(layer - T) % 2]
+            if i % 2:
+                slot.bias = grads[-1].data_ptr()
+            else:
+                slot.weight = grads[-1].data_ptr()
+        _groups_call(flat, full, obs, lambda c, G, ws, nb, d, st: _lib.mbots_policy_grad_groups(
+            c, G, _ptr(segments), _ptr(obs), _ptr(hidden), _ptr(action), n, _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
+            out, ws, nb, d, st))
+        return (None,) * 6 + tuple(grads)
 
 
 def policy_activation(act, x):

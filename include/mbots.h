@@ -926,6 +926,67 @@ int mbots_policy_seq_grad(const struct mbots_policy_net *net, const float *obs, 
                           const float *g_value, const float *g_entropy, const struct mbots_policy_grads *out,
                           void *workspace, uint64_t workspace_bytes, int32_t device, void *stream);
 
+/* Every group's recurrent nets in one call: mbots_policy_seq_eval / _grad for
+ * policy groups (DESIGN.md "Grouped evaluate_sequences" is the specification).
+ * The conventions are mbots_policy_eval_groups': `device` / `stream`,
+ * nets[groups][4] with n_trunk == 0 for a pair without a net, out[groups][4].
+ * Every net present must have a memory head and MBOTS_POLICY_MEMORY_IN; any
+ * other is refused, naming the pair (mbots_policy_eval_groups evaluates those).
+ * obs, action, length, hidden0, the outputs and g_* are mbots_policy_seq_eval's,
+ * the whole batch of B columns; nothing is copied out of it.
+ *
+ * mbots_policy_seq_order: net_id int32 [B], entry b the column's 4 * group +
+ * (species - 1); any value outside [0, 4 * groups) means no net.  Writes order
+ * int32 [B] and segments int32 [groups][4][2]: order[lo .. hi) of pair (g, s)
+ * holds exactly the columns with net_id == 4 g + s, ascending; the segments lie
+ * in ascending 4 g + s from position 0; order past the last segment is -1.  A
+ * stable counting sort: on the device three launches that use no atomic, never
+ * wait for the host and can be captured; workspace (device path only; NULL is
+ * fine on the host) MBOTS_POLICY_SEQ_ORDER_WORKSPACE(B) bytes, 4-byte aligned.
+ *
+ * Position p of segment (g, s), lo <= p < hi, stands for column order[p].
+ * mbots_policy_seq_eval_groups: column order[p] receives, bit for bit, what
+ * mbots_policy_seq_eval of nets[g][s] on the columns order[lo .. hi) alone gives
+ * it; a column named by no evaluated segment, or by the segment of a pair
+ * without a net, receives +0 at every step.
+ *
+ * mbots_policy_seq_grad_groups: every non-NULL pointer of out[g][s],
+ * out[g][s].memory included, receives bit for bit what mbots_policy_seq_grad of
+ * nets[g][s] on those columns and their g_* leaves there: the sums in that
+ * call's order, counted in positions from lo (tiles of 64 positions, tile i
+ * into accumulator i mod 256); zeros for an empty segment.
+ *
+ * Contract: 0 <= lo <= hi <= B, segments pairwise disjoint, every order[p] of
+ * an evaluated segment in [0, B) and no column twice, lengths in [0, L],
+ * present actions in 0..5.  The host path refuses each violation
+ * (MBOTS_E_INVALID, naming the pair).  The device reads hi as min(hi, B) and lo
+ * as min(lo, hi), a length as clamped to [0, L], and an order entry outside
+ * [0, B) as a column of length 0 that is neither read nor written; duplicates
+ * and overlaps are the caller's contract there.
+ *
+ * workspace: mbots_policy_seq_groups_workspace(nets, groups, L, B, &bytes)
+ * bytes, 16-byte aligned, of the rows' memory kind; it grows with the nets'
+ * weights and with 8 x min(256, ceil(B / 64)) slabs, stashes and [L][64][16] h
+ * stores, not with 256 slabs per net.  The calls allocate nothing and never
+ * wait for the host: they can be captured into a graph, and a replay reads
+ * order and segments as they are then. */
+#define MBOTS_POLICY_SEQ_ORDER_WORKSPACE(B) (((((uint64_t)(B)) + 1023u) / 1024u) * 1024u + 256u)
+int mbots_policy_seq_order(const int32_t *net_id, uint64_t B, uint32_t groups, int32_t *order, int32_t *segments,
+                           void *workspace, uint64_t workspace_bytes, int32_t device, void *stream);
+int mbots_policy_seq_groups_workspace(const struct mbots_policy_net *nets /* [groups][4] */, uint32_t groups, uint32_t L,
+                                      uint64_t B, uint64_t *bytes);
+int mbots_policy_seq_eval_groups(const struct mbots_policy_net *nets, uint32_t groups, const int32_t *order,
+                                 const int32_t *segments, const float *obs, const int32_t *action,
+                                 const int32_t *length, const float *hidden0, uint32_t L, uint64_t B, float *logp,
+                                 float *value, float *entropy, float *hidden, void *workspace, uint64_t workspace_bytes,
+                                 int32_t device, void *stream);
+int mbots_policy_seq_grad_groups(const struct mbots_policy_net *nets, uint32_t groups, const int32_t *order,
+                                 const int32_t *segments, const float *obs, const int32_t *action,
+                                 const int32_t *length, const float *hidden0, uint32_t L, uint64_t B,
+                                 const float *g_logp, const float *g_value, const float *g_entropy,
+                                 const struct mbots_policy_grads *out /* [groups][4] */, void *workspace,
+                                 uint64_t workspace_bytes, int32_t device, void *stream);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That

@@ -1146,11 +1146,15 @@ inline uint32_t seq_len(const PolSeqIO &io, uint64_t b)
     const int32_t n = io.length[b];
     return n < 0 ? 0u : std::min((uint32_t)n, io.L);
 }
+// the batch column position p of a call stands for, and the positions it runs
+inline uint64_t seq_col(const PolSeqCols &cols, uint64_t p) { return cols.idx ? (uint64_t)cols.idx[p] : p; }
+inline uint64_t seq_cols(const PolSeqCols &cols, const PolSeqIO &io) { return cols.idx ? cols.n : io.B; }
 }  // namespace
 
-void policy_seq_eval(const PolNet &net, const PolSeqIO &io)
+void policy_seq_eval(const PolNet &net, const PolSeqIO &io, const PolSeqCols &cols)
 {
-    par_for(io.B, 16, [&](uint64_t b) {
+    par_for(seq_cols(cols, io), 16, [&](uint64_t p) {
+        const uint64_t b = seq_col(cols, p);
         RowForward f;
         float h[kHidden], y[kHidden];
         for (int c = 0; c < kHidden; ++c) h[c] = io.hidden0[b * kHidden + c];
@@ -1179,9 +1183,11 @@ void policy_seq_eval(const PolNet &net, const PolSeqIO &io)
     });
 }
 
-void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &S, float *hws, const PolGradOut &out)
+void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &S, float *hws, const PolGradOut &out,
+                     const PolSeqCols &cols)
 {
-    const uint64_t tiles = (io.B + kPolGradRows - 1u) / kPolGradRows;
+    const uint64_t ncols = seq_cols(cols, io);
+    const uint64_t tiles = (ncols + kPolGradRows - 1u) / kPolGradRows;
     const uint32_t T = net.n_trunk;
     constexpr int kM = kPolGradLayers;   // the memory head's slot
     par_for(S.nacc, 1, [&](uint64_t a) {
@@ -1193,19 +1199,20 @@ void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &
         float dh[kPolGradRows][kHidden];
         for (uint64_t tile = a; tile < tiles; tile += kPolGradAcc) {
             const uint64_t b0 = tile * kPolGradRows;
-            const uint32_t nb = (uint32_t)std::min<uint64_t>(kPolGradRows, io.B - b0);
+            const uint32_t nb = (uint32_t)std::min<uint64_t>(kPolGradRows, ncols - b0);
             // the forward sweep: every present element's h_k
             uint32_t maxlen = 0;
             for (uint32_t r = 0; r < nb; ++r) {
-                const uint32_t n = seq_len(io, b0 + r);
+                const uint64_t b = seq_col(cols, b0 + r);
+                const uint32_t n = seq_len(io, b);
                 maxlen = std::max(maxlen, n);
                 float h[kHidden];
-                for (int c = 0; c < kHidden; ++c) h[c] = io.hidden0[(b0 + r) * kHidden + c];
+                for (int c = 0; c < kHidden; ++c) h[c] = io.hidden0[b * kHidden + c];
                 for (uint32_t k = 0; k < n; ++k) {
                     float *o = hk + ((size_t)k * kPolGradRows + r) * kHidden;
                     for (int c = 0; c < kHidden; ++c) o[c] = h[c];
                     if (k + 1u == n) break;
-                    row_forward(net, io.obs + ((uint64_t)k * io.B + b0 + r) * kPolObs, h, f);
+                    row_forward(net, io.obs + ((uint64_t)k * io.B + b) * kPolObs, h, f);
                     policy_layer_host(net.memory, kActTanh, f.y[T], h);
                 }
                 for (int c = 0; c < kHidden; ++c) dh[r][c] = 0.0f;
@@ -1214,8 +1221,9 @@ void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &
             // gradients: it leaves every chain as it is, and is skipped.)
             for (uint32_t k = maxlen; k-- > 0u;)
                 for (uint32_t r = 0; r < nb; ++r) {
-                    if (k >= seq_len(io, b0 + r)) continue;
-                    const uint64_t e = (uint64_t)k * io.B + b0 + r;
+                    const uint64_t b = seq_col(cols, b0 + r);
+                    if (k >= seq_len(io, b)) continue;
+                    const uint64_t e = (uint64_t)k * io.B + b;
                     row_forward(net, io.obs + e * kPolObs, hk + ((size_t)k * kPolGradRows + r) * kHidden, f);
                     const float *top = f.y[T];
                     policy_layer_host(net.memory, kActTanh, top, y);

@@ -157,10 +157,12 @@ private:
 // accumulators, then adds them in ascending index into `out`.
 void policy_eval(const PolNet &net, const PolEvalIO &io);
 void policy_grad(const PolNet &net, const PolEvalIO &io, const PolGradSlabs &slabs, const PolGradOut &out);
-// evaluate_sequences on the host threads; hws as the device's (mbots_kernels.hpp)
-void policy_seq_eval(const PolNet &net, const PolSeqIO &io);
+// evaluate_sequences on the host threads; hws as the device's (mbots_kernels.hpp).
+// cols: the batch columns the call runs, position p standing for column
+// cols.idx[p] (the grouped call's segments); tiles and chains count positions.
+void policy_seq_eval(const PolNet &net, const PolSeqIO &io, const PolSeqCols &cols = PolSeqCols{nullptr, 0});
 void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &slabs, float *hws,
-                     const PolGradOut &out);
+                     const PolGradOut &out, const PolSeqCols &cols = PolSeqCols{nullptr, 0});
 
 }  // namespace cpu
 }  // namespace mbots

@@ -326,5 +326,23 @@ hipError_t launch_policy_grad_groups(const PolEvalIO &io, const int32_t *segment
 hipError_t launch_policy_seq_eval(const PolSeqIO &io, const PolNet &net, hipStream_t st);
 hipError_t launch_policy_seq_grad(const PolSeqIO &io, const PolNet &net, const PolNet &back, const PolGradSlabs &slabs,
                                   float *stash, float *hws, const PolGradOut &out, hipStream_t st);
+// grouped evaluate_sequences (mbots_policy.hpp): launch_policy_eval_groups'
+// arguments for nets with a memory head (nseg * kPolSeqGroupUploads repack
+// entries), the columns through `order`; the backward's waves also share `hws`,
+// kPolGroupWave * wave_acc h stores of [L][64][16]
+hipError_t launch_policy_seq_eval_groups(const PolSeqIO &io, const int32_t *order, const int32_t *segments,
+                                         const PolSeqGroupSpec *specs, uint32_t nseg, float *ws, PolGroupEntry *table,
+                                         PolUpload *uploads, hipStream_t st);
+hipError_t launch_policy_seq_grad_groups(const PolSeqIO &io, const int32_t *order, const int32_t *segments,
+                                         const PolSeqGroupSpec *specs, uint32_t nseg, const PolGroupWave *waves,
+                                         const PolSeqGroupGrads *grads, uint32_t nwaves, float *ws, PolGroupEntry *table,
+                                         PolUpload *uploads, float *slabs, uint64_t slab_stride, float *stash, float *hws,
+                                         uint32_t wave_acc, hipStream_t st);
+// sequence_segments: the columns sorted by net_id (stable, nkeys <= 256 keys)
+// into `order` [B] and their [lo, hi) into `segments` [nkeys][2]; `counts` holds
+// policy_seq_order_workspace(B) bytes
+size_t policy_seq_order_workspace(uint64_t B);
+hipError_t launch_policy_seq_order(const int32_t *net_id, uint64_t B, uint32_t nkeys, int32_t *order, int32_t *segments,
+                                   uint32_t *counts, hipStream_t st);
 
 }  // namespace mbots

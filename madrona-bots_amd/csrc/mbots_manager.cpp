@@ -3544,6 +3544,26 @@ int groups_plan(const mbots_policy_net *nets, uint32_t groups, uint64_t n, Group
     return MBOTS_OK;
 }
 
+// the host path reads the segments: 0 <= lo <= hi <= n, pairwise disjoint
+int segments_check_host(const int32_t *segments, uint32_t groups, uint64_t n, const char *what)
+{
+    std::vector<std::pair<int64_t, uint32_t>> by_lo;
+    for (uint32_t e = 0; e < 4u * groups; ++e) {
+        const int64_t lo = segments[2u * e], hi = segments[2u * e + 1u];
+        if (lo < 0 || lo > hi || hi > (int64_t)n)
+            return fail(MBOTS_E_INVALID, "the segment [" + std::to_string(lo) + ", " + std::to_string(hi) + ") of " +
+                                             pair_name(e) + " is not inside the " + std::to_string(n) + " " + what);
+        if (hi > lo) by_lo.emplace_back(lo, e);
+    }
+    std::sort(by_lo.begin(), by_lo.end());
+    for (size_t i = 1; i < by_lo.size(); ++i) {
+        const uint32_t a = by_lo[i - 1].second, b = by_lo[i].second;
+        if (segments[2u * a + 1u] > segments[2u * b])
+            return fail(MBOTS_E_INVALID, "the segments of " + pair_name(a) + " and " + pair_name(b) + " overlap");
+    }
+    return MBOTS_OK;
+}
+
 int groups_check(const mbots_policy_net *nets, uint32_t groups, const int32_t *segments, const float *obs,
                  const float *hidden, const int32_t *action, uint64_t n, void *ws, uint64_t ws_bytes, int32_t device,
                  GroupsPlan &P)
@@ -3559,22 +3579,7 @@ int groups_check(const mbots_policy_net *nets, uint32_t groups, const int32_t *s
                                          std::to_string(P.floats * sizeof(float)) +
                                          " needed (mbots_policy_groups_workspace)");
     if (device >= 0) return MBOTS_OK;
-    // the host path reads the segments: 0 <= lo <= hi <= n, pairwise disjoint
-    std::vector<std::pair<int64_t, uint32_t>> by_lo;
-    for (uint32_t e = 0; e < 4u * groups; ++e) {
-        const int64_t lo = segments[2u * e], hi = segments[2u * e + 1u];
-        if (lo < 0 || lo > hi || hi > (int64_t)n)
-            return fail(MBOTS_E_INVALID, "the segment [" + std::to_string(lo) + ", " + std::to_string(hi) + ") of " +
-                                             pair_name(e) + " is not inside the " + std::to_string(n) + " rows");
-        if (hi > lo) by_lo.emplace_back(lo, e);
-    }
-    std::sort(by_lo.begin(), by_lo.end());
-    for (size_t i = 1; i < by_lo.size(); ++i) {
-        const uint32_t a = by_lo[i - 1].second, b = by_lo[i].second;
-        if (segments[2u * a + 1u] > segments[2u * b])
-            return fail(MBOTS_E_INVALID, "the segments of " + pair_name(a) + " and " + pair_name(b) + " overlap");
-    }
-    return MBOTS_OK;
+    return segments_check_host(segments, groups, n, "rows");
 }
 }  // namespace
 
@@ -3751,6 +3756,258 @@ int mbots_policy_seq_grad(const struct mbots_policy_net *net, const float *obs, 
         return MBOTS_OK;
     }
     HIP_TRY(launch_policy_seq_grad(io, P.net, P.back, P.slabs, ws + P.stash_off, ws + P.h_off, P.out, as_stream(stream)));
+    return MBOTS_OK;
+}
+
+// ---- grouped evaluate_sequences (include/mbots.h "Every group's recurrent nets
+// in one call") ----
+namespace {
+// where a grouped sequence call's pieces lie in the caller's workspace (floats):
+// GroupsPlan's, and one wave's h stores
+struct SeqGroupsPlan {
+    std::vector<mbots::PolSeqGroupSpec> spec;   // [4 groups]; n_trunk == 0: no net
+    std::vector<uint32_t> present;
+    size_t table_off = 0, upload_off = 0, slab_off = 0, stash_off = 0, h_off = 0, floats = 0;
+    uint64_t slab_stride = 0;
+    uint32_t wave_acc = 0;
+};
+
+int seq_groups_plan(const mbots_policy_net *nets, uint32_t groups, uint32_t L, uint64_t B, SeqGroupsPlan &P)
+{
+    using namespace mbots;
+    if (!nets) return fail(MBOTS_E_INVALID, "null nets");
+    if (groups < 1 || groups > kPolMaxGroups)
+        return fail(MBOTS_E_INVALID, "1.." + std::to_string(kPolMaxGroups) + " groups, not " + std::to_string(groups));
+    if (B > 0x7FFFFFFFull) return fail(MBOTS_E_INVALID, "order addresses columns as int32: at most 2^31 - 1 sequences");
+    const uint32_t nseg = 4u * groups;
+    P.spec.assign(nseg, PolSeqGroupSpec{});
+    size_t off = 0, cpu_floats = 0;
+    auto take = [&](size_t floats) {
+        const size_t at = off;
+        off += (floats + 63u) & ~size_t(63);
+        return at;
+    };
+    P.table_off = take((size_t)nseg * sizeof(PolGroupEntry) / sizeof(float));
+    P.upload_off = take((size_t)nseg * kPolSeqGroupUploads * sizeof(PolUpload) / sizeof(float));
+    for (uint32_t e = 0; e < nseg; ++e) {
+        const mbots_policy_net &src = nets[e];
+        if (src.n_trunk == 0) continue;
+        PolNet d;
+        if (int rc = policy_describe(&src, d)) return fail_pair(rc, e);
+        if (!(d.has_memory && (d.flags & kPolMemoryIn)))
+            return fail(MBOTS_E_INVALID, pair_name(e) + ": sequences are evaluated by a net with a memory head and "
+                                                        "MBOTS_POLICY_MEMORY_IN (mbots_policy_eval_groups evaluates "
+                                                        "the nets without them)");
+        PolGroupSpec &s = P.spec[e].s;
+        s.w_off = off;
+        s.n_trunk = d.n_trunk;
+        s.H = d.H;
+        s.flags = d.flags;
+        for (uint32_t l = 0; l < d.n_trunk; ++l) {
+            s.act |= d.trunk[l].act << (8u * l);
+            s.w[l] = src.trunk[l].weight, s.b[l] = src.trunk[l].bias;
+        }
+        for (int i = 0; i < 2; ++i) {
+            s.w[kPolMaxTrunk + i] = src.actor[i].weight, s.b[kPolMaxTrunk + i] = src.actor[i].bias;
+            s.w[kPolMaxTrunk + 2 + i] = src.critic[i].weight, s.b[kPolMaxTrunk + 2 + i] = src.critic[i].bias;
+        }
+        P.spec[e].mw = src.memory.weight;
+        P.spec[e].mb = src.memory.bias;
+        PolGroupEntry E;
+        off += pol_group_entry(s, nullptr, E, nullptr, kPolSeqGroupUploads, true, nullptr, nullptr);
+        P.slab_stride = std::max<uint64_t>(P.slab_stride, E.slab_floats);
+        P.present.push_back(e);
+        // (the host path runs evaluate_sequences' own plan, one net at a time, in the same memory)
+        EvalPlan one;
+        if (int rc = eval_plan(&src, B, true, nullptr, one, EvalMode{true, L})) return fail_pair(rc, e);
+        cpu_floats = std::max(cpu_floats, one.floats);
+    }
+    P.wave_acc = (uint32_t)std::min<uint64_t>((B + kPolGradRows - 1u) / kPolGradRows, kPolGradAcc);
+    const size_t wave_blocks = (size_t)kPolGroupWave * P.wave_acc;
+    P.slab_off = take(wave_blocks * P.slab_stride);
+    P.stash_off = take(policy_grad_stash_floats((uint32_t)wave_blocks));
+    P.h_off = take(pol_seq_h_floats((uint32_t)wave_blocks, L));
+    P.floats = std::max(off, cpu_floats);
+    return MBOTS_OK;
+}
+
+int seq_groups_check(const mbots_policy_net *nets, uint32_t groups, const int32_t *order, const int32_t *segments,
+                     const float *obs, const int32_t *action, const int32_t *length, const float *hidden0, uint32_t L,
+                     uint64_t B, void *ws, uint64_t ws_bytes, int32_t device, SeqGroupsPlan &P)
+{
+    if (int rc = seq_groups_plan(nets, groups, L, B, P)) return rc;
+    if (!segments) return fail(MBOTS_E_INVALID, "null segments");
+    if (B && !order) return fail(MBOTS_E_INVALID, "null order");
+    if (B && L && (!obs || !action)) return fail(MBOTS_E_INVALID, "null obs or action");
+    if (B && (!length || !hidden0)) return fail(MBOTS_E_INVALID, "null length or hidden0");
+    if (!ws || ((uintptr_t)ws & 15u)) return fail(MBOTS_E_INVALID, "the workspace must be 16-byte aligned memory");
+    if (ws_bytes < P.floats * sizeof(float))
+        return fail(MBOTS_E_INVALID, "workspace of " + std::to_string(ws_bytes) + " bytes, " +
+                                         std::to_string(P.floats * sizeof(float)) +
+                                         " needed (mbots_policy_seq_groups_workspace)");
+    if (device >= 0) return MBOTS_OK;
+    // the host path reads everything: the segments, then every evaluated column
+    if (int rc = segments_check_host(segments, groups, B, "positions of order")) return rc;
+    std::vector<uint8_t> seen(B, 0);
+    for (uint32_t e : P.present)
+        for (int64_t p = segments[2u * e]; p < segments[2u * e + 1u]; ++p) {
+            const int64_t b = order[p];
+            const std::string at = pair_name(e) + ": order[" + std::to_string(p) + "] = " + std::to_string(b);
+            if (b < 0 || b >= (int64_t)B)
+                return fail(MBOTS_E_INVALID, at + " is outside the " + std::to_string(B) + " sequences");
+            if (seen[b]) return fail(MBOTS_E_INVALID, at + " names a sequence a second time");
+            seen[b] = 1;
+            if (length[b] < 0 || (uint32_t)length[b] > L)
+                return fail(MBOTS_E_INVALID, pair_name(e) + ": length " + std::to_string(length[b]) + " of sequence " +
+                                                 std::to_string(b) + " is outside [0, " + std::to_string(L) + "]");
+            for (int32_t k = 0; k < length[b]; ++k) {
+                const int32_t a = action[(uint64_t)k * B + b];
+                if (a < 0 || a >= mbots::kPolActions)
+                    return fail(MBOTS_E_INVALID, pair_name(e) + ": action " + std::to_string(a) + " of step " +
+                                                     std::to_string(k) + " of sequence " + std::to_string(b) +
+                                                     " is outside 0..5");
+            }
+        }
+    return MBOTS_OK;
+}
+
+// the caller's gradient pointers of net `src`'s layers, in PolGradOut's slots
+void seq_grad_slots(const mbots_policy_grads &out, uint32_t n_trunk, float **w, float **b)
+{
+    using namespace mbots;
+    for (int i = 0; i < kPolSeqLayers; ++i) w[i] = b[i] = nullptr;
+    for (uint32_t l = 0; l < n_trunk; ++l) w[l] = out.trunk[l].weight, b[l] = out.trunk[l].bias;
+    for (int i = 0; i < 2; ++i) {
+        w[kPolMaxTrunk + i] = out.actor[i].weight, b[kPolMaxTrunk + i] = out.actor[i].bias;
+        w[kPolMaxTrunk + 2 + i] = out.critic[i].weight, b[kPolMaxTrunk + 2 + i] = out.critic[i].bias;
+    }
+    w[kPolGradLayers] = out.memory.weight, b[kPolGradLayers] = out.memory.bias;
+}
+}  // namespace
+
+int mbots_policy_seq_order(const int32_t *net_id, uint64_t B, uint32_t groups, int32_t *order, int32_t *segments,
+                           void *workspace, uint64_t workspace_bytes, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (groups < 1 || groups > kPolMaxGroups)
+        return fail(MBOTS_E_INVALID, "1.." + std::to_string(kPolMaxGroups) + " groups, not " + std::to_string(groups));
+    if (B > 0x7FFFFFFFull) return fail(MBOTS_E_INVALID, "order addresses columns as int32: at most 2^31 - 1 sequences");
+    if (!segments || (B && (!net_id || !order))) return fail(MBOTS_E_INVALID, "null argument");
+    const uint32_t nkeys = 4u * groups;
+    if (device < 0) {
+        // the stable counting sort on the host: count, scan, scatter in column order
+        std::vector<uint32_t> at(nkeys + 1u, 0u);
+        for (uint64_t b = 0; b < B; ++b)
+            if (pol_seq_key(net_id[b], nkeys)) ++at[(uint32_t)net_id[b] + 1u];
+        for (uint32_t k = 0; k < nkeys; ++k) {
+            at[k + 1u] += at[k];
+            segments[2u * k] = (int32_t)at[k];
+            segments[2u * k + 1u] = (int32_t)at[k + 1u];
+        }
+        for (uint64_t p = at[nkeys]; p < B; ++p) order[p] = -1;
+        for (uint64_t b = 0; b < B; ++b)
+            if (pol_seq_key(net_id[b], nkeys)) order[at[(uint32_t)net_id[b]]++] = (int32_t)b;
+        return MBOTS_OK;
+    }
+    const uint64_t need = policy_seq_order_workspace(B);
+    if (!workspace || ((uintptr_t)workspace & 3u) || workspace_bytes < need)
+        return fail(MBOTS_E_INVALID, "workspace of " + std::to_string(workspace_bytes) + " bytes, " + std::to_string(need) +
+                                         " needed (MBOTS_POLICY_SEQ_ORDER_WORKSPACE(B))");
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_policy_seq_order(net_id, B, nkeys, order, segments, static_cast<uint32_t *>(workspace),
+                                    as_stream(stream)));
+    return MBOTS_OK;
+}
+
+int mbots_policy_seq_groups_workspace(const struct mbots_policy_net *nets, uint32_t groups, uint32_t L, uint64_t B,
+                                      uint64_t *bytes)
+{
+    if (!bytes) return fail(MBOTS_E_INVALID, "null argument");
+    SeqGroupsPlan P;
+    if (int rc = seq_groups_plan(nets, groups, L, B, P)) return rc;
+    *bytes = P.floats * sizeof(float);
+    return MBOTS_OK;
+}
+
+int mbots_policy_seq_eval_groups(const struct mbots_policy_net *nets, uint32_t groups, const int32_t *order,
+                                 const int32_t *segments, const float *obs, const int32_t *action,
+                                 const int32_t *length, const float *hidden0, uint32_t L, uint64_t B, float *logp,
+                                 float *value, float *entropy, float *hidden, void *workspace, uint64_t workspace_bytes,
+                                 int32_t device, void *stream)
+{
+    using namespace mbots;
+    SeqGroupsPlan P;
+    if (int rc = seq_groups_check(nets, groups, order, segments, obs, action, length, hidden0, L, B, workspace,
+                                  workspace_bytes, device, P))
+        return rc;
+    const PolSeqIO io{obs, hidden0, action, length, nullptr, nullptr, nullptr, logp, value, entropy, hidden, L, B};
+    float *ws = static_cast<float *>(workspace);
+    if (device < 0) {
+        // columns of no segment, or of a pair without a net: +0
+        for (float *o : {logp, value, entropy})
+            if (o) std::fill(o, o + (uint64_t)L * B, 0.0f);
+        if (hidden) std::fill(hidden, hidden + (uint64_t)L * B * kHidden, 0.0f);
+        for (uint32_t e : P.present) {
+            const uint64_t lo = (uint64_t)segments[2u * e], len = (uint64_t)segments[2u * e + 1u] - lo;
+            if (!len) continue;
+            EvalPlan one;
+            if (int rc = eval_plan(&nets[e], len, true, ws, one, EvalMode{true, L})) return fail_pair(rc, e);
+            if (int rc = eval_upload(one, false, -1, nullptr)) return fail_pair(rc, e);
+            cpu::policy_seq_eval(one.net, io, PolSeqCols{order + lo, len});
+        }
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_policy_seq_eval_groups(io, order, segments, P.spec.data(), 4u * groups, ws,
+                                          reinterpret_cast<PolGroupEntry *>(ws + P.table_off),
+                                          reinterpret_cast<PolUpload *>(ws + P.upload_off), as_stream(stream)));
+    return MBOTS_OK;
+}
+
+int mbots_policy_seq_grad_groups(const struct mbots_policy_net *nets, uint32_t groups, const int32_t *order,
+                                 const int32_t *segments, const float *obs, const int32_t *action,
+                                 const int32_t *length, const float *hidden0, uint32_t L, uint64_t B,
+                                 const float *g_logp, const float *g_value, const float *g_entropy,
+                                 const struct mbots_policy_grads *out, void *workspace, uint64_t workspace_bytes,
+                                 int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (!out) return fail(MBOTS_E_INVALID, "null argument");
+    SeqGroupsPlan P;
+    if (int rc = seq_groups_check(nets, groups, order, segments, obs, action, length, hidden0, L, B, workspace,
+                                  workspace_bytes, device, P))
+        return rc;
+    const PolSeqIO io{obs, hidden0, action, length, g_logp, g_value, g_entropy, nullptr, nullptr, nullptr, nullptr, L, B};
+    float *ws = static_cast<float *>(workspace);
+    if (device < 0) {
+        for (uint32_t e : P.present) {
+            const uint64_t lo = (uint64_t)segments[2u * e], len = (uint64_t)segments[2u * e + 1u] - lo;
+            EvalPlan one;
+            if (int rc = eval_plan(&nets[e], len, true, ws, one, EvalMode{true, L})) return fail_pair(rc, e);
+            seq_grad_slots(out[e], one.net.n_trunk, one.out.w, one.out.b);
+            if (int rc = eval_upload(one, true, -1, nullptr)) return fail_pair(rc, e);
+            cpu::policy_seq_grad(one.net, io, one.slabs, ws + one.h_off, one.out, PolSeqCols{order + lo, len});
+        }
+        return MBOTS_OK;
+    }
+    // the present segments in waves, each with the pointers its reduce writes
+    std::vector<PolGroupWave> waves((P.present.size() + kPolGroupWave - 1u) / kPolGroupWave);
+    std::vector<PolSeqGroupGrads> grads(waves.size());
+    for (size_t i = 0; i < P.present.size(); ++i) {
+        const uint32_t e = P.present[i], c = (uint32_t)(i % kPolGroupWave);
+        PolGroupWave &W = waves[i / kPolGroupWave];
+        PolSeqGroupGrads &O = grads[i / kPolGroupWave];
+        if (c == 0) W = PolGroupWave{}, O = PolSeqGroupGrads{};
+        W.seg[c] = e;
+        W.n = c + 1u;
+        seq_grad_slots(out[e], P.spec[e].s.n_trunk, O.w[c], O.b[c]);
+    }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(launch_policy_seq_grad_groups(io, order, segments, P.spec.data(), 4u * groups, waves.data(), grads.data(),
+                                          (uint32_t)waves.size(), ws,
+                                          reinterpret_cast<PolGroupEntry *>(ws + P.table_off),
+                                          reinterpret_cast<PolUpload *>(ws + P.upload_off), ws + P.slab_off,
+                                          P.slab_stride, ws + P.stash_off, ws + P.h_off, P.wave_acc, as_stream(stream)));
     return MBOTS_OK;
 }
 

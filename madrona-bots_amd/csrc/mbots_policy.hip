@@ -767,10 +767,11 @@ __global__ __launch_bounds__(64) void policy_groups_setup_kernel(PolGroupSpecs S
 }
 
 // every net's weights into the fragment orders: block (x, layer, net) of the
-// repack list (fwd_only: the transposed layers are not wanted)
+// repack list, gridDim.y entries per net (fwd_only: the transposed layers are
+// not wanted)
 __global__ __launch_bounds__(256) void policy_repack_groups_kernel(const PolUpload *uploads, uint32_t fwd_only)
 {
-    const PolUpload L = uploads[(size_t)blockIdx.z * kPolGroupUploads + blockIdx.y];
+    const PolUpload L = uploads[(size_t)blockIdx.z * gridDim.y + blockIdx.y];
     if (L.w_dst == nullptr || (fwd_only && L.tr)) return;
     pol_repack_layer(L);
 }
@@ -901,13 +902,45 @@ constexpr size_t kPolSeqEvalLds = (2 * kPolTile + kPolRows * (kPolLogitStride + 
 constexpr size_t kPolSeqGradLds =
     (4 * kPolTile + kPolRows * (kPolLogitStride + 1) + kPolHTile + kPolRows * kPolDmStride + kPolRows) * sizeof(float);
 
+// A tile's columns.  kIndex false: the batch's own, b0 + row.  kIndex true: the
+// entries idx[0 .. nb) of `order`, kept in s_col; an entry outside [0, B) (and
+// every row past nb) is kPolNoColumn there -- a column of length 0 that is
+// neither read nor written.
+// element (k, row's column) of an [L][B] array; e0 = k B + b0
+template <bool kIndex>
+__device__ __forceinline__ uint64_t pol_seq_elem(const PolSeqIO &A, const uint32_t *s_col, uint32_t k, uint64_t e0,
+                                                 uint32_t row)
+{
+    if constexpr (kIndex) return (uint64_t)k * A.B + s_col[row];
+    else return e0 + row;
+}
+template <bool kIndex> __device__ __forceinline__ bool pol_seq_has_col(const uint32_t *s_col, uint32_t nb, uint32_t row)
+{
+    if constexpr (kIndex) return s_col[row] != kPolNoColumn;
+    else return row < nb;
+}
+
 // the lengths of the tile's columns (clamped to [0, L]; 0 past B) into s_len, and the largest
-__device__ __forceinline__ uint32_t pol_seq_lengths(uint32_t *s_len, const PolSeqIO &A, uint64_t b0, uint32_t nb,
-                                                    uint32_t t)
+template <bool kIndex>
+__device__ __forceinline__ uint32_t pol_seq_lengths(uint32_t *s_len, uint32_t *s_col, const PolSeqIO &A,
+                                                    const int32_t *idx, uint64_t b0, uint32_t nb, uint32_t t)
 {
     __syncthreads();   // the previous tile's readers
     if (t < (uint32_t)kPolRows) {
-        const int32_t n = t < nb ? A.length[b0 + t] : 0;
+        int32_t n = 0;
+        if constexpr (kIndex) {
+            uint32_t col = kPolNoColumn;
+            if (t < nb) {
+                const int32_t c = idx[t];
+                if (c >= 0 && (uint64_t)c < A.B) {
+                    col = (uint32_t)c;
+                    n = A.length[col];
+                }
+            }
+            s_col[t] = col;
+        } else {
+            n = t < nb ? A.length[b0 + t] : 0;
+        }
         s_len[t] = n < 0 ? 0u : min((uint32_t)n, A.L);
     }
     __syncthreads();
@@ -918,89 +951,131 @@ __device__ __forceinline__ uint32_t pol_seq_lengths(uint32_t *s_len, const PolSe
 
 // step k's inputs of the tile: X[64][kp] = obs[k, b0 + row] | h[row], +0 for the
 // pads and the absent elements (h: [64][16], LDS or the block's store)
+// (kIndex: a row's 69 obs floats lie at its own column, s_col[row]; they are
+// contiguous whichever column that is.)
+template <bool kIndex>
 __device__ __forceinline__ void pol_stage_seq(float *x, const PolSeqIO &A, uint32_t k, uint64_t b0,
-                                              const uint32_t *s_len, const float *h, uint32_t kp, uint32_t t)
+                                              const uint32_t *s_len, const uint32_t *s_col, const float *h, uint32_t kp,
+                                              uint32_t t)
 {
     const float *o = A.obs + ((uint64_t)k * A.B + b0) * kPolObs;
     for (uint32_t i = t; i < (uint32_t)kPolRows * kp; i += 256u) {
         const uint32_t row = i / kp, c = i - row * kp;
         float v = 0.0f;
         if (k < s_len[row]) {
-            if (c < (uint32_t)kPolObs) v = o[(size_t)row * kPolObs + c];
-            else if (c < (uint32_t)(kPolObs + kHidden)) v = h[row * kHidden + (c - kPolObs)];
+            if (c < (uint32_t)kPolObs) {
+                if constexpr (kIndex) v = A.obs[((uint64_t)k * A.B + s_col[row]) * kPolObs + c];
+                else v = o[(size_t)row * kPolObs + c];
+            } else if (c < (uint32_t)(kPolObs + kHidden)) v = h[row * kHidden + (c - kPolObs)];
         }
         x[row * kPolStride + c] = v;
     }
 }
 
-// logp, value, entropy (and the h_k read) of every element, grid-stride over
-// the column tiles, k ascending inside a tile with h carried in LDS
-__global__ __launch_bounds__(256, 2) void policy_seq_eval_kernel(PolSeqIO A, PolNet net)
+// One column tile of evaluate_sequences: logp, value, entropy (and the h_k read)
+// of every element of its nb columns, k ascending with h carried in LDS.  kTable:
+// `net` lies in device memory (the grouped call's descriptor table).  kIndex:
+// the columns are idx[0 .. nb) (pol_seq_col), else b0 .. b0 + nb.
+template <bool kTable, bool kIndex>
+__device__ __forceinline__ void pol_seq_eval_tile(const PolSeqIO &A, const PolNet &net, const int32_t *idx, uint64_t b0,
+                                                  uint32_t nb, float *s_pol, uint32_t t, uint32_t wv, uint32_t lane)
 {
-    extern __shared__ float s_pol[];
     float *buf0 = s_pol, *buf1 = s_pol + kPolTile;
     float *s_logit = s_pol + 2 * kPolTile, *s_val = s_logit + kPolRows * kPolLogitStride;
     float *s_h = s_val + kPolRows;
     uint32_t *s_len = reinterpret_cast<uint32_t *>(s_h + kPolHTile);
+    uint32_t *s_col = s_len + kPolRows;   // (kIndex only)
+    const uint32_t T = pol_u<kTable>(net.n_trunk), kp0 = pol_u<kTable>(net.trunk[0].kp);
+
+    const uint32_t maxlen = pol_seq_lengths<kIndex>(s_len, s_col, A, idx, b0, nb, t);
+    for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) {
+        if constexpr (kIndex) {
+            const uint32_t col = s_col[i >> 4];
+            s_h[i] = col != kPolNoColumn ? A.hidden0[(uint64_t)col * kHidden + (i & 15u)] : 0.0f;
+        } else {
+            s_h[i] = (i >> 4) < nb ? A.hidden0[b0 * kHidden + i] : 0.0f;
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = 0; k < maxlen; ++k) {
+        const uint64_t e0 = (uint64_t)k * A.B + b0;
+        if (A.hidden)
+            for (uint32_t i = t; i < nb * (uint32_t)kHidden; i += 256u) {
+                const float v = k < s_len[i >> 4] ? s_h[i] : 0.0f;
+                if constexpr (kIndex) {
+                    const uint32_t col = s_col[i >> 4];
+                    if (col != kPolNoColumn) A.hidden[((uint64_t)k * A.B + col) * kHidden + (i & 15u)] = v;
+                } else {
+                    A.hidden[e0 * kHidden + i] = v;
+                }
+            }
+        pol_stage_seq<kIndex>(buf0, A, k, b0, s_len, s_col, s_h, kp0, t);
+        __syncthreads();
+        float *cur = buf0, *oth = buf1;
+        for (uint32_t l = 0; l < T; ++l) {
+            pol_layer(pol_pick<kTable>(net.trunk[l]), (int)pol_u<kTable>(net.trunk[l].act), cur, oth, kPolStride, wv, 0u,
+                      lane);
+            __syncthreads();
+            float *sw = cur;
+            cur = oth;
+            oth = sw;
+        }
+        pol_layer(pol_pick<kTable>(net.actor[0]), kActRelu, cur, oth, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(pol_pick<kTable>(net.actor[1]), kActIdentity, oth, s_logit, kPolLogitStride, wv, 0u, lane);
+        pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_h, kHidden, wv, 1u, lane);   // h_{k+1}, as act() writes it
+        __syncthreads();
+        pol_layer(pol_pick<kTable>(net.critic[0]), kActRelu, cur, oth, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(pol_pick<kTable>(net.critic[1]), kActIdentity, oth, s_val, 1u, wv, 0u, lane);
+        __syncthreads();
+        if (t < nb && pol_seq_has_col<kIndex>(s_col, nb, t)) {
+            const uint64_t e = pol_seq_elem<kIndex>(A, s_col, k, e0, t);
+            float logp = 0.0f, ent = 0.0f, val = 0.0f;
+            if (k < s_len[t]) {
+                float z[kPolActions], dz[kPolActions];
+#pragma unroll
+                for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
+                pol_head(z, A.action[e], 0.0f, 0.0f, &logp, &ent, dz);
+                val = s_val[t];
+            }
+            if (A.logp) A.logp[e] = logp;
+            if (A.value) A.value[e] = val;
+            if (A.entropy) A.entropy[e] = ent;
+        }
+    }
+    // the steps past the tile's largest length
+    for (uint32_t k = maxlen; k < A.L; ++k) {
+        const uint64_t e0 = (uint64_t)k * A.B + b0;
+        if (t < nb && pol_seq_has_col<kIndex>(s_col, nb, t)) {
+            const uint64_t e = pol_seq_elem<kIndex>(A, s_col, k, e0, t);
+            if (A.logp) A.logp[e] = 0.0f;
+            if (A.value) A.value[e] = 0.0f;
+            if (A.entropy) A.entropy[e] = 0.0f;
+        }
+        if (A.hidden)
+            for (uint32_t i = t; i < nb * (uint32_t)kHidden; i += 256u) {
+                if constexpr (kIndex) {
+                    const uint32_t col = s_col[i >> 4];
+                    if (col != kPolNoColumn) A.hidden[((uint64_t)k * A.B + col) * kHidden + (i & 15u)] = 0.0f;
+                } else {
+                    A.hidden[e0 * kHidden + i] = 0.0f;
+                }
+            }
+    }
+}
+
+// every column of the batch through one net, grid-stride over the column tiles
+__global__ __launch_bounds__(256, 2) void policy_seq_eval_kernel(PolSeqIO A, PolNet net)
+{
+    extern __shared__ float s_pol[];
     const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
     const uint64_t tiles = (A.B + kPolRows - 1u) / kPolRows;
 
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const uint64_t b0 = tile * kPolRows;
         const uint32_t nb = A.B - b0 < (uint64_t)kPolRows ? (uint32_t)(A.B - b0) : (uint32_t)kPolRows;
-        const uint32_t maxlen = pol_seq_lengths(s_len, A, b0, nb, t);
-        for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u)
-            s_h[i] = (i >> 4) < nb ? A.hidden0[b0 * kHidden + i] : 0.0f;
-        __syncthreads();
-        for (uint32_t k = 0; k < maxlen; ++k) {
-            const uint64_t e0 = (uint64_t)k * A.B + b0;
-            if (A.hidden)
-                for (uint32_t i = t; i < nb * (uint32_t)kHidden; i += 256u)
-                    A.hidden[e0 * kHidden + i] = k < s_len[i >> 4] ? s_h[i] : 0.0f;
-            pol_stage_seq(buf0, A, k, b0, s_len, s_h, net.trunk[0].kp, t);
-            __syncthreads();
-            float *cur = buf0, *oth = buf1;
-            for (uint32_t l = 0; l < net.n_trunk; ++l) {
-                pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
-                __syncthreads();
-                float *sw = cur;
-                cur = oth;
-                oth = sw;
-            }
-            pol_layer(net.actor[0], kActRelu, cur, oth, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            pol_layer(net.actor[1], kActIdentity, oth, s_logit, kPolLogitStride, wv, 0u, lane);
-            pol_layer(net.memory, kActTanh, cur, s_h, kHidden, wv, 1u, lane);   // h_{k+1}, as act() writes it
-            __syncthreads();
-            pol_layer(net.critic[0], kActRelu, cur, oth, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            pol_layer(net.critic[1], kActIdentity, oth, s_val, 1u, wv, 0u, lane);
-            __syncthreads();
-            if (t < nb) {
-                float logp = 0.0f, ent = 0.0f, val = 0.0f;
-                if (k < s_len[t]) {
-                    float z[kPolActions], dz[kPolActions];
-#pragma unroll
-                    for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
-                    pol_head(z, A.action[e0 + t], 0.0f, 0.0f, &logp, &ent, dz);
-                    val = s_val[t];
-                }
-                if (A.logp) A.logp[e0 + t] = logp;
-                if (A.value) A.value[e0 + t] = val;
-                if (A.entropy) A.entropy[e0 + t] = ent;
-            }
-        }
-        // the steps past the tile's largest length
-        for (uint32_t k = maxlen; k < A.L; ++k) {
-            const uint64_t e0 = (uint64_t)k * A.B + b0;
-            if (t < nb) {
-                if (A.logp) A.logp[e0 + t] = 0.0f;
-                if (A.value) A.value[e0 + t] = 0.0f;
-                if (A.entropy) A.entropy[e0 + t] = 0.0f;
-            }
-            if (A.hidden)
-                for (uint32_t i = t; i < nb * (uint32_t)kHidden; i += 256u) A.hidden[e0 * kHidden + i] = 0.0f;
-        }
+        pol_seq_eval_tile<false, false>(A, net, nullptr, b0, nb, s_pol, t, wv, lane);
     }
 }
 
@@ -1011,157 +1086,379 @@ struct PolSeqGradDev {
     float *hws;           // [blocks][L][64][16]
 };
 
-// Block b is accumulator b and takes the column tiles b, b + kPolGradAcc, ...
-// in order.  Per tile: a forward sweep that keeps only h_k (in the block's
-// store); then for k descending that step's forward again from (obs_k, h_k),
-// and policy_eval_kernel's backward with the memory head's gradients, d mem_pre
-// from the carried dh tile, and the next dh from the first layer's gradient.
-__global__ __launch_bounds__(256, 1) void policy_seq_grad_kernel(PolSeqIO A, PolNet net, PolSeqGradDev G)
+// One column tile of evaluate_sequences' backward pass, continuing the chains
+// of the block's slab (`started`: they have begun; returns whether they have
+// now): a forward sweep that keeps
+// only h_k (in the block's store hk, [L][64][16]); then for k descending that
+// step's forward again from (obs_k, h_k), and policy_eval_kernel's backward with
+// the memory head's gradients (slot kPolGradLayers), d mem_pre from the carried
+// dh tile, and the next dh from the first layer's gradient (back.trunk[0], the
+// H -> 16 layer over W0[:, 69:85]).  kTable, kIndex, idx, b0: as
+// pol_seq_eval_tile; layer l's dW at sw[l], db at sb[l] of the slab.
+template <bool kTable, bool kIndex>
+__device__ __forceinline__ bool pol_seq_grad_tile(const PolSeqIO &A, const PolNet &net, const PolNet &back,
+                                                  const uint32_t *sw, const uint32_t *sb, float *slab, float *stash,
+                                                  float *hk, const int32_t *idx, uint64_t b0, uint32_t nb, bool started,
+                                                  float *s_pol, uint32_t t, uint32_t wv, uint32_t lane)
 {
-    extern __shared__ float s_pol[];
     float *buf0 = s_pol, *buf1 = s_pol + kPolTile, *ha = s_pol + 2 * kPolTile, *hc = s_pol + 3 * kPolTile;
     float *s_logit = s_pol + 4 * kPolTile, *s_val = s_logit + kPolRows * kPolLogitStride;
     float *s_hd = s_val + kPolRows;        // h during the sweep, dh on the way back
     float *s_dm = s_hd + kPolHTile;        // the memory head's output y, then d mem_pre
     uint32_t *s_len = reinterpret_cast<uint32_t *>(s_dm + kPolRows * kPolDmStride);
+    uint32_t *s_col = s_len + kPolRows;    // (kIndex only)
+    const uint32_t T = pol_u<kTable>(net.n_trunk), kp0 = pol_u<kTable>(net.trunk[0].kp);
+    constexpr int kM = kPolGradLayers;   // the memory head's slot
+    auto dw = [&](int l) { return slab + pol_u<kTable>(sw[l]); };
+    auto db = [&](int l) { return slab + pol_u<kTable>(sb[l]); };
+
+    const uint32_t maxlen = pol_seq_lengths<kIndex>(s_len, s_col, A, idx, b0, nb, t);
+    // ---- the forward sweep: h_k of every step ----
+    for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) {
+        if constexpr (kIndex) {
+            const uint32_t col = s_col[i >> 4];
+            s_hd[i] = col != kPolNoColumn ? A.hidden0[(uint64_t)col * kHidden + (i & 15u)] : 0.0f;
+        } else {
+            s_hd[i] = (i >> 4) < nb ? A.hidden0[b0 * kHidden + i] : 0.0f;
+        }
+    }
+    __syncthreads();
+    for (uint32_t k = 0; k < maxlen; ++k) {
+        for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) hk[(size_t)k * kPolHTile + i] = s_hd[i];
+        if (k + 1u == maxlen) break;
+        pol_stage_seq<kIndex>(buf0, A, k, b0, s_len, s_col, s_hd, kp0, t);
+        __syncthreads();
+        float *cur = buf0, *oth = buf1;
+        for (uint32_t l = 0; l < T; ++l) {
+            pol_layer(pol_pick<kTable>(net.trunk[l]), (int)pol_u<kTable>(net.trunk[l].act), cur, oth, kPolStride, wv, 0u,
+                      lane);
+            __syncthreads();
+            float *sw_ = cur;
+            cur = oth;
+            oth = sw_;
+        }
+        pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_hd, kHidden, wv, 0u, lane);
+        __syncthreads();
+    }
+    __syncthreads();
+    for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) s_hd[i] = 0.0f;   // dh past the last step
+    // ---- backward in time ----
+    for (uint32_t k = maxlen; k-- > 0u;) {
+        const float *h = hk + (size_t)k * kPolHTile;
+        const uint64_t e0 = (uint64_t)k * A.B + b0;
+        const bool first = !started;
+        pol_stage_seq<kIndex>(buf0, A, k, b0, s_len, s_col, h, kp0, t);
+        __syncthreads();
+        float *cur = buf0, *oth = buf1;
+        for (uint32_t l = 0; l < T; ++l) {
+            pol_layer(pol_pick<kTable>(net.trunk[l]), (int)pol_u<kTable>(net.trunk[l].act), cur, oth, kPolStride, wv, 0u,
+                      lane);
+            __syncthreads();
+            float *sw_ = cur;
+            cur = oth;
+            oth = sw_;
+            if (l + 1u < T) pol_copy_tile(stash + (size_t)l * kPolTile, cur, t);
+        }
+        pol_layer(pol_pick<kTable>(net.actor[0]), kActRelu, cur, ha, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(pol_pick<kTable>(net.actor[1]), kActIdentity, ha, s_logit, kPolLogitStride, wv, 0u, lane);
+        pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_dm, kPolDmStride, wv, 1u, lane);
+        __syncthreads();
+        pol_layer(pol_pick<kTable>(net.critic[0]), kActRelu, cur, hc, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer(pol_pick<kTable>(net.critic[1]), kActIdentity, hc, s_val, 1u, wv, 0u, lane);
+        __syncthreads();
+        // d loss / d logits | d value as in policy_eval_kernel, and d mem_pre = dh (1 - y^2)
+        if (t < (uint32_t)kPolRows) {
+            float dz[kPolActions] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, dv = 0.0f;
+            const bool present = k < s_len[t];
+            if (present) {
+                const uint64_t e = pol_seq_elem<kIndex>(A, s_col, k, e0, t);
+                float z[kPolActions];
+#pragma unroll
+                for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
+                const float gl = A.g_logp ? A.g_logp[e] : 0.0f, ge = A.g_entropy ? A.g_entropy[e] : 0.0f;
+                float logp, ent;
+                pol_head(z, A.action[e], gl, ge, &logp, &ent, dz);
+                if (A.g_value) dv = A.g_value[e];
+            }
+            float *o = oth + t * kPolStride;
+#pragma unroll
+            for (int i = 0; i < 32; ++i) o[i] = 0.0f;
+            if (present) {
+#pragma unroll
+                for (int i = 0; i < kPolActions; ++i) o[i] = dz[i];
+                o[16] = dv;
+            }
+        }
+        {
+            const uint32_t row = t >> 2, c0 = (t & 3u) * 4u;
+            const bool present = k < s_len[row];
+#pragma unroll
+            for (uint32_t u = 0; u < 4u; ++u) {
+                float *y = s_dm + row * kPolDmStride + c0 + u;
+                *y = present ? s_hd[row * kHidden + c0 + u] * pol_activation_grad(kActTanh, *y) : 0.0f;
+            }
+        }
+        __syncthreads();
+        // heads' second layers, and the memory head
+        pol_grad_w(pol_pick<kTable>(net.actor[1]), oth, ha, dw(kPolMaxTrunk + 1), db(kPolMaxTrunk + 1), first, wv, lane, t);
+        pol_grad_w(pol_pick<kTable>(net.critic[1]), oth + 16, hc, dw(kPolMaxTrunk + 3), db(kPolMaxTrunk + 3), first, wv,
+                   lane, t);
+        pol_grad_w<kPolDmStride>(pol_pick<kTable>(net.memory), s_dm, cur, dw(kM), db(kM), first, wv, lane, t);
+        __syncthreads();
+        pol_layer<true>(pol_pick<kTable>(back.actor[1]), kActRelu, oth, ha, kPolStride, wv, 0u, lane);
+        pol_layer<true>(pol_pick<kTable>(back.critic[1]), kActRelu, oth + 16, hc, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        // heads' first layers; the trunk's last output receives the actor's input
+        // gradient, plus the critic's, plus the memory head's, times its
+        // activation's derivative
+        pol_grad_w(pol_pick<kTable>(net.actor[0]), ha, cur, dw(kPolMaxTrunk), db(kPolMaxTrunk), first, wv, lane, t);
+        pol_grad_w(pol_pick<kTable>(net.critic[0]), hc, cur, dw(kPolMaxTrunk + 2), db(kPolMaxTrunk + 2), first, wv, lane,
+                   t);
+        pol_layer<true>(pol_pick<kTable>(back.actor[0]), -1, ha, oth, kPolStride, wv, 0u, lane);
+        __syncthreads();
+        pol_layer<true>(pol_pick<kTable>(back.critic[0]), -1, hc, oth, kPolStride, wv, 0u, lane, oth);
+        __syncthreads();
+        pol_layer<true, kPolDmStride>(pol_pick<kTable>(back.memory), (int)pol_u<kTable>(net.trunk[T - 1u].act), s_dm, cur,
+                                      kPolStride, wv, 0u, lane, oth);
+        __syncthreads();
+        // the trunk, last layer first: d in `cur`, the layer's input in `oth`
+        for (uint32_t l = T; l-- > 0u;) {
+            if (l == 0u) pol_stage_seq<kIndex>(oth, A, k, b0, s_len, s_col, h, kp0, t);
+            else pol_copy_tile(oth, stash + (size_t)(l - 1u) * kPolTile, t);
+            __syncthreads();
+            pol_grad_w(pol_pick<kTable>(net.trunk[l]), cur, oth, dw((int)l), db((int)l), first, wv, lane, t);
+            __syncthreads();
+            if (l == 0u) break;
+            pol_layer<true>(pol_pick<kTable>(back.trunk[l]), (int)pol_u<kTable>(net.trunk[l - 1u].act), cur, oth,
+                            kPolStride, wv, 0u, lane);
+            __syncthreads();
+            float *sw_ = cur;
+            cur = oth;
+            oth = sw_;
+        }
+        // dh_k[c] = sum_j d0[j] W0[j][69 + c]
+        pol_layer<true>(pol_pick<kTable>(back.trunk[0]), -1, cur, s_hd, kHidden, wv, 0u, lane);
+        __syncthreads();
+        started = true;
+    }
+    return started;
+}
+
+// Block b is accumulator b and takes the column tiles b, b + kPolGradAcc, ...
+// in order.
+__global__ __launch_bounds__(256, 1) void policy_seq_grad_kernel(PolSeqIO A, PolNet net, PolSeqGradDev G)
+{
+    extern __shared__ float s_pol[];
     const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
     const uint64_t tiles = (A.B + kPolRows - 1u) / kPolRows;
     const PolGradSlabs &S = G.slabs;
     float *slab = S.base + (size_t)blockIdx.x * S.slab_floats;
     float *stash = G.stash + (size_t)blockIdx.x * kPolStashTiles * kPolTile;
     float *hk = G.hws + (size_t)blockIdx.x * A.L * kPolHTile;
-    const uint32_t T = net.n_trunk, kp0 = net.trunk[0].kp;
-    constexpr int kM = kPolGradLayers;   // the memory head's slot
     bool started = false;                // the slab's chains have begun
 
     for (uint64_t tile = blockIdx.x; tile < tiles; tile += (uint64_t)kPolGradAcc) {
         const uint64_t b0 = tile * kPolRows;
         const uint32_t nb = A.B - b0 < (uint64_t)kPolRows ? (uint32_t)(A.B - b0) : (uint32_t)kPolRows;
-        const uint32_t maxlen = pol_seq_lengths(s_len, A, b0, nb, t);
-        // ---- the forward sweep: h_k of every step ----
-        for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u)
-            s_hd[i] = (i >> 4) < nb ? A.hidden0[b0 * kHidden + i] : 0.0f;
-        __syncthreads();
-        for (uint32_t k = 0; k < maxlen; ++k) {
-            for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) hk[(size_t)k * kPolHTile + i] = s_hd[i];
-            if (k + 1u == maxlen) break;
-            pol_stage_seq(buf0, A, k, b0, s_len, s_hd, kp0, t);
-            __syncthreads();
-            float *cur = buf0, *oth = buf1;
-            for (uint32_t l = 0; l < T; ++l) {
-                pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
-                __syncthreads();
-                float *sw = cur;
-                cur = oth;
-                oth = sw;
-            }
-            pol_layer(net.memory, kActTanh, cur, s_hd, kHidden, wv, 0u, lane);
-            __syncthreads();
-        }
-        __syncthreads();
-        for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) s_hd[i] = 0.0f;   // dh past the last step
-        // ---- backward in time ----
-        for (uint32_t k = maxlen; k-- > 0u;) {
-            const float *h = hk + (size_t)k * kPolHTile;
-            const uint64_t e0 = (uint64_t)k * A.B + b0;
-            const bool first = !started;
-            pol_stage_seq(buf0, A, k, b0, s_len, h, kp0, t);
-            __syncthreads();
-            float *cur = buf0, *oth = buf1;
-            for (uint32_t l = 0; l < T; ++l) {
-                pol_layer(net.trunk[l], (int)net.trunk[l].act, cur, oth, kPolStride, wv, 0u, lane);
-                __syncthreads();
-                float *sw = cur;
-                cur = oth;
-                oth = sw;
-                if (l + 1u < T) pol_copy_tile(stash + (size_t)l * kPolTile, cur, t);
-            }
-            pol_layer(net.actor[0], kActRelu, cur, ha, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            pol_layer(net.actor[1], kActIdentity, ha, s_logit, kPolLogitStride, wv, 0u, lane);
-            pol_layer(net.memory, kActTanh, cur, s_dm, kPolDmStride, wv, 1u, lane);
-            __syncthreads();
-            pol_layer(net.critic[0], kActRelu, cur, hc, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            pol_layer(net.critic[1], kActIdentity, hc, s_val, 1u, wv, 0u, lane);
-            __syncthreads();
-            // d loss / d logits | d value as in policy_eval_kernel, and d mem_pre = dh (1 - y^2)
-            if (t < (uint32_t)kPolRows) {
-                float dz[kPolActions] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f}, dv = 0.0f;
-                const bool present = k < s_len[t];
-                if (present) {
-                    const uint64_t e = e0 + t;
-                    float z[kPolActions];
-#pragma unroll
-                    for (int i = 0; i < kPolActions; ++i) z[i] = s_logit[t * kPolLogitStride + i];
-                    const float gl = A.g_logp ? A.g_logp[e] : 0.0f, ge = A.g_entropy ? A.g_entropy[e] : 0.0f;
-                    float logp, ent;
-                    pol_head(z, A.action[e], gl, ge, &logp, &ent, dz);
-                    if (A.g_value) dv = A.g_value[e];
-                }
-                float *o = oth + t * kPolStride;
-#pragma unroll
-                for (int i = 0; i < 32; ++i) o[i] = 0.0f;
-                if (present) {
-#pragma unroll
-                    for (int i = 0; i < kPolActions; ++i) o[i] = dz[i];
-                    o[16] = dv;
-                }
-            }
-            {
-                const uint32_t row = t >> 2, c0 = (t & 3u) * 4u;
-                const bool present = k < s_len[row];
-#pragma unroll
-                for (uint32_t u = 0; u < 4u; ++u) {
-                    float *y = s_dm + row * kPolDmStride + c0 + u;
-                    *y = present ? s_hd[row * kHidden + c0 + u] * pol_activation_grad(kActTanh, *y) : 0.0f;
-                }
-            }
-            __syncthreads();
-            // heads' second layers, and the memory head
-            pol_grad_w(net.actor[1], oth, ha, slab + S.w[kPolMaxTrunk + 1], slab + S.b[kPolMaxTrunk + 1], first, wv, lane, t);
-            pol_grad_w(net.critic[1], oth + 16, hc, slab + S.w[kPolMaxTrunk + 3], slab + S.b[kPolMaxTrunk + 3], first, wv,
-                       lane, t);
-            pol_grad_w<kPolDmStride>(net.memory, s_dm, cur, slab + S.w[kM], slab + S.b[kM], first, wv, lane, t);
-            __syncthreads();
-            pol_layer<true>(G.back.actor[1], kActRelu, oth, ha, kPolStride, wv, 0u, lane);
-            pol_layer<true>(G.back.critic[1], kActRelu, oth + 16, hc, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            // heads' first layers; the trunk's last output receives the actor's input
-            // gradient, plus the critic's, plus the memory head's, times its
-            // activation's derivative
-            pol_grad_w(net.actor[0], ha, cur, slab + S.w[kPolMaxTrunk], slab + S.b[kPolMaxTrunk], first, wv, lane, t);
-            pol_grad_w(net.critic[0], hc, cur, slab + S.w[kPolMaxTrunk + 2], slab + S.b[kPolMaxTrunk + 2], first, wv, lane,
-                       t);
-            pol_layer<true>(G.back.actor[0], -1, ha, oth, kPolStride, wv, 0u, lane);
-            __syncthreads();
-            pol_layer<true>(G.back.critic[0], -1, hc, oth, kPolStride, wv, 0u, lane, oth);
-            __syncthreads();
-            pol_layer<true, kPolDmStride>(G.back.memory, (int)net.trunk[T - 1u].act, s_dm, cur, kPolStride, wv, 0u, lane,
-                                          oth);
-            __syncthreads();
-            // the trunk, last layer first: d in `cur`, the layer's input in `oth`
-            for (uint32_t l = T; l-- > 0u;) {
-                if (l == 0u) pol_stage_seq(oth, A, k, b0, s_len, h, kp0, t);
-                else pol_copy_tile(oth, stash + (size_t)(l - 1u) * kPolTile, t);
-                __syncthreads();
-                pol_grad_w(net.trunk[l], cur, oth, slab + S.w[l], slab + S.b[l], first, wv, lane, t);
-                __syncthreads();
-                if (l == 0u) break;
-                pol_layer<true>(G.back.trunk[l], (int)net.trunk[l - 1u].act, cur, oth, kPolStride, wv, 0u, lane);
-                __syncthreads();
-                float *sw = cur;
-                cur = oth;
-                oth = sw;
-            }
-            // dh_k[c] = sum_j d0[j] W0[j][69 + c]
-            pol_layer<true>(G.back.trunk[0], -1, cur, s_hd, kHidden, wv, 0u, lane);
-            __syncthreads();
-            started = true;
-        }
+        started = pol_seq_grad_tile<false, false>(A, net, G.back, S.w, S.b, slab, stash, hk, nullptr, b0, nb, started,
+                                                  s_pol, t, wv, lane);
     }
     if (!started)   // no step at all: the chains are their +0 starts
         for (size_t i = t; i < S.slab_floats; i += 256u) slab[i] = 0.0f;
+}
+
+// ---- grouped evaluate_sequences (mbots_policy.hpp; DESIGN.md "Grouped
+// evaluate_sequences") ----
+// the seq nets [S.first, S.first + S.n) into the descriptor table and the repack list
+__global__ __launch_bounds__(64) void policy_seq_groups_setup_kernel(PolSeqGroupSpecs S, float *ws, PolGroupEntry *table,
+                                                                     PolUpload *uploads)
+{
+    const uint32_t i = threadIdx.x;
+    if (i >= S.n) return;
+    const uint32_t e = S.first + i;
+    PolGroupEntry E;
+    pol_group_entry(S.s[i].s, ws, E, uploads + (size_t)e * kPolSeqGroupUploads, kPolSeqGroupUploads, true, S.s[i].mw,
+                    S.s[i].mb);
+    table[e] = E;
+}
+
+// the segment table of policy_eval_groups_kernel behind evaluate_sequences' tile
+// and the tile's 64 column indices
+constexpr size_t kPolSeqEvalTileLds = kPolSeqEvalLds + kPolRows * sizeof(uint32_t);
+constexpr size_t kPolSeqEvalGroupLds = kPolSeqEvalTileLds + (3u * kPolEvalMaxSegs + 4u) * sizeof(uint32_t);
+constexpr size_t kPolSeqGradGroupLds = kPolSeqGradLds + kPolRows * sizeof(uint32_t);
+static_assert(kPolSeqEvalGroupLds <= 80u * 1024u, "two blocks of policy_seq_eval_groups_kernel share a compute unit's LDS");
+static_assert(kPolSeqGradGroupLds <= 160u * 1024u, "a block of policy_seq_grad_groups_kernel fits a compute unit's LDS");
+
+// logp, value, entropy (and h_k) of every column of every segment that has a
+// net, grid-stride over the segments' tiles of 64 positions of `order` (a tile
+// never straddles two segments)
+__global__ __launch_bounds__(256, 2) void policy_seq_eval_groups_kernel(PolSeqIO A, const int32_t *order,
+                                                                        const int32_t *segments,
+                                                                        const PolGroupEntry *table, uint32_t nseg)
+{
+    extern __shared__ float s_pol[];
+    uint32_t *s_start = reinterpret_cast<uint32_t *>(s_pol) + kPolSeqEvalTileLds / sizeof(uint32_t);
+    uint32_t *s_len = s_start + kPolEvalMaxSegs, *s_scan = s_len + kPolEvalMaxSegs, *s_wsum = s_scan + kPolEvalMaxSegs;
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    {
+        uint32_t lo = 0, len = 0;
+        if (t < nseg && table[t].net.set) pol_segment(segments, t, A.B, lo, len);
+        s_start[t] = lo;
+        s_len[t] = len;
+        uint32_t incl = (len + kPolRows - 1u) / kPolRows;
+        for (uint32_t d = 1; d < 64u; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63u) s_wsum[wv] = incl;
+        __syncthreads();
+        for (uint32_t q = 0; q < wv; ++q) incl += s_wsum[q];
+        s_scan[t] = incl;
+        __syncthreads();
+    }
+    const uint32_t tiles = uniform(s_scan[kPolEvalMaxSegs - 1u]);
+
+    for (uint32_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        uint32_t lo = 0, hi = nseg - 1u;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (s_scan[mid] > tile) hi = mid;
+            else lo = mid + 1u;
+        }
+        const uint32_t e = uniform(lo);
+        const uint32_t rest = tile - (e ? uniform(s_scan[e - 1u]) : 0u);
+        const uint32_t len = uniform(s_len[e]);
+        const uint32_t p0 = uniform(s_start[e]) + rest * kPolRows;
+        const uint32_t nb = min((uint32_t)kPolRows, len - rest * kPolRows);
+        pol_seq_eval_tile<true, true>(A, table[e].net, order + p0, 0u, nb, s_pol, t, wv, lane);
+    }
+}
+
+// Block (a, c) is accumulator a of the wave's segment c: the tiles a, a +
+// kPolGradAcc, ... of the segment's positions, into slab, stash and h store (c,
+// a).  A block without a tile leaves its slab alone: the reduce never reads it.
+__global__ __launch_bounds__(256, 1) void policy_seq_grad_groups_kernel(PolSeqIO A, const int32_t *order,
+                                                                        const int32_t *segments,
+                                                                        const PolGroupEntry *table, PolGroupWave Wv,
+                                                                        float *slabs, uint64_t slab_stride, float *stash,
+                                                                        float *hws)
+{
+    extern __shared__ float s_pol[];
+    const uint32_t t = threadIdx.x, wv = uniform(t >> 6), lane = t & 63u;
+    const uint32_t a = blockIdx.x, c = blockIdx.y, e = Wv.seg[c];
+    uint32_t lo, len;
+    pol_segment(segments, e, A.B, lo, len);
+    lo = uniform(lo);
+    len = uniform(len);
+    const uint32_t tiles = (len + kPolRows - 1u) / kPolRows;
+    if (a >= tiles) return;
+    const size_t blk = (size_t)c * gridDim.x + a;
+    float *slab = slabs + blk * slab_stride;
+    float *st = stash + blk * kPolStashTiles * kPolTile;
+    float *hk = hws + blk * A.L * kPolHTile;
+    const PolGroupEntry &E = table[e];
+    bool started = false;
+    for (uint32_t tile = a; tile < tiles; tile += kPolGradAcc) {
+        const uint32_t nb = min((uint32_t)kPolRows, len - tile * kPolRows);
+        started = pol_seq_grad_tile<true, true>(A, E.net, E.back, E.sw, E.sb, slab, st, hk,
+                                                order + lo + tile * kPolRows, 0u, nb, started, s_pol, t, wv, lane);
+    }
+    if (!started) {   // tiles without a step: the chains are their +0 starts
+        const uint32_t n = uniform(E.slab_floats);
+        for (uint32_t i = t; i < n; i += 256u) slab[i] = 0.0f;
+    }
+}
+
+// block (x, layer, c): policy_grad_groups_reduce_kernel with the memory head's slot
+__global__ __launch_bounds__(256) void policy_seq_grad_groups_reduce_kernel(const int32_t *segments, uint64_t n,
+                                                                            const PolGroupEntry *table, PolGroupWave Wv,
+                                                                            PolSeqGroupGrads O, const float *slabs,
+                                                                            uint64_t slab_stride, uint32_t wave_acc)
+{
+    const uint32_t l = blockIdx.y, c = blockIdx.z, e = Wv.seg[c];
+    const PolGroupEntry &E = table[e];
+    if (l < (uint32_t)kPolMaxTrunk && l >= E.net.n_trunk) return;
+    const uint32_t h = l - (uint32_t)kPolMaxTrunk;
+    const PolLayer &f = l < (uint32_t)kPolMaxTrunk ? E.net.trunk[l]
+                        : h < 2u                   ? E.net.actor[h]
+                        : h < 4u                   ? E.net.critic[h - 2u]
+                                                   : E.net.memory;
+    uint32_t lo, len;
+    pol_segment(segments, e, n, lo, len);
+    const uint32_t nacc = min(min((len + kPolRows - 1u) / kPolRows, kPolGradAcc), wave_acc);
+    pol_reduce_layer(slabs + (size_t)c * wave_acc * slab_stride, slab_stride, nacc, E.sw[l], E.sb[l], f.in, f.out,
+                     pol_grad_nkt(f.kp), O.w[c][l], O.b[c][l]);
+}
+
+// ---- sequence_segments: a stable counting sort of the columns by net_id, at
+// most 256 keys.  Chunks of kPolOrderChunk columns, one block each; thread k is
+// key k throughout, and walks its chunk in column order, so no atomic and no
+// race decides a position. ----
+constexpr uint32_t kPolOrderChunk = 1024;
+
+// counts[chunk][key]
+__global__ __launch_bounds__(256) void policy_seq_order_count_kernel(const int32_t *net_id, uint64_t B, uint32_t *counts)
+{
+    __shared__ int32_t s_id[kPolOrderChunk];
+    const uint64_t c0 = (uint64_t)blockIdx.x * kPolOrderChunk;
+    const uint32_t n = (uint32_t)min((uint64_t)kPolOrderChunk, B - c0);
+    for (uint32_t i = threadIdx.x; i < n; i += 256u) s_id[i] = net_id[c0 + i];
+    __syncthreads();
+    const int32_t key = (int32_t)threadIdx.x;
+    uint32_t cnt = 0;
+    for (uint32_t i = 0; i < n; ++i) cnt += s_id[i] == key ? 1u : 0u;
+    counts[(size_t)blockIdx.x * 256u + threadIdx.x] = cnt;
+}
+
+// one block: counts[chunk][key] becomes the position of the chunk's first
+// column of the key; segments[key] = [lo, hi); counts[nchunks][0] the total
+__global__ __launch_bounds__(256) void policy_seq_order_scan_kernel(uint32_t *counts, uint32_t nchunks, uint32_t nkeys,
+                                                                    int32_t *segments)
+{
+    __shared__ uint32_t s_tot[256];
+    const uint32_t key = threadIdx.x;
+    uint32_t tot = 0;
+    if (key < nkeys)
+        for (uint32_t c = 0; c < nchunks; ++c) tot += counts[(size_t)c * 256u + key];
+    s_tot[key] = tot;
+    __syncthreads();
+    uint32_t lo = 0;
+    for (uint32_t q = 0; q < key; ++q) lo += s_tot[q];
+    if (key < nkeys) {
+        segments[2u * key] = (int32_t)lo;
+        segments[2u * key + 1u] = (int32_t)(lo + tot);
+        uint32_t run = lo;
+        for (uint32_t c = 0; c < nchunks; ++c) {
+            const uint32_t n = counts[(size_t)c * 256u + key];
+            counts[(size_t)c * 256u + key] = run;
+            run += n;
+        }
+    }
+    if (key == 255u) counts[(size_t)nchunks * 256u] = lo + tot;
+}
+
+// order[position] = column, each chunk's columns of a key ascending from the
+// chunk's base; the tail past the last segment -1
+__global__ __launch_bounds__(256) void policy_seq_order_scatter_kernel(const int32_t *net_id, uint64_t B,
+                                                                       const uint32_t *counts, uint32_t nchunks,
+                                                                       uint32_t nkeys, int32_t *order)
+{
+    __shared__ int32_t s_id[kPolOrderChunk];
+    const uint64_t c0 = (uint64_t)blockIdx.x * kPolOrderChunk;
+    const uint32_t n = (uint32_t)min((uint64_t)kPolOrderChunk, B - c0);
+    for (uint32_t i = threadIdx.x; i < n; i += 256u) s_id[i] = net_id[c0 + i];
+    __syncthreads();
+    const uint32_t key = threadIdx.x;
+    if (key < nkeys) {
+        uint64_t p = counts[(size_t)blockIdx.x * 256u + key];
+        for (uint32_t i = 0; i < n; ++i)
+            if (s_id[i] == (int32_t)key && p < B) order[p++] = (int32_t)(c0 + i);
+    }
+    const uint64_t total = counts[(size_t)nchunks * 256u];
+    for (uint64_t p = total + c0 + threadIdx.x; p < min(B, total + c0 + kPolOrderChunk); p += 256u) order[p] = -1;
 }
 
 template <bool kGrad> static hipError_t policy_eval_lds()
@@ -1264,6 +1561,97 @@ hipError_t launch_policy_grad_groups(const PolEvalIO &io, const int32_t *segment
         }
         hipLaunchKernelGGL(policy_grad_groups_reduce_kernel, dim3(16, kPolGradLayers, waves[w].n), dim3(256), 0, st,
                            segments, io.n, table, waves[w], grads[w], slabs, slab_stride, wave_acc);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
+
+// ---- grouped evaluate_sequences: policy_groups_prepare for nets with a memory
+// head, then the zeroed outputs and the forward, or the backward in waves ----
+static hipError_t policy_seq_groups_prepare(const PolSeqGroupSpec *specs, uint32_t nseg, float *ws, PolGroupEntry *table,
+                                            PolUpload *uploads, bool fwd_only, hipStream_t st)
+{
+    for (uint32_t first = 0; first < nseg; first += kPolSeqGroupChunk) {
+        PolSeqGroupSpecs S{};
+        S.first = first;
+        S.n = std::min(kPolSeqGroupChunk, nseg - first);
+        std::copy(specs + first, specs + first + S.n, S.s);
+        hipLaunchKernelGGL(policy_seq_groups_setup_kernel, dim3(1), dim3(64), 0, st, S, ws, table, uploads);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(policy_repack_groups_kernel, dim3(8, kPolSeqGroupUploads, nseg), dim3(256), 0, st, uploads,
+                       fwd_only ? 1u : 0u);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_seq_eval_groups(const PolSeqIO &io, const int32_t *order, const int32_t *segments,
+                                         const PolSeqGroupSpec *specs, uint32_t nseg, float *ws, PolGroupEntry *table,
+                                         PolUpload *uploads, hipStream_t st)
+{
+    if (io.B == 0 || io.L == 0) return hipSuccess;
+    static bool set = false;
+    if (const hipError_t e =
+            policy_seq_lds(reinterpret_cast<const void *>(policy_seq_eval_groups_kernel), kPolSeqEvalGroupLds, set))
+        return e;
+    if (const hipError_t e = policy_seq_groups_prepare(specs, nseg, ws, table, uploads, true, st)) return e;
+    const uint64_t n = (uint64_t)io.L * io.B;
+    hipLaunchKernelGGL(policy_zero_rows_kernel, dim3((unsigned)std::min<uint64_t>((n + 255u) / 256u, 2048u)), dim3(256), 0,
+                       st, io.logp, io.value, io.entropy, n);
+    if (const hipError_t e = hipGetLastError()) return e;
+    if (io.hidden) {
+        hipLaunchKernelGGL(policy_zero_rows_kernel, dim3((unsigned)std::min<uint64_t>((n * kHidden + 255u) / 256u, 2048u)),
+                           dim3(256), 0, st, io.hidden, nullptr, nullptr, n * kHidden);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    const unsigned blocks = (unsigned)std::min<uint64_t>(io.B / kPolRows + nseg, 512u);
+    hipLaunchKernelGGL(policy_seq_eval_groups_kernel, dim3(blocks), dim3(256), kPolSeqEvalGroupLds, st, io, order,
+                       segments, table, nseg);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_seq_grad_groups(const PolSeqIO &io, const int32_t *order, const int32_t *segments,
+                                         const PolSeqGroupSpec *specs, uint32_t nseg, const PolGroupWave *waves,
+                                         const PolSeqGroupGrads *grads, uint32_t nwaves, float *ws, PolGroupEntry *table,
+                                         PolUpload *uploads, float *slabs, uint64_t slab_stride, float *stash, float *hws,
+                                         uint32_t wave_acc, hipStream_t st)
+{
+    static bool set = false;
+    if (const hipError_t e =
+            policy_seq_lds(reinterpret_cast<const void *>(policy_seq_grad_groups_kernel), kPolSeqGradGroupLds, set))
+        return e;
+    if (const hipError_t e = policy_seq_groups_prepare(specs, nseg, ws, table, uploads, false, st)) return e;
+    for (uint32_t w = 0; w < nwaves; ++w) {
+        if (wave_acc && io.L) {
+            hipLaunchKernelGGL(policy_seq_grad_groups_kernel, dim3(wave_acc, waves[w].n), dim3(256), kPolSeqGradGroupLds,
+                               st, io, order, segments, table, waves[w], slabs, slab_stride, stash, hws);
+            if (const hipError_t e = hipGetLastError()) return e;
+        }
+        hipLaunchKernelGGL(policy_seq_grad_groups_reduce_kernel, dim3(16, kPolSeqLayers, waves[w].n), dim3(256), 0, st,
+                           segments, io.B, table, waves[w], grads[w], slabs, slab_stride, io.L ? wave_acc : 0u);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    return hipSuccess;
+}
+
+// counts[chunks][256] and the total (MBOTS_POLICY_SEQ_ORDER_WORKSPACE)
+size_t policy_seq_order_workspace(uint64_t B)
+{
+    return ((size_t)((B + kPolOrderChunk - 1u) / kPolOrderChunk) * 256u + 64u) * 4u;
+}
+
+hipError_t launch_policy_seq_order(const int32_t *net_id, uint64_t B, uint32_t nkeys, int32_t *order, int32_t *segments,
+                                   uint32_t *counts, hipStream_t st)
+{
+    const uint32_t nchunks = (uint32_t)((B + kPolOrderChunk - 1u) / kPolOrderChunk);
+    if (nchunks) {
+        hipLaunchKernelGGL(policy_seq_order_count_kernel, dim3(nchunks), dim3(256), 0, st, net_id, B, counts);
+        if (const hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(policy_seq_order_scan_kernel, dim3(1), dim3(256), 0, st, counts, nchunks, nkeys, segments);
+    if (const hipError_t e = hipGetLastError()) return e;
+    if (nchunks) {
+        hipLaunchKernelGGL(policy_seq_order_scatter_kernel, dim3(nchunks), dim3(256), 0, st, net_id, B, counts, nchunks,
+                           nkeys, order);
         if (const hipError_t e = hipGetLastError()) return e;
     }
     return hipSuccess;

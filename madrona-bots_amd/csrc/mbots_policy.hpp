@@ -406,9 +406,11 @@ struct PolGroupSpec {
 };
 // The net's descriptors in the workspace: forward and transposed layers (as
 // evaluate's plan lays them out) and where each layer's dW / db lie in a slab.
+// (The grouped evaluate_sequences adds the memory head: its layer and slab slot
+// kPolGradLayers, back.memory, and back.trunk[0] the H -> 16 layer of dh.)
 struct PolGroupEntry {
     PolNet net, back;
-    uint32_t sw[kPolGradLayers], sb[kPolGradLayers];
+    uint32_t sw[kPolSeqLayers], sb[kPolSeqLayers];
     uint32_t slab_floats, pad;
 };
 MB_HD float *pol_group_take(float *ws, uint64_t base, size_t &off, size_t floats)
@@ -417,9 +419,13 @@ MB_HD float *pol_group_take(float *ws, uint64_t base, size_t &off, size_t floats
     off += (floats + 63u) & ~size_t(63);
     return p;
 }
-// `e` (and, `up` not null, the kPolGroupUploads repacks that fill its weights)
-// from `s`; returns the floats the weights take from ws + s.w_off on.
-MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e, PolUpload *up)
+// `e` (and, `up` not null, the `nup` repacks that fill its weights) from `s`;
+// returns the floats the weights take from ws + s.w_off on.  seq: the net as
+// evaluate_sequences runs it, with the memory head (parameters mw, mb) as layer
+// kPolGradLayers and the transposed W0[:, 69:85] slice as back.trunk[0].
+MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e, PolUpload *up,
+                             int nup = kPolGroupUploads, bool seq = false, const float *mw = nullptr,
+                             const float *mb = nullptr)
 {
     e = PolGroupEntry{};
     size_t off = 0;
@@ -430,11 +436,16 @@ MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e,
         e.net.n_trunk = s.n_trunk;
         e.net.H = H;
         e.net.flags = s.flags;
+        e.net.has_memory = seq ? 1u : 0u;
         uint32_t slab = 0;
-        for (int i = 0; i < kPolGradLayers; ++i) {
+        for (int i = 0; i < (seq ? kPolSeqLayers : kPolGradLayers); ++i) {
             PolLayer *f, *b;
             uint32_t in = H, out = H, act = 0;
-            if (i < kPolMaxTrunk) {
+            if (i == kPolGradLayers) {
+                f = &e.net.memory;
+                b = &e.back.memory;
+                out = (uint32_t)kHidden;
+            } else if (i < kPolMaxTrunk) {
                 if ((uint32_t)i >= s.n_trunk) continue;
                 f = &e.net.trunk[i];
                 b = i ? &e.back.trunk[i] : nullptr;
@@ -454,7 +465,19 @@ MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e,
             f->act = act;
             f->w = pol_group_take(ws, s.w_off, off, pol_w_floats(*f));
             f->b = pol_group_take(ws, s.w_off, off, pol_b_floats(*f));
-            if (up) up[nu++] = PolUpload{s.w[i], s.b[i], f->w, f->b, in, out, f->kp, f->nt, 0u, 0u, 0u};
+            const float *pw = i == kPolGradLayers ? mw : s.w[i], *pb = i == kPolGradLayers ? mb : s.b[i];
+            if (up) up[nu++] = PolUpload{pw, pb, f->w, f->b, in, out, f->kp, f->nt, 0u, 0u, 0u};
+            if (seq && i == 0) {   // W0[:, 69:85] alone: dh_k
+                PolLayer *d = &e.back.trunk[0];
+                d->in = out;
+                d->out = (uint32_t)kHidden;
+                d->kp = (out + 7u) & ~7u;
+                d->nt = 1u;
+                d->w = pol_group_take(ws, s.w_off, off, pol_w_floats(*d));
+                d->b = pol_group_take(ws, s.w_off, off, pol_b_floats(*d));
+                if (up)
+                    up[nu++] = PolUpload{pw, nullptr, d->w, d->b, d->in, d->out, d->kp, d->nt, 1u, in, (uint32_t)kPolObs};
+            }
             if (b) {
                 b->in = out;
                 b->out = in;
@@ -462,7 +485,7 @@ MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e,
                 b->nt = (in + 15u) / 16u;
                 b->w = pol_group_take(ws, s.w_off, off, pol_w_floats(*b));
                 b->b = pol_group_take(ws, s.w_off, off, pol_b_floats(*b));
-                if (up) up[nu++] = PolUpload{s.w[i], nullptr, b->w, b->b, b->in, b->out, b->kp, b->nt, 1u, 0u, 0u};
+                if (up) up[nu++] = PolUpload{pw, nullptr, b->w, b->b, b->in, b->out, b->kp, b->nt, 1u, 0u, 0u};
             }
             e.sw[i] = slab;
             slab += f->nt * pol_grad_nkt(f->kp) * 256u;
@@ -472,7 +495,7 @@ MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e,
         e.slab_floats = slab;
     }
     if (up)
-        for (; nu < kPolGroupUploads; ++nu) up[nu] = PolUpload{};
+        for (; nu < nup; ++nu) up[nu] = PolUpload{};
     return off;
 }
 // the segments of one backward wave, and where their gradients go ([out][in] /
@@ -510,5 +533,34 @@ struct PolSeqIO {
 };
 // floats of the per-accumulator h_k store of the backward pass
 MB_HD size_t pol_seq_h_floats(uint32_t nacc, uint32_t L) { return (size_t)nacc * L * kPolGradRows * kHidden; }
+
+// ---- grouped evaluate_sequences: every (group, species) net along its own
+// columns of one padded batch (DESIGN.md "Grouped evaluate_sequences") ----
+// Position p of segment e = 4 g + s, lo <= p < hi of `segments` [G][4][2],
+// stands for column order[p] of the batch; tiles, accumulators and chains are
+// evaluate_sequences', counted in positions from lo.
+constexpr int kPolSeqGroupUploads = 20;   // a net's 9 forward and 9 transposed layers, rounded up
+constexpr uint32_t kPolNoColumn = 0xFFFFFFFFu;   // an order entry outside [0, B): length 0, never read or written
+struct PolSeqGroupSpec {
+    PolGroupSpec s;
+    const float *mw, *mb;   // the memory head's parameters
+};
+constexpr uint32_t kPolSeqGroupChunk = 20;
+struct PolSeqGroupSpecs {
+    PolSeqGroupSpec s[kPolSeqGroupChunk];
+    uint32_t first, n;
+};
+static_assert(sizeof(PolSeqGroupSpecs) + 64u <= 4096u, "a setup launch's specs travel as kernel arguments");
+struct PolSeqGroupGrads {
+    float *w[kPolGroupWave][kPolSeqLayers], *b[kPolGroupWave][kPolSeqLayers];
+};
+// the columns a host evaluate_sequences call runs: idx[0 .. n) of the batch's B
+// (idx null: all B, in place)
+struct PolSeqCols {
+    const int32_t *idx;
+    uint64_t n;
+};
+// sequence_segments' keys: net_id outside [0, nkeys) has no net
+MB_HD bool pol_seq_key(int32_t id, uint32_t nkeys) { return id >= 0 && (uint32_t)id < nkeys; }
 
 }  // namespace mbots

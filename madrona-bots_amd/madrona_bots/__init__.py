@@ -29,7 +29,8 @@ import torch  # loads the HIP runtime libmbots.so links against (same soname)
 __all__ = ["SimManager", "ScriptBotsViewer", "Tensor", "madrona", "ExportID", "ExecMode", "unpack_rollout",
            "unpack_learner", "rebuild_learner", "CapacityWarning", "CapacityError", "MAX_CAPACITY",
            "CAPACITY_CLASSES", "TrajectoryWindow", "RENDER_PALETTE", "RENDER_SCALES", "CLS_FLOOR", "CLS_WALL",
-           "CLS_FOOD", "CLS_BODY", "CLS_MARK", "PolicyNet", "policy_activation", "ACTIVATIONS", "evaluate_groups"]
+           "CLS_FOOD", "CLS_BODY", "CLS_MARK", "PolicyNet", "policy_activation", "ACTIVATIONS", "evaluate_groups",
+           "sequence_segments", "evaluate_sequences_groups"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmbots.so")
@@ -170,6 +171,12 @@ def _load():
                                   ctypes.c_uint64, i32, vp],
         "mbots_policy_seq_grad": [P(_PolicyNet), vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp, P(_PolicyGrads), vp,
                                   ctypes.c_uint64, i32, vp],
+        "mbots_policy_seq_order": [vp, ctypes.c_uint64, u32, vp, vp, vp, ctypes.c_uint64, i32, vp],
+        "mbots_policy_seq_groups_workspace": [P(_PolicyNet), u32, u32, ctypes.c_uint64, P(ctypes.c_uint64)],
+        "mbots_policy_seq_eval_groups": [P(_PolicyNet), u32, vp, vp, vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp,
+                                         vp, vp, ctypes.c_uint64, i32, vp],
+        "mbots_policy_seq_grad_groups": [P(_PolicyNet), u32, vp, vp, vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp,
+                                         P(_PolicyGrads), vp, ctypes.c_uint64, i32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -1760,6 +1767,207 @@ class _EvaluateGroups(torch.autograd.Function):
             c, G, _ptr(segments), _ptr(obs), _ptr(hidden), _ptr(action), n, _ptr(g[0]), _ptr(g[1]), _ptr(g[2]),
             out, ws, nb, d, st))
         return (None,) * 6 + tuple(grads)
+
+
+def sequence_segments(net_id, groups):
+    """(order int32 [B], segments int32 [groups, 4, 2]) on net_id's device:
+    the columns of a padded sequence batch sorted by their net, for
+    evaluate_sequences_groups.  net_id int32 [B]: each column's group * 4 +
+    (species - 1); anything outside [0, 4 * groups) means "no net".
+    order[lo:hi] of pair (g, s) holds exactly the columns with net_id == 4 g +
+    s, ascending (torch.nonzero(net_id == 4 g + s)); the segments lie in
+    ascending 4 g + s from position 0, and order past the last one is -1.  On a
+    GPU it is a stable counting sort in the library: no wait for the host,
+    nothing allocated beyond its cached workspace, capturable; CPU tensors run
+    on the host and give the same values."""
+    groups = int(groups)
+    if not 1 <= groups <= 64:
+        raise ValueError(f"groups must be 1..64, not {groups}")
+    if net_id.dtype != torch.int32 or net_id.dim() != 1:
+        raise ValueError(f"net_id must be int32 [B], not {net_id.dtype} {list(net_id.shape)}")
+    net_id = net_id.detach().contiguous()
+    dev, B = net_id.device, net_id.shape[0]
+    order = torch.empty(B, dtype=torch.int32, device=dev)
+    segments = torch.empty(groups, 4, 2, dtype=torch.int32, device=dev)
+    if dev.type == "cuda":
+        need = (B + 1023) // 1024 * 1024 + 256   # MBOTS_POLICY_SEQ_ORDER_WORKSPACE(B)
+        key = (dev, need)
+        ws = _workspaces.get(key)
+        if ws is None:
+            ws = _workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            _check(_lib.mbots_policy_seq_order(_ptr(net_id), B, groups, _ptr(order), _ptr(segments),
+                                               ctypes.c_void_p(ws.data_ptr()), need, dev.index,
+                                               ctypes.c_void_p(_raw_stream(dev.index))))
+    else:
+        _check(_lib.mbots_policy_seq_order(_ptr(net_id), B, groups, _ptr(order), _ptr(segments), None, 0, -1, None))
+    return order, segments
+
+
+def evaluate_sequences_groups(nets, obs, action, length, hidden0, order, segments, return_hidden=False):
+    """(logp, value, entropy), float32 [L, B] each on obs's device: every
+    (group, species) net along its own columns of one padded sequence batch,
+    in one forward call and one backward call (the recurrent learner's half of
+    policy groups; DESIGN.md "Grouped evaluate_sequences").  nets as
+    evaluate_groups': 1..64 groups, each four PolicyNet or one for all four,
+    None where a pair has no net; every net present needs a memory head and
+    memory_in (evaluate_groups is for the others); they may differ in H, depth
+    and activations.  obs float32 [L, B, 69], action int32 [L, B] or [L, B, 1],
+    length int32 [B], hidden0 float32 [B, 16]: the whole batch as
+    TrajectoryWindow.batch() / gather() hand it out, read in place.  order
+    int32 [B] and segments int32 [G, 4, 2] are sequence_segments': position p
+    of segment (g, s) stands for column order[p]; on a GPU both are read by the
+    kernels only.
+
+    Column order[p], lo <= p < hi of (g, s), gets bit for bit what
+    nets[g][s].evaluate_sequences(obs.index_select(1, order[lo:hi]), ...) gives
+    it; a column named by no evaluated segment, or by the segment of a None,
+    gets +0 at every step and takes no part in any gradient.  backward() leaves
+    a gradient in every parameter of every net, memory head included: for a net
+    that owns its parameters bit for bit the per-net call's (sums in
+    evaluate_sequences' order, counted in positions from lo; zeros for an empty
+    segment); a tensor shared between segments receives autograd's sum.  obs
+    and hidden0 receive none.  return_hidden: a fourth result, float32 [L, B,
+    16], in the batch's own column layout like the others.
+
+    Contract: 0 <= lo <= hi <= B, segments pairwise disjoint, every order[p] of
+    an evaluated segment in [0, B), no column twice, length in [0, L], present
+    actions in 0..5.  CPU tensors are checked (a violation names the pair); on
+    a GPU bounds are clamped as in evaluate_groups, an order entry outside
+    [0, B) is a column of length 0 that is neither read nor written, and
+    duplicates and overlaps are the caller's contract.  After the first call of
+    a shape forward and backward allocate no workspace and never wait for the
+    host, so both can be captured; a replay reads order and segments as they
+    are then."""
+    groups = [list(g) if isinstance(g, (list, tuple)) else [g] * 4 for g in nets]
+    G = len(groups)
+    if not 1 <= G <= 64:
+        raise ValueError(f"nets must hold 1..64 groups, not {G}")
+    for g, four in enumerate(groups):
+        if len(four) != 4 or any(x is not None and not isinstance(x, PolicyNet) for x in four):
+            raise ValueError(f"nets[{g}] must be four PolicyNet (or None), or one PolicyNet for all species")
+    dev = obs.device
+    if obs.dtype != torch.float32 or obs.dim() != 3 or obs.shape[2] != 69:
+        raise ValueError(f"obs must be float32 [L, B, 69], not {obs.dtype} {list(obs.shape)}")
+    L, B = obs.shape[0], obs.shape[1]
+    if action.dtype != torch.int32 or action.device != dev or tuple(action.shape) not in ((L, B), (L, B, 1)):
+        raise ValueError(f"action must be int32 [L, B] or [L, B, 1] on {dev} with obs's steps and sequences, not "
+                         f"{action.dtype} {list(action.shape)} on {action.device}")
+    if length.dtype != torch.int32 or length.device != dev or tuple(length.shape) != (B,):
+        raise ValueError(f"length must be int32 [B] on {dev}, not {length.dtype} {list(length.shape)} on "
+                         f"{length.device}")
+    if hidden0.dtype != torch.float32 or hidden0.device != dev or tuple(hidden0.shape) != (B, 16):
+        raise ValueError(f"hidden0 must be float32 [B, 16] on {dev}, not {hidden0.dtype} {list(hidden0.shape)} on "
+                         f"{hidden0.device}")
+    if order.dtype != torch.int32 or order.device != dev or tuple(order.shape) != (B,):
+        raise ValueError(f"order must be int32 [B] on {dev} (sequence_segments()), not {order.dtype} "
+                         f"{list(order.shape)} on {order.device}")
+    if segments.dtype != torch.int32 or segments.device != dev or tuple(segments.shape) != (G, 4, 2):
+        raise ValueError(f"segments must be int32 [{G}, 4, 2] on {dev} (sequence_segments() of the nets' {G} groups), "
+                         f"not {segments.dtype} {list(segments.shape)} on {segments.device}")
+    flat = [x for four in groups for x in four]
+    index, params = [], []       # (segment, slot of the net's parameters) of every parameter passed on
+    for e, x in enumerate(flat):
+        if x is None:
+            continue
+        where = _species_name(e // 4, e % 4)
+        try:
+            x._validate()
+        except ValueError as err:
+            raise ValueError(f"{where}: {err}") from None
+        if x.memory is None or not x.memory_in:
+            raise ValueError(f"{where}: evaluate_sequences_groups needs a net with a memory head and memory_in=True "
+                             "(there is no state to carry otherwise): use evaluate_groups()")
+        named = x._named_params() + [("memory Linear weight", x.memory[0]), ("memory Linear bias", x.memory[1])]
+        for i, (name, p) in enumerate(named):
+            if p is None:
+                continue
+            if p.dtype != torch.float32 or p.device != dev:
+                raise ValueError(f"{where}: {name} must be float32 on {dev} (obs's device), not {p.dtype} on {p.device}")
+            index.append((e, i))
+            params.append(p)
+    out = _EvaluateSequencesGroups.apply(flat, obs.detach().contiguous(), action.detach().reshape(L, B).contiguous(),
+                                         length.detach().contiguous(), hidden0.detach().contiguous(),
+                                         order.detach().contiguous(), segments.detach().contiguous(),
+                                         bool(return_hidden), index, *params)
+    return out if return_hidden else out[:3]
+
+
+def _seq_groups_call(flat, full, obs, fn):
+    """_groups_call for evaluate_sequences_groups: obs is [L, B, 69] and the
+    workspace is mbots_policy_seq_groups_workspace's."""
+    dev = obs.device
+    c = (_PolicyNet * len(flat))()
+    for e, x in enumerate(flat):
+        if x is not None:
+            c[e] = x._c_net(full[e])
+    G = len(flat) // 4
+    need = ctypes.c_uint64()
+    _check(_lib.mbots_policy_seq_groups_workspace(c, G, obs.shape[0], obs.shape[1], ctypes.byref(need)))
+    key = (dev, need.value)
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.empty(max(need.value, 64), dtype=torch.uint8, device=dev)
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            _check(fn(c, G, ctypes.c_void_p(ws.data_ptr()), need.value, dev.index,
+                      ctypes.c_void_p(_raw_stream(dev.index))))
+    else:
+        _check(fn(c, G, ctypes.c_void_p(ws.data_ptr()), need.value, -1, None))
+
+
+class _EvaluateSequencesGroups(torch.autograd.Function):
+    """evaluate_sequences_groups: mbots_policy_seq_eval_groups forward,
+    mbots_policy_seq_grad_groups backward, one node over the parameters of
+    every net."""
+
+    @staticmethod
+    def forward(ctx, flat, obs, action, length, hidden0, order, segments, want_hidden, index, *params):
+        full = [None if x is None else [None] * (2 * (len(x.trunk) + 5)) for x in flat]
+        for (e, i), p in zip(index, params):
+            full[e][i] = p.detach().contiguous()
+        L, B = obs.shape[0], obs.shape[1]
+        logp, value, entropy = (torch.empty(L, B, dtype=torch.float32, device=obs.device) for _ in range(3))
+        hidden = torch.empty(L, B, 16, dtype=torch.float32, device=obs.device) if want_hidden else None
+        _seq_groups_call(flat, full, obs, lambda c, G, ws, nb, d, st: _lib.mbots_policy_seq_eval_groups(
+            c, G, _ptr(order), _ptr(segments), _ptr(obs), _ptr(action), _ptr(length), _ptr(hidden0), L, B, _ptr(logp),
+            _ptr(value), _ptr(entropy), _ptr(hidden), ws, nb, d, st))
+        ctx.flat, ctx.rows, ctx.index, ctx.full = flat, (obs, action, length, hidden0, order, segments), index, full
+        ctx.set_materialize_grads(False)
+        if hidden is None:
+            hidden = torch.empty(0, dtype=torch.float32, device=obs.device)
+        ctx.mark_non_differentiable(hidden)
+        return logp, value, entropy, hidden
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_logp, g_value, g_entropy, _g_hidden):
+        flat, (obs, action, length, hidden0, order, segments), index, full = ctx.flat, ctx.rows, ctx.index, ctx.full
+        L, B = obs.shape[0], obs.shape[1]
+        g = [None if t is None else t.to(torch.float32).contiguous() for t in (g_logp, g_value, g_entropy)]
+        out = (_PolicyGrads * len(flat))()
+        grads = []
+        for k, (e, i) in enumerate(index):
+            if not ctx.needs_input_grad[9 + k]:
+                grads.append(None)
+                continue
+            grads.append(torch.empty_like(full[e][i]))
+            T = len(flat[e].trunk)
+            layer, slots = i // 2, out[e]
+            if layer < T:
+                slot = slots.trunk[layer]
+            elif layer < T + 4:
+                slot = (slots.actor, slots.critic)[(layer - T) // 2][(layer - T) % 2]
+            else:
+                slot = slots.memory
+            if i % 2:
+                slot.bias = grads[-1].data_ptr()
+            else:
+                slot.weight = grads[-1].data_ptr()
+        _seq_groups_call(flat, full, obs, lambda c, G, ws, nb, d, st: _lib.mbots_policy_seq_grad_groups(
+            c, G, _ptr(order), _ptr(segments), _ptr(obs), _ptr(action), _ptr(length), _ptr(hidden0), L, B, _ptr(g[0]),
+            _ptr(g[1]), _ptr(g[2]), out, ws, nb, d, st))
+        return (None,) * 9 + tuple(grads)
 
 
 def policy_activation(act, x):

@@ -692,15 +692,30 @@ int mbots_render_palette(uint8_t rgb[36]);
  * Every Linear output is bias[j] followed by fmaf(x[k], W[j][k], acc) for k
  * ascending, so both execution modes and any sharding give the same bits.
  *
+ * The gated memory head (DESIGN.md "Gated memory head"): with MBOTS_POLICY_GATE
+ * in flags the net carries a gate head Linear(H, 16), Sigmoid beside its memory
+ * head, and the row's new HiddenState is the update-gate blend of the old one
+ * h (as the call read it) and the memory head's output c,
+ *   z_j = sigmoid(bg_j + sum_k f_k Wg[j][k]),  h'_j = fmaf(z_j, c_j, fmaf(-z_j, h_j, h_j)),
+ * f the trunk's last output: z == 1 gives c and z == 0 gives h bit for bit (a
+ * -0 may come out as +0).  The sigmoid is 1 / (1 + e) for x >= 0 and e / (1 + e)
+ * below, e the actor's exp(-|x|): exactly 1 from about 17 up, exactly 0 below
+ * -104.  A gate needs a memory head and MBOTS_POLICY_MEMORY_IN; `gate` is read
+ * only under the flag, so a caller that never sets it is untouched whatever
+ * its memory holds there.  mbots_policy_eval and mbots_policy_grad ignore the
+ * gate as they ignore the memory head; mbots_policy_seq_eval carries h' from
+ * step to step and mbots_policy_seq_grad returns the gate's gradients.
+ *
  * mbots_policy_set(h, species, net, stream): pointers are memory of the
  * manager's device (host memory in CPU mode), read in stream order on `stream`
  * (they may be freed stream-ordered after the call).  The first call for a
- * species, and a call whose widths, depth or heads differ from the net in
- * place, allocates (after the device has drained) and is refused under stream
+ * species, and a call whose widths, depth or heads (the gate among them) differ
+ * from the net in place, allocates (after the device has drained) and is refused under stream
  * capture; a call with the same architecture only re-uploads on `stream` --
  * what a learner does after every optimiser step -- and is capturable.  A
  * captured mbots_policy_act pins the architecture in place at capture time.
- * MBOTS_E_INVALID for any width, depth, code or NULL weight outside the above.
+ * MBOTS_E_INVALID for any width, depth, code or NULL weight outside the above,
+ * a gate without a memory head or without MBOTS_POLICY_MEMORY_IN included.
  * mbots_policy_clear(h, species) removes the net (after the device has
  * drained; refused under capture).
  *
@@ -711,7 +726,8 @@ int mbots_render_palette(uint8_t rgb[36]);
  *   u = u01(threefry2x32(seed, draw, global world, (species - 1) << 16 | k).x),
  * k the row's index inside its (world, species) segment, so N shards draw what
  * one device draws.  Unless MBOTS_ACT_NO_WRITE, Action receives the one-hot and
- * (nets with a memory head) HiddenState the head's output, exactly as
+ * (nets with a memory head) HiddenState the head's output (a gated net's: the
+ * blend with the row's HiddenState as the call read it), exactly as
  * mbots_write_actions(rows = mbots_num_rows()) of the same values would.  The
  * outputs (device memory, host memory in CPU mode; any may be NULL) receive
  * rows [0, min(rows, out_rows)): action int32, logp and value f32, [rows, 1].
@@ -730,7 +746,7 @@ int mbots_render_palette(uint8_t rgb[36]);
  *
  * mbots_policy_activation(act, x, y, n, device, stream): learner side, no
  * manager: y[i] = the actor's own activation `act` of x[i] (codes 0..5; 6 the
- * actor's exp, 7 its log), device >= 0: device memory of that GPU on `stream`,
+ * actor's exp, 7 its log, 8 the gate's sigmoid), device >= 0: device memory of that GPU on `stream`,
  * device == -1: host memory.  Both give the same bits.
  *
  * Policy groups (DESIGN.md "Policy groups"): contiguous ranges of global world
@@ -759,6 +775,7 @@ int mbots_render_palette(uint8_t rgb[36]);
  * where there is none --, stream-ordered, no host wait, capturable. */
 #define MBOTS_POLICY_MAX_GROUPS 64
 #define MBOTS_POLICY_MEMORY_IN  1u
+#define MBOTS_POLICY_GATE       2u
 #define MBOTS_ACT_GREEDY    1u
 #define MBOTS_ACT_NO_WRITE  2u
 #define MBOTS_POLICY_MAX_TRUNK 4
@@ -773,7 +790,8 @@ struct mbots_policy_net {
     struct mbots_policy_layer trunk[MBOTS_POLICY_MAX_TRUNK];
     struct mbots_policy_layer actor[2], critic[2];
     struct mbots_policy_layer memory;   /* weight NULL: no memory head */
-    uint32_t flags;          /* MBOTS_POLICY_MEMORY_IN */
+    uint32_t flags;          /* MBOTS_POLICY_MEMORY_IN | MBOTS_POLICY_GATE */
+    struct mbots_policy_layer gate;     /* read only with MBOTS_POLICY_GATE: Linear(H, 16), Sigmoid */
 };
 int mbots_policy_set(mbots_handle *h, uint32_t species /* 1..4 */, const struct mbots_policy_net *net, void *stream);
 int mbots_policy_clear(mbots_handle *h, uint32_t species);
@@ -827,6 +845,7 @@ struct mbots_policy_grads {
     struct mbots_policy_grad_layer trunk[MBOTS_POLICY_MAX_TRUNK];
     struct mbots_policy_grad_layer actor[2], critic[2];
     struct mbots_policy_grad_layer memory;   /* mbots_policy_seq_grad only; mbots_policy_grad ignores it */
+    struct mbots_policy_grad_layer gate;     /* read only when the net has MBOTS_POLICY_GATE (mbots_policy_seq_grad) */
 };
 int mbots_policy_grad_workspace(const struct mbots_policy_net *net, uint64_t n, uint64_t *bytes);
 int mbots_policy_eval(const struct mbots_policy_net *net, const float *obs, const float *hidden,
@@ -910,6 +929,20 @@ int mbots_policy_grad_groups(const struct mbots_policy_net *nets, uint32_t group
  * added in ascending index.  With L == 1 and every length 1 the outputs and
  * the trunk / actor / critic gradients are mbots_policy_grad's bits.  B == 0
  * or L == 0 writes zeros.
+ *
+ * A gated net (MBOTS_POLICY_GATE): h_{k+1} is the blend above of h_k and the
+ * memory head's output, and the pass back through time runs, per element and
+ * HiddenState float, with z the gate's and c the memory head's output and dh
+ * the carried d loss / d h_{k+1},
+ *   d mem_pre  = (dh z) (1 - c^2),
+ *   d gate_pre = (dh (c - h_k)) (z (1 - z)),
+ *   dh_k       = dh (1 - z) + sum_j d0[j] W0[j][69 + .],
+ * the two heads' input gradients joining the actor's and the critic's as
+ * ((actor + critic) + memory) + gate.  out->gate receives the gate head's
+ * gradients, summed in the order above (their accumulators follow the memory
+ * head's, and the workspace grows by them).  With z exactly 1 the gate's
+ * gradients and the direct dh term are zeros and every other gradient equals
+ * the ungated net's as a value; with z exactly 0 d mem_pre is zero.
  *
  * workspace: mbots_policy_seq_workspace(net, L, B, &bytes) bytes, as above.
  * The calls allocate nothing and never wait for the host.  A length outside

@@ -921,7 +921,7 @@ inline void policy_layer_host(const PolLayer &L, int act, const float *in, float
         const float *wr = L.w + (size_t)j * L.kp;
         float acc = L.b[j];
         for (uint32_t k = 0; k < L.kp; ++k) acc = pol_fma(in[k], wr[k], acc);
-        out[j] = pol_activation(act, acc);
+        out[j] = pol_activation_any(act, acc);
     }
 }
 }  // namespace
@@ -947,7 +947,7 @@ void Sim::policy_act(const PolGroups &groups, uint32_t flags, uint32_t draw, int
     const uint8_t *dep = fixd ? t.depth.data() : reinterpret_cast<const uint8_t *>(t.sem.data());
     const bool write = !(flags & kActNoWrite), greedy = (flags & kActGreedy) != 0;
     for_worlds([&](uint32_t w) {
-        float a[kPolMaxH + 4], b[kPolMaxH + 4], hid[kPolMaxH], z[16], v[1], mem[kHidden];
+        float a[kPolMaxH + 4], b[kPolMaxH + 4], hid[kPolMaxH], z[16], v[1], mem[kHidden], gate[kHidden];
         uint32_t g = groups.ghost;   // the world's group: the ghost's, or the one whose local range holds w
         if (w < Wx_)
             for (g = 0; groups.first[g + 1u] <= w; ++g) {}
@@ -969,6 +969,10 @@ void Sim::policy_act(const PolGroups &groups, uint32_t flags, uint32_t draw, int
                 policy_layer_host(net.critic[0], kActRelu, cur, hid);
                 policy_layer_host(net.critic[1], kActIdentity, hid, v);
                 if (net.has_memory) policy_layer_host(net.memory, kActTanh, cur, mem);
+                if (net.gated) {   // the blend with the HiddenState the row read
+                    policy_layer_host(net.gate, kActSigmoid, cur, gate);
+                    for (int i = 0; i < kHidden; ++i) mem[i] = pol_gate_blend(gate[i], mem[i], t.hidden[r * kHidden + i]);
+                }
                 const float u = pol_uniform(cfg_.rand_seed, draw, cfg_.world_offset + w, (uint32_t)s + 1u, (uint32_t)k);
                 float logp;
                 const int32_t act = pol_sample(z, u, greedy, &logp);
@@ -1149,6 +1153,18 @@ inline uint32_t seq_len(const PolSeqIO &io, uint64_t b)
 // the batch column position p of a call stands for, and the positions it runs
 inline uint64_t seq_col(const PolSeqCols &cols, uint64_t p) { return cols.idx ? (uint64_t)cols.idx[p] : p; }
 inline uint64_t seq_cols(const PolSeqCols &cols, const PolSeqIO &io) { return cols.idx ? cols.n : io.B; }
+// h_{k+1} from the trunk's last output and h_k: the memory head's output, a
+// gated net's blended with h_k (out may be h)
+inline void seq_next_h(const PolNet &net, const float *top, const float *h, float *out)
+{
+    float c[kHidden], z[kHidden];
+    policy_layer_host(net.memory, kActTanh, top, c);
+    if (net.gated) {
+        policy_layer_host(net.gate, kActSigmoid, top, z);
+        for (int i = 0; i < kHidden; ++i) c[i] = pol_gate_blend(z[i], c[i], h[i]);
+    }
+    for (int i = 0; i < kHidden; ++i) out[i] = c[i];
+}
 }  // namespace
 
 void policy_seq_eval(const PolNet &net, const PolSeqIO &io, const PolSeqCols &cols)
@@ -1170,7 +1186,7 @@ void policy_seq_eval(const PolNet &net, const PolSeqIO &io, const PolSeqCols &co
                 continue;
             }
             row_forward(net, io.obs + e * kPolObs, h, f);
-            policy_layer_host(net.memory, kActTanh, f.y[net.n_trunk], y);
+            seq_next_h(net, f.y[net.n_trunk], h, y);
             float logp, ent, dz[kPolActions];
             pol_head(f.z, io.action[e], 0.0f, 0.0f, &logp, &ent, dz);
             if (io.logp) io.logp[e] = logp;
@@ -1190,12 +1206,14 @@ void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &
     const uint64_t tiles = (ncols + kPolGradRows - 1u) / kPolGradRows;
     const uint32_t T = net.n_trunk;
     constexpr int kM = kPolGradLayers;   // the memory head's slot
+    constexpr int kG = kPolSeqLayers;    // the gate head's
     par_for(S.nacc, 1, [&](uint64_t a) {
         float *slab = S.base + a * S.slab_floats;
         std::fill(slab, slab + S.slab_floats, 0.0f);
         float *hk = hws + a * (size_t)io.L * kPolGradRows * kHidden;   // [L][64][16]
         RowForward f;
-        float d0[kPolMaxH], d1[kPolMaxH], ga[kPolMaxH], gc[kPolMaxH], gm[kPolMaxH], y[kHidden], dm[kHidden];
+        float d0[kPolMaxH], d1[kPolMaxH], ga[kPolMaxH], gc[kPolMaxH], gm[kPolMaxH], gg[kPolMaxH], y[kHidden], dm[kHidden],
+            zg[kHidden], dg[kHidden], dd[kHidden];
         float dh[kPolGradRows][kHidden];
         for (uint64_t tile = a; tile < tiles; tile += kPolGradAcc) {
             const uint64_t b0 = tile * kPolGradRows;
@@ -1213,7 +1231,7 @@ void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &
                     for (int c = 0; c < kHidden; ++c) o[c] = h[c];
                     if (k + 1u == n) break;
                     row_forward(net, io.obs + ((uint64_t)k * io.B + b) * kPolObs, h, f);
-                    policy_layer_host(net.memory, kActTanh, f.y[T], h);
+                    seq_next_h(net, f.y[T], h, h);
                 }
                 for (int c = 0; c < kHidden; ++c) dh[r][c] = 0.0f;
             }
@@ -1224,17 +1242,24 @@ void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &
                     const uint64_t b = seq_col(cols, b0 + r);
                     if (k >= seq_len(io, b)) continue;
                     const uint64_t e = (uint64_t)k * io.B + b;
-                    row_forward(net, io.obs + e * kPolObs, hk + ((size_t)k * kPolGradRows + r) * kHidden, f);
+                    const float *hcur = hk + ((size_t)k * kPolGradRows + r) * kHidden;
+                    row_forward(net, io.obs + e * kPolObs, hcur, f);
                     const float *top = f.y[T];
                     policy_layer_host(net.memory, kActTanh, top, y);
                     float logp, ent, dz[kPolActions];
                     pol_head(f.z, io.action[e], io.g_logp ? io.g_logp[e] : 0.0f, io.g_entropy ? io.g_entropy[e] : 0.0f,
                              &logp, &ent, dz);
                     const float dv[1] = {io.g_value ? io.g_value[e] : 0.0f};
-                    for (int c = 0; c < kHidden; ++c) dm[c] = dh[r][c] * pol_activation_grad(kActTanh, y[c]);
+                    if (!net.gated) {
+                        for (int c = 0; c < kHidden; ++c) dm[c] = dh[r][c] * pol_activation_grad(kActTanh, y[c]);
+                    } else {
+                        policy_layer_host(net.gate, kActSigmoid, top, zg);
+                        for (int c = 0; c < kHidden; ++c) pol_gate_back(dh[r][c], zg[c], y[c], hcur[c], &dm[c], &dg[c], &dd[c]);
+                    }
                     grad_w_row(net.actor[1], dz, f.ha, slab + S.w[kPolMaxTrunk + 1], slab + S.b[kPolMaxTrunk + 1]);
                     grad_w_row(net.critic[1], dv, f.hc, slab + S.w[kPolMaxTrunk + 3], slab + S.b[kPolMaxTrunk + 3]);
                     grad_w_row(net.memory, dm, top, slab + S.w[kM], slab + S.b[kM]);
+                    if (net.gated) grad_w_row(net.gate, dg, top, slab + S.w[kG], slab + S.b[kG]);
                     grad_x_row(net.actor[1], dz, d0);
                     grad_x_row(net.critic[1], dv, d1);
                     for (uint32_t j = 0; j < net.H; ++j) {
@@ -1246,9 +1271,13 @@ void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &
                     grad_x_row(net.actor[0], d0, ga);
                     grad_x_row(net.critic[0], d1, gc);
                     grad_x_row(net.memory, dm, gm);
+                    if (net.gated) grad_x_row(net.gate, dg, gg);
                     float *d = d0, *g = d1;
-                    for (uint32_t j = 0; j < net.H; ++j)
-                        d[j] = ((ga[j] + gc[j]) + gm[j]) * pol_activation_grad((int)net.trunk[T - 1u].act, top[j]);
+                    for (uint32_t j = 0; j < net.H; ++j) {
+                        float in = (ga[j] + gc[j]) + gm[j];
+                        if (net.gated) in = in + gg[j];
+                        d[j] = in * pol_activation_grad((int)net.trunk[T - 1u].act, top[j]);
+                    }
                     for (uint32_t l = T; l-- > 0u;) {
                         grad_w_row(net.trunk[l], d, f.y[l], slab + S.w[l], slab + S.b[l]);
                         if (l == 0u) break;
@@ -1262,7 +1291,7 @@ void policy_seq_grad(const PolNet &net, const PolSeqIO &io, const PolGradSlabs &
                         float acc = 0.0f;
                         for (uint32_t j = 0; j < net.H; ++j)
                             acc = pol_fma(d[j], net.trunk[0].w[(size_t)j * net.trunk[0].kp + kPolObs + c], acc);
-                        dh[r][c] = acc;
+                        dh[r][c] = net.gated ? dd[c] + acc : acc;
                     }
                 }
         }

@@ -288,12 +288,14 @@ hipError_t launch_render(const SimState &S, const uint32_t *worlds, uint32_t k, 
 // outputs may be null; max_rows: the table's row slots --, the counter's
 // advance, the upload of a net's layers into fragment order, and the
 // activations of mbots_policy_activation.  groups null: one group, the four
-// nets of `nets` by value; else the groups' net table (`nets` unused).
+// nets of `nets` by value; else the groups' net table (`nets` unused).  gated:
+// a net of the launch has a gate head (the kernels with the gate's code).
 // launch_policy_segments: out [G][4][2], the exported rows of every (group,
 // species) of the current table
 hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *hidden_in, const PolNets &nets,
-                             const PolGroups *groups, uint32_t flags, const uint32_t *draw, int32_t *action_out,
-                             float *logp_out, float *value_out, uint32_t out_rows, uint32_t max_rows, hipStream_t st);
+                             const PolGroups *groups, bool gated, uint32_t flags, const uint32_t *draw,
+                             int32_t *action_out, float *logp_out, float *value_out, uint32_t out_rows,
+                             uint32_t max_rows, hipStream_t st);
 hipError_t launch_policy_segments(const SimState &S, const PolGroups &groups, int32_t *out, hipStream_t st);
 hipError_t launch_policy_draw_next(uint32_t *draw, hipStream_t st);
 hipError_t launch_policy_repack(const PolUploads &U, hipStream_t st);

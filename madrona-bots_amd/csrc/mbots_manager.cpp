@@ -2850,7 +2850,7 @@ int mbots_traj_gather(mbots_handle *h, uint64_t lo, uint64_t hi, const void *con
 }
 
 // ---- the device actor (include/mbots.h "Acting on the device") ----
-// the layers of a net in upload order: trunk, actor, critic, memory
+// the layers of a net in upload order: trunk, actor, critic, memory, gate
 static std::vector<mbots::PolLayer *> policy_layers(mbots::PolNet &n)
 {
     std::vector<mbots::PolLayer *> v;
@@ -2860,6 +2860,7 @@ static std::vector<mbots::PolLayer *> policy_layers(mbots::PolNet &n)
     v.push_back(&n.critic[0]);
     v.push_back(&n.critic[1]);
     if (n.has_memory) v.push_back(&n.memory);
+    if (n.gated) v.push_back(&n.gate);
     return v;
 }
 
@@ -2870,7 +2871,8 @@ static int policy_describe(const mbots_policy_net *src, mbots::PolNet &n)
     n = PolNet{};
     if (src->n_trunk < 1 || src->n_trunk > (uint32_t)kPolMaxTrunk)
         return fail(MBOTS_E_INVALID, "a policy net has 1..4 trunk layers");
-    if (src->flags & ~MBOTS_POLICY_MEMORY_IN) return fail(MBOTS_E_INVALID, "unknown policy net flags");
+    if (src->flags & ~(MBOTS_POLICY_MEMORY_IN | MBOTS_POLICY_GATE))
+        return fail(MBOTS_E_INVALID, "unknown policy net flags");
     const uint32_t H = src->trunk[0].out, in0 = (src->flags & MBOTS_POLICY_MEMORY_IN) ? kPolObs + kHidden : kPolObs;
     if (H < 16 || H > (uint32_t)kPolMaxH || H % 16u)
         return fail(MBOTS_E_INVALID, "the trunk width must be a multiple of 16 in [16, 128], not " + std::to_string(H));
@@ -2903,6 +2905,18 @@ static int policy_describe(const mbots_policy_net *src, mbots::PolNet &n)
     if (int rc = lay(src->critic[1], n.critic[1], H, 1, "the critic's second layer")) return rc;
     if (n.has_memory)
         if (int rc = lay(src->memory, n.memory, H, kHidden, "the memory head")) return rc;
+    // (src->gate is read under the flag alone: a caller that never sets it may
+    // have built against the struct without the field)
+    if (src->flags & MBOTS_POLICY_GATE) {
+        if (!n.has_memory)
+            return fail(MBOTS_E_INVALID, "MBOTS_POLICY_GATE: a gate head blends the memory head's output into "
+                                         "HiddenState, and the net has no memory head");
+        if (!(src->flags & MBOTS_POLICY_MEMORY_IN))
+            return fail(MBOTS_E_INVALID, "MBOTS_POLICY_GATE: a gated net reads the HiddenState it blends "
+                                         "(MBOTS_POLICY_MEMORY_IN)");
+        if (int rc = lay(src->gate, n.gate, H, kHidden, "the gate head")) return rc;
+        n.gated = 1;
+    }
     n.set = 1;
     return MBOTS_OK;
 }
@@ -2919,7 +2933,8 @@ static void policy_fill_host(const mbots::PolLayer &d, const mbots_policy_layer 
 
 static bool policy_same_arch(mbots::PolNet &a, mbots::PolNet &b)
 {
-    if (!a.set || !b.set || a.n_trunk != b.n_trunk || a.H != b.H || a.flags != b.flags || a.has_memory != b.has_memory)
+    if (!a.set || !b.set || a.n_trunk != b.n_trunk || a.H != b.H || a.flags != b.flags || a.has_memory != b.has_memory ||
+        a.gated != b.gated)
         return false;
     for (uint32_t l = 0; l < a.n_trunk; ++l)
         if (a.trunk[l].in != b.trunk[l].in || a.trunk[l].act != b.trunk[l].act) return false;
@@ -3009,6 +3024,7 @@ static int policy_set_one(mbots_handle *h, uint32_t group, uint32_t species, con
     S.push_back(&net->critic[0]);
     S.push_back(&net->critic[1]);
     if (cur.has_memory) S.push_back(&net->memory);
+    if (cur.gated) S.push_back(&net->gate);
     if (h->cpu) {
         for (size_t i = 0; i < D.size(); ++i) policy_fill_host(*D[i], *S[i]);
         return MBOTS_OK;
@@ -3163,7 +3179,7 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
     // the nets of every (group, species) that owns one of the manager's worlds,
     // and what they do with HiddenState
     const uint32_t nG = h->pol.groups();
-    bool writes_hidden = false, reads_hidden = false, all_hidden = true;
+    bool writes_hidden = false, reads_hidden = false, all_hidden = true, any_gated = false;
     for (uint32_t g = 0; g < nG; ++g) {
         if (!policy_group_needed(h, g)) continue;
         for (int s = 0; s < mbots::kNumSpecies; ++s) {
@@ -3174,6 +3190,7 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
             writes_hidden |= n.has_memory != 0;
             all_hidden &= n.has_memory != 0;
             reads_hidden |= (n.flags & mbots::kPolMemoryIn) != 0u;
+            any_gated |= n.gated != 0u;
         }
     }
     if (out_rows > 0xFFFFFFFFull) out_rows = 0xFFFFFFFFull;
@@ -3214,7 +3231,8 @@ int mbots_policy_act(mbots_handle *h, uint32_t flags, int32_t *action_out, float
     if (nG == 1)
         for (int s = 0; s < mbots::kNumSpecies; ++s) four.net[s] = h->pol.nets[s];
     rc = timed(h, MBOTS_TK_ACTIONS, st, [&] {
-        return mbots::launch_policy_act(h->S, h->T[tb], hidden_in, four, nG > 1 ? &G : nullptr, flags, h->pol.draw,
+        return mbots::launch_policy_act(h->S, h->T[tb], hidden_in, four, nG > 1 ? &G : nullptr, any_gated, flags,
+                                        h->pol.draw,
                                         action_out, logp_out, value_out, (uint32_t)out_rows,
                                         (uint32_t)((uint64_t)h->S.W * h->S.cap), st);
     });
@@ -3249,9 +3267,9 @@ int mbots_policy_draw(mbots_handle *h, int32_t set, uint32_t *value)
 int mbots_policy_activation(int32_t act, const float *x, float *y, uint64_t n, int32_t device, void *stream)
 {
     if ((!x || !y) && n) return fail(MBOTS_E_INVALID, "null argument");
-    if (act < 0 || act > mbots::kActLog) return fail(MBOTS_E_INVALID, "unknown activation code " + std::to_string(act));
+    if (act < 0 || act > mbots::kActSigmoid) return fail(MBOTS_E_INVALID, "unknown activation code " + std::to_string(act));
     if (device < 0) {
-        for (uint64_t i = 0; i < n; ++i) y[i] = mbots::pol_activation(act, x[i]);
+        for (uint64_t i = 0; i < n; ++i) y[i] = mbots::pol_activation_any(act, x[i]);
         return MBOTS_OK;
     }
     HIP_TRY(hipSetDevice(device));
@@ -3265,13 +3283,13 @@ namespace {
 // where a call's pieces lie in the caller's workspace
 struct EvalPlan {
     mbots::PolNet net, back;                  // w / b point into the workspace once bound
-    const mbots_policy_layer *src[mbots::kPolSeqLayers];
-    mbots::PolLayer *fwd[mbots::kPolSeqLayers], *bwd[mbots::kPolSeqLayers];   // null: no such layer
+    const mbots_policy_layer *src[mbots::kPolGateLayers];
+    mbots::PolLayer *fwd[mbots::kPolGateLayers], *bwd[mbots::kPolGateLayers];   // null: no such layer
     mbots::PolGradSlabs slabs;                // base bound; the device's layout, or the CPU mode's
     mbots::PolGradOut out;
     // the slice of src's weight a back layer transposes: its row stride (0: the
     // layer's own width) and first column
-    uint32_t bwd_ld[mbots::kPolSeqLayers], bwd_off[mbots::kPolSeqLayers];
+    uint32_t bwd_ld[mbots::kPolGateLayers], bwd_off[mbots::kPolGateLayers];
     size_t stash_off, h_off, floats;
 };
 
@@ -3285,7 +3303,8 @@ constexpr EvalMode kEvalRows{false, 0u};
 
 // With mode.seq the memory head takes part (slot kPolGradLayers), bwd[0] is the
 // H -> 16 layer over the first layer's HiddenState columns, and the workspace
-// ends with the accumulators' h_k store; without, the layout is evaluate's.
+// ends with the accumulators' h_k store; without, the layout is evaluate's.  A
+// gated net's gate head follows the memory head (slot kPolSeqLayers).
 int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, EvalPlan &P, EvalMode mode)
 {
     using namespace mbots;
@@ -3294,16 +3313,21 @@ int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, Eval
     if (seq && !(P.net.has_memory && (P.net.flags & kPolMemoryIn)))
         return fail(MBOTS_E_INVALID, "sequences are evaluated by a net with a memory head and MBOTS_POLICY_MEMORY_IN "
                                      "(a net without them has no state to carry: mbots_policy_eval)");
-    if (!seq) P.net.has_memory = 0;
+    if (!seq) P.net.has_memory = 0, P.net.gated = 0;   // evaluate ignores both heads
     P.back = PolNet{};
     const uint32_t T = P.net.n_trunk;
-    for (int i = 0; i < kPolSeqLayers; ++i)
+    for (int i = 0; i < kPolGateLayers; ++i)
         P.src[i] = nullptr, P.fwd[i] = nullptr, P.bwd[i] = nullptr, P.bwd_ld[i] = 0u, P.bwd_off[i] = 0u;
     if (seq) {
         P.bwd[0] = &P.back.trunk[0];
         P.src[kPolGradLayers] = &src->memory;
         P.fwd[kPolGradLayers] = &P.net.memory;
         P.bwd[kPolGradLayers] = &P.back.memory;
+        if (P.net.gated) {
+            P.src[kPolSeqLayers] = &src->gate;
+            P.fwd[kPolSeqLayers] = &P.net.gate;
+            P.bwd[kPolSeqLayers] = &P.back.gate;
+        }
     }
     for (uint32_t l = 0; l < T; ++l) {
         P.src[l] = &src->trunk[l];
@@ -3328,7 +3352,7 @@ int eval_plan(const mbots_policy_net *src, uint64_t n, bool cpu, float *ws, Eval
     P.slabs = PolGradSlabs{};
     P.slabs.nacc = (uint32_t)std::min<uint64_t>(tiles, kPolGradAcc);
     P.out = PolGradOut{};
-    P.out.n = seq ? kPolSeqLayers : kPolGradLayers;
+    P.out.n = seq ? (P.net.gated ? kPolGateLayers : kPolSeqLayers) : kPolGradLayers;
     size_t slab = 0, slab_cpu = 0;
     for (int i = 0; i < (int)P.out.n; ++i) {
         if (!P.fwd[i]) continue;
@@ -3747,6 +3771,10 @@ int mbots_policy_seq_grad(const struct mbots_policy_net *net, const float *obs, 
     }
     P.out.w[kPolGradLayers] = out->memory.weight;
     P.out.b[kPolGradLayers] = out->memory.bias;
+    if (P.net.gated) {
+        P.out.w[kPolSeqLayers] = out->gate.weight;
+        P.out.b[kPolSeqLayers] = out->gate.bias;
+    }
     const PolSeqIO io{obs, hidden0, action, length, g_logp, g_value, g_entropy, nullptr, nullptr, nullptr, nullptr, L, B};
     float *ws = static_cast<float *>(workspace);
     if (device >= 0) HIP_TRY(hipSetDevice(device));
@@ -3813,8 +3841,12 @@ int seq_groups_plan(const mbots_policy_net *nets, uint32_t groups, uint32_t L, u
         }
         P.spec[e].mw = src.memory.weight;
         P.spec[e].mb = src.memory.bias;
+        if (d.gated) {
+            P.spec[e].gw = src.gate.weight;
+            P.spec[e].gb = src.gate.bias;
+        }
         PolGroupEntry E;
-        off += pol_group_entry(s, nullptr, E, nullptr, kPolSeqGroupUploads, true, nullptr, nullptr);
+        off += pol_group_entry(s, nullptr, E, nullptr, kPolSeqGroupUploads, true);
         P.slab_stride = std::max<uint64_t>(P.slab_stride, E.slab_floats);
         P.present.push_back(e);
         // (the host path runs evaluate_sequences' own plan, one net at a time, in the same memory)
@@ -3872,10 +3904,11 @@ int seq_groups_check(const mbots_policy_net *nets, uint32_t groups, const int32_
 }
 
 // the caller's gradient pointers of net `src`'s layers, in PolGradOut's slots
-void seq_grad_slots(const mbots_policy_grads &out, uint32_t n_trunk, float **w, float **b)
+void seq_grad_slots(const mbots_policy_grads &out, uint32_t n_trunk, bool gated, float **w, float **b)
 {
     using namespace mbots;
-    for (int i = 0; i < kPolSeqLayers; ++i) w[i] = b[i] = nullptr;
+    for (int i = 0; i < kPolGateLayers; ++i) w[i] = b[i] = nullptr;
+    if (gated) w[kPolSeqLayers] = out.gate.weight, b[kPolSeqLayers] = out.gate.bias;
     for (uint32_t l = 0; l < n_trunk; ++l) w[l] = out.trunk[l].weight, b[l] = out.trunk[l].bias;
     for (int i = 0; i < 2; ++i) {
         w[kPolMaxTrunk + i] = out.actor[i].weight, b[kPolMaxTrunk + i] = out.actor[i].bias;
@@ -3984,7 +4017,7 @@ int mbots_policy_seq_grad_groups(const struct mbots_policy_net *nets, uint32_t g
             const uint64_t lo = (uint64_t)segments[2u * e], len = (uint64_t)segments[2u * e + 1u] - lo;
             EvalPlan one;
             if (int rc = eval_plan(&nets[e], len, true, ws, one, EvalMode{true, L})) return fail_pair(rc, e);
-            seq_grad_slots(out[e], one.net.n_trunk, one.out.w, one.out.b);
+            seq_grad_slots(out[e], one.net.n_trunk, one.net.gated != 0u, one.out.w, one.out.b);
             if (int rc = eval_upload(one, true, -1, nullptr)) return fail_pair(rc, e);
             cpu::policy_seq_grad(one.net, io, one.slabs, ws + one.h_off, one.out, PolSeqCols{order + lo, len});
         }
@@ -4000,7 +4033,7 @@ int mbots_policy_seq_grad_groups(const struct mbots_policy_net *nets, uint32_t g
         if (c == 0) W = PolGroupWave{}, O = PolSeqGroupGrads{};
         W.seg[c] = e;
         W.n = c + 1u;
-        seq_grad_slots(out[e], P.spec[e].s.n_trunk, O.w[c], O.b[c]);
+        seq_grad_slots(out[e], P.spec[e].s.n_trunk, (P.spec[e].s.flags & kPolGate) != 0u, O.w[c], O.b[c]);
     }
     HIP_TRY(hipSetDevice(device));
     HIP_TRY(launch_policy_seq_grad_groups(io, order, segments, P.spec.data(), 4u * groups, waves.data(), grads.data(),

@@ -32,8 +32,9 @@ constexpr size_t kPolLds =
 // bias): the epilogue stores (add[r][j] +) acc times the derivative of
 // activation `act` at the value dst[r][j] holds -- the forward's output, which
 // the gradient replaces in place; act < 0: no derivative factor.  kSrc: floats
-// per row of `src`.
-template <bool kBack = false, int kSrc = kPolStride>
+// per row of `src`.  kSigmoid: the gate head -- the activation is pol_sigmoid,
+// whatever `act` says.
+template <bool kBack = false, int kSrc = kPolStride, bool kSigmoid = false>
 __device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const float *src, float *dst,
                                           uint32_t dst_stride, uint32_t wv, uint32_t woff, uint32_t lane,
                                           const float *add = nullptr)
@@ -115,8 +116,13 @@ __device__ __forceinline__ void pol_layer(const PolLayer &L, int act, const floa
                     *o = v;
                 }
             } else {
-                if (col0 < L.out) dst[row * dst_stride + col0] = pol_activation(act, acc0[mt][r]);
-                if (two && col1 < L.out) dst[row * dst_stride + col1] = pol_activation(act, acc1[mt][r]);
+                if constexpr (kSigmoid) {
+                    if (col0 < L.out) dst[row * dst_stride + col0] = pol_sigmoid(acc0[mt][r]);
+                    if (two && col1 < L.out) dst[row * dst_stride + col1] = pol_sigmoid(acc1[mt][r]);
+                } else {
+                    if (col0 < L.out) dst[row * dst_stride + col0] = pol_activation(act, acc0[mt][r]);
+                    if (two && col1 < L.out) dst[row * dst_stride + col1] = pol_activation(act, acc1[mt][r]);
+                }
             }
         }
 }
@@ -146,6 +152,15 @@ template <bool kTable> __device__ __forceinline__ uint32_t pol_u(uint32_t v)
     if constexpr (kTable) return uniform(v);
     else return v;
 }
+// The lane index behind a barrier the optimiser cannot look through: what a
+// gated net's extra layers derive from it (their per-lane addresses) is worked
+// out where they run, not hoisted out of the surrounding loop and kept in
+// registers across the ungated path.
+__device__ __forceinline__ uint32_t pol_opaque(uint32_t v)
+{
+    asm volatile("" : "+v"(v));
+    return v;
+}
 __device__ __forceinline__ float *pol_uniform_ptr(float *p)
 {
     const uint64_t v = reinterpret_cast<uint64_t>(p);
@@ -171,8 +186,10 @@ template <bool kTable> __device__ __forceinline__ decltype(auto) pol_pick(const 
 
 // One tile of policy_act: rows [r0, r0 + nr) of species sp + 1 (one (group,
 // species) segment, `ghost`: the shard ghost's) through `net`, sampled and
-// written.  kTable: `net` is an entry of the groups' table.
-template <bool kTable>
+// written.  kTable: `net` is an entry of the groups' table.  kGate: a net of the
+// launch may be gated (without, the gate's code is not in the kernel at all: a
+// manager none of whose nets has a gate launches the kernels it always did).
+template <bool kTable, bool kGate>
 __device__ __forceinline__ void pol_act_tile(const PolActArgs &A, const PolNet &net, bool ghost, uint32_t sp,
                                              uint32_t r0, uint32_t nr, uint32_t draw, float *s_pol)
 {
@@ -186,6 +203,7 @@ __device__ __forceinline__ void pol_act_tile(const PolActArgs &A, const PolNet &
     const bool mem_in = (pol_u<kTable>(net.flags) & kPolMemoryIn) != 0u;
     const uint32_t n_trunk = pol_u<kTable>(net.n_trunk);
     const bool has_memory = pol_u<kTable>(net.has_memory) != 0u;
+    const bool gated = kGate && pol_u<kTable>(net.gated) != 0u;
 
     // ---- stage the tile's inputs, coalesced, as the f32 tile X[64][Kp] ----
     {
@@ -294,6 +312,13 @@ __device__ __forceinline__ void pol_act_tile(const PolActArgs &A, const PolNet &
     __syncthreads();
     pol_layer(pol_pick<kTable>(net.critic[1]), kActIdentity, oth, s_val, 1u, wv, 0u, lane);
     __syncthreads();
+    // the gate head's z, in the tile the critic has done with (DESIGN.md "Gated memory head")
+    float *s_z = oth;
+    if (gated) {
+        pol_layer<false, kPolStride, true>(pol_pick<kTable>(net.gate), kActSigmoid, cur, s_z, kPolMemStride, wv, 0u,
+                                           pol_opaque(lane));
+        __syncthreads();
+    }
 
     // ---- epilogue: sample, log-probability, the table's writes ----
     if (t < nr) {
@@ -321,13 +346,20 @@ __device__ __forceinline__ void pol_act_tile(const PolActArgs &A, const PolNet &
         const uint32_t row = t >> 2, g = t & 3u;
         if (row < nr) {
             const float *m = s_mem + row * kPolMemStride + 4u * g;
-            reinterpret_cast<float4 *>(A.hidden_out + (size_t)r0 * kHidden)[t] = make_float4(m[0], m[1], m[2], m[3]);
+            float4 o = make_float4(m[0], m[1], m[2], m[3]);
+            if (gated) {   // (hidden_out may be the column hidden_in is: this thread reads before it writes)
+                const float4 h = reinterpret_cast<const float4 *>(A.hidden_in + (size_t)r0 * kHidden)[t];
+                const float *z = s_z + row * kPolMemStride + 4u * g;
+                o = make_float4(pol_gate_blend(z[0], o.x, h.x), pol_gate_blend(z[1], o.y, h.y),
+                                pol_gate_blend(z[2], o.z, h.z), pol_gate_blend(z[3], o.w, h.w));
+            }
+            reinterpret_cast<float4 *>(A.hidden_out + (size_t)r0 * kHidden)[t] = o;
         }
     }
     __syncthreads();
 }
 
-__global__ __launch_bounds__(256, 2) void policy_act_kernel(PolActArgs A, PolNets P)
+template <bool kGate> __global__ __launch_bounds__(256, 2) void policy_act_kernel(PolActArgs A, PolNets P)
 {
     extern __shared__ float s_pol[];
 
@@ -361,7 +393,7 @@ __global__ __launch_bounds__(256, 2) void policy_act_kernel(PolActArgs A, PolNet
         const uint32_t sp = seg & 3u;   // species - 1
         const uint32_t r0 = seg_start[seg] + rest * kPolRows;
         const uint32_t nr = min((uint32_t)kPolRows, seg_len[seg] - rest * kPolRows);
-        pol_act_tile<false>(A, P.net[sp], seg >= 4u, sp, r0, nr, draw, s_pol);
+        pol_act_tile<false, kGate>(A, P.net[sp], seg >= 4u, sp, r0, nr, draw, s_pol);
     }
 }
 
@@ -378,7 +410,7 @@ constexpr size_t kPolGroupLds = kPolLds + (3u * kPolMaxSegs + 4u) * sizeof(uint3
 static_assert(kPolGroupLds <= 80u * 1024u, "two blocks of policy_act_groups_kernel share a compute unit's LDS");
 static_assert(kPolMaxSegs <= 2u * 256u, "two segment entries per thread");
 
-__global__ __launch_bounds__(256, 2) void policy_act_groups_kernel(PolActArgs A, PolGroups G)
+template <bool kGate> __global__ __launch_bounds__(256, 2) void policy_act_groups_kernel(PolActArgs A, PolGroups G)
 {
     extern __shared__ float s_pol[];
     uint32_t *s_start = reinterpret_cast<uint32_t *>(s_pol) + kPolLds / sizeof(uint32_t);
@@ -444,7 +476,7 @@ __global__ __launch_bounds__(256, 2) void policy_act_groups_kernel(PolActArgs A,
         const uint32_t len = uniform(s_len[e]);
         const uint32_t r0 = uniform(s_start[e]) + rest * kPolRows;
         const uint32_t nr = min((uint32_t)kPolRows, len - rest * kPolRows);
-        pol_act_tile<true>(A, G.table[4u * g + sp], ghost, sp, r0, nr, draw, s_pol);
+        pol_act_tile<true, kGate>(A, G.table[4u * g + sp], ghost, sp, r0, nr, draw, s_pol);
     }
 }
 
@@ -489,7 +521,7 @@ __global__ __launch_bounds__(256) void policy_repack_kernel(PolUploads U) { pol_
 __global__ __launch_bounds__(256) void policy_activation_kernel(int act, const float *x, float *y, uint64_t n)
 {
     for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256u)
-        y[i] = pol_activation(act, x[i]);
+        y[i] = pol_activation_any(act, x[i]);
 }
 
 // ---- evaluate and its backward pass (mbots_policy.hpp; DESIGN.md "Differentiable
@@ -900,7 +932,8 @@ constexpr int kPolDmStride = 20;   // floats per row of the d mem_pre tile: 16 +
 constexpr int kPolHTile = kPolRows * kHidden;
 constexpr size_t kPolSeqEvalLds = (2 * kPolTile + kPolRows * (kPolLogitStride + 1) + kPolHTile + kPolRows) * sizeof(float);
 constexpr size_t kPolSeqGradLds =
-    (4 * kPolTile + kPolRows * (kPolLogitStride + 1) + kPolHTile + kPolRows * kPolDmStride + kPolRows) * sizeof(float);
+    (4 * kPolTile + kPolRows * (kPolLogitStride + 1) + kPolHTile + 2 * kPolRows * kPolDmStride + kPolRows) *
+    sizeof(float);
 
 // A tile's columns.  kIndex false: the batch's own, b0 + row.  kIndex true: the
 // entries idx[0 .. nb) of `order`, kept in s_col; an entry outside [0, B) (and
@@ -986,6 +1019,7 @@ __device__ __forceinline__ void pol_seq_eval_tile(const PolSeqIO &A, const PolNe
     uint32_t *s_len = reinterpret_cast<uint32_t *>(s_h + kPolHTile);
     uint32_t *s_col = s_len + kPolRows;   // (kIndex only)
     const uint32_t T = pol_u<kTable>(net.n_trunk), kp0 = pol_u<kTable>(net.trunk[0].kp);
+    const bool gated = pol_u<kTable>(net.gated) != 0u;
 
     const uint32_t maxlen = pol_seq_lengths<kIndex>(s_len, s_col, A, idx, b0, nb, t);
     for (uint32_t i = t; i < (uint32_t)kPolHTile; i += 256u) {
@@ -1023,12 +1057,25 @@ __device__ __forceinline__ void pol_seq_eval_tile(const PolSeqIO &A, const PolNe
         pol_layer(pol_pick<kTable>(net.actor[0]), kActRelu, cur, oth, kPolStride, wv, 0u, lane);
         __syncthreads();
         pol_layer(pol_pick<kTable>(net.actor[1]), kActIdentity, oth, s_logit, kPolLogitStride, wv, 0u, lane);
-        pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_h, kHidden, wv, 1u, lane);   // h_{k+1}, as act() writes it
+        // h_{k+1}, as act() writes it (a gated net's: below)
+        if (!gated) pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_h, kHidden, wv, 1u, lane);
         __syncthreads();
         pol_layer(pol_pick<kTable>(net.critic[0]), kActRelu, cur, oth, kPolStride, wv, 0u, lane);
         __syncthreads();
         pol_layer(pol_pick<kTable>(net.critic[1]), kActIdentity, oth, s_val, 1u, wv, 0u, lane);
         __syncthreads();
+        if (gated) {
+            // c and z side by side in the tile the critic has done with (waves 0
+            // and 1), then the blend with the h this step read
+            float *s_c = oth, *s_z = oth + kPolHTile;
+            const uint32_t gl = pol_opaque(lane);
+            pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_c, kHidden, wv, 0u, gl);
+            pol_layer<false, kPolStride, true>(pol_pick<kTable>(net.gate), kActSigmoid, cur, s_z, kHidden, wv, 1u, gl);
+            __syncthreads();
+            for (uint32_t i = wv * 64u + gl; i < (uint32_t)kPolHTile; i += 256u)
+                s_h[i] = pol_gate_blend(s_z[i], s_c[i], s_h[i]);
+            __syncthreads();   // the next step stages from s_h
+        }
         if (t < nb && pol_seq_has_col<kIndex>(s_col, nb, t)) {
             const uint64_t e = pol_seq_elem<kIndex>(A, s_col, k, e0, t);
             float logp = 0.0f, ent = 0.0f, val = 0.0f;
@@ -1105,10 +1152,13 @@ __device__ __forceinline__ bool pol_seq_grad_tile(const PolSeqIO &A, const PolNe
     float *s_logit = s_pol + 4 * kPolTile, *s_val = s_logit + kPolRows * kPolLogitStride;
     float *s_hd = s_val + kPolRows;        // h during the sweep, dh on the way back
     float *s_dm = s_hd + kPolHTile;        // the memory head's output y, then d mem_pre
-    uint32_t *s_len = reinterpret_cast<uint32_t *>(s_dm + kPolRows * kPolDmStride);
+    float *s_dg = s_dm + kPolRows * kPolDmStride;   // (gated) the gate's output z, then d gate_pre
+    uint32_t *s_len = reinterpret_cast<uint32_t *>(s_dg + kPolRows * kPolDmStride);
     uint32_t *s_col = s_len + kPolRows;    // (kIndex only)
     const uint32_t T = pol_u<kTable>(net.n_trunk), kp0 = pol_u<kTable>(net.trunk[0].kp);
+    const bool gated = pol_u<kTable>(net.gated) != 0u;
     constexpr int kM = kPolGradLayers;   // the memory head's slot
+    constexpr int kG = kPolSeqLayers;    // the gate head's
     auto dw = [&](int l) { return slab + pol_u<kTable>(sw[l]); };
     auto db = [&](int l) { return slab + pol_u<kTable>(sb[l]); };
 
@@ -1137,7 +1187,19 @@ __device__ __forceinline__ bool pol_seq_grad_tile(const PolSeqIO &A, const PolNe
             cur = oth;
             oth = sw_;
         }
-        pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_hd, kHidden, wv, 0u, lane);
+        if (!gated) {
+            pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_hd, kHidden, wv, 0u, lane);
+        } else {
+            const uint32_t gl = pol_opaque(lane);
+            pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_dm, kPolDmStride, wv, 0u, gl);
+            pol_layer<false, kPolStride, true>(pol_pick<kTable>(net.gate), kActSigmoid, cur, s_dg, kPolDmStride, wv, 1u,
+                                               gl);
+            __syncthreads();
+            for (uint32_t i = wv * 64u + gl; i < (uint32_t)kPolHTile; i += 256u) {
+                const uint32_t d = (i >> 4) * kPolDmStride + (i & 15u);
+                s_hd[i] = pol_gate_blend(s_dg[d], s_dm[d], s_hd[i]);
+            }
+        }
         __syncthreads();
     }
     __syncthreads();
@@ -1163,6 +1225,9 @@ __device__ __forceinline__ bool pol_seq_grad_tile(const PolSeqIO &A, const PolNe
         __syncthreads();
         pol_layer(pol_pick<kTable>(net.actor[1]), kActIdentity, ha, s_logit, kPolLogitStride, wv, 0u, lane);
         pol_layer(pol_pick<kTable>(net.memory), kActTanh, cur, s_dm, kPolDmStride, wv, 1u, lane);
+        if (gated)
+            pol_layer<false, kPolStride, true>(pol_pick<kTable>(net.gate), kActSigmoid, cur, s_dg, kPolDmStride, wv, 2u,
+                                               pol_opaque(lane));
         __syncthreads();
         pol_layer(pol_pick<kTable>(net.critic[0]), kActRelu, cur, hc, kPolStride, wv, 0u, lane);
         __syncthreads();
@@ -1194,10 +1259,25 @@ __device__ __forceinline__ bool pol_seq_grad_tile(const PolSeqIO &A, const PolNe
         {
             const uint32_t row = t >> 2, c0 = (t & 3u) * 4u;
             const bool present = k < s_len[row];
+            if (!gated) {
 #pragma unroll
-            for (uint32_t u = 0; u < 4u; ++u) {
-                float *y = s_dm + row * kPolDmStride + c0 + u;
-                *y = present ? s_hd[row * kHidden + c0 + u] * pol_activation_grad(kActTanh, *y) : 0.0f;
+                for (uint32_t u = 0; u < 4u; ++u) {
+                    float *y = s_dm + row * kPolDmStride + c0 + u;
+                    *y = present ? s_hd[row * kHidden + c0 + u] * pol_activation_grad(kActTanh, *y) : 0.0f;
+                }
+            } else {
+                // d mem_pre, d gate_pre, and in place of dh_{k+1} its direct term dh (1 - z)
+                const uint32_t e0_ = pol_opaque(row * kPolDmStride + c0), h0_ = pol_opaque(row * kHidden + c0);
+#pragma unroll
+                for (uint32_t u = 0; u < 4u; ++u) {
+                    float *y = s_dm + e0_ + u, *z = s_dg + e0_ + u;
+                    float *d = s_hd + h0_ + u;
+                    float dc = 0.0f, dg = 0.0f, dd = 0.0f;
+                    if (present) pol_gate_back(*d, *z, *y, h[h0_ + u], &dc, &dg, &dd);
+                    *y = dc;
+                    *z = dg;
+                    *d = dd;
+                }
             }
         }
         __syncthreads();
@@ -1206,6 +1286,10 @@ __device__ __forceinline__ bool pol_seq_grad_tile(const PolSeqIO &A, const PolNe
         pol_grad_w(pol_pick<kTable>(net.critic[1]), oth + 16, hc, dw(kPolMaxTrunk + 3), db(kPolMaxTrunk + 3), first, wv,
                    lane, t);
         pol_grad_w<kPolDmStride>(pol_pick<kTable>(net.memory), s_dm, cur, dw(kM), db(kM), first, wv, lane, t);
+        if (gated) {
+            const uint32_t gl = pol_opaque(lane);
+            pol_grad_w<kPolDmStride>(pol_pick<kTable>(net.gate), s_dg, cur, dw(kG), db(kG), first, wv, gl, wv * 64u + gl);
+        }
         __syncthreads();
         pol_layer<true>(pol_pick<kTable>(back.actor[1]), kActRelu, oth, ha, kPolStride, wv, 0u, lane);
         pol_layer<true>(pol_pick<kTable>(back.critic[1]), kActRelu, oth + 16, hc, kPolStride, wv, 0u, lane);
@@ -1220,8 +1304,16 @@ __device__ __forceinline__ bool pol_seq_grad_tile(const PolSeqIO &A, const PolNe
         __syncthreads();
         pol_layer<true>(pol_pick<kTable>(back.critic[0]), -1, hc, oth, kPolStride, wv, 0u, lane, oth);
         __syncthreads();
-        pol_layer<true, kPolDmStride>(pol_pick<kTable>(back.memory), (int)pol_u<kTable>(net.trunk[T - 1u].act), s_dm, cur,
-                                      kPolStride, wv, 0u, lane, oth);
+        if (!gated) {
+            pol_layer<true, kPolDmStride>(pol_pick<kTable>(back.memory), (int)pol_u<kTable>(net.trunk[T - 1u].act), s_dm,
+                                          cur, kPolStride, wv, 0u, lane, oth);
+        } else {   // ... plus the gate's, joined last
+            const uint32_t gl = pol_opaque(lane);
+            pol_layer<true, kPolDmStride>(pol_pick<kTable>(back.memory), -1, s_dm, oth, kPolStride, wv, 0u, gl, oth);
+            __syncthreads();
+            pol_layer<true, kPolDmStride>(pol_pick<kTable>(back.gate), (int)pol_u<kTable>(net.trunk[T - 1u].act), s_dg,
+                                          cur, kPolStride, wv, 0u, gl, oth);
+        }
         __syncthreads();
         // the trunk, last layer first: d in `cur`, the layer's input in `oth`
         for (uint32_t l = T; l-- > 0u;) {
@@ -1238,8 +1330,9 @@ __device__ __forceinline__ bool pol_seq_grad_tile(const PolSeqIO &A, const PolNe
             cur = oth;
             oth = sw_;
         }
-        // dh_k[c] = sum_j d0[j] W0[j][69 + c]
-        pol_layer<true>(pol_pick<kTable>(back.trunk[0]), -1, cur, s_hd, kHidden, wv, 0u, lane);
+        // dh_k[c] = sum_j d0[j] W0[j][69 + c] (gated: added to the direct term s_hd holds)
+        if (!gated) pol_layer<true>(pol_pick<kTable>(back.trunk[0]), -1, cur, s_hd, kHidden, wv, 0u, lane);
+        else pol_layer<true>(pol_pick<kTable>(back.trunk[0]), -1, cur, s_hd, kHidden, wv, 0u, pol_opaque(lane), s_hd);
         __syncthreads();
         started = true;
     }
@@ -1280,7 +1373,7 @@ __global__ __launch_bounds__(64) void policy_seq_groups_setup_kernel(PolSeqGroup
     const uint32_t e = S.first + i;
     PolGroupEntry E;
     pol_group_entry(S.s[i].s, ws, E, uploads + (size_t)e * kPolSeqGroupUploads, kPolSeqGroupUploads, true, S.s[i].mw,
-                    S.s[i].mb);
+                    S.s[i].mb, S.s[i].gw, S.s[i].gb);
     table[e] = E;
 }
 
@@ -1381,11 +1474,13 @@ __global__ __launch_bounds__(256) void policy_seq_grad_groups_reduce_kernel(cons
     const uint32_t l = blockIdx.y, c = blockIdx.z, e = Wv.seg[c];
     const PolGroupEntry &E = table[e];
     if (l < (uint32_t)kPolMaxTrunk && l >= E.net.n_trunk) return;
+    if (l == (uint32_t)kPolSeqLayers && !E.net.gated) return;
     const uint32_t h = l - (uint32_t)kPolMaxTrunk;
     const PolLayer &f = l < (uint32_t)kPolMaxTrunk ? E.net.trunk[l]
                         : h < 2u                   ? E.net.actor[h]
                         : h < 4u                   ? E.net.critic[h - 2u]
-                                                   : E.net.memory;
+                        : h < 5u                   ? E.net.memory
+                                                   : E.net.gate;
     uint32_t lo, len;
     pol_segment(segments, e, n, lo, len);
     const uint32_t nacc = min(min((len + kPolRows - 1u) / kPolRows, kPolGradAcc), wave_acc);
@@ -1626,7 +1721,7 @@ hipError_t launch_policy_seq_grad_groups(const PolSeqIO &io, const int32_t *orde
                                st, io, order, segments, table, waves[w], slabs, slab_stride, stash, hws);
             if (const hipError_t e = hipGetLastError()) return e;
         }
-        hipLaunchKernelGGL(policy_seq_grad_groups_reduce_kernel, dim3(16, kPolSeqLayers, waves[w].n), dim3(256), 0, st,
+        hipLaunchKernelGGL(policy_seq_grad_groups_reduce_kernel, dim3(16, kPolGateLayers, waves[w].n), dim3(256), 0, st,
                            segments, io.B, table, waves[w], grads[w], slabs, slab_stride, io.L ? wave_acc : 0u);
         if (const hipError_t e = hipGetLastError()) return e;
     }
@@ -1686,18 +1781,22 @@ hipError_t launch_policy_seq_grad(const PolSeqIO &io, const PolNet &net, const P
 }
 
 hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *hidden_in, const PolNets &nets,
-                             const PolGroups *groups, uint32_t flags, const uint32_t *draw, int32_t *action_out,
-                             float *logp_out, float *value_out, uint32_t out_rows, uint32_t max_rows, hipStream_t st)
+                             const PolGroups *groups, bool gated, uint32_t flags, const uint32_t *draw,
+                             int32_t *action_out, float *logp_out, float *value_out, uint32_t out_rows,
+                             uint32_t max_rows, hipStream_t st)
 {
-    static bool lds_set[2] = {false, false};
-    if (!lds_set[groups ? 1 : 0]) {
-        const hipError_t e =
-            groups ? hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_groups_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolGroupLds)
-                   : hipFuncSetAttribute(reinterpret_cast<const void *>(policy_act_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPolLds);
+    // four kernels: one group or the groups' table, with or without the gate's code
+    const void *fn = groups ? (gated ? reinterpret_cast<const void *>(policy_act_groups_kernel<true>)
+                                     : reinterpret_cast<const void *>(policy_act_groups_kernel<false>))
+                            : (gated ? reinterpret_cast<const void *>(policy_act_kernel<true>)
+                                     : reinterpret_cast<const void *>(policy_act_kernel<false>));
+    static bool lds_set[4] = {false, false, false, false};
+    const int which = (groups ? 2 : 0) + (gated ? 1 : 0);
+    if (!lds_set[which]) {
+        const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                 (int)(groups ? kPolGroupLds : kPolLds));
         if (e != hipSuccess) return e;
-        lds_set[groups ? 1 : 0] = true;
+        lds_set[which] = true;
     }
     PolActArgs A{};
     A.totals = S.totals;
@@ -1727,8 +1826,12 @@ hipError_t launch_policy_act(const SimState &S, const ObsTable &t, const float *
     // (with groups: 4 G + 4 segments)
     const uint64_t tiles = (uint64_t)max_rows / kPolRows + (groups ? 4u * groups->G + 4u : 8u);
     const unsigned blocks = (unsigned)std::min<uint64_t>(tiles, 512u);
-    if (groups) hipLaunchKernelGGL(policy_act_groups_kernel, dim3(blocks), dim3(256), kPolGroupLds, st, A, *groups);
-    else hipLaunchKernelGGL(policy_act_kernel, dim3(blocks), dim3(256), kPolLds, st, A, nets);
+    if (groups && gated)
+        hipLaunchKernelGGL(policy_act_groups_kernel<true>, dim3(blocks), dim3(256), kPolGroupLds, st, A, *groups);
+    else if (groups)
+        hipLaunchKernelGGL(policy_act_groups_kernel<false>, dim3(blocks), dim3(256), kPolGroupLds, st, A, *groups);
+    else if (gated) hipLaunchKernelGGL(policy_act_kernel<true>, dim3(blocks), dim3(256), kPolLds, st, A, nets);
+    else hipLaunchKernelGGL(policy_act_kernel<false>, dim3(blocks), dim3(256), kPolLds, st, A, nets);
     return hipGetLastError();
 }
 

@@ -20,13 +20,14 @@ constexpr int kPolObs = 69;            // construct_obs(prev = False) floats of 
 constexpr int kPolActions = 6;
 constexpr int kPolMaxH = 128;          // trunk width: a multiple of 16 in [16, 128]
 constexpr int kPolMaxTrunk = 4;
-constexpr int kPolLayers = kPolMaxTrunk + 5;   // trunk, actor 2, critic 2, memory
+constexpr int kPolLayers = kPolMaxTrunk + 6;   // trunk, actor 2, critic 2, memory, gate
 constexpr uint32_t kPolMemoryIn = 1u;  // MBOTS_POLICY_MEMORY_IN
+constexpr uint32_t kPolGate = 2u;      // MBOTS_POLICY_GATE
 constexpr uint32_t kActGreedy = 1u, kActNoWrite = 2u;   // MBOTS_ACT_*
-// activation codes (mbots_policy_layer.act; 6 and 7 only through
+// activation codes (mbots_policy_layer.act; 6, 7 and 8 only through
 // mbots_policy_activation)
 constexpr int kActIdentity = 0, kActRelu = 1, kActLeaky = 2, kActTanh = 3, kActElu = 4, kActLogSigmoid = 5,
-              kActExp = 6, kActLog = 7;
+              kActExp = 6, kActLog = 7, kActSigmoid = 8;
 
 // input width rounded up to the k-step of the matrix instruction
 MB_HD uint32_t pol_kp(uint32_t in) { return (in + 3u) & ~3u; }
@@ -170,6 +171,31 @@ MB_HD float pol_logsigmoid(float x)
     return x < 0.0f ? x - l : -l;
 }
 
+// sigmoid(x) = 1 / (1 + exp(-|x|)) for x >= 0, exp(-|x|) / (1 + exp(-|x|)) below:
+// exactly 1 from where 1 + e rounds to 1, exactly 0 where pol_exp gives 0
+MB_HD float pol_sigmoid(float x)
+{
+    if (!(x == x)) return x;
+    const float a = x < 0.0f ? -x : x;
+    const float e = pol_exp(-a), d = 1.0f + e;
+    return x < 0.0f ? e / d : 1.0f / d;
+}
+
+// The gated memory head's new state (DESIGN.md "Gated memory head"): (1 - z) h
+// + z c in two fmaf, exact at both ends -- z == 1 gives c, z == 0 gives h (a -0
+// may come out as +0).
+MB_HD float pol_gate_blend(float z, float c, float h) { return pol_fma(z, c, pol_fma(-z, h, h)); }
+// Its point-wise backward from dh = d loss / d h': the gradients at the memory
+// head's and the gate's pre-activations, and the direct term of d loss / d h.
+// With z == 1 dpre_z and dh_direct are zeros, with z == 0 dpre_c is.
+MB_HD void pol_gate_back(float dh, float z, float c, float h, float *dpre_c, float *dpre_z, float *dh_direct)
+{
+    const float omz = 1.0f - z;
+    *dpre_c = (dh * z) * pol_fma(-c, c, 1.0f);
+    *dpre_z = (dh * (c - h)) * (z * omz);
+    *dh_direct = dh * omz;
+}
+
 MB_HD float pol_activation(int code, float x)
 {
     switch (code) {
@@ -182,6 +208,14 @@ MB_HD float pol_activation(int code, float x)
     case kActLog: return pol_log(x);
     default: return x;
     }
+}
+
+// pol_activation and the gate head's sigmoid (code 8): what
+// mbots_policy_activation evaluates.  Kept out of pol_activation's switch, which
+// the trunk layers run on a code that is never 8.
+MB_HD float pol_activation_any(int code, float x)
+{
+    return code == kActSigmoid ? pol_sigmoid(x) : pol_activation(code, x);
 }
 
 // the row's uniform: keyed by (seed, draw) and counted by (global world,
@@ -236,8 +270,8 @@ struct PolLayer {
 };
 struct PolNet {
     uint32_t set, n_trunk, H, flags;   // flags: kPolMemoryIn
-    uint32_t has_memory, pad[3];
-    PolLayer trunk[kPolMaxTrunk], actor[2], critic[2], memory;
+    uint32_t has_memory, gated, pad[2];   // gated: the gate head blends the memory head's output into HiddenState
+    PolLayer trunk[kPolMaxTrunk], actor[2], critic[2], memory, gate;
 };
 struct PolNets {
     PolNet net[kNumSpecies];
@@ -314,6 +348,8 @@ constexpr uint32_t kPolGradRows = 64, kPolGradAcc = 256;
 constexpr int kPolGradLayers = kPolMaxTrunk + 4;   // trunk, actor 2, critic 2 (the memory head takes no part)
 // evaluate_sequences' gradients: those, then the memory head (slot kPolGradLayers)
 constexpr int kPolSeqLayers = kPolGradLayers + 1;
+// a gated net's: those, then the gate head (slot kPolSeqLayers)
+constexpr int kPolGateLayers = kPolSeqLayers + 1;
 
 // d activation / d input, from the layer's output y
 MB_HD float pol_activation_grad(int code, float y)
@@ -378,15 +414,15 @@ struct PolEvalIO {
 struct PolGradSlabs {
     float *base;
     uint64_t slab_floats;
-    uint32_t w[kPolSeqLayers], b[kPolSeqLayers];
+    uint32_t w[kPolGateLayers], b[kPolGateLayers];
     uint32_t nacc;
 };
 // the gradients as the caller wants them ([out][in] / [out], null: not wanted), in
 // the order trunk, actor, critic
 struct PolGradOut {
-    float *w[kPolSeqLayers], *b[kPolSeqLayers];
-    uint32_t in[kPolSeqLayers], out[kPolSeqLayers], kp[kPolSeqLayers];
-    uint32_t n;   // slots in use: kPolGradLayers, or kPolSeqLayers
+    float *w[kPolGateLayers], *b[kPolGateLayers];
+    uint32_t in[kPolGateLayers], out[kPolGateLayers], kp[kPolGateLayers];
+    uint32_t n;   // slots in use: kPolGradLayers, kPolSeqLayers, or kPolGateLayers
 };
 MB_HD uint32_t pol_grad_nkt(uint32_t kp) { return (kp + 15u) >> 4; }
 
@@ -407,10 +443,11 @@ struct PolGroupSpec {
 // The net's descriptors in the workspace: forward and transposed layers (as
 // evaluate's plan lays them out) and where each layer's dW / db lie in a slab.
 // (The grouped evaluate_sequences adds the memory head: its layer and slab slot
-// kPolGradLayers, back.memory, and back.trunk[0] the H -> 16 layer of dh.)
+// kPolGradLayers, back.memory, and back.trunk[0] the H -> 16 layer of dh; a
+// gated net's gate head is layer and slot kPolSeqLayers, with back.gate.)
 struct PolGroupEntry {
     PolNet net, back;
-    uint32_t sw[kPolSeqLayers], sb[kPolSeqLayers];
+    uint32_t sw[kPolGateLayers], sb[kPolGateLayers];
     uint32_t slab_floats, pad;
 };
 MB_HD float *pol_group_take(float *ws, uint64_t base, size_t &off, size_t floats)
@@ -422,10 +459,11 @@ MB_HD float *pol_group_take(float *ws, uint64_t base, size_t &off, size_t floats
 // `e` (and, `up` not null, the `nup` repacks that fill its weights) from `s`;
 // returns the floats the weights take from ws + s.w_off on.  seq: the net as
 // evaluate_sequences runs it, with the memory head (parameters mw, mb) as layer
-// kPolGradLayers and the transposed W0[:, 69:85] slice as back.trunk[0].
+// kPolGradLayers and the transposed W0[:, 69:85] slice as back.trunk[0]; with
+// kPolGate in s.flags the gate head (gw, gb) follows as layer kPolSeqLayers.
 MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e, PolUpload *up,
                              int nup = kPolGroupUploads, bool seq = false, const float *mw = nullptr,
-                             const float *mb = nullptr)
+                             const float *mb = nullptr, const float *gw = nullptr, const float *gb = nullptr)
 {
     e = PolGroupEntry{};
     size_t off = 0;
@@ -437,11 +475,16 @@ MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e,
         e.net.H = H;
         e.net.flags = s.flags;
         e.net.has_memory = seq ? 1u : 0u;
+        e.net.gated = seq && (s.flags & kPolGate) ? 1u : 0u;
         uint32_t slab = 0;
-        for (int i = 0; i < (seq ? kPolSeqLayers : kPolGradLayers); ++i) {
+        for (int i = 0; i < (seq ? (e.net.gated ? kPolGateLayers : kPolSeqLayers) : kPolGradLayers); ++i) {
             PolLayer *f, *b;
             uint32_t in = H, out = H, act = 0;
-            if (i == kPolGradLayers) {
+            if (i == kPolSeqLayers) {
+                f = &e.net.gate;
+                b = &e.back.gate;
+                out = (uint32_t)kHidden;
+            } else if (i == kPolGradLayers) {
                 f = &e.net.memory;
                 b = &e.back.memory;
                 out = (uint32_t)kHidden;
@@ -465,7 +508,8 @@ MB_HD size_t pol_group_entry(const PolGroupSpec &s, float *ws, PolGroupEntry &e,
             f->act = act;
             f->w = pol_group_take(ws, s.w_off, off, pol_w_floats(*f));
             f->b = pol_group_take(ws, s.w_off, off, pol_b_floats(*f));
-            const float *pw = i == kPolGradLayers ? mw : s.w[i], *pb = i == kPolGradLayers ? mb : s.b[i];
+            const float *pw = i == kPolSeqLayers ? gw : i == kPolGradLayers ? mw : s.w[i];
+            const float *pb = i == kPolSeqLayers ? gb : i == kPolGradLayers ? mb : s.b[i];
             if (up) up[nu++] = PolUpload{pw, pb, f->w, f->b, in, out, f->kp, f->nt, 0u, 0u, 0u};
             if (seq && i == 0) {   // W0[:, 69:85] alone: dh_k
                 PolLayer *d = &e.back.trunk[0];
@@ -539,11 +583,12 @@ MB_HD size_t pol_seq_h_floats(uint32_t nacc, uint32_t L) { return (size_t)nacc *
 // Position p of segment e = 4 g + s, lo <= p < hi of `segments` [G][4][2],
 // stands for column order[p] of the batch; tiles, accumulators and chains are
 // evaluate_sequences', counted in positions from lo.
-constexpr int kPolSeqGroupUploads = 20;   // a net's 9 forward and 9 transposed layers, rounded up
+constexpr int kPolSeqGroupUploads = 20;   // a net's 10 forward and 10 transposed layers at most (the gate's included)
 constexpr uint32_t kPolNoColumn = 0xFFFFFFFFu;   // an order entry outside [0, B): length 0, never read or written
 struct PolSeqGroupSpec {
     PolGroupSpec s;
     const float *mw, *mb;   // the memory head's parameters
+    const float *gw, *gb;   // the gate head's (s.flags has kPolGate)
 };
 constexpr uint32_t kPolSeqGroupChunk = 20;
 struct PolSeqGroupSpecs {
@@ -552,7 +597,7 @@ struct PolSeqGroupSpecs {
 };
 static_assert(sizeof(PolSeqGroupSpecs) + 64u <= 4096u, "a setup launch's specs travel as kernel arguments");
 struct PolSeqGroupGrads {
-    float *w[kPolGroupWave][kPolSeqLayers], *b[kPolGroupWave][kPolSeqLayers];
+    float *w[kPolGroupWave][kPolGateLayers], *b[kPolGroupWave][kPolGateLayers];
 };
 // the columns a host evaluate_sequences call runs: idx[0 .. n) of the batch's B
 // (idx null: all B, in place)

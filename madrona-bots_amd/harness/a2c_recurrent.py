@@ -15,6 +15,11 @@ Losses and optimisers are plain torch.
 
     python madrona-bots_amd/harness/a2c_recurrent.py --worlds 64 --iters 10 --exec-mode cpu
     python madrona-bots_amd/harness/a2c_recurrent.py --worlds 4096 --iters 50
+    python madrona-bots_amd/harness/a2c_recurrent.py --worlds 4096 --iters 50 --gated
+
+--gated: every species' net also carries a gate head Linear(H, 16), Sigmoid, and
+its new HiddenState is (1 - z) h + z c (INTEGRATION.md "Training the memory
+head"): the update gate lets an agent keep what it knew.
 """
 import argparse
 import json
@@ -26,9 +31,10 @@ import torch
 NUM_SPECIES = 4
 
 
-def make_modules(hidden=128, device="cpu", seed=0):
+def make_modules(hidden=128, device="cpu", seed=0, gated=False):
     """Per species a2c.py's stacks with the 16 HiddenState floats after the 69
-    observation floats as the input, and the memory head Linear(H, 16), Tanh."""
+    observation floats as the input, and the memory head Linear(H, 16), Tanh;
+    gated: and the gate head Linear(H, 16), Sigmoid."""
     nn = torch.nn
     torch.manual_seed(seed)
     mods = []
@@ -40,8 +46,18 @@ def make_modules(hidden=128, device="cpu", seed=0):
         memory = nn.Sequential(nn.Linear(hidden, 16), nn.Tanh())
         with torch.no_grad():
             feature[0].weight[:, :69].mul_(0.01)
-        mods.append(nn.ModuleDict({"feature": feature, "actor": actor, "critic": critic, "memory": memory}).to(device))
+        parts = {"feature": feature, "actor": actor, "critic": critic, "memory": memory}
+        if gated:
+            parts["gate"] = nn.Sequential(nn.Linear(hidden, 16), nn.Sigmoid())
+        mods.append(nn.ModuleDict(parts).to(device))
     return mods
+
+
+def policy_net(m):
+    """The PolicyNet over one species' modules of make_modules()."""
+    import madrona_bots as mb
+    return mb.PolicyNet.from_torch(m["feature"], m["actor"], m["critic"], m["memory"], memory_in=True,
+                                   gate=m["gate"] if "gate" in m else None)
 
 
 def species_of_rows(sim):
@@ -80,9 +96,7 @@ def rollout(sim, win, horizon, gamma=0.99, lam=0.95, death_reward=-1.0):
 def train(sim, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0, value_coef=0.5,
           entropy_coef=0.01, log=None):
     """`iters` updates of `horizon - 1` steps each.  Returns the losses (floats)."""
-    import madrona_bots as mb
-    nets = [mb.PolicyNet.from_torch(m["feature"], m["actor"], m["critic"], m["memory"], memory_in=True)
-            for m in modules]
+    nets = [policy_net(m) for m in modules]
     sim.set_policy(nets)
     win = sim.trajectory_window(horizon, max_rows=sim.num_worlds * sim.agent_capacity, record_obs=True,
                                 record_state=True)
@@ -134,11 +148,12 @@ def main():
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--seed", type=int, default=69)
     ap.add_argument("--exec-mode", choices=("hip", "cpu"), default="hip" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--gated", action="store_true", help="add the gate head to every species' net")
     args = ap.parse_args()
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     import madrona_bots as mb
     sim = mb.SimManager(0, args.worlds, args.seed, args.agents, exec_mode=args.exec_mode)
-    modules = make_modules(args.hidden, sim.device, args.seed)
+    modules = make_modules(args.hidden, sim.device, args.seed, args.gated)
     optimizers = [torch.optim.Adam(m.parameters(), lr=args.lr) for m in modules]
     train(sim, modules, optimizers, args.iters, args.horizon, log=print)
 

@@ -37,7 +37,7 @@ import sys
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from a2c_recurrent import make_modules, rollout  # noqa: E402
+from a2c_recurrent import make_modules, policy_net, rollout  # noqa: E402
 
 
 def window_batch(sim, win, starts_dev, horizon, actions, species, worlds):
@@ -73,8 +73,7 @@ def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.
     import madrona_bots as mb
     G = len(starts)
     sim.set_policy_groups(starts)
-    nets = [[mb.PolicyNet.from_torch(m["feature"], m["actor"], m["critic"], m["memory"], memory_in=True)
-             for m in modules[u]] for u in range(G)]
+    nets = [[policy_net(m) for m in modules[u]] for u in range(G)]
     for u in range(G):
         sim.set_policy(nets[u], group=u)
     starts_dev = torch.tensor(list(starts), dtype=torch.int64, device=sim.device)
@@ -153,6 +152,7 @@ def main():
     ap.add_argument("--seed", type=int, default=69)
     ap.add_argument("--exec-mode", choices=("hip", "cpu"), default="hip" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--reward-fixed", action="store_true", help="rewards[speciesID - 1]: universes fully apart")
+    ap.add_argument("--gated", action="store_true", help="add the gate head to every net (a2c_recurrent.py --gated)")
     ap.add_argument("--grouped-evaluate", action="store_true",
                     help="one evaluate_sequences_groups and one backward() per update instead of one "
                          "evaluate_sequences per (group, species)")
@@ -164,7 +164,8 @@ def main():
     sim = mb.SimManager(0, args.worlds, args.seed, args.agents, exec_mode=args.exec_mode,
                         reward_fixed=args.reward_fixed)
     starts = [u * args.worlds // args.groups for u in range(args.groups)]
-    modules = [make_modules(args.hidden[u % len(args.hidden)], sim.device, args.seed + u) for u in range(args.groups)]
+    modules = [make_modules(args.hidden[u % len(args.hidden)], sim.device, args.seed + u, args.gated)
+               for u in range(args.groups)]
     optimizers = [[torch.optim.Adam(m.parameters(), lr=args.lr) for m in four] for four in modules]
     train(sim, starts, modules, optimizers, args.iters, args.horizon, log=print,
           grouped_evaluate=args.grouped_evaluate)

@@ -70,7 +70,8 @@ class _PolicyLayer(ctypes.Structure):   # struct mbots_policy_layer
 
 class _PolicyNet(ctypes.Structure):     # struct mbots_policy_net
     _fields_ = [("n_trunk", ctypes.c_uint32), ("trunk", _PolicyLayer * 4), ("actor", _PolicyLayer * 2),
-                ("critic", _PolicyLayer * 2), ("memory", _PolicyLayer), ("flags", ctypes.c_uint32)]
+                ("critic", _PolicyLayer * 2), ("memory", _PolicyLayer), ("flags", ctypes.c_uint32),
+                ("gate", _PolicyLayer)]
 
 
 class _PolicyGradLayer(ctypes.Structure):   # struct mbots_policy_grad_layer
@@ -79,7 +80,7 @@ class _PolicyGradLayer(ctypes.Structure):   # struct mbots_policy_grad_layer
 
 class _PolicyGrads(ctypes.Structure):   # struct mbots_policy_grads
     _fields_ = [("trunk", _PolicyGradLayer * 4), ("actor", _PolicyGradLayer * 2), ("critic", _PolicyGradLayer * 2),
-                ("memory", _PolicyGradLayer)]
+                ("memory", _PolicyGradLayer), ("gate", _PolicyGradLayer)]
 
 
 class _CTensor(ctypes.Structure):
@@ -999,6 +1000,9 @@ class SimManager:
         if net.memory is not None:
             c.memory = layer(net.memory)
         c.flags = 1 if net.memory_in else 0
+        if net.gate is not None:
+            c.gate = layer(net.gate)
+            c.flags |= 2   # MBOTS_POLICY_GATE
         # (the upload reads the tensors in stream order on torch's current
         # stream, where the caching allocator also orders their release)
         if group is None:
@@ -1297,9 +1301,10 @@ class SimManager:
         return {k: (ms[i], n[i]) for i, k in enumerate(KERNELS)}
 
 
-# activation codes of the device actor (include/mbots.h; 6 and 7: its own exp
-# and log, through policy_activation only)
-ACTIVATIONS = {"Identity": 0, "ReLU": 1, "LeakyReLU": 2, "Tanh": 3, "ELU": 4, "LogSigmoid": 5, "exp": 6, "log": 7}
+# activation codes of the device actor (include/mbots.h; 6, 7 and 8: its own
+# exp and log and the gate head's sigmoid, through policy_activation only)
+ACTIVATIONS = {"Identity": 0, "ReLU": 1, "LeakyReLU": 2, "Tanh": 3, "ELU": 4, "LogSigmoid": 5, "exp": 6, "log": 7,
+               "Sigmoid": 8}
 
 
 def _activation_code(m, where):
@@ -1330,12 +1335,19 @@ class PolicyNet:
     two (weight, bias, 0) layers each -- Linear(H, H), ReLU, Linear(H, 6 / 1);
     memory, a (weight [16, H], bias, 0) Linear followed by Tanh whose output
     becomes HiddenState, or None; memory_in: the row's 16 HiddenState floats
-    follow its 69 observation floats as the input.  The tensors are referenced,
-    not copied: set_policy() uploads their values of that moment."""
+    follow its 69 observation floats as the input; gate, a (weight [16, H],
+    bias, 0) Linear followed by a sigmoid, or None: with it the new HiddenState
+    is (1 - z) h + z c, z the gate's and c the memory head's output, h the
+    state the row read (it needs memory and memory_in; DESIGN.md "Gated memory
+    head").  The tensors are referenced, not copied: set_policy() uploads their
+    values of that moment."""
 
-    def __init__(self, trunk, actor, critic, memory=None, memory_in=False):
+    def __init__(self, trunk, actor, critic, memory=None, memory_in=False, gate=None):
         self.trunk, self.actor, self.critic = list(trunk), list(actor), list(critic)
-        self.memory, self.memory_in = memory, bool(memory_in)
+        self.memory, self.memory_in, self.gate = memory, bool(memory_in), gate
+        if gate is not None and (memory is None or not self.memory_in):
+            raise ValueError("a gate needs a memory head and memory_in=True: it blends the memory head's output into "
+                             "the HiddenState the net read")
         if not 1 <= len(self.trunk) <= 4:
             raise ValueError(f"a policy net has 1..4 trunk Linear layers, not {len(self.trunk)}")
         if len(self.actor) != 2 or len(self.critic) != 2:
@@ -1363,11 +1375,12 @@ class PolicyNet:
         return [(w, b, c) for w, b, c, _ in out]
 
     @classmethod
-    def from_torch(cls, feature, actor, critic, memory=None, memory_in=False):
+    def from_torch(cls, feature, actor, critic, memory=None, memory_in=False, gate=None):
         """From nn.Sequential stacks of Linear plus {Tanh, ELU, LogSigmoid,
         LeakyReLU, ReLU}: the reference's a2c_nets.feature / .actor / .critic
         load unchanged (its recurrent module is not executed: see
-        INTEGRATION.md).  memory: Sequential(Linear(H, 16), Tanh) or None."""
+        INTEGRATION.md).  memory: Sequential(Linear(H, 16), Tanh) or None; gate:
+        Sequential(Linear(H, 16), Sigmoid) or None (with memory and memory_in)."""
         trunk = cls._linears(feature, "feature")
         heads = []
         for name, seq, width in (("actor", actor, 6), ("critic", critic, 1)):
@@ -1383,7 +1396,18 @@ class PolicyNet:
             if len(ls) != 1 or ls[0][2] != 3 or ls[0][0].shape[0] != 16:
                 raise ValueError("memory: expected Linear(H, 16), Tanh")
             mem = (ls[0][0], ls[0][1], 0)
-        net = cls(trunk, heads[0], heads[1], mem, memory_in)
+        gat = None
+        if gate is not None:
+            mods = list(gate) if isinstance(gate, torch.nn.Sequential) else [gate]
+            if len(mods) != 2 or not isinstance(mods[0], torch.nn.Linear) or not isinstance(mods[1], torch.nn.Sigmoid):
+                bad = next((f"gate[{i}] ({type(m).__name__})" for i, m in enumerate(mods)
+                            if not isinstance(m, (torch.nn.Linear, torch.nn.Sigmoid) if i else torch.nn.Linear)),
+                           f"gate ({len(mods)} modules)")
+                raise ValueError(f"{bad}: expected Linear(H, 16), Sigmoid")
+            if mods[0].weight.shape[0] != 16:
+                raise ValueError(f"gate[0] (Linear): expected Linear(H, 16), not {mods[0].weight.shape[0]} outputs")
+            gat = (mods[0].weight, mods[0].bias, 0)
+        net = cls(trunk, heads[0], heads[1], mem, memory_in, gat)
         net._validate()
         return net
 
@@ -1401,6 +1425,16 @@ class PolicyNet:
                 raise ValueError(f"{name}: expected Linear({H}, {H}), ReLU, Linear({H}, {width})")
         if self.memory is not None and tuple(self.memory[0].shape) != (16, H):
             raise ValueError(f"memory: expected Linear({H}, 16)")
+        if self.gate is not None and tuple(self.gate[0].shape) != (16, H):
+            raise ValueError(f"gate: expected Linear({H}, 16), not {list(self.gate[0].shape)}")
+
+    def _seq_params(self):
+        """_named_params() and what evaluate_sequences adds: the memory head's,
+        then a gated net's gate head's."""
+        out = self._named_params() + [("memory Linear weight", self.memory[0]), ("memory Linear bias", self.memory[1])]
+        if self.gate is not None:
+            out += [("gate Linear weight", self.gate[0]), ("gate Linear bias", self.gate[1])]
+        return out
 
     # -- learning from what act() did -----------------------------------------
     def _named_params(self):
@@ -1427,6 +1461,11 @@ class PolicyNet:
             c.memory.in_, c.memory.out, c.memory.act = w.shape[1], w.shape[0], 0
             c.memory.weight, c.memory.bias = w.data_ptr(), None if b is None else b.data_ptr()
         c.flags = 1 if self.memory_in else 0
+        if len(params) > 2 * len(slots) + 2:   # a gated net's gate head after it
+            w, b = params[2 * len(slots) + 2], params[2 * len(slots) + 3]
+            c.gate.in_, c.gate.out, c.gate.act = w.shape[1], w.shape[0], 0
+            c.gate.weight, c.gate.bias = w.data_ptr(), None if b is None else b.data_ptr()
+            c.flags |= 2   # MBOTS_POLICY_GATE
         return c
 
     def evaluate(self, obs, action, hidden=None):
@@ -1500,7 +1539,7 @@ class PolicyNet:
         if hidden0.dtype != torch.float32 or hidden0.device != dev or tuple(hidden0.shape) != (B, 16):
             raise ValueError(f"hidden0 must be float32 [B, 16] on {dev}, not {hidden0.dtype} {list(hidden0.shape)} on "
                              f"{hidden0.device}")
-        named = self._named_params() + [("memory Linear weight", self.memory[0]), ("memory Linear bias", self.memory[1])]
+        named = self._seq_params()
         for name, p in named:
             if p is not None and (p.dtype != torch.float32 or p.device != dev):
                 raise ValueError(f"{name} must be float32 on {dev} (obs's device), not {p.dtype} on {p.device}")
@@ -1583,7 +1622,7 @@ class _EvaluateSequences(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, net, obs, action, length, hidden0, want_hidden, present, *params):
-        full = [None] * (2 * (len(net.trunk) + 5))
+        full = [None] * (2 * (len(net.trunk) + (5 if net.gate is None else 6)))
         for i, p in zip(present, params):
             full[i] = p.detach().contiguous()
         L, B = obs.shape[0], obs.shape[1]
@@ -1611,7 +1650,7 @@ class _EvaluateSequences(torch.autograd.Function):
                 grads[i] = torch.empty_like(full[i])
         out = _PolicyGrads()
         slots = [out.trunk[i] for i in range(len(net.trunk))] + [out.actor[0], out.actor[1], out.critic[0], out.critic[1],
-                                                                 out.memory]
+                                                                 out.memory] + ([] if net.gate is None else [out.gate])
         for i, slot in enumerate(slots):
             slot.weight, slot.bias = _ptr(grads[2 * i]).value, _ptr(grads[2 * i + 1]).value
         _eval_call(net, obs, None, None, full, lambda c, ws, nb, d, st: _lib.mbots_policy_seq_grad(
@@ -1878,7 +1917,7 @@ def evaluate_sequences_groups(nets, obs, action, length, hidden0, order, segment
         if x.memory is None or not x.memory_in:
             raise ValueError(f"{where}: evaluate_sequences_groups needs a net with a memory head and memory_in=True "
                              "(there is no state to carry otherwise): use evaluate_groups()")
-        named = x._named_params() + [("memory Linear weight", x.memory[0]), ("memory Linear bias", x.memory[1])]
+        named = x._seq_params()
         for i, (name, p) in enumerate(named):
             if p is None:
                 continue
@@ -1923,7 +1962,7 @@ class _EvaluateSequencesGroups(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, flat, obs, action, length, hidden0, order, segments, want_hidden, index, *params):
-        full = [None if x is None else [None] * (2 * (len(x.trunk) + 5)) for x in flat]
+        full = [None if x is None else [None] * (2 * (len(x.trunk) + (5 if x.gate is None else 6))) for x in flat]
         for (e, i), p in zip(index, params):
             full[e][i] = p.detach().contiguous()
         L, B = obs.shape[0], obs.shape[1]
@@ -1958,8 +1997,10 @@ class _EvaluateSequencesGroups(torch.autograd.Function):
                 slot = slots.trunk[layer]
             elif layer < T + 4:
                 slot = (slots.actor, slots.critic)[(layer - T) // 2][(layer - T) % 2]
-            else:
+            elif layer == T + 4:
                 slot = slots.memory
+            else:
+                slot = slots.gate
             if i % 2:
                 slot.bias = grads[-1].data_ptr()
             else:

@@ -1020,6 +1020,75 @@ int mbots_policy_seq_grad_groups(const struct mbots_policy_net *nets, uint32_t g
                                  const struct mbots_policy_grads *out /* [groups][4] */, void *workspace,
                                  uint64_t workspace_bytes, int32_t device, void *stream);
 
+/* The update on the device: the A2C loss of recorded rows and one Adam step
+ * over every net's parameters (DESIGN.md "Device learner step" is the
+ * specification).  The conventions are mbots_policy_eval's: handle-free,
+ * `device` >= 0 device memory on `stream`, -1 host memory; both give the same
+ * bits, whatever the grid; the calls allocate nothing, never wait for the host
+ * and can be captured into a graph.  Every operation written below is one
+ * correctly rounded f32 operation, in the written order, never fused.
+ *
+ * mbots_policy_group_rows: rows[g] += sum over the four species of hi - lo of
+ * segments[g] (int32 [groups][4][2], what mbots_policy_segments wrote, in the
+ * memory of `rows`; on the device read by the kernel only).  The caller zeroes
+ * rows (int64 [groups]) and calls it once per table of an update.  The host
+ * path refuses lo < 0 or lo > hi; the device counts such a segment as empty.
+ *
+ * mbots_policy_a2c_loss: logp, value, entropy (the evaluate's outputs), adv,
+ * ret [n] f32; end int32 [n], the window's END column, or NULL: every row is
+ * kept; segments as above, with the contract of mbots_policy_eval_groups (the
+ * host refuses a violation, the device clamps); rows int64 [groups], every
+ * group's row total over the whole update.  For row r of a segment of group g:
+ *     w         = keep_r * scale_g    keep_r 0 iff end[r] == MBOTS_TRAJ_END_RESET,
+ *                                     else 1; scale_g = 1.0f / (float)rows[g],
+ *                                     0 when rows[g] == 0
+ *     g_logp    = (-adv) * w
+ *     d         = value - ret
+ *     g_value   = ((2 * value_coef) * d) * w
+ *     g_entropy = (-entropy_coef) * w
+ *     per_row   = (((-adv) * logp + value_coef * (d * d)) - entropy_coef * entropy) * w
+ * Rows in no segment receive +0 in g_logp, g_value, g_entropy and take no part
+ * in loss.  loss[g] (f64 [groups]) += the group's per_row values in a fixed
+ * order: per species segment, row i counted from lo into f64 accumulator
+ * i mod 256 in ascending i; the 256 accumulators added in ascending index to
+ * +0; the four species' sums added in ascending species to +0; that sum added
+ * to loss[g].  Any of the four outputs may be NULL.
+ *
+ * mbots_policy_adam: `tensors` (host memory, read during the call) describes
+ * `count` parameter tensors: param, grad, m, v of n floats in the memory kind
+ * of the call and the tensor's group < groups (<= MBOTS_POLICY_MAX_GROUPS);
+ * n == 0 entries are passed over.  state [groups] in that memory starts as
+ * {0, 1.0f, 1.0f}.  rows int64 [groups] in that memory, or NULL: a group with
+ * rows[g] == 0 is left untouched entirely -- param, m, v and state.  Else,
+ * with om1 = 1 - beta1 and om2 = 1 - beta2 computed once on the host:
+ *     b1t' = b1t * beta1;  b2t' = b2t * beta2;  c1 = 1 - b1t';  c2 = 1 - b2t'
+ *     m'   = beta1 * m + om1 * g
+ *     v'   = beta2 * v + (om2 * g) * g
+ *     p'   = p - (lr * (m' / c1)) / (sqrtf(v' / c2) + eps)
+ * for every element, and then state[g] = {t + 1, b1t', b2t'}: the state is
+ * advanced by a trailing launch, after every element has read it.  Tensors
+ * must not overlap.  m and v 16-byte aligned let the kernel use 16-byte
+ * accesses where param and grad are aligned too; any alignment of 4 works. */
+struct mbots_policy_adam_tensor {
+    float *param;
+    const float *grad;
+    float *m, *v;
+    uint64_t n;
+    uint32_t group;
+};
+struct mbots_policy_adam_state {
+    uint32_t t;              /* steps taken */
+    float b1t, b2t;          /* beta1^t, beta2^t as running f32 products */
+};
+int mbots_policy_group_rows(const int32_t *segments, uint32_t groups, int64_t *rows, int32_t device, void *stream);
+int mbots_policy_a2c_loss(const float *logp, const float *value, const float *entropy, const float *adv,
+                          const float *ret, const int32_t *end, uint64_t n, const int32_t *segments, uint32_t groups,
+                          const int64_t *rows, float value_coef, float entropy_coef, float *g_logp, float *g_value,
+                          float *g_entropy, double *loss, int32_t device, void *stream);
+int mbots_policy_adam(const struct mbots_policy_adam_tensor *tensors, uint64_t count,
+                      struct mbots_policy_adam_state *state, uint32_t groups, const int64_t *rows, float lr,
+                      float beta1, float beta2, float eps, int32_t device, void *stream);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That

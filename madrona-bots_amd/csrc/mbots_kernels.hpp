@@ -346,5 +346,13 @@ hipError_t launch_policy_seq_grad_groups(const PolSeqIO &io, const int32_t *orde
 size_t policy_seq_order_workspace(uint64_t B);
 hipError_t launch_policy_seq_order(const int32_t *net_id, uint64_t B, uint32_t nkeys, int32_t *order, int32_t *segments,
                                    uint32_t *counts, hipStream_t st);
+// the update on the device (mbots_policy.hpp): the groups' row totals; the
+// loss, one block per group after a fill of the three gradients with +0; Adam
+// over `tensors` (host memory) in launches of kAdamTensors descriptors each,
+// then the one-block launch that advances the active groups' state
+hipError_t launch_policy_group_rows(const int32_t *segments, uint32_t groups, int64_t *rows, hipStream_t st);
+hipError_t launch_policy_a2c_loss(const PolLossIO &io, uint32_t groups, hipStream_t st);
+hipError_t launch_policy_adam(const AdamTensor *tensors, uint64_t count, AdamState *state, uint32_t groups,
+                              const int64_t *rows, const AdamCoef &C, hipStream_t st);
 
 }  // namespace mbots

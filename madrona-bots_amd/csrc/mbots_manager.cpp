@@ -3697,6 +3697,120 @@ int mbots_policy_grad_groups(const struct mbots_policy_net *nets, uint32_t group
     return MBOTS_OK;
 }
 
+// ---- the update on the device (include/mbots.h "The update on the device") ----
+static_assert(sizeof(mbots_policy_adam_tensor) == sizeof(mbots::AdamTensor) &&
+                  offsetof(mbots_policy_adam_tensor, group) == offsetof(mbots::AdamTensor, group) &&
+                  sizeof(mbots_policy_adam_state) == sizeof(mbots::AdamState),
+              "mbots.h's Adam structs are the kernels'");
+
+int mbots_policy_group_rows(const int32_t *segments, uint32_t groups, int64_t *rows, int32_t device, void *stream)
+{
+    if (!segments || !rows) return fail(MBOTS_E_INVALID, "null argument");
+    if (groups < 1u || groups > MBOTS_POLICY_MAX_GROUPS)
+        return fail(MBOTS_E_INVALID, "groups must be 1.." + std::to_string(MBOTS_POLICY_MAX_GROUPS));
+    if (device < 0) {
+        for (uint32_t e = 0; e < 4u * groups; ++e)
+            if (segments[2u * e] < 0 || segments[2u * e] > segments[2u * e + 1u])
+                return fail(MBOTS_E_INVALID, "the segment [" + std::to_string(segments[2u * e]) + ", " +
+                                                 std::to_string(segments[2u * e + 1u]) + ") of " + pair_name(e) +
+                                                 " is no row range");
+        for (uint32_t e = 0; e < 4u * groups; ++e) rows[e / 4u] += (int64_t)segments[2u * e + 1u] - segments[2u * e];
+        return MBOTS_OK;
+    }
+    HIP_TRY(hipSetDevice(device));
+    HIP_TRY(mbots::launch_policy_group_rows(segments, groups, rows, as_stream(stream)));
+    return MBOTS_OK;
+}
+
+int mbots_policy_a2c_loss(const float *logp, const float *value, const float *entropy, const float *adv,
+                          const float *ret, const int32_t *end, uint64_t n, const int32_t *segments, uint32_t groups,
+                          const int64_t *rows, float value_coef, float entropy_coef, float *g_logp, float *g_value,
+                          float *g_entropy, double *loss, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (!segments || !rows) return fail(MBOTS_E_INVALID, "null segments or rows");
+    if (groups < 1u || groups > MBOTS_POLICY_MAX_GROUPS)
+        return fail(MBOTS_E_INVALID, "groups must be 1.." + std::to_string(MBOTS_POLICY_MAX_GROUPS));
+    if (n && (!logp || !value || !entropy || !adv || !ret)) return fail(MBOTS_E_INVALID, "null argument");
+    if (n > (uint64_t)INT32_MAX) return fail(MBOTS_E_INVALID, "more rows than a segment can name");
+    const PolLossIO io{logp,   value,   entropy,   adv,  ret, end,        segments,    rows,
+                       g_logp, g_value, g_entropy, loss, n,   value_coef, entropy_coef};
+    if (device >= 0) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_a2c_loss(io, groups, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    if (int rc = segments_check_host(segments, groups, n, "rows")) return rc;
+    for (float *o : {g_logp, g_value, g_entropy})
+        if (o) std::fill(o, o + n, 0.0f);
+    for (uint32_t g = 0; g < groups; ++g) {
+        const float scale = pol_loss_scale(rows[g]);
+        double group_sum = 0.0;
+        for (uint32_t s = 0; s < 4u; ++s) {
+            const uint64_t lo = (uint64_t)segments[2u * (4u * g + s)];
+            const uint64_t len = (uint64_t)segments[2u * (4u * g + s) + 1u] - lo;
+            double acc[kLossAcc] = {};
+            for (uint64_t i = 0; i < len; ++i) {
+                const uint64_t r = lo + i;
+                const float w = (end && end[r] == kTrajEndReset ? 0.0f : 1.0f) * scale;
+                float gl, gv, ge;
+                const float per_row = pol_loss_row(logp[r], value[r], entropy[r], adv[r], ret[r], w, value_coef,
+                                                   entropy_coef, gl, gv, ge);
+                if (g_logp) g_logp[r] = gl;
+                if (g_value) g_value[r] = gv;
+                if (g_entropy) g_entropy[r] = ge;
+                acc[i % kLossAcc] += (double)per_row;
+            }
+            double q = 0.0;
+            for (uint32_t k = 0; k < kLossAcc; ++k) q += acc[k];
+            group_sum += q;
+        }
+        if (loss) loss[g] += group_sum;
+    }
+    return MBOTS_OK;
+}
+
+int mbots_policy_adam(const struct mbots_policy_adam_tensor *tensors, uint64_t count,
+                      struct mbots_policy_adam_state *state, uint32_t groups, const int64_t *rows, float lr,
+                      float beta1, float beta2, float eps, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if ((!tensors && count) || !state) return fail(MBOTS_E_INVALID, "null argument");
+    if (groups < 1u || groups > MBOTS_POLICY_MAX_GROUPS)
+        return fail(MBOTS_E_INVALID, "groups must be 1.." + std::to_string(MBOTS_POLICY_MAX_GROUPS));
+    for (uint64_t i = 0; i < count; ++i) {
+        const mbots_policy_adam_tensor &T = tensors[i];
+        if (T.n == 0) continue;
+        const uintptr_t bits = (uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.m | (uintptr_t)T.v;
+        const char *bad = !T.param || !T.grad || !T.m || !T.v ? "has a null pointer"
+                          : (bits & 3u)                       ? "is not 4-byte aligned"
+                          : T.group >= groups                 ? "names a group past `groups`"
+                          : T.n > (1ull << 31)                ? "has more than 2^31 elements"
+                                                              : nullptr;
+        if (bad) return fail(MBOTS_E_INVALID, "Adam tensor " + std::to_string(i) + " " + bad);
+    }
+    const AdamCoef C{lr, beta1, beta2, 1.0f - beta1, 1.0f - beta2, eps};
+    if (device >= 0) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_adam(reinterpret_cast<const AdamTensor *>(tensors), count,
+                                   reinterpret_cast<AdamState *>(state), groups, rows, C, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    for (uint64_t i = 0; i < count; ++i) {
+        const mbots_policy_adam_tensor &T = tensors[i];
+        if (T.n == 0 || (rows && rows[T.group] == 0)) continue;
+        const float c1 = 1.0f - state[T.group].b1t * beta1, c2 = 1.0f - state[T.group].b2t * beta2;
+        for (uint64_t k = 0; k < T.n; ++k) pol_adam(T.param[k], T.grad[k], T.m[k], T.v[k], C, c1, c2);
+    }
+    for (uint32_t g = 0; g < groups; ++g) {
+        if (rows && rows[g] == 0) continue;
+        state[g].t += 1u;
+        state[g].b1t = state[g].b1t * beta1;
+        state[g].b2t = state[g].b2t * beta2;
+    }
+    return MBOTS_OK;
+}
+
 // ---- evaluate_sequences (include/mbots.h "Training the memory head") ----
 namespace {
 int seq_check(const mbots_policy_net *net, const float *obs, const int32_t *action, const int32_t *length,

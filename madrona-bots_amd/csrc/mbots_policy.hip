@@ -1862,4 +1862,193 @@ hipError_t launch_policy_activation(int act, const float *x, float *y, uint64_t 
     return hipGetLastError();
 }
 
+// ---- the update on the device (mbots_policy.hpp; DESIGN.md "Device learner
+// step") ----
+// thread g: rows[g] += the group's four hi - lo (a segment with lo > hi or a
+// negative bound counts as empty)
+__global__ __launch_bounds__(64) void policy_group_rows_kernel(const int32_t *segments, uint32_t groups, int64_t *rows)
+{
+    for (uint32_t g = threadIdx.x; g < groups; g += 64u) {
+        int64_t sum = 0;
+        for (uint32_t s = 0; s < 4u; ++s) {
+            const int32_t lo = segments[2u * (4u * g + s)], hi = segments[2u * (4u * g + s) + 1u];
+            if (lo >= 0 && hi > lo) sum += (int64_t)hi - lo;
+        }
+        rows[g] += sum;
+    }
+}
+
+// Block g is group g; its threads [256 s, 256 s + 256) are the accumulators of
+// species s: thread a takes the rows a, a + 256, ... of the segment in
+// ascending order, four in flight.  The order of the sums does not depend on
+// the launch: the 256 accumulators in ascending index, the species ascending.
+constexpr uint32_t kLossFlight = 4;
+__global__ __launch_bounds__(1024) void policy_a2c_loss_kernel(PolLossIO A)
+{
+    __shared__ double s_acc[4u * kLossAcc];
+    __shared__ double s_sum[4];
+    const uint32_t g = blockIdx.x, s = uniform(threadIdx.x >> 8), a = threadIdx.x & (kLossAcc - 1u);
+    uint32_t lo, len;
+    pol_segment(A.segments, 4u * g + s, A.n, lo, len);
+    lo = uniform(lo);
+    len = uniform(len);
+    const float scale = pol_loss_scale(A.rows[g]);
+    const float *__restrict__ logp = A.logp, *__restrict__ value = A.value, *__restrict__ entropy = A.entropy;
+    const float *__restrict__ adv = A.adv, *__restrict__ ret = A.ret;
+    const int32_t *__restrict__ end = A.end;
+    double acc = 0.0;
+    for (uint32_t i0 = a; i0 < len; i0 += kLossFlight * kLossAcc) {
+        float x[kLossFlight][5];
+        int32_t e[kLossFlight];
+#pragma unroll
+        for (uint32_t k = 0; k < kLossFlight; ++k) {
+            const uint32_t i = i0 + k * kLossAcc;
+            if (i < len) {
+                const uint64_t r = (uint64_t)lo + i;
+                x[k][0] = logp[r], x[k][1] = value[r], x[k][2] = entropy[r], x[k][3] = adv[r], x[k][4] = ret[r];
+                e[k] = end ? end[r] : 0;
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kLossFlight; ++k) {
+            const uint32_t i = i0 + k * kLossAcc;
+            if (i < len) {
+                const uint64_t r = (uint64_t)lo + i;
+                const float w = (e[k] == kTrajEndReset ? 0.0f : 1.0f) * scale;
+                float gl, gv, ge;
+                const float per_row = pol_loss_row(x[k][0], x[k][1], x[k][2], x[k][3], x[k][4], w, A.value_coef,
+                                                   A.entropy_coef, gl, gv, ge);
+                if (A.g_logp) A.g_logp[r] = gl;
+                if (A.g_value) A.g_value[r] = gv;
+                if (A.g_entropy) A.g_entropy[r] = ge;
+                acc += (double)per_row;
+            }
+        }
+    }
+    if (A.loss == nullptr) return;
+    s_acc[threadIdx.x] = acc;
+    __syncthreads();
+    if (a == 0u) {
+        double q = 0.0;
+        for (uint32_t k = 0; k < kLossAcc; ++k) q += s_acc[s * kLossAcc + k];
+        s_sum[s] = q;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        double q = 0.0;
+        for (uint32_t k = 0; k < 4u; ++k) q += s_sum[k];
+        A.loss[g] += q;
+    }
+}
+
+hipError_t launch_policy_group_rows(const int32_t *segments, uint32_t groups, int64_t *rows, hipStream_t st)
+{
+    hipLaunchKernelGGL(policy_group_rows_kernel, dim3(1), dim3(64), 0, st, segments, groups, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_a2c_loss(const PolLossIO &io, uint32_t groups, hipStream_t st)
+{
+    if (io.n && (io.g_logp || io.g_value || io.g_entropy)) {
+        const unsigned blocks = (unsigned)std::min<uint64_t>((io.n + 255u) / 256u, 2048u);
+        hipLaunchKernelGGL(policy_zero_rows_kernel, dim3(blocks), dim3(256), 0, st, io.g_logp, io.g_value, io.g_entropy,
+                           io.n);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(policy_a2c_loss_kernel, dim3(groups), dim3(1024), 0, st, io);
+    return hipGetLastError();
+}
+
+// Adam over the launch's tensors: block b on one chunk of one tensor, found in
+// the launch's prefix of chunk counts.  Every block reads its group's state as
+// the previous step left it; policy_adam_advance_kernel follows in the stream.
+__global__ __launch_bounds__(256) void policy_adam_kernel(AdamLaunch L, const AdamState *state, const int64_t *rows,
+                                                          AdamCoef C)
+{
+    const uint32_t b = blockIdx.x;
+    uint32_t lo = 0, hi = L.n - 1u;   // the last tensor whose first block is <= b
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (L.first[mid] <= b) lo = mid;
+        else hi = mid - 1u;
+    }
+    const uint32_t i = uniform(lo);
+    const uint32_t group = L.t[i].group;
+    if (rows != nullptr && rows[group] == 0) return;
+    const AdamState S = state[group];
+    const float c1 = 1.0f - S.b1t * C.beta1, c2 = 1.0f - S.b2t * C.beta2;
+    const uint64_t base = (uint64_t)(b - L.first[i]) * kAdamChunk;
+    const uint32_t cnt = (uint32_t)min((uint64_t)kAdamChunk, L.t[i].n - base);
+    float *__restrict__ p = L.t[i].param + base;
+    const float *__restrict__ g = L.t[i].grad + base;
+    float *__restrict__ m = L.t[i].m + base;
+    float *__restrict__ v = L.t[i].v + base;
+    const uint32_t t = threadIdx.x;
+    const bool wide = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) == 0u;
+    if (wide) {
+        static_assert(kAdamChunk == 4u * 256u, "policy_adam_kernel: one 16-byte access per thread and stream");
+        if (4u * t + 4u <= cnt) {
+            float4 P = reinterpret_cast<float4 *>(p)[t];
+            const float4 Gr = reinterpret_cast<const float4 *>(g)[t];
+            float4 M = reinterpret_cast<float4 *>(m)[t], V = reinterpret_cast<float4 *>(v)[t];
+            pol_adam(P.x, Gr.x, M.x, V.x, C, c1, c2);
+            pol_adam(P.y, Gr.y, M.y, V.y, C, c1, c2);
+            pol_adam(P.z, Gr.z, M.z, V.z, C, c1, c2);
+            pol_adam(P.w, Gr.w, M.w, V.w, C, c1, c2);
+            reinterpret_cast<float4 *>(p)[t] = P;
+            reinterpret_cast<float4 *>(m)[t] = M;
+            reinterpret_cast<float4 *>(v)[t] = V;
+        }
+        const uint32_t k = (cnt & ~3u) + t;   // the scalar tail
+        if (t < (cnt & 3u)) {
+            float P = p[k], M = m[k], V = v[k];
+            pol_adam(P, g[k], M, V, C, c1, c2);
+            p[k] = P, m[k] = M, v[k] = V;
+        }
+        return;
+    }
+    for (uint32_t k = t; k < cnt; k += 256u) {
+        float P = p[k], M = m[k], V = v[k];
+        pol_adam(P, g[k], M, V, C, c1, c2);
+        p[k] = P, m[k] = M, v[k] = V;
+    }
+}
+
+__global__ __launch_bounds__(64) void policy_adam_advance_kernel(AdamState *state, const int64_t *rows, uint32_t groups,
+                                                                 float beta1, float beta2)
+{
+    for (uint32_t g = threadIdx.x; g < groups; g += 64u) {
+        if (rows != nullptr && rows[g] == 0) continue;
+        AdamState S = state[g];
+        S.t += 1u;
+        S.b1t = S.b1t * beta1;
+        S.b2t = S.b2t * beta2;
+        state[g] = S;
+    }
+}
+
+hipError_t launch_policy_adam(const AdamTensor *tensors, uint64_t count, AdamState *state, uint32_t groups,
+                              const int64_t *rows, const AdamCoef &C, hipStream_t st)
+{
+    AdamLaunch L;
+    L.n = 0;
+    L.first[0] = 0;
+    auto flush = [&]() -> hipError_t {
+        if (L.n == 0 || L.first[L.n] == 0) return hipSuccess;
+        hipLaunchKernelGGL(policy_adam_kernel, dim3(L.first[L.n]), dim3(256), 0, st, L, state, rows, C);
+        L.n = 0;
+        return hipGetLastError();
+    };
+    for (uint64_t i = 0; i < count; ++i) {
+        if (tensors[i].n == 0) continue;
+        L.t[L.n] = tensors[i];
+        L.first[L.n + 1u] = L.first[L.n] + (uint32_t)((tensors[i].n + kAdamChunk - 1u) / kAdamChunk);
+        if (++L.n == kAdamTensors)
+            if (hipError_t e = flush()) return e;
+    }
+    if (hipError_t e = flush()) return e;
+    hipLaunchKernelGGL(policy_adam_advance_kernel, dim3(1), dim3(64), 0, st, state, rows, groups, C.beta1, C.beta2);
+    return hipGetLastError();
+}
+
 }  // namespace mbots

@@ -608,4 +608,71 @@ struct PolSeqCols {
 // sequence_segments' keys: net_id outside [0, nkeys) has no net
 MB_HD bool pol_seq_key(int32_t id, uint32_t nkeys) { return id >= 0 && (uint32_t)id < nkeys; }
 
+// ---- the update on the device (include/mbots.h "The update on the device";
+// DESIGN.md "Device learner step"): the per-row and per-element arithmetic the
+// kernels and the host loops share.  Plain + - * / and sqrt, one rounding each
+// (the build never contracts), so a float32 restatement is exact.
+constexpr uint32_t kLossAcc = 256;        // f64 accumulators of a (group, species) segment: row i into i mod 256
+
+MB_HD float pol_loss_scale(int64_t rows) { return rows != 0 ? 1.0f / (float)rows : 0.0f; }
+
+// a row's three upstream gradients and its share of the loss
+MB_HD float pol_loss_row(float logp, float value, float entropy, float adv, float ret, float w, float value_coef,
+                         float entropy_coef, float &g_logp, float &g_value, float &g_entropy)
+{
+    const float na = -adv;
+    g_logp = na * w;
+    const float d = value - ret;
+    g_value = ((2.0f * value_coef) * d) * w;
+    g_entropy = (-entropy_coef) * w;
+    return ((na * logp + value_coef * (d * d)) - entropy_coef * entropy) * w;
+}
+
+struct PolLossIO {            // mbots_policy_a2c_loss's arguments
+    const float *logp, *value, *entropy, *adv, *ret;
+    const int32_t *end;       // null: every row kept
+    const int32_t *segments;
+    const int64_t *rows;
+    float *g_logp, *g_value, *g_entropy;
+    double *loss;
+    uint64_t n;
+    float value_coef, entropy_coef;
+};
+
+struct AdamTensor {           // struct mbots_policy_adam_tensor
+    float *param;
+    const float *grad;
+    float *m, *v;
+    uint64_t n;
+    uint32_t group;
+};
+struct AdamState {            // struct mbots_policy_adam_state
+    uint32_t t;
+    float b1t, b2t;
+};
+struct AdamCoef {
+    float lr, beta1, beta2, om1, om2, eps;   // om: 1 - beta, rounded once on the host
+};
+MB_HD void pol_adam(float &p, float g, float &m, float &v, const AdamCoef &C, float c1, float c2)
+{
+    m = C.beta1 * m + C.om1 * g;
+    v = C.beta2 * v + (C.om2 * g) * g;
+#ifdef __HIP_DEVICE_COMPILE__
+    const float root = sqrtf(v / c2);
+#else
+    const float root = std::sqrt(v / c2);
+#endif
+    p = p - (C.lr * (m / c1)) / (root + C.eps);
+}
+// One launch's tensors travel as kernel arguments: block b of the launch works
+// on chunk b - first[i] (kAdamChunk elements) of tensor t[i], first[i] <= b <
+// first[i + 1].
+constexpr uint32_t kAdamTensors = 64, kAdamChunk = 1024;
+struct AdamLaunch {
+    AdamTensor t[kAdamTensors];
+    uint32_t first[kAdamTensors + 1];
+    uint32_t n;
+};
+static_assert(sizeof(AdamLaunch) + 128u <= 4096u, "a launch's tensor descriptors travel as kernel arguments");
+
 }  // namespace mbots

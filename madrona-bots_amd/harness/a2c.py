@@ -10,7 +10,9 @@ bit for bit on the recorded rows and is differentiable with respect to the
 nets' parameters through the library's own backward kernel, so the importance
 ratio of the first epoch is exactly 1 and the update gives the same bits in
 CPU mode, on the device and in a sharded run.  Losses and optimisers are plain
-torch.
+torch; with --device-update they are the library's too (a2c_loss_groups and
+PolicyAdam: a2c_groups.py's device update with one group), and the parameters
+after the optimiser's step are the same bits in CPU mode and on the device.
 
     python madrona-bots_amd/harness/a2c.py --worlds 64 --iters 10 --exec-mode cpu
     python madrona-bots_amd/harness/a2c.py --worlds 4096 --iters 50
@@ -50,9 +52,16 @@ def species_slices(sim):
 
 
 def train(sim, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0, value_coef=0.5,
-          entropy_coef=0.01, log=None):
-    """`iters` updates of `horizon - 1` steps each.  Returns the losses (floats)."""
+          entropy_coef=0.01, log=None, device_update=False, lr=3e-4):
+    """`iters` updates of `horizon - 1` steps each.  Returns the losses (floats).
+    device_update: a2c_groups.train's device update with one group;
+    `optimizers` is then a madrona_bots.PolicyAdam or None."""
     import madrona_bots as mb
+    if device_update:
+        import a2c_groups
+        per_group = a2c_groups.train(sim, [0], [modules], optimizers, iters, horizon, gamma, lam, death_reward,
+                                     value_coef, entropy_coef, log, device_update=True, lr=lr)
+        return [x[0] for x in per_group]
     nets = [mb.PolicyNet.from_torch(m["feature"], m["actor"], m["critic"]) for m in modules]
     sim.set_policy(nets)
     win = sim.trajectory_window(horizon, max_rows=sim.num_worlds * sim.agent_capacity)
@@ -105,13 +114,16 @@ def main():
     ap.add_argument("--lr", type=float, default=3e-4)
     ap.add_argument("--seed", type=int, default=69)
     ap.add_argument("--exec-mode", choices=("hip", "cpu"), default="hip" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--device-update", action="store_true",
+                    help="the loss and the optimiser in the library: a2c_loss_groups and one PolicyAdam.step")
     args = ap.parse_args()
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     import madrona_bots as mb
     sim = mb.SimManager(0, args.worlds, args.seed, args.agents, exec_mode=args.exec_mode)
     modules = make_modules(args.hidden, sim.device, args.seed)
-    optimizers = [torch.optim.Adam(m.parameters(), lr=args.lr) for m in modules]
-    train(sim, modules, optimizers, args.iters, args.horizon, log=print)
+    optimizers = None if args.device_update else [torch.optim.Adam(m.parameters(), lr=args.lr) for m in modules]
+    train(sim, modules, optimizers, args.iters, args.horizon, log=print, device_update=args.device_update, lr=args.lr)
 
 
 if __name__ == "__main__":

@@ -39,18 +39,24 @@ from a2c import make_modules  # noqa: E402
 
 
 def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0,
-          value_coef=0.5, entropy_coef=0.01, log=None, grouped_evaluate=False):
+          value_coef=0.5, entropy_coef=0.01, log=None, grouped_evaluate=False, device_update=False, lr=3e-4):
     """`iters` updates of `horizon - 1` steps each of every group.  modules[u],
     optimizers[u]: a2c.make_modules' four ModuleDicts and their optimizers for
     group u.  grouped_evaluate: one evaluate_groups per table and one
-    backward() (train_grouped_update) in place of the per-net loop.  Returns
-    the losses, [iters][groups] floats."""
+    backward() (train_grouped_update) in place of the per-net loop.
+    device_update: the loss and the optimiser in the library as well
+    (device_update_step); `optimizers` is then a madrona_bots.PolicyAdam over
+    the groups' nets, or None for one with learning rate `lr`.  Returns the
+    losses, [iters][groups] floats."""
     import madrona_bots as mb
     G = len(starts)
     sim.set_policy_groups(starts)
     nets = [[mb.PolicyNet.from_torch(m["feature"], m["actor"], m["critic"]) for m in modules[u]] for u in range(G)]
     for u in range(G):
         sim.set_policy(nets[u], group=u)
+    if device_update:
+        grouped_evaluate = True
+        adam = optimizers if isinstance(optimizers, mb.PolicyAdam) else mb.PolicyAdam(nets, lr=lr)
     win = sim.trajectory_window(horizon, max_rows=sim.num_worlds * sim.agent_capacity)
     seg = torch.empty((G, 4, 2), dtype=torch.int32, device=sim.device)
     losses = []
@@ -68,7 +74,11 @@ def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.
                     sim.step()
             out = win.compute(gamma=gamma, lam=lam, death_reward=death_reward)
             if grouped_evaluate:
-                loss, total = grouped_update(mb, nets, optimizers, rows, out, win.END_RESET, value_coef, entropy_coef)
+                if device_update:
+                    loss, total = device_update_step(mb, nets, adam, rows, out, value_coef, entropy_coef)
+                else:
+                    loss, total = grouped_update(mb, nets, optimizers, rows, out, win.END_RESET, value_coef,
+                                                 entropy_coef)
                 for u in range(G):
                     sim.set_policy(nets[u], group=u)
                 win.clear()
@@ -148,6 +158,30 @@ def grouped_update(mb, nets, optimizers, rows, out, end_reset, value_coef, entro
     return [float(x) for x in host[:G]], [int(x) for x in host[G:]]
 
 
+def device_update_step(mb, nets, adam, rows, out, value_coef, entropy_coef):
+    """grouped_update with the loss and the optimiser in the library: per table
+    evaluate_groups, a2c_loss_groups (the three upstream gradients and the
+    groups' losses, float64 [G] on the device) and one autograd.backward into
+    the gradient buffer `adam` owns; then one PolicyAdam.step over every net.
+    A group without a row is left untouched, as the loop leaves it.  Returns
+    ([G] losses, [G] rows), read from the device once, after the step."""
+    G = len(nets)
+    dev = rows[0][0].device
+    total = torch.zeros(G, dtype=torch.int64, device=dev)
+    for _, _, sg in rows:
+        mb.policy_group_rows(sg, total)
+    loss = torch.zeros(G, dtype=torch.float64, device=dev)
+    adam.zero_grad()
+    for t, (obs, action, sg) in enumerate(rows):
+        outs = mb.evaluate_groups(nets, obs, action, sg)
+        g = mb.a2c_loss_groups(*outs, out["adv"][t], out["ret"][t], out["end"][t], sg, total, value_coef, entropy_coef,
+                               loss=loss)
+        torch.autograd.backward(list(outs), list(g[:3]))
+    adam.step(total)
+    host = torch.cat([loss, total.to(torch.float64)]).cpu()
+    return [float(x) for x in host[:G]], [int(x) for x in host[G:]]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worlds", type=int, default=64)
@@ -163,6 +197,9 @@ def main():
     ap.add_argument("--reward-fixed", action="store_true", help="rewards[speciesID - 1]: universes fully apart")
     ap.add_argument("--grouped-evaluate", action="store_true",
                     help="one evaluate_groups and one backward() per update instead of one evaluate per (group, species)")
+    ap.add_argument("--device-update", action="store_true",
+                    help="--grouped-evaluate with a2c_loss_groups and one PolicyAdam.step in place of torch's loss "
+                         "and optimizers")
     args = ap.parse_args()
     if not 1 <= args.groups <= 64 or args.worlds < args.groups:
         ap.error("--groups must be in [1, 64] and at most --worlds")
@@ -172,9 +209,10 @@ def main():
                         reward_fixed=args.reward_fixed)
     starts = [u * args.worlds // args.groups for u in range(args.groups)]
     modules = [make_modules(args.hidden[u % len(args.hidden)], sim.device, args.seed + u) for u in range(args.groups)]
-    optimizers = [[torch.optim.Adam(m.parameters(), lr=args.lr) for m in four] for four in modules]
+    optimizers = None if args.device_update else \
+        [[torch.optim.Adam(m.parameters(), lr=args.lr) for m in four] for four in modules]
     train(sim, starts, modules, optimizers, args.iters, args.horizon, log=print,
-          grouped_evaluate=args.grouped_evaluate)
+          grouped_evaluate=args.grouped_evaluate, device_update=args.device_update, lr=args.lr)
 
 
 if __name__ == "__main__":

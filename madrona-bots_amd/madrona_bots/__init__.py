@@ -30,7 +30,7 @@ __all__ = ["SimManager", "ScriptBotsViewer", "Tensor", "madrona", "ExportID", "E
            "unpack_learner", "rebuild_learner", "CapacityWarning", "CapacityError", "MAX_CAPACITY",
            "CAPACITY_CLASSES", "TrajectoryWindow", "RENDER_PALETTE", "RENDER_SCALES", "CLS_FLOOR", "CLS_WALL",
            "CLS_FOOD", "CLS_BODY", "CLS_MARK", "PolicyNet", "policy_activation", "ACTIVATIONS", "evaluate_groups",
-           "sequence_segments", "evaluate_sequences_groups"]
+           "sequence_segments", "evaluate_sequences_groups", "policy_group_rows", "a2c_loss_groups", "PolicyAdam"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmbots.so")
@@ -81,6 +81,11 @@ class _PolicyGradLayer(ctypes.Structure):   # struct mbots_policy_grad_layer
 class _PolicyGrads(ctypes.Structure):   # struct mbots_policy_grads
     _fields_ = [("trunk", _PolicyGradLayer * 4), ("actor", _PolicyGradLayer * 2), ("critic", _PolicyGradLayer * 2),
                 ("memory", _PolicyGradLayer), ("gate", _PolicyGradLayer)]
+
+
+class _AdamTensor(ctypes.Structure):   # struct mbots_policy_adam_tensor
+    _fields_ = [("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p),
+                ("n", ctypes.c_uint64), ("group", ctypes.c_uint32)]
 
 
 class _CTensor(ctypes.Structure):
@@ -178,6 +183,11 @@ def _load():
                                          vp, vp, ctypes.c_uint64, i32, vp],
         "mbots_policy_seq_grad_groups": [P(_PolicyNet), u32, vp, vp, vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, vp,
                                          P(_PolicyGrads), vp, ctypes.c_uint64, i32, vp],
+        "mbots_policy_group_rows": [vp, u32, vp, i32, vp],
+        "mbots_policy_a2c_loss": [vp, vp, vp, vp, vp, vp, ctypes.c_uint64, vp, u32, vp, ctypes.c_float, ctypes.c_float,
+                                  vp, vp, vp, vp, i32, vp],
+        "mbots_policy_adam": [P(_AdamTensor), ctypes.c_uint64, vp, u32, vp, ctypes.c_float, ctypes.c_float,
+                              ctypes.c_float, ctypes.c_float, i32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -2029,6 +2039,218 @@ def policy_activation(act, x):
         _check(_lib.mbots_policy_activation(code, ctypes.c_void_p(x.data_ptr()), ctypes.c_void_p(y.data_ptr()),
                                             x.numel(), -1, None))
     return y
+
+
+def _on_device(dev, fn):
+    """fn(device index, stream) of a handle-free call on `dev`'s memory."""
+    if dev.type == "cuda":
+        with torch.cuda.device(dev):
+            _check(fn(dev.index, ctypes.c_void_p(_raw_stream(dev.index))))
+    else:
+        _check(fn(-1, None))
+
+
+def policy_group_rows(segments, rows):
+    """rows[g] += the rows of group g's four segments (mbots_policy_group_rows).
+    segments int32 [G, 4, 2] as policy_segments() returns it, rows int64 [G] on
+    the same device, zeroed by the caller and passed once per table of an
+    update; returns rows.  On a GPU nothing is read by the host."""
+    if segments.dtype != torch.int32 or segments.dim() != 3 or tuple(segments.shape[1:]) != (4, 2):
+        raise ValueError(f"segments must be int32 [G, 4, 2], not {segments.dtype} {list(segments.shape)}")
+    G = segments.shape[0]
+    if rows.dtype != torch.int64 or tuple(rows.shape) != (G,) or rows.device != segments.device \
+            or not rows.is_contiguous():
+        raise ValueError(f"rows must be a contiguous int64 [{G}] on {segments.device}, not {rows.dtype} "
+                         f"{list(rows.shape)} on {rows.device}")
+    segments = segments.detach().contiguous()
+    _on_device(rows.device, lambda d, st: _lib.mbots_policy_group_rows(_ptr(segments), G, _ptr(rows), d, st))
+    return rows
+
+
+def a2c_loss_groups(logp, value, entropy, adv, ret, end, segments, rows, value_coef=0.5, entropy_coef=0.01, loss=None):
+    """(g_logp, g_value, g_entropy, loss): the A2C loss of a table's recorded
+    rows and its gradients with respect to evaluate's three outputs, in one
+    pass of the library's own arithmetic (mbots_policy_a2c_loss; DESIGN.md
+    "Device learner step").  logp, value, entropy: float32 [n], what
+    evaluate_groups() (or evaluate()) returned, read detached; adv, ret: the
+    window's columns of the table, float32 [n] or [n, 1]; end: its END column,
+    int32 [n] or [n, 1], or None to keep every row; segments int32 [G, 4, 2];
+    rows int64 [G], every group's row total over the whole update
+    (policy_group_rows).  A row of group g weighs (end != END_RESET) / rows[g]:
+
+        per_row = (-adv * logp + value_coef * (value - ret)**2 - entropy_coef * entropy) * weight
+
+    and g_* are its derivatives; rows in no segment get +0.  loss: float64 [G],
+    accumulated into (None: zeros); the sums run in a fixed order, so CPU and
+    GPU tensors give the same bits.  Then
+
+        torch.autograd.backward([logp, value, entropy], [g_logp, g_value, g_entropy])
+
+    runs evaluate's backward.  Nothing waits for the host; capturable."""
+    dev = logp.device
+    n = logp.numel()
+    G = segments.shape[0] if segments.dim() == 3 else 0
+    if segments.dtype != torch.int32 or segments.device != dev or tuple(segments.shape) != (G, 4, 2) or not 1 <= G <= 64:
+        raise ValueError(f"segments must be int32 [G, 4, 2] of 1..64 groups on {dev}, not {segments.dtype} "
+                         f"{list(segments.shape)} on {segments.device}")
+    cols = []
+    for name, t in (("logp", logp), ("value", value), ("entropy", entropy), ("adv", adv), ("ret", ret)):
+        if t.dtype != torch.float32 or t.device != dev or t.numel() != n or tuple(t.shape) not in ((n,), (n, 1)):
+            raise ValueError(f"{name} must be float32 [n] or [n, 1] on {dev} with logp's {n} rows, not {t.dtype} "
+                             f"{list(t.shape)} on {t.device}")
+        cols.append(t.detach().reshape(n).contiguous())
+    if end is not None:
+        if end.dtype != torch.int32 or end.device != dev or tuple(end.shape) not in ((n,), (n, 1)):
+            raise ValueError(f"end must be int32 [n] or [n, 1] on {dev}, not {end.dtype} {list(end.shape)} on "
+                             f"{end.device}")
+        end = end.detach().reshape(n).contiguous()
+    if rows.dtype != torch.int64 or rows.device != dev or tuple(rows.shape) != (G,) or not rows.is_contiguous():
+        raise ValueError(f"rows must be a contiguous int64 [{G}] on {dev}, not {rows.dtype} {list(rows.shape)} on "
+                         f"{rows.device}")
+    if loss is None:
+        loss = torch.zeros(G, dtype=torch.float64, device=dev)
+    elif loss.dtype != torch.float64 or loss.device != dev or tuple(loss.shape) != (G,) or not loss.is_contiguous():
+        raise ValueError(f"loss must be a contiguous float64 [{G}] on {dev}, not {loss.dtype} {list(loss.shape)} on "
+                         f"{loss.device}")
+    segments = segments.detach().contiguous()
+    g = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3)]
+    _on_device(dev, lambda d, st: _lib.mbots_policy_a2c_loss(
+        _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), _ptr(end), n, _ptr(segments), G,
+        _ptr(rows), value_coef, entropy_coef, _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(loss), d, st))
+    return g[0], g[1], g[2], loss
+
+
+class PolicyAdam:
+    """Adam over the parameters of every net of every policy group in one call
+    (mbots_policy_adam; DESIGN.md "Device learner step"): torch.optim.Adam's
+    update without weight decay, in the library's own float32 arithmetic, so
+    host tensors and GPU tensors end with the same bits.  nets as
+    evaluate_groups': a list of G groups, each four PolicyNet or one for all
+    four, None where a pair has none; a flat list of four nets, or one net,
+    is one group.  Every distinct tensor the nets reference with
+    requires_grad -- memory head and gate included -- is updated, once, with
+    its group's step count; a tensor shared across groups raises.
+
+    step(rows=None) reads every parameter's .grad (None: skipped) and updates
+    the parameters in place; rows int64 [G] on the parameters' device: a group
+    with rows[g] == 0 is left untouched, state included.  zero_grad() binds
+    every .grad to a slice of one buffer the optimiser owns and zeroes that
+    buffer with one stream-ordered fill, so the gradients keep their
+    addresses from update to update and a captured update replays.  Neither
+    waits for the host."""
+
+    def __init__(self, nets, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+        if isinstance(nets, PolicyNet):
+            nets = [[nets] * 4]
+        nets = list(nets)
+        if len(nets) == 4 and all(x is None or isinstance(x, PolicyNet) for x in nets):
+            nets = [nets]
+        groups = [list(g) if isinstance(g, (list, tuple)) else [g] * 4 for g in nets]
+        G = len(groups)
+        if not 1 <= G <= 64:
+            raise ValueError(f"nets must hold 1..64 groups, not {G}")
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.params, self.names, self.param_group = [], [], []
+        seen = {}                                     # id(tensor) -> (group, name)
+        for g, four in enumerate(groups):
+            if len(four) != 4 or any(x is not None and not isinstance(x, PolicyNet) for x in four):
+                raise ValueError(f"nets[{g}] must be four PolicyNet (or None), or one PolicyNet for all species")
+            for s, x in enumerate(four):
+                if x is None:
+                    continue
+                named = x._named_params()
+                if x.memory is not None:
+                    named += [("memory Linear weight", x.memory[0]), ("memory Linear bias", x.memory[1])]
+                if x.gate is not None:
+                    named += [("gate Linear weight", x.gate[0]), ("gate Linear bias", x.gate[1])]
+                for name, p in named:
+                    if p is None or not p.requires_grad:
+                        continue
+                    where = f"{_species_name(g, s)}: {name}"
+                    if id(p) in seen:
+                        g0, first = seen[id(p)]
+                        if g0 != g:
+                            raise ValueError(f"{where} is also {first}: a parameter tensor shared across groups has "
+                                             "no one step count")
+                        continue
+                    if p.dtype != torch.float32 or not p.is_contiguous():
+                        raise ValueError(f"{where} must be a contiguous float32 tensor, not {p.dtype} with strides "
+                                         f"{list(p.stride())}")
+                    if self.params and p.device != self.params[0].device:
+                        raise ValueError(f"{where} is on {p.device}, other parameters on {self.params[0].device}")
+                    seen[id(p)] = (g, where)
+                    self.params.append(p)
+                    self.names.append(where)
+                    self.param_group.append(g)
+        if not self.params:
+            raise ValueError("the nets hold no parameter with requires_grad")
+        self.groups, dev = G, self.params[0].device
+        self.device = dev
+        # every tensor's slice of m, v and the gradient buffer starts 16-byte aligned
+        self.offsets, total = [], 0
+        for p in self.params:
+            self.offsets.append(total)
+            total += (p.numel() + 3) // 4 * 4
+        self._m = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._v = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._g = torch.zeros(total, dtype=torch.float32, device=dev)
+        self._views = [self._g[o:o + p.numel()].view(p.shape) for o, p in zip(self.offsets, self.params)]
+        # struct mbots_policy_adam_state [G]: {t, bits of b1t, bits of b2t}
+        self._state = torch.tensor([[0, 0x3F800000, 0x3F800000]] * G, dtype=torch.int32, device=dev)
+        self._desc = (_AdamTensor * len(self.params))()
+        for i, (p, o, g) in enumerate(zip(self.params, self.offsets, self.param_group)):
+            d = self._desc[i]
+            d.param, d.group = p.data_ptr(), g
+            d.m, d.v = self._m.data_ptr() + 4 * o, self._v.data_ptr() + 4 * o
+
+    def zero_grad(self):
+        for p, view in zip(self.params, self._views):
+            g = p.grad
+            if g is None or g.data_ptr() != view.data_ptr():
+                p.grad = view
+        self._g.zero_()
+
+    def step(self, rows=None):
+        G, dev = self.groups, self.device
+        if rows is not None and (rows.dtype != torch.int64 or rows.device != dev or tuple(rows.shape) != (G,)
+                                 or not rows.is_contiguous()):
+            raise ValueError(f"rows must be a contiguous int64 [{G}] on {dev}, not {rows.dtype} {list(rows.shape)} "
+                             f"on {rows.device}")
+        desc = self._desc
+        for i, p in enumerate(self.params):
+            g = p.grad
+            if g is None:
+                desc[i].n = 0
+                continue
+            if g.dtype != torch.float32 or g.device != dev or g.shape != p.shape or not g.is_contiguous():
+                raise ValueError(f"{self.names[i]}: .grad must be a contiguous float32 tensor of the parameter's "
+                                 f"shape on {dev}, not {g.dtype} {list(g.shape)} on {g.device}")
+            desc[i].param, desc[i].grad, desc[i].n = p.data_ptr(), g.data_ptr(), p.numel()
+        with torch.no_grad():
+            _on_device(dev, lambda d, st: _lib.mbots_policy_adam(
+                desc, len(self.params), _ptr(self._state), G, _ptr(rows), self.lr, self.betas[0], self.betas[1],
+                self.eps, d, st))
+
+    @property
+    def steps(self):
+        """int32 [G] on the parameters' device: the steps every group has taken."""
+        return self._state[:, 0].clone()
+
+    def state_dict(self):
+        """{"m", "v": float32 [P], "state": int32 [G, 3]} -- copies; the
+        moments of the parameters in the optimiser's order, each slice padded
+        to a multiple of 4 floats; state rows are (t, bits of beta1^t, bits of
+        beta2^t)."""
+        return {"m": self._m.clone(), "v": self._v.clone(), "state": self._state.clone()}
+
+    def load_state_dict(self, sd):
+        for key, mine in (("m", self._m), ("v", self._v), ("state", self._state)):
+            t = sd[key]
+            if t.dtype != mine.dtype or tuple(t.shape) != tuple(mine.shape):
+                raise ValueError(f"state_dict[{key!r}] must be {mine.dtype} {list(mine.shape)}, not {t.dtype} "
+                                 f"{list(t.shape)}: the nets differ from those it was saved for")
+        for key, mine in (("m", self._m), ("v", self._v), ("state", self._state)):
+            mine.copy_(sd[key])
 
 
 class TrajectoryWindow:

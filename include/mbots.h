@@ -1089,6 +1089,76 @@ int mbots_policy_adam(const struct mbots_policy_adam_tensor *tensors, uint64_t c
                       struct mbots_policy_adam_state *state, uint32_t groups, const int64_t *rows, float lr,
                       float beta1, float beta2, float eps, int32_t device, void *stream);
 
+/* The recurrent update on the device: the same for the padded [L, B] sequence
+ * batches of mbots_traj_batch, and Adam with per-group gradient clipping and
+ * decoupled weight decay.  Conventions and rounding as above.
+ *
+ * Kept elements.  len, t0, end: int32 [B], the batch's columns; order int32
+ * [B] and segments int32 [groups][4][2] as mbots_policy_seq_order wrote them
+ * (positions lo..hi of pair (g, s) name the columns order[p]), with the
+ * contract of mbots_policy_seq_eval_groups: the host path refuses a segment
+ * outside [0, B], overlapping segments, an order entry outside [0, B) or one
+ * named twice, and names the pair; the device clamps the bounds, and an entry
+ * outside [0, B) is a column of length 0.  Element (k, b) is kept iff
+ *     k < len[b]  and  (last_table < 0 or t0[b] + k < last_table)  and
+ *     not (end[b] == MBOTS_TRAJ_END_RESET and k == len[b] - 1)
+ * (a learner passes horizon - 1, the table that only bootstraps).  What is
+ * dropped is a suffix of the column, so the kept elements are k < kept(b),
+ *     kept(b) = m - (end[b] == MBOTS_TRAJ_END_RESET and m == len[b] ? 1 : 0),
+ *     m = len[b] if last_table < 0 else min(len[b], max(last_table - t0[b], 0)),
+ * and 0 where len[b] <= 0.
+ *
+ * mbots_policy_seq_group_rows: rows[g] (int64 [groups], zeroed by the caller)
+ * += kept(b) over the columns of group g's four segments.
+ *
+ * mbots_policy_seq_a2c_loss: logp, value, entropy, adv, ret f32 [L][B]; rows
+ * the groups' kept totals of the whole update.  A group with rows[g] == 0 is
+ * passed over.  Else every kept element of a column of a segment of group g
+ * takes mbots_policy_a2c_loss's formulas with w = 1.0f / (float)rows[g] at
+ * address k * B + b; every other element of g_logp, g_value, g_entropy
+ * receives +0 and takes no part in loss.  loss[g] (f64 [groups]) += the kept
+ * per_row values in a fixed order: per species segment, position i = p - lo
+ * into f64 accumulator i mod 256, in ascending i and within a column in
+ * ascending k; the 256 accumulators added in ascending index to +0; the four
+ * species' sums added in ascending species to +0; that sum added to loss[g].
+ * Any of the four outputs may be NULL.  The host path also refuses a named
+ * column's len outside [0, L]; the device reads it as min(len, L).
+ *
+ * mbots_policy_adam_clip: mbots_policy_adam's tensors, state and rows, and
+ *   - the squared gradient norm of every group in f64: per chunk of 1024
+ *     elements of a tensor, 256 accumulators a_j = ((x_4j^2 + x_4j+1^2) +
+ *     x_4j+2^2) + x_4j+3^2 of the exact squares (double)g * (double)g, absent
+ *     elements +0, folded as a tree a_i = a_i + a_{i+h} for i < h, h = 128, 64,
+ *     .., 1; a tensor's chunks added in ascending order to +0; the group's
+ *     tensors with n > 0 added in descriptor order to +0;
+ *   - nrm = (float)sqrt(that) with the f64 sqrt, grad_norm[g] = nrm (f32
+ *     [groups], may be NULL; written for every group);
+ *   - coef = max_norm / (nrm + 1e-6f), and 1.0f where that is not < 1 or where
+ *     max_norm is not a positive finite number (no clipping);
+ *   - a group whose squared norm is inf or NaN is left untouched entirely, as
+ *     one with rows[g] == 0;
+ *   - per element gc = g * coef (when clipping), p1 = p - lw * p with lw = lr *
+ *     weight_decay rounded once on the host (when weight_decay != 0), then
+ *     mbots_policy_adam's update of (p1, gc, m, v).
+ * workspace: 8-byte aligned memory of the call's kind, of at least the bytes
+ * mbots_policy_adam_clip_workspace gives for the same tensors (their n) and
+ * groups; its content is scratch. */
+int mbots_policy_seq_group_rows(const int32_t *len, const int32_t *t0, const int32_t *end, uint64_t B,
+                                const int32_t *order, const int32_t *segments, uint32_t groups, int32_t last_table,
+                                int64_t *rows, int32_t device, void *stream);
+int mbots_policy_seq_a2c_loss(const float *logp, const float *value, const float *entropy, const float *adv,
+                              const float *ret, const int32_t *len, const int32_t *t0, const int32_t *end, uint32_t L,
+                              uint64_t B, const int32_t *order, const int32_t *segments, uint32_t groups,
+                              int32_t last_table, const int64_t *rows, float value_coef, float entropy_coef,
+                              float *g_logp, float *g_value, float *g_entropy, double *loss, int32_t device,
+                              void *stream);
+int mbots_policy_adam_clip_workspace(const struct mbots_policy_adam_tensor *tensors, uint64_t count, uint32_t groups,
+                                     uint64_t *bytes);
+int mbots_policy_adam_clip(const struct mbots_policy_adam_tensor *tensors, uint64_t count,
+                           struct mbots_policy_adam_state *state, uint32_t groups, const int64_t *rows, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, float max_norm, float *grad_norm,
+                           void *workspace, uint64_t workspace_bytes, int32_t device, void *stream);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That

@@ -354,5 +354,18 @@ hipError_t launch_policy_group_rows(const int32_t *segments, uint32_t groups, in
 hipError_t launch_policy_a2c_loss(const PolLossIO &io, uint32_t groups, hipStream_t st);
 hipError_t launch_policy_adam(const AdamTensor *tensors, uint64_t count, AdamState *state, uint32_t groups,
                               const int64_t *rows, const AdamCoef &C, hipStream_t st);
+// the same for the padded [L, B] sequence batches: every group's kept elements
+// (io's len, t0, end, order, segments, B and last_table); the loss, one block
+// per group after the fill
+hipError_t launch_policy_seq_group_rows(const PolSeqLossIO &io, uint32_t groups, int64_t *rows, hipStream_t st);
+hipError_t launch_policy_seq_a2c_loss(const PolSeqLossIO &io, uint32_t groups, hipStream_t st);
+// Adam with the groups' gradient norms, clipping and weight decay: per launch
+// of kAdamTensors descriptors the chunks' squared norms and their fold; the
+// groups' norms and clip factors; the element launches; the state's advance.
+// `workspace`: pol_adam_clip_bytes of policy_adam_clip_counts' two numbers
+void policy_adam_clip_counts(const AdamTensor *tensors, uint64_t count, uint64_t &chunks, uint64_t &present);
+hipError_t launch_policy_adam_clip(const AdamTensor *tensors, uint64_t count, AdamState *state, uint32_t groups,
+                                   const int64_t *rows, const AdamCoef &C, const AdamClipCoef &K, float *grad_norm,
+                                   void *workspace, hipStream_t st);
 
 }  // namespace mbots

@@ -3703,6 +3703,28 @@ static_assert(sizeof(mbots_policy_adam_tensor) == sizeof(mbots::AdamTensor) &&
                   sizeof(mbots_policy_adam_state) == sizeof(mbots::AdamState),
               "mbots.h's Adam structs are the kernels'");
 
+namespace {
+int adam_check(const mbots_policy_adam_tensor *tensors, uint64_t count, const mbots_policy_adam_state *state,
+               uint32_t groups)
+{
+    if ((!tensors && count) || !state) return fail(MBOTS_E_INVALID, "null argument");
+    if (groups < 1u || groups > MBOTS_POLICY_MAX_GROUPS)
+        return fail(MBOTS_E_INVALID, "groups must be 1.." + std::to_string(MBOTS_POLICY_MAX_GROUPS));
+    for (uint64_t i = 0; i < count; ++i) {
+        const mbots_policy_adam_tensor &T = tensors[i];
+        if (T.n == 0) continue;
+        const uintptr_t bits = (uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.m | (uintptr_t)T.v;
+        const char *bad = !T.param || !T.grad || !T.m || !T.v ? "has a null pointer"
+                          : (bits & 3u)                       ? "is not 4-byte aligned"
+                          : T.group >= groups                 ? "names a group past `groups`"
+                          : T.n > (1ull << 31)                ? "has more than 2^31 elements"
+                                                              : nullptr;
+        if (bad) return fail(MBOTS_E_INVALID, "Adam tensor " + std::to_string(i) + " " + bad);
+    }
+    return MBOTS_OK;
+}
+}  // namespace
+
 int mbots_policy_group_rows(const int32_t *segments, uint32_t groups, int64_t *rows, int32_t device, void *stream)
 {
     if (!segments || !rows) return fail(MBOTS_E_INVALID, "null argument");
@@ -3775,20 +3797,7 @@ int mbots_policy_adam(const struct mbots_policy_adam_tensor *tensors, uint64_t c
                       float beta1, float beta2, float eps, int32_t device, void *stream)
 {
     using namespace mbots;
-    if ((!tensors && count) || !state) return fail(MBOTS_E_INVALID, "null argument");
-    if (groups < 1u || groups > MBOTS_POLICY_MAX_GROUPS)
-        return fail(MBOTS_E_INVALID, "groups must be 1.." + std::to_string(MBOTS_POLICY_MAX_GROUPS));
-    for (uint64_t i = 0; i < count; ++i) {
-        const mbots_policy_adam_tensor &T = tensors[i];
-        if (T.n == 0) continue;
-        const uintptr_t bits = (uintptr_t)T.param | (uintptr_t)T.grad | (uintptr_t)T.m | (uintptr_t)T.v;
-        const char *bad = !T.param || !T.grad || !T.m || !T.v ? "has a null pointer"
-                          : (bits & 3u)                       ? "is not 4-byte aligned"
-                          : T.group >= groups                 ? "names a group past `groups`"
-                          : T.n > (1ull << 31)                ? "has more than 2^31 elements"
-                                                              : nullptr;
-        if (bad) return fail(MBOTS_E_INVALID, "Adam tensor " + std::to_string(i) + " " + bad);
-    }
+    if (int rc = adam_check(tensors, count, state, groups)) return rc;
     const AdamCoef C{lr, beta1, beta2, 1.0f - beta1, 1.0f - beta2, eps};
     if (device >= 0) {
         HIP_TRY(hipSetDevice(device));
@@ -4155,6 +4164,204 @@ int mbots_policy_seq_grad_groups(const struct mbots_policy_net *nets, uint32_t g
                                           reinterpret_cast<PolGroupEntry *>(ws + P.table_off),
                                           reinterpret_cast<PolUpload *>(ws + P.upload_off), ws + P.slab_off,
                                           P.slab_stride, ws + P.stash_off, ws + P.h_off, P.wave_acc, as_stream(stream)));
+    return MBOTS_OK;
+}
+
+// ---- the recurrent update on the device (include/mbots.h "The update on the
+// device": the sequence batches, clipping and weight decay) ----
+namespace {
+// the host path of the sequence loss reads everything first: the segments, then
+// every column they name (L == 0: the lengths are not bounded)
+int seq_loss_check_host(const int32_t *order, const int32_t *segments, uint32_t groups, const int32_t *len, uint32_t L,
+                        uint64_t B)
+{
+    if (int rc = segments_check_host(segments, groups, B, "positions of order")) return rc;
+    std::vector<uint8_t> seen(B, 0);
+    for (uint32_t e = 0; e < 4u * groups; ++e)
+        for (int64_t p = segments[2u * e]; p < segments[2u * e + 1u]; ++p) {
+            const int64_t b = order[p];
+            const std::string at = pair_name(e) + ": order[" + std::to_string(p) + "] = " + std::to_string(b);
+            if (b < 0 || b >= (int64_t)B)
+                return fail(MBOTS_E_INVALID, at + " is outside the " + std::to_string(B) + " sequences");
+            if (seen[b]) return fail(MBOTS_E_INVALID, at + " names a sequence a second time");
+            seen[b] = 1;
+            if (L && (len[b] < 0 || (uint32_t)len[b] > L))
+                return fail(MBOTS_E_INVALID, pair_name(e) + ": length " + std::to_string(len[b]) + " of sequence " +
+                                                 std::to_string(b) + " is outside [0, " + std::to_string(L) + "]");
+        }
+    return MBOTS_OK;
+}
+
+int seq_loss_args(uint32_t groups, uint64_t B, const int32_t *len, const int32_t *t0, const int32_t *end,
+                  const int32_t *order, const int32_t *segments, const int64_t *rows)
+{
+    if (groups < 1u || groups > MBOTS_POLICY_MAX_GROUPS)
+        return fail(MBOTS_E_INVALID, "groups must be 1.." + std::to_string(MBOTS_POLICY_MAX_GROUPS));
+    if (B > 0x7FFFFFFFull) return fail(MBOTS_E_INVALID, "order addresses columns as int32: at most 2^31 - 1 sequences");
+    if (!segments || !rows) return fail(MBOTS_E_INVALID, "null segments or rows");
+    if (B && (!len || !t0 || !end || !order)) return fail(MBOTS_E_INVALID, "null len, t0, end or order");
+    return MBOTS_OK;
+}
+
+// a chunk's squared norm on the host: policy_adam_sq_kernel's accumulators and tree
+double adam_chunk_sq(const float *g, uint32_t cnt)
+{
+    using namespace mbots;
+    double a[kAdamChunk / 4u];
+    for (uint32_t j = 0; j < kAdamChunk / 4u; ++j) {
+        float x[4];
+        for (uint32_t k = 0; k < 4u; ++k) x[k] = 4u * j + k < cnt ? g[4u * j + k] : 0.0f;
+        a[j] = pol_sq4(x[0], x[1], x[2], x[3]);
+    }
+    for (uint32_t h = kAdamChunk / 8u; h > 0u; h >>= 1)
+        for (uint32_t i = 0; i < h; ++i) a[i] = a[i] + a[i + h];
+    return a[0];
+}
+}  // namespace
+
+int mbots_policy_seq_group_rows(const int32_t *len, const int32_t *t0, const int32_t *end, uint64_t B,
+                                const int32_t *order, const int32_t *segments, uint32_t groups, int32_t last_table,
+                                int64_t *rows, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (int rc = seq_loss_args(groups, B, len, t0, end, order, segments, rows)) return rc;
+    if (device >= 0) {
+        PolSeqLossIO io{};
+        io.len = len, io.t0 = t0, io.end = end, io.order = order, io.segments = segments;
+        io.B = B, io.last_table = last_table;
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_seq_group_rows(io, groups, rows, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    if (int rc = seq_loss_check_host(order, segments, groups, len, 0, B)) return rc;
+    for (uint32_t e = 0; e < 4u * groups; ++e)
+        for (int64_t p = segments[2u * e]; p < segments[2u * e + 1u]; ++p) {
+            const int32_t b = order[p];
+            rows[e / 4u] += pol_seq_kept(len[b], t0[b], end[b], last_table);
+        }
+    return MBOTS_OK;
+}
+
+int mbots_policy_seq_a2c_loss(const float *logp, const float *value, const float *entropy, const float *adv,
+                              const float *ret, const int32_t *len, const int32_t *t0, const int32_t *end, uint32_t L,
+                              uint64_t B, const int32_t *order, const int32_t *segments, uint32_t groups,
+                              int32_t last_table, const int64_t *rows, float value_coef, float entropy_coef,
+                              float *g_logp, float *g_value, float *g_entropy, double *loss, int32_t device,
+                              void *stream)
+{
+    using namespace mbots;
+    if (int rc = seq_loss_args(groups, B, len, t0, end, order, segments, rows)) return rc;
+    if (L && B && (!logp || !value || !entropy || !adv || !ret)) return fail(MBOTS_E_INVALID, "null argument");
+    if (L > (uint32_t)INT32_MAX) return fail(MBOTS_E_INVALID, "L is no int32 length");
+    const PolSeqLossIO io{logp,   value,   entropy,   adv,  ret, len, t0, end,        order,      segments,    rows,
+                          g_logp, g_value, g_entropy, loss, L,   B,   last_table, value_coef, entropy_coef};
+    if (device >= 0) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_seq_a2c_loss(io, groups, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    if (int rc = seq_loss_check_host(order, segments, groups, len, L ? L : 1u, B)) return rc;
+    for (float *o : {g_logp, g_value, g_entropy})
+        if (o) std::fill(o, o + (uint64_t)L * B, 0.0f);
+    for (uint32_t g = 0; g < groups; ++g) {
+        if (rows[g] == 0) continue;   // the +0 stay, the loss is not touched
+        const float w = pol_loss_scale(rows[g]);
+        double group_sum = 0.0;
+        for (uint32_t s = 0; s < 4u; ++s) {
+            const uint64_t lo = (uint64_t)segments[2u * (4u * g + s)];
+            const uint64_t n = (uint64_t)segments[2u * (4u * g + s) + 1u] - lo;
+            double acc[kLossAcc] = {};
+            for (uint64_t i = 0; i < n; ++i) {
+                const int32_t b = order[lo + i];
+                const int32_t nk = std::min(pol_seq_kept(len[b], t0[b], end[b], last_table), (int32_t)L);
+                for (int32_t k = 0; k < nk; ++k) {
+                    const uint64_t r = (uint64_t)k * B + (uint32_t)b;
+                    float gl, gv, ge;
+                    const float per_row = pol_loss_row(logp[r], value[r], entropy[r], adv[r], ret[r], w, value_coef,
+                                                       entropy_coef, gl, gv, ge);
+                    if (g_logp) g_logp[r] = gl;
+                    if (g_value) g_value[r] = gv;
+                    if (g_entropy) g_entropy[r] = ge;
+                    acc[i % kLossAcc] += (double)per_row;
+                }
+            }
+            double q = 0.0;
+            for (uint32_t k = 0; k < kLossAcc; ++k) q += acc[k];
+            group_sum += q;
+        }
+        if (loss) loss[g] += group_sum;
+    }
+    return MBOTS_OK;
+}
+
+int mbots_policy_adam_clip_workspace(const struct mbots_policy_adam_tensor *tensors, uint64_t count, uint32_t groups,
+                                     uint64_t *bytes)
+{
+    using namespace mbots;
+    if ((!tensors && count) || !bytes) return fail(MBOTS_E_INVALID, "null argument");
+    if (groups < 1u || groups > MBOTS_POLICY_MAX_GROUPS)
+        return fail(MBOTS_E_INVALID, "groups must be 1.." + std::to_string(MBOTS_POLICY_MAX_GROUPS));
+    uint64_t chunks, present;
+    policy_adam_clip_counts(reinterpret_cast<const AdamTensor *>(tensors), count, chunks, present);
+    *bytes = pol_adam_clip_bytes(chunks, present, groups);
+    return MBOTS_OK;
+}
+
+int mbots_policy_adam_clip(const struct mbots_policy_adam_tensor *tensors, uint64_t count,
+                           struct mbots_policy_adam_state *state, uint32_t groups, const int64_t *rows, float lr,
+                           float beta1, float beta2, float eps, float weight_decay, float max_norm, float *grad_norm,
+                           void *workspace, uint64_t workspace_bytes, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (int rc = adam_check(tensors, count, state, groups)) return rc;
+    const AdamTensor *T = reinterpret_cast<const AdamTensor *>(tensors);
+    uint64_t chunks, present;
+    policy_adam_clip_counts(T, count, chunks, present);
+    const uint64_t need = pol_adam_clip_bytes(chunks, present, groups);
+    if (!workspace || ((uintptr_t)workspace & 7u) || workspace_bytes < need)
+        return fail(MBOTS_E_INVALID, "8-byte aligned workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                         std::to_string(need) + " needed (mbots_policy_adam_clip_workspace)");
+    const AdamCoef C{lr, beta1, beta2, 1.0f - beta1, 1.0f - beta2, eps};
+    const AdamClipCoef K{lr * weight_decay, max_norm, max_norm > 0.0f && max_norm < INFINITY ? 1u : 0u,
+                         weight_decay != 0.0f ? 1u : 0u};
+    if (device >= 0) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_adam_clip(T, count, reinterpret_cast<AdamState *>(state), groups, rows, C, K, grad_norm,
+                                        workspace, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    const AdamClipWs W = pol_adam_clip_ws(workspace, chunks, present, groups);
+    for (uint32_t g = 0; g < groups; ++g) W.normsq[g] = 0.0;
+    uint64_t c = 0, slot = 0;
+    for (uint64_t i = 0; i < count; ++i) {
+        if (T[i].n == 0) continue;
+        double sum = 0.0;
+        for (uint64_t base = 0; base < T[i].n; base += kAdamChunk) {
+            W.q[c] = adam_chunk_sq(T[i].grad + base, (uint32_t)std::min<uint64_t>(kAdamChunk, T[i].n - base));
+            sum += W.q[c++];
+        }
+        W.tsum[slot++] = sum;
+        W.normsq[T[i].group] += sum;
+    }
+    for (uint32_t g = 0; g < groups; ++g) {
+        float nrm;
+        const bool finite = pol_clip_coef(W.normsq[g], K, nrm, W.coef[g]);
+        W.live[g] = finite && (!rows || rows[g] != 0) ? 1u : 0u;
+        if (grad_norm) grad_norm[g] = nrm;
+    }
+    for (uint64_t i = 0; i < count; ++i) {
+        const uint32_t g = T[i].group;
+        if (T[i].n == 0 || !W.live[g]) continue;
+        const float c1 = 1.0f - state[g].b1t * beta1, c2 = 1.0f - state[g].b2t * beta2;
+        for (uint64_t k = 0; k < T[i].n; ++k)
+            pol_adam_clip(T[i].param[k], T[i].grad[k], T[i].m[k], T[i].v[k], C, K, W.coef[g], c1, c2);
+    }
+    for (uint32_t g = 0; g < groups; ++g) {
+        if (!W.live[g]) continue;
+        state[g].t += 1u;
+        state[g].b1t = state[g].b1t * beta1;
+        state[g].b2t = state[g].b2t * beta2;
+    }
     return MBOTS_OK;
 }
 

@@ -2051,4 +2051,341 @@ hipError_t launch_policy_adam(const AdamTensor *tensors, uint64_t count, AdamSta
     return hipGetLastError();
 }
 
+// ---- the sequence loss: the padded [L, B] batches of the recurrent learners ----
+// column order[p]'s kept elements, its length read as at most `cap`: 0 where
+// the entry names no column
+__device__ __forceinline__ int32_t seq_kept(const PolSeqLossIO &A, int32_t col, int32_t cap)
+{
+    if ((uint64_t)(uint32_t)col >= A.B) return 0;
+    return pol_seq_kept(min(A.len[col], cap), A.t0[col], A.end[col], A.last_table);
+}
+
+// blocks (g, 0 .. gridDim.y) share group g's positions; the counts are
+// integers, so the order of the sum is free
+__global__ __launch_bounds__(256) void policy_seq_group_rows_kernel(PolSeqLossIO A, int64_t *rows)
+{
+    __shared__ int64_t s_sum[256];
+    const uint32_t g = blockIdx.x, t = threadIdx.x;
+    int64_t sum = 0;
+    for (uint32_t s = 0; s < 4u; ++s) {
+        uint32_t lo, len;
+        pol_segment(A.segments, 4u * g + s, A.B, lo, len);
+        for (uint32_t i = blockIdx.y * 256u + t; i < len; i += gridDim.y * 256u) sum += seq_kept(A, A.order[lo + i], INT32_MAX);
+    }
+    s_sum[t] = sum;
+    __syncthreads();
+    for (uint32_t h = 128u; h > 0u; h >>= 1) {
+        if (t < h) s_sum[t] += s_sum[t + h];
+        __syncthreads();
+    }
+    if (t == 0u && s_sum[0] != 0)
+        atomicAdd(reinterpret_cast<unsigned long long *>(rows + g), (unsigned long long)s_sum[0]);
+}
+
+// Block g is group g, threads [256 s, 256 s + 256) the accumulators of species
+// s, as policy_a2c_loss_kernel: thread a takes the columns at positions a,
+// a + 256, ... of the segment in ascending order and each column's kept steps
+// in ascending k, so the order of the sums is a property of the indices alone.
+// The metadata and the first kSeqSteps steps of kSeqFlight columns are loaded
+// before the first is consumed; a longer column reloads its own registers.
+constexpr uint32_t kSeqFlight = 4, kSeqSteps = 4;
+__global__ __launch_bounds__(1024) void policy_seq_a2c_loss_kernel(PolSeqLossIO A)
+{
+    __shared__ double s_acc[4u * kLossAcc];
+    __shared__ double s_sum[4];
+    const uint32_t g = blockIdx.x, s = uniform(threadIdx.x >> 8), a = threadIdx.x & (kLossAcc - 1u);
+    const int64_t rows = A.rows[g];
+    if (rows == 0) return;   // the whole block: the fill's +0 stay, the loss is not touched
+    uint32_t lo, len;
+    pol_segment(A.segments, 4u * g + s, A.B, lo, len);
+    lo = uniform(lo);
+    len = uniform(len);
+    const float w = pol_loss_scale(rows);
+    const float *__restrict__ logp = A.logp, *__restrict__ value = A.value, *__restrict__ entropy = A.entropy;
+    const float *__restrict__ adv = A.adv, *__restrict__ ret = A.ret;
+    const uint64_t B = A.B;
+    double acc = 0.0;
+    for (uint32_t i0 = a; i0 < len; i0 += kSeqFlight * kLossAcc) {
+        int32_t col[kSeqFlight], nk[kSeqFlight];
+        float x[kSeqFlight][kSeqSteps][5];
+#pragma unroll
+        for (uint32_t c = 0; c < kSeqFlight; ++c) {
+            const uint32_t i = i0 + c * kLossAcc;
+            col[c] = i < len ? A.order[lo + i] : -1;
+        }
+#pragma unroll
+        for (uint32_t c = 0; c < kSeqFlight; ++c) nk[c] = seq_kept(A, col[c], (int32_t)A.L);
+        auto load = [&](uint32_t c, int32_t k0) {
+#pragma unroll
+            for (uint32_t j = 0; j < kSeqSteps; ++j)
+                if (k0 + (int32_t)j < nk[c]) {
+                    const uint64_t r = (uint64_t)(k0 + (int32_t)j) * B + (uint32_t)col[c];
+                    x[c][j][0] = logp[r], x[c][j][1] = value[r], x[c][j][2] = entropy[r], x[c][j][3] = adv[r];
+                    x[c][j][4] = ret[r];
+                }
+        };
+#pragma unroll
+        for (uint32_t c = 0; c < kSeqFlight; ++c) load(c, 0);
+#pragma unroll
+        for (uint32_t c = 0; c < kSeqFlight; ++c) {
+            for (int32_t k0 = 0; k0 < nk[c]; k0 += (int32_t)kSeqSteps) {
+                if (k0) load(c, k0);
+#pragma unroll
+                for (uint32_t j = 0; j < kSeqSteps; ++j)
+                    if (k0 + (int32_t)j < nk[c]) {
+                        const uint64_t r = (uint64_t)(k0 + (int32_t)j) * B + (uint32_t)col[c];
+                        float gl, gv, ge;
+                        const float per_row = pol_loss_row(x[c][j][0], x[c][j][1], x[c][j][2], x[c][j][3], x[c][j][4],
+                                                           w, A.value_coef, A.entropy_coef, gl, gv, ge);
+                        if (A.g_logp) A.g_logp[r] = gl;
+                        if (A.g_value) A.g_value[r] = gv;
+                        if (A.g_entropy) A.g_entropy[r] = ge;
+                        acc += (double)per_row;
+                    }
+            }
+        }
+    }
+    if (A.loss == nullptr) return;
+    s_acc[threadIdx.x] = acc;
+    __syncthreads();
+    if (a == 0u) {
+        double q = 0.0;
+        for (uint32_t k = 0; k < kLossAcc; ++k) q += s_acc[s * kLossAcc + k];
+        s_sum[s] = q;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0u) {
+        double q = 0.0;
+        for (uint32_t k = 0; k < 4u; ++k) q += s_sum[k];
+        A.loss[g] += q;
+    }
+}
+
+hipError_t launch_policy_seq_group_rows(const PolSeqLossIO &io, uint32_t groups, int64_t *rows, hipStream_t st)
+{
+    if (io.B == 0) return hipSuccess;
+    const unsigned per = (unsigned)std::min<uint64_t>((io.B + 1023u) / 1024u, 32u);
+    hipLaunchKernelGGL(policy_seq_group_rows_kernel, dim3(groups, per), dim3(256), 0, st, io, rows);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_seq_a2c_loss(const PolSeqLossIO &io, uint32_t groups, hipStream_t st)
+{
+    const uint64_t n = (uint64_t)io.L * io.B;
+    if (n && (io.g_logp || io.g_value || io.g_entropy)) {
+        const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255u) / 256u, 2048u);
+        hipLaunchKernelGGL(policy_zero_rows_kernel, dim3(blocks), dim3(256), 0, st, io.g_logp, io.g_value, io.g_entropy, n);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(policy_seq_a2c_loss_kernel, dim3(groups), dim3(1024), 0, st, io);
+    return hipGetLastError();
+}
+
+// ---- mbots_policy_adam_clip ----
+// block b's tensor of the launch: the last whose first block is <= b
+__device__ __forceinline__ uint32_t adam_tensor_of(const uint32_t *first, uint32_t n, uint32_t b)
+{
+    uint32_t lo = 0, hi = n - 1u;
+    while (lo < hi) {
+        const uint32_t mid = (lo + hi + 1u) >> 1;
+        if (first[mid] <= b) lo = mid;
+        else hi = mid - 1u;
+    }
+    return uniform(lo);
+}
+
+// q[chunk0 + b]: the squared norm of block b's chunk of the gradient, thread t
+// the accumulator of elements 4t .. 4t + 3 -- from one 16-byte load or from
+// four 4-byte loads, the same values either way -- and the tree over the 256
+__global__ __launch_bounds__(256) void policy_adam_sq_kernel(AdamLaunch L, uint32_t chunk0, double *q)
+{
+    __shared__ double s_a[256];
+    const uint32_t b = blockIdx.x, t = threadIdx.x;
+    const uint32_t i = adam_tensor_of(L.first, L.n, b);
+    const uint64_t base = (uint64_t)(b - L.first[i]) * kAdamChunk;
+    const uint32_t cnt = (uint32_t)min((uint64_t)kAdamChunk, L.t[i].n - base);
+    const float *__restrict__ g = L.t[i].grad + base;
+    static_assert(kAdamChunk == 4u * 256u, "policy_adam_sq_kernel: four elements per thread");
+    float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (((uintptr_t)g & 15u) == 0u && 4u * t + 4u <= cnt) {
+        const float4 G = reinterpret_cast<const float4 *>(g)[t];
+        x[0] = G.x, x[1] = G.y, x[2] = G.z, x[3] = G.w;
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 4u; ++k)
+            if (4u * t + k < cnt) x[k] = g[4u * t + k];
+    }
+    s_a[t] = pol_sq4(x[0], x[1], x[2], x[3]);
+    __syncthreads();
+    for (uint32_t h = 128u; h > 0u; h >>= 1) {
+        if (t < h) s_a[t] = s_a[t] + s_a[t + h];
+        __syncthreads();
+    }
+    if (t == 0u) q[chunk0 + b] = s_a[0];
+}
+
+// one block: thread i the ascending sum of tensor i's chunk partials, then
+// thread g group g's tensors of this launch in descriptor order, onto what
+// the earlier launches of the call left (`first`: onto +0)
+__global__ __launch_bounds__(64) void policy_adam_fold_kernel(AdamFold F, AdamClipWs W, uint32_t groups, int first)
+{
+    __shared__ double s_t[kAdamTensors];
+    const uint32_t t = threadIdx.x;
+    if (t < F.n) {
+        double sum = 0.0;
+        for (uint32_t c = F.first[t]; c < F.first[t + 1u]; ++c) sum += W.q[c];
+        s_t[t] = sum;
+        W.tsum[F.slot[t]] = sum;
+    }
+    __syncthreads();
+    static_assert(kPolMaxGroups <= 64u, "policy_adam_fold_kernel: one thread per group");
+    if (t < groups) {
+        double n2 = first ? 0.0 : W.normsq[t];
+        for (uint32_t i = 0; i < F.n; ++i)
+            if (F.group[i] == t) n2 += s_t[i];
+        W.normsq[t] = n2;
+    }
+}
+
+// thread g: group g's norm, clip factor and whether it takes the step
+__global__ __launch_bounds__(64) void policy_adam_finish_kernel(AdamClipWs W, const int64_t *rows, uint32_t groups,
+                                                                AdamClipCoef K, float *grad_norm)
+{
+    const uint32_t g = threadIdx.x;
+    if (g >= groups) return;
+    float nrm, coef;
+    const bool finite = pol_clip_coef(W.normsq[g], K, nrm, coef);
+    W.coef[g] = coef;
+    W.live[g] = finite && (rows == nullptr || rows[g] != 0) ? 1u : 0u;
+    if (grad_norm) grad_norm[g] = nrm;
+}
+
+// policy_adam_kernel on the clipped gradient and the decayed parameter, for
+// the groups the finish kernel left live
+__global__ __launch_bounds__(256) void policy_adam_clip_kernel(AdamLaunch L, const AdamState *state, AdamClipWs W,
+                                                               AdamCoef C, AdamClipCoef K)
+{
+    const uint32_t b = blockIdx.x;
+    const uint32_t i = adam_tensor_of(L.first, L.n, b);
+    const uint32_t group = L.t[i].group;
+    if (W.live[group] == 0u) return;
+    const float coef = W.coef[group];
+    const AdamState S = state[group];
+    const float c1 = 1.0f - S.b1t * C.beta1, c2 = 1.0f - S.b2t * C.beta2;
+    const uint64_t base = (uint64_t)(b - L.first[i]) * kAdamChunk;
+    const uint32_t cnt = (uint32_t)min((uint64_t)kAdamChunk, L.t[i].n - base);
+    float *__restrict__ p = L.t[i].param + base;
+    const float *__restrict__ g = L.t[i].grad + base;
+    float *__restrict__ m = L.t[i].m + base;
+    float *__restrict__ v = L.t[i].v + base;
+    const uint32_t t = threadIdx.x;
+    const bool wide = (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15u) == 0u;
+    if (wide) {
+        if (4u * t + 4u <= cnt) {
+            float4 P = reinterpret_cast<float4 *>(p)[t];
+            const float4 Gr = reinterpret_cast<const float4 *>(g)[t];
+            float4 M = reinterpret_cast<float4 *>(m)[t], V = reinterpret_cast<float4 *>(v)[t];
+            pol_adam_clip(P.x, Gr.x, M.x, V.x, C, K, coef, c1, c2);
+            pol_adam_clip(P.y, Gr.y, M.y, V.y, C, K, coef, c1, c2);
+            pol_adam_clip(P.z, Gr.z, M.z, V.z, C, K, coef, c1, c2);
+            pol_adam_clip(P.w, Gr.w, M.w, V.w, C, K, coef, c1, c2);
+            reinterpret_cast<float4 *>(p)[t] = P;
+            reinterpret_cast<float4 *>(m)[t] = M;
+            reinterpret_cast<float4 *>(v)[t] = V;
+        }
+        const uint32_t k = (cnt & ~3u) + t;   // the scalar tail
+        if (t < (cnt & 3u)) {
+            float P = p[k], M = m[k], V = v[k];
+            pol_adam_clip(P, g[k], M, V, C, K, coef, c1, c2);
+            p[k] = P, m[k] = M, v[k] = V;
+        }
+        return;
+    }
+    for (uint32_t k = t; k < cnt; k += 256u) {
+        float P = p[k], M = m[k], V = v[k];
+        pol_adam_clip(P, g[k], M, V, C, K, coef, c1, c2);
+        p[k] = P, m[k] = M, v[k] = V;
+    }
+}
+
+__global__ __launch_bounds__(64) void policy_adam_clip_advance_kernel(AdamState *state, const uint32_t *live,
+                                                                      uint32_t groups, float beta1, float beta2)
+{
+    for (uint32_t g = threadIdx.x; g < groups; g += 64u) {
+        if (live[g] == 0u) continue;
+        AdamState S = state[g];
+        S.t += 1u;
+        S.b1t = S.b1t * beta1;
+        S.b2t = S.b2t * beta2;
+        state[g] = S;
+    }
+}
+
+void policy_adam_clip_counts(const AdamTensor *tensors, uint64_t count, uint64_t &chunks, uint64_t &present)
+{
+    chunks = present = 0;
+    for (uint64_t i = 0; i < count; ++i)
+        if (tensors[i].n) chunks += (tensors[i].n + kAdamChunk - 1u) / kAdamChunk, ++present;
+}
+
+hipError_t launch_policy_adam_clip(const AdamTensor *tensors, uint64_t count, AdamState *state, uint32_t groups,
+                                   const int64_t *rows, const AdamCoef &C, const AdamClipCoef &K, float *grad_norm,
+                                   void *workspace, hipStream_t st)
+{
+    uint64_t chunks, present;
+    policy_adam_clip_counts(tensors, count, chunks, present);
+    const AdamClipWs W = pol_adam_clip_ws(workspace, chunks, present, groups);
+    // the launches of 64 tensors, as launch_policy_adam cuts them
+    AdamLaunch L;
+    AdamFold F;
+    uint32_t chunk0 = 0, slot = 0;
+    int first = 1;
+    auto each_launch = [&](auto &&fn) -> hipError_t {
+        L.n = 0, L.first[0] = 0;
+        for (uint64_t i = 0; i <= count; ++i) {
+            if (i < count && tensors[i].n) {
+                L.t[L.n] = tensors[i];
+                L.first[L.n + 1u] = L.first[L.n] + (uint32_t)((tensors[i].n + kAdamChunk - 1u) / kAdamChunk);
+                ++L.n;
+            }
+            if (L.n == kAdamTensors || (i == count && L.n)) {
+                if (hipError_t e = fn()) return e;
+                L.n = 0;
+            }
+        }
+        return hipSuccess;
+    };
+    if (hipError_t e = each_launch([&]() -> hipError_t {
+            hipLaunchKernelGGL(policy_adam_sq_kernel, dim3(L.first[L.n]), dim3(256), 0, st, L, chunk0, W.q);
+            if (hipError_t e = hipGetLastError()) return e;
+            F.n = L.n;
+            for (uint32_t i = 0; i < L.n; ++i) {
+                F.first[i] = chunk0 + L.first[i];
+                F.slot[i] = slot++;
+                F.group[i] = L.t[i].group;
+            }
+            F.first[L.n] = chunk0 + L.first[L.n];
+            chunk0 += L.first[L.n];
+            hipLaunchKernelGGL(policy_adam_fold_kernel, dim3(1), dim3(64), 0, st, F, W, groups, first);
+            first = 0;
+            return hipGetLastError();
+        }))
+        return e;
+    if (first) {   // no gradient at all: every norm is +0
+        F.n = 0;
+        hipLaunchKernelGGL(policy_adam_fold_kernel, dim3(1), dim3(64), 0, st, F, W, groups, 1);
+        if (hipError_t e = hipGetLastError()) return e;
+    }
+    hipLaunchKernelGGL(policy_adam_finish_kernel, dim3(1), dim3(64), 0, st, W, rows, groups, K, grad_norm);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (hipError_t e = each_launch([&]() -> hipError_t {
+            hipLaunchKernelGGL(policy_adam_clip_kernel, dim3(L.first[L.n]), dim3(256), 0, st, L, state, W, C, K);
+            return hipGetLastError();
+        }))
+        return e;
+    hipLaunchKernelGGL(policy_adam_clip_advance_kernel, dim3(1), dim3(64), 0, st, state, W.live, groups, C.beta1, C.beta2);
+    return hipGetLastError();
+}
+
 }  // namespace mbots

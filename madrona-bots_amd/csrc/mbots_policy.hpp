@@ -639,6 +639,37 @@ struct PolLossIO {            // mbots_policy_a2c_loss's arguments
     float value_coef, entropy_coef;
 };
 
+// ---- the sequence loss (mbots_policy_seq_a2c_loss): the padded [L, B] batches
+// of the recurrent learners.  Element (k, b) is kept iff k < len, its table
+// t0 + k lies before last_table (negative: no such bound) and it is not the
+// last row of a lifeline a reset ended.  What is dropped is a suffix of the
+// column, so the kept elements are k < pol_seq_kept(): the steps before the
+// bound, less the reset's last row when the bound leaves it in.
+MB_HD int32_t pol_seq_kept(int32_t len, int32_t t0, int32_t end, int32_t last_table)
+{
+    if (len <= 0) return 0;
+    int64_t m = len;
+    if (last_table >= 0) {
+        const int64_t room = (int64_t)last_table - (int64_t)t0;
+        m = room < 0 ? 0 : (room < m ? room : m);
+    }
+    if (end == 2 /* MBOTS_TRAJ_END_RESET */ && m == (int64_t)len) m -= 1;
+    return (int32_t)m;
+}
+
+struct PolSeqLossIO {         // mbots_policy_seq_a2c_loss's (and mbots_policy_seq_group_rows') arguments
+    const float *logp, *value, *entropy, *adv, *ret;   // [L, B]
+    const int32_t *len, *t0, *end;                     // [B]
+    const int32_t *order, *segments;
+    const int64_t *rows;
+    float *g_logp, *g_value, *g_entropy;
+    double *loss;
+    uint32_t L;
+    uint64_t B;
+    int32_t last_table;
+    float value_coef, entropy_coef;
+};
+
 struct AdamTensor {           // struct mbots_policy_adam_tensor
     float *param;
     const float *grad;
@@ -674,5 +705,74 @@ struct AdamLaunch {
     uint32_t n;
 };
 static_assert(sizeof(AdamLaunch) + 128u <= 4096u, "a launch's tensor descriptors travel as kernel arguments");
+
+// ---- mbots_policy_adam_clip: the global gradient norm of every group in a
+// fixed order, then Adam on the clipped gradient and the decayed parameter.
+// Accumulator j of a chunk: the exact f64 squares of its elements 4j .. 4j + 3
+// (absent ones +0), added in ascending order; the 256 accumulators then fold
+// as a tree, a_i += a_{i + h} for h = 128 .. 1.
+MB_HD double pol_sq4(float a, float b, float c, float d)
+{
+    return (((double)a * (double)a + (double)b * (double)b) + (double)c * (double)c) + (double)d * (double)d;
+}
+// the workspace of a call over `chunks` chunks of `tensors` tensors with n > 0:
+// [chunks] f64 chunk partials, [tensors] f64 tensor sums, [groups] f64 squared
+// norms, [groups] f32 coef, [groups] u32 live (the group takes the step)
+struct AdamClipWs {
+    double *q, *tsum, *normsq;
+    float *coef;
+    uint32_t *live;
+};
+MB_HD uint64_t pol_adam_clip_bytes(uint64_t chunks, uint64_t tensors, uint32_t groups)
+{
+    return (chunks + tensors + groups) * sizeof(double) + (uint64_t)groups * (sizeof(float) + sizeof(uint32_t));
+}
+MB_HD AdamClipWs pol_adam_clip_ws(void *base, uint64_t chunks, uint64_t tensors, uint32_t groups)
+{
+    AdamClipWs W;
+    W.q = static_cast<double *>(base);
+    W.tsum = W.q + chunks;
+    W.normsq = W.tsum + tensors;
+    W.coef = reinterpret_cast<float *>(W.normsq + groups);
+    W.live = reinterpret_cast<uint32_t *>(W.coef + groups);
+    return W;
+}
+struct AdamClipCoef {
+    float lw;         // lr * weight_decay, rounded once on the host
+    float max_norm;
+    uint32_t clip;    // max_norm is a positive finite number
+    uint32_t decay;   // weight_decay != 0
+};
+// a group's norm and clip factor from its squared norm; false: the norm is not
+// finite and the group is left untouched
+MB_HD bool pol_clip_coef(double normsq, const AdamClipCoef &K, float &nrm, float &coef)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    nrm = (float)sqrt(normsq);
+#else
+    nrm = (float)std::sqrt(normsq);
+#endif
+    coef = 1.0f;
+    if (K.clip) {
+        const float c = K.max_norm / (nrm + 1e-6f);
+        if (c < 1.0f) coef = c;
+    }
+    return normsq - normsq == 0.0;   // neither inf nor NaN
+}
+MB_HD void pol_adam_clip(float &p, float g, float &m, float &v, const AdamCoef &C, const AdamClipCoef &K, float coef,
+                         float c1, float c2)
+{
+    const float gc = K.clip ? g * coef : g;
+    if (K.decay) p = p - K.lw * p;
+    pol_adam(p, gc, m, v, C, c1, c2);
+}
+// a fold launch's tensors: chunk partials q[first[i] .. first[i + 1]) are tensor
+// slot[i]'s, of group group[i]
+struct AdamFold {
+    uint32_t first[kAdamTensors + 1];
+    uint32_t slot[kAdamTensors];
+    uint32_t group[kAdamTensors];
+    uint32_t n;
+};
 
 }  // namespace mbots

@@ -52,7 +52,7 @@ def species_slices(sim):
 
 
 def train(sim, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0, value_coef=0.5,
-          entropy_coef=0.01, log=None, device_update=False, lr=3e-4):
+          entropy_coef=0.01, log=None, device_update=False, lr=3e-4, max_grad_norm=None, weight_decay=0.0):
     """`iters` updates of `horizon - 1` steps each.  Returns the losses (floats).
     device_update: a2c_groups.train's device update with one group;
     `optimizers` is then a madrona_bots.PolicyAdam or None."""
@@ -60,7 +60,8 @@ def train(sim, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, deat
     if device_update:
         import a2c_groups
         per_group = a2c_groups.train(sim, [0], [modules], optimizers, iters, horizon, gamma, lam, death_reward,
-                                     value_coef, entropy_coef, log, device_update=True, lr=lr)
+                                     value_coef, entropy_coef, log, device_update=True, lr=lr,
+                                     max_grad_norm=max_grad_norm, weight_decay=weight_decay)
         return [x[0] for x in per_group]
     nets = [mb.PolicyNet.from_torch(m["feature"], m["actor"], m["critic"]) for m in modules]
     sim.set_policy(nets)
@@ -116,14 +117,20 @@ def main():
     ap.add_argument("--exec-mode", choices=("hip", "cpu"), default="hip" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--device-update", action="store_true",
                     help="the loss and the optimiser in the library: a2c_loss_groups and one PolicyAdam.step")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="with --device-update: clip the global gradient norm to this")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="with --device-update: decoupled weight decay")
     args = ap.parse_args()
+    if (args.max_grad_norm is not None or args.weight_decay) and not args.device_update:
+        ap.error("--max-grad-norm and --weight-decay need --device-update")
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     import madrona_bots as mb
     sim = mb.SimManager(0, args.worlds, args.seed, args.agents, exec_mode=args.exec_mode)
     modules = make_modules(args.hidden, sim.device, args.seed)
     optimizers = None if args.device_update else [torch.optim.Adam(m.parameters(), lr=args.lr) for m in modules]
-    train(sim, modules, optimizers, args.iters, args.horizon, log=print, device_update=args.device_update, lr=args.lr)
+    train(sim, modules, optimizers, args.iters, args.horizon, log=print, device_update=args.device_update, lr=args.lr,
+          max_grad_norm=args.max_grad_norm, weight_decay=args.weight_decay)
 
 
 if __name__ == "__main__":

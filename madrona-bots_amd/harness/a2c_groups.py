@@ -39,15 +39,17 @@ from a2c import make_modules  # noqa: E402
 
 
 def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0,
-          value_coef=0.5, entropy_coef=0.01, log=None, grouped_evaluate=False, device_update=False, lr=3e-4):
+          value_coef=0.5, entropy_coef=0.01, log=None, grouped_evaluate=False, device_update=False, lr=3e-4,
+          max_grad_norm=None, weight_decay=0.0):
     """`iters` updates of `horizon - 1` steps each of every group.  modules[u],
     optimizers[u]: a2c.make_modules' four ModuleDicts and their optimizers for
     group u.  grouped_evaluate: one evaluate_groups per table and one
     backward() (train_grouped_update) in place of the per-net loop.
     device_update: the loss and the optimiser in the library as well
     (device_update_step); `optimizers` is then a madrona_bots.PolicyAdam over
-    the groups' nets, or None for one with learning rate `lr`.  Returns the
-    losses, [iters][groups] floats."""
+    the groups' nets, or None for one with learning rate `lr`, max_grad_norm
+    and weight_decay (PolicyAdam's clipping and decoupled weight decay).
+    Returns the losses, [iters][groups] floats."""
     import madrona_bots as mb
     G = len(starts)
     sim.set_policy_groups(starts)
@@ -56,7 +58,8 @@ def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.
         sim.set_policy(nets[u], group=u)
     if device_update:
         grouped_evaluate = True
-        adam = optimizers if isinstance(optimizers, mb.PolicyAdam) else mb.PolicyAdam(nets, lr=lr)
+        adam = optimizers if isinstance(optimizers, mb.PolicyAdam) else \
+            mb.PolicyAdam(nets, lr=lr, max_grad_norm=max_grad_norm, weight_decay=weight_decay)
     win = sim.trajectory_window(horizon, max_rows=sim.num_worlds * sim.agent_capacity)
     seg = torch.empty((G, 4, 2), dtype=torch.int32, device=sim.device)
     losses = []
@@ -200,7 +203,12 @@ def main():
     ap.add_argument("--device-update", action="store_true",
                     help="--grouped-evaluate with a2c_loss_groups and one PolicyAdam.step in place of torch's loss "
                          "and optimizers")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="with --device-update: clip every group's global gradient norm to this")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="with --device-update: decoupled weight decay")
     args = ap.parse_args()
+    if (args.max_grad_norm is not None or args.weight_decay) and not args.device_update:
+        ap.error("--max-grad-norm and --weight-decay need --device-update")
     if not 1 <= args.groups <= 64 or args.worlds < args.groups:
         ap.error("--groups must be in [1, 64] and at most --worlds")
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -212,7 +220,8 @@ def main():
     optimizers = None if args.device_update else \
         [[torch.optim.Adam(m.parameters(), lr=args.lr) for m in four] for four in modules]
     train(sim, starts, modules, optimizers, args.iters, args.horizon, log=print,
-          grouped_evaluate=args.grouped_evaluate, device_update=args.device_update, lr=args.lr)
+          grouped_evaluate=args.grouped_evaluate, device_update=args.device_update, lr=args.lr,
+          max_grad_norm=args.max_grad_norm, weight_decay=args.weight_decay)
 
 
 if __name__ == "__main__":

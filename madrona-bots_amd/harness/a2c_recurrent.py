@@ -11,7 +11,10 @@ records it, and evaluate_sequences() runs each net along its agents' padded
 lifelines -- logp, value and the carried state bit for bit what act() produced
 -- and backpropagates through time with the library's own kernels, so the
 memory head learns, with the same gradient bits in CPU mode and on the device.
-Losses and optimisers are plain torch.
+Losses and optimisers are plain torch; with --device-update they are the
+library's too (sequence_group_rows, a2c_loss_sequences and PolicyAdam:
+a2c_recurrent_groups.py's device update with one group), and the parameters
+after the optimiser's step are the same bits in CPU mode and on the device.
 
     python madrona-bots_amd/harness/a2c_recurrent.py --worlds 64 --iters 10 --exec-mode cpu
     python madrona-bots_amd/harness/a2c_recurrent.py --worlds 4096 --iters 50
@@ -94,8 +97,18 @@ def rollout(sim, win, horizon, gamma=0.99, lam=0.95, death_reward=-1.0):
 
 
 def train(sim, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0, value_coef=0.5,
-          entropy_coef=0.01, log=None):
-    """`iters` updates of `horizon - 1` steps each.  Returns the losses (floats)."""
+          entropy_coef=0.01, log=None, device_update=False, lr=3e-4, max_grad_norm=None, weight_decay=0.0):
+    """`iters` updates of `horizon - 1` steps each.  Returns the losses (floats).
+    device_update: a2c_recurrent_groups.train's device update with one group;
+    `optimizers` is then a madrona_bots.PolicyAdam or None.  An update with no
+    kept element leaves the nets untouched then, where the torch path steps
+    them with zero gradients."""
+    if device_update:
+        import a2c_recurrent_groups
+        per_group = a2c_recurrent_groups.train(sim, [0], [modules], optimizers, iters, horizon, gamma, lam,
+                                               death_reward, value_coef, entropy_coef, log, device_update=True, lr=lr,
+                                               max_grad_norm=max_grad_norm, weight_decay=weight_decay)
+        return [x[0] for x in per_group]
     nets = [policy_net(m) for m in modules]
     sim.set_policy(nets)
     win = sim.trajectory_window(horizon, max_rows=sim.num_worlds * sim.agent_capacity, record_obs=True,
@@ -149,13 +162,23 @@ def main():
     ap.add_argument("--seed", type=int, default=69)
     ap.add_argument("--exec-mode", choices=("hip", "cpu"), default="hip" if torch.cuda.is_available() else "cpu")
     ap.add_argument("--gated", action="store_true", help="add the gate head to every species' net")
+    ap.add_argument("--device-update", action="store_true",
+                    help="the mask, the loss and the optimiser in the library: sequence_group_rows, "
+                         "a2c_loss_sequences and one PolicyAdam.step")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="with --device-update: clip the global gradient norm to this")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="with --device-update: decoupled weight decay")
     args = ap.parse_args()
+    if (args.max_grad_norm is not None or args.weight_decay) and not args.device_update:
+        ap.error("--max-grad-norm and --weight-decay need --device-update")
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
     import madrona_bots as mb
     sim = mb.SimManager(0, args.worlds, args.seed, args.agents, exec_mode=args.exec_mode)
     modules = make_modules(args.hidden, sim.device, args.seed, args.gated)
-    optimizers = [torch.optim.Adam(m.parameters(), lr=args.lr) for m in modules]
-    train(sim, modules, optimizers, args.iters, args.horizon, log=print)
+    optimizers = None if args.device_update else [torch.optim.Adam(m.parameters(), lr=args.lr) for m in modules]
+    train(sim, modules, optimizers, args.iters, args.horizon, log=print, device_update=args.device_update, lr=args.lr,
+          max_grad_norm=args.max_grad_norm, weight_decay=args.weight_decay)
 
 
 if __name__ == "__main__":

@@ -26,8 +26,21 @@ own their parameters it leaves the same bits in every parameter as the loop.
 (A net without a column receives zero gradients here, where the loop leaves
 its gradients unset and its optimizer skips it.)
 
+--device-update: --grouped-evaluate with the loss and the optimiser in the
+library as well --
+
+    sequence_segments -> evaluate_sequences_groups -> sequence_group_rows ->
+    a2c_loss_sequences -> autograd.backward -> PolicyAdam.step(rows) -> set_policy
+
+-- the mask, the groups' normalisation and the loss sums in a fixed order, one
+optimiser call for all nets (--max-grad-norm, --weight-decay: clipping of every
+group's global gradient norm and decoupled weight decay inside it), so the
+parameters after the step are the same bits in CPU mode and on the device.  The
+update reads the float64 losses once and nothing else.
+
     python madrona-bots_amd/harness/a2c_recurrent_groups.py --worlds 64 --groups 4 --iters 5 --exec-mode cpu
     python madrona-bots_amd/harness/a2c_recurrent_groups.py --worlds 65536 --groups 32 --iters 20 --grouped-evaluate
+    python madrona-bots_amd/harness/a2c_recurrent_groups.py --worlds 65536 --groups 32 --iters 20 --device-update --max-grad-norm 0.5
 """
 import argparse
 import json
@@ -40,10 +53,10 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from a2c_recurrent import make_modules, policy_net, rollout  # noqa: E402
 
 
-def window_batch(sim, win, starts_dev, horizon, actions, species, worlds):
+def window_columns(sim, win, starts_dev, actions, species, worlds):
     """The window's sequences as the learner reads them: (batch dict, action
-    [L, B], net_id [B] = group * 4 + species, keep [L, B] float32), all on the
-    device and without a host wait."""
+    [L, B], net_id [B] = group * 4 + species, group [B]), all on the device
+    and without a host wait."""
     win.sequences()
     b = win.batch(keys=("rows", "t0", "len", "end", "obs", "adv", "ret", "hidden0"))
     action = win.gather(actions)[:, :, 0]
@@ -51,6 +64,13 @@ def window_batch(sim, win, starts_dev, horizon, actions, species, worlds):
     world = win.gather(worlds)[0, :, 0].to(torch.int64)  # and its world
     group = torch.bucketize(world, starts_dev, right=True) - 1
     net_id = (group * 4 + sp.to(torch.int64)).to(torch.int32)
+    return b, action, net_id, group
+
+
+def window_batch(sim, win, starts_dev, horizon, actions, species, worlds):
+    """window_columns and keep [L, B] float32, the mask of the elements the
+    loss counts: (batch dict, action, net_id, group, keep)."""
+    b, action, net_id, group = window_columns(sim, win, starts_dev, actions, species, worlds)
     L = b["rows"].shape[0]
     k = torch.arange(L, device=sim.device, dtype=torch.int32)[:, None]
     keep = (b["rows"] >= 0) & (b["t0"][None, :] + k < horizon - 1)                    # not the bootstrap table
@@ -64,18 +84,27 @@ def per_element(logp, value, entropy, adv, ret, value_coef, entropy_coef):
 
 
 def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.95, death_reward=-1.0,
-          value_coef=0.5, entropy_coef=0.01, log=None, grouped_evaluate=False):
+          value_coef=0.5, entropy_coef=0.01, log=None, grouped_evaluate=False, device_update=False, lr=3e-4,
+          max_grad_norm=None, weight_decay=0.0):
     """`iters` updates of `horizon - 1` steps each of every group.  modules[u],
     optimizers[u]: a2c_recurrent.make_modules' four ModuleDicts and their
     optimizers for group u.  grouped_evaluate: sequence_segments, one
     evaluate_sequences_groups and one backward() in place of the per-net loop.
-    Returns the losses, [iters][groups] floats."""
+    device_update: the mask, the loss and the optimiser in the library as well
+    (device_update_step); `optimizers` is then a madrona_bots.PolicyAdam over
+    the groups' nets, or None for one with learning rate `lr`, max_grad_norm
+    and weight_decay.  A group with no kept element is left untouched then --
+    parameters, moments and step count -- where the torch paths step it with
+    zero gradients.  Returns the losses, [iters][groups] floats."""
     import madrona_bots as mb
     G = len(starts)
     sim.set_policy_groups(starts)
     nets = [[policy_net(m) for m in modules[u]] for u in range(G)]
     for u in range(G):
         sim.set_policy(nets[u], group=u)
+    if device_update:
+        adam = optimizers if isinstance(optimizers, mb.PolicyAdam) else \
+            mb.PolicyAdam(nets, lr=lr, max_grad_norm=max_grad_norm, weight_decay=weight_decay)
     starts_dev = torch.tensor(list(starts), dtype=torch.int64, device=sim.device)
     win = sim.trajectory_window(horizon, max_rows=sim.num_worlds * sim.agent_capacity, record_obs=True,
                                 record_state=True)
@@ -83,6 +112,17 @@ def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.
     try:
         for it in range(iters):
             out, actions, _, species = rollout(sim, win, horizon, gamma, lam, death_reward)
+            if device_update:
+                b, action, net_id, _ = window_columns(sim, win, starts_dev, actions, species,
+                                                      [w.to(torch.int32) for w in out["world"]])
+                loss = device_update_step(mb, nets, adam, b, action, net_id, horizon - 1, value_coef, entropy_coef)
+                for u in range(G):
+                    sim.set_policy(nets[u], group=u)
+                win.clear()
+                losses.append([float(x) for x in loss.cpu()])                        # the update's one host read
+                if log:
+                    log(json.dumps({"iter": it, "loss": losses[-1]}))
+                continue
             b, action, net_id, group, keep = window_batch(sim, win, starts_dev, horizon, actions, species,
                                                           [w.to(torch.int32) for w in out["world"]])
             # every group's kept elements, at least 1, as a float32 [G] on the device
@@ -139,6 +179,27 @@ def train(sim, starts, modules, optimizers, iters, horizon=8, gamma=0.99, lam=0.
     return losses
 
 
+def device_update_step(mb, nets, adam, b, action, net_id, last_table, value_coef, entropy_coef):
+    """One update of every group with the loss and the optimiser in the
+    library: sequence_segments, evaluate_sequences_groups, the groups' kept
+    elements (sequence_group_rows), a2c_loss_sequences -- the three upstream
+    gradients and the groups' losses -- one autograd.backward into the
+    gradient buffer `adam` owns and one PolicyAdam.step over every net.
+    Returns the losses, float64 [G] on the device; nothing here waits for the
+    host, so the whole of it can be captured into a graph."""
+    G = len(nets)
+    order, seg = mb.sequence_segments(net_id, G)
+    outs = mb.evaluate_sequences_groups(nets, b["obs"], action, b["len"], b["hidden0"], order, seg)
+    total = torch.zeros(G, dtype=torch.int64, device=net_id.device)
+    mb.sequence_group_rows(b["len"], b["t0"], b["end"], order, seg, total, last_table)
+    adam.zero_grad()
+    g = mb.a2c_loss_sequences(*outs, b["adv"], b["ret"], b["len"], b["t0"], b["end"], order, seg, total, last_table,
+                              value_coef, entropy_coef)
+    torch.autograd.backward(list(outs), list(g[:3]))
+    adam.step(total)
+    return g[3]
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--worlds", type=int, default=64)
@@ -156,7 +217,15 @@ def main():
     ap.add_argument("--grouped-evaluate", action="store_true",
                     help="one evaluate_sequences_groups and one backward() per update instead of one "
                          "evaluate_sequences per (group, species)")
+    ap.add_argument("--device-update", action="store_true",
+                    help="--grouped-evaluate with sequence_group_rows, a2c_loss_sequences and one PolicyAdam.step in "
+                         "place of torch's mask, loss and optimizers")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="with --device-update: clip every group's global gradient norm to this")
+    ap.add_argument("--weight-decay", type=float, default=0.0, help="with --device-update: decoupled weight decay")
     args = ap.parse_args()
+    if (args.max_grad_norm is not None or args.weight_decay) and not args.device_update:
+        ap.error("--max-grad-norm and --weight-decay need --device-update")
     if not 1 <= args.groups <= 64 or args.worlds < args.groups:
         ap.error("--groups must be in [1, 64] and at most --worlds")
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
@@ -166,9 +235,11 @@ def main():
     starts = [u * args.worlds // args.groups for u in range(args.groups)]
     modules = [make_modules(args.hidden[u % len(args.hidden)], sim.device, args.seed + u, args.gated)
                for u in range(args.groups)]
-    optimizers = [[torch.optim.Adam(m.parameters(), lr=args.lr) for m in four] for four in modules]
+    optimizers = None if args.device_update else \
+        [[torch.optim.Adam(m.parameters(), lr=args.lr) for m in four] for four in modules]
     train(sim, starts, modules, optimizers, args.iters, args.horizon, log=print,
-          grouped_evaluate=args.grouped_evaluate)
+          grouped_evaluate=args.grouped_evaluate, device_update=args.device_update, lr=args.lr,
+          max_grad_norm=args.max_grad_norm, weight_decay=args.weight_decay)
 
 
 if __name__ == "__main__":

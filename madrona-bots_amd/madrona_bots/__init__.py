@@ -30,7 +30,8 @@ __all__ = ["SimManager", "ScriptBotsViewer", "Tensor", "madrona", "ExportID", "E
            "unpack_learner", "rebuild_learner", "CapacityWarning", "CapacityError", "MAX_CAPACITY",
            "CAPACITY_CLASSES", "TrajectoryWindow", "RENDER_PALETTE", "RENDER_SCALES", "CLS_FLOOR", "CLS_WALL",
            "CLS_FOOD", "CLS_BODY", "CLS_MARK", "PolicyNet", "policy_activation", "ACTIVATIONS", "evaluate_groups",
-           "sequence_segments", "evaluate_sequences_groups", "policy_group_rows", "a2c_loss_groups", "PolicyAdam"]
+           "sequence_segments", "evaluate_sequences_groups", "policy_group_rows", "a2c_loss_groups", "PolicyAdam",
+           "sequence_group_rows", "a2c_loss_sequences"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmbots.so")
@@ -188,6 +189,13 @@ def _load():
                                   vp, vp, vp, vp, i32, vp],
         "mbots_policy_adam": [P(_AdamTensor), ctypes.c_uint64, vp, u32, vp, ctypes.c_float, ctypes.c_float,
                               ctypes.c_float, ctypes.c_float, i32, vp],
+        "mbots_policy_seq_group_rows": [vp, vp, vp, ctypes.c_uint64, vp, vp, u32, i32, vp, i32, vp],
+        "mbots_policy_seq_a2c_loss": [vp, vp, vp, vp, vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, u32, i32, vp,
+                                      ctypes.c_float, ctypes.c_float, vp, vp, vp, vp, i32, vp],
+        "mbots_policy_adam_clip_workspace": [P(_AdamTensor), ctypes.c_uint64, u32, P(ctypes.c_uint64)],
+        "mbots_policy_adam_clip": [P(_AdamTensor), ctypes.c_uint64, vp, u32, vp, ctypes.c_float, ctypes.c_float,
+                                   ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp,
+                                   ctypes.c_uint64, i32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -2120,6 +2128,86 @@ def a2c_loss_groups(logp, value, entropy, adv, ret, end, segments, rows, value_c
     return g[0], g[1], g[2], loss
 
 
+def _sequence_columns(length, t0, end, order, segments, rows, dev):
+    """The checked [B] columns, order and segments of the sequence loss calls:
+    (B, G, length, t0, end, order, segments), contiguous."""
+    G = segments.shape[0] if segments.dim() == 3 else 0
+    if segments.dtype != torch.int32 or segments.device != dev or tuple(segments.shape) != (G, 4, 2) or not 1 <= G <= 64:
+        raise ValueError(f"segments must be int32 [G, 4, 2] of 1..64 groups on {dev} (sequence_segments()), not "
+                         f"{segments.dtype} {list(segments.shape)} on {segments.device}")
+    B = length.numel()
+    cols = []
+    for name, t in (("length", length), ("t0", t0), ("end", end), ("order", order)):
+        if t.dtype != torch.int32 or t.device != dev or tuple(t.shape) != (B,):
+            raise ValueError(f"{name} must be int32 [{B}] on {dev}, not {t.dtype} {list(t.shape)} on {t.device}")
+        cols.append(t.detach().contiguous())
+    if rows.dtype != torch.int64 or rows.device != dev or tuple(rows.shape) != (G,) or not rows.is_contiguous():
+        raise ValueError(f"rows must be a contiguous int64 [{G}] on {dev}, not {rows.dtype} {list(rows.shape)} on "
+                         f"{rows.device}")
+    return (B, G, *cols, segments.detach().contiguous())
+
+
+def sequence_group_rows(length, t0, end, order, segments, rows, last_table=-1):
+    """rows[g] += the kept elements of the columns of group g's four segments
+    (mbots_policy_seq_group_rows).  length, t0, end: int32 [B], the "len",
+    "t0" and "end" columns of TrajectoryWindow.batch(); order int32 [B] and
+    segments int32 [G, 4, 2] from sequence_segments(); rows int64 [G] on the
+    same device, zeroed by the caller; returns rows.  Element (k, b) is kept
+    iff k < length[b], t0[b] + k < last_table (a learner passes horizon - 1,
+    the table that only bootstraps; negative: no bound) and it is not the last
+    row of a lifeline a reset ended.  On a GPU nothing is read by the host."""
+    dev = rows.device
+    B, G, length, t0, end, order, segments = _sequence_columns(length, t0, end, order, segments, rows, dev)
+    _on_device(dev, lambda d, st: _lib.mbots_policy_seq_group_rows(
+        _ptr(length), _ptr(t0), _ptr(end), B, _ptr(order), _ptr(segments), G, int(last_table), _ptr(rows), d, st))
+    return rows
+
+
+def a2c_loss_sequences(logp, value, entropy, adv, ret, length, t0, end, order, segments, rows, last_table=-1,
+                       value_coef=0.5, entropy_coef=0.01, loss=None):
+    """(g_logp, g_value, g_entropy, loss): a2c_loss_groups for the padded
+    [L, B] sequence batches (mbots_policy_seq_a2c_loss; DESIGN.md "Device
+    learner step").  logp, value, entropy: float32 [L, B], what
+    evaluate_sequences_groups() returned, read detached; adv, ret: the batch's
+    float32 [L, B]; length, t0, end, order, segments, last_table as
+    sequence_group_rows'; rows int64 [G], every group's kept elements over
+    the whole update.  A kept element of a column of group g weighs
+    1 / rows[g] in a2c_loss_groups' formulas; every other element gets +0 in
+    the three gradients and takes no part in loss, and so does all of a group
+    with rows[g] == 0.  loss: float64 [G], accumulated into (None: zeros), in
+    a fixed order, so CPU and GPU tensors give the same bits.  Then
+
+        torch.autograd.backward([logp, value, entropy], [g_logp, g_value, g_entropy])
+
+    runs evaluate_sequences_groups' backward.  Nothing waits for the host;
+    capturable."""
+    dev = logp.device
+    if logp.dim() != 2:
+        raise ValueError(f"logp must be float32 [L, B], not {list(logp.shape)}")
+    L, B = logp.shape
+    cols = []
+    for name, t in (("logp", logp), ("value", value), ("entropy", entropy), ("adv", adv), ("ret", ret)):
+        if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (L, B):
+            raise ValueError(f"{name} must be float32 [{L}, {B}] on {dev}, not {t.dtype} {list(t.shape)} on "
+                             f"{t.device}")
+        cols.append(t.detach().contiguous())
+    if length.numel() != B:
+        raise ValueError(f"length must be int32 [{B}] on {dev}, not {length.dtype} {list(length.shape)} on "
+                         f"{length.device}")
+    _, G, length, t0, end, order, segments = _sequence_columns(length, t0, end, order, segments, rows, dev)
+    if loss is None:
+        loss = torch.zeros(G, dtype=torch.float64, device=dev)
+    elif loss.dtype != torch.float64 or loss.device != dev or tuple(loss.shape) != (G,) or not loss.is_contiguous():
+        raise ValueError(f"loss must be a contiguous float64 [{G}] on {dev}, not {loss.dtype} {list(loss.shape)} on "
+                         f"{loss.device}")
+    g = [torch.empty((L, B), dtype=torch.float32, device=dev) for _ in range(3)]
+    _on_device(dev, lambda d, st: _lib.mbots_policy_seq_a2c_loss(
+        _ptr(cols[0]), _ptr(cols[1]), _ptr(cols[2]), _ptr(cols[3]), _ptr(cols[4]), _ptr(length), _ptr(t0), _ptr(end),
+        L, B, _ptr(order), _ptr(segments), G, int(last_table), _ptr(rows), value_coef, entropy_coef, _ptr(g[0]),
+        _ptr(g[1]), _ptr(g[2]), _ptr(loss), d, st))
+    return g[0], g[1], g[2], loss
+
+
 class PolicyAdam:
     """Adam over the parameters of every net of every policy group in one call
     (mbots_policy_adam; DESIGN.md "Device learner step"): torch.optim.Adam's
@@ -2137,9 +2225,18 @@ class PolicyAdam:
     every .grad to a slice of one buffer the optimiser owns and zeroes that
     buffer with one stream-ordered fill, so the gradients keep their
     addresses from update to update and a captured update replays.  Neither
-    waits for the host."""
+    waits for the host.
 
-    def __init__(self, nets, lr=3e-4, betas=(0.9, 0.999), eps=1e-8):
+    max_grad_norm (None: off) clips every group's gradient to that global
+    norm by torch.nn.utils.clip_grad_norm_'s rule, and weight_decay is
+    torch.optim.AdamW's decoupled p -= lr * weight_decay * p, both inside the
+    one call (mbots_policy_adam_clip) with the norm summed in a fixed order.
+    With either, grad_norm (float32 [G] on the parameters' device) holds the
+    last step's norms of all groups, idle ones included, and a group whose
+    norm is inf or NaN is left untouched -- parameters, moments and step
+    count -- as an idle group is.  Without both, step() is the plain call."""
+
+    def __init__(self, nets, lr=3e-4, betas=(0.9, 0.999), eps=1e-8, max_grad_norm=None, weight_decay=0.0):
         if isinstance(nets, PolicyNet):
             nets = [[nets] * 4]
         nets = list(nets)
@@ -2150,6 +2247,12 @@ class PolicyAdam:
         if not 1 <= G <= 64:
             raise ValueError(f"nets must hold 1..64 groups, not {G}")
         self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.weight_decay = float(weight_decay)
+        if self.max_grad_norm is not None and not self.max_grad_norm > 0.0:
+            raise ValueError(f"max_grad_norm must be a positive number or None, not {max_grad_norm}")
+        if not 0.0 <= self.weight_decay < float("inf"):
+            raise ValueError(f"weight_decay must be a finite number >= 0, not {weight_decay}")
         self.params, self.names, self.param_group = [], [], []
         seen = {}                                     # id(tensor) -> (group, name)
         for g, four in enumerate(groups):
@@ -2202,6 +2305,16 @@ class PolicyAdam:
             d = self._desc[i]
             d.param, d.group = p.data_ptr(), g
             d.m, d.v = self._m.data_ptr() + 4 * o, self._v.data_ptr() + 4 * o
+        # the clipped call's workspace and norms, sized for every parameter with a gradient
+        self._clip = self.max_grad_norm is not None or self.weight_decay != 0.0
+        self.grad_norm = torch.zeros(G, dtype=torch.float32, device=dev)
+        self._ws = None
+        if self._clip:
+            for d, p in zip(self._desc, self.params):
+                d.n = p.numel()
+            need = ctypes.c_uint64()
+            _check(_lib.mbots_policy_adam_clip_workspace(self._desc, len(self.params), G, ctypes.byref(need)))
+            self._ws = torch.zeros((need.value + 7) // 8, dtype=torch.float64, device=dev)
 
     def zero_grad(self):
         for p, view in zip(self.params, self._views):
@@ -2227,6 +2340,13 @@ class PolicyAdam:
                                  f"shape on {dev}, not {g.dtype} {list(g.shape)} on {g.device}")
             desc[i].param, desc[i].grad, desc[i].n = p.data_ptr(), g.data_ptr(), p.numel()
         with torch.no_grad():
+            if self._clip:
+                max_norm = -1.0 if self.max_grad_norm is None else self.max_grad_norm
+                _on_device(dev, lambda d, st: _lib.mbots_policy_adam_clip(
+                    desc, len(self.params), _ptr(self._state), G, _ptr(rows), self.lr, self.betas[0], self.betas[1],
+                    self.eps, self.weight_decay, max_norm, _ptr(self.grad_norm), _ptr(self._ws),
+                    self._ws.numel() * 8, d, st))
+                return
             _on_device(dev, lambda d, st: _lib.mbots_policy_adam(
                 desc, len(self.params), _ptr(self._state), G, _ptr(rows), self.lr, self.betas[0], self.betas[1],
                 self.eps, d, st))

@@ -1159,6 +1159,107 @@ int mbots_policy_adam_clip(const struct mbots_policy_adam_tensor *tensors, uint6
                            float beta1, float beta2, float eps, float weight_decay, float max_norm, float *grad_norm,
                            void *workspace, uint64_t workspace_bytes, int32_t device, void *stream);
 
+/* PPO on the device: the clipped surrogate and clipped value loss of recorded
+ * rows, advantage normalisation and the KL early stop (DESIGN.md "PPO on the
+ * device" is the specification).  Conventions and rounding as above: handle-
+ * free, `device` >= 0 device memory on `stream`, -1 host memory, the same bits
+ * from both whatever the grid; nothing allocates or waits for the host; the
+ * calls can be captured.  segments, rows, end and (for the sequence calls) len,
+ * t0, order, last_table and the kept elements are mbots_policy_a2c_loss's and
+ * mbots_policy_seq_a2c_loss's, with the same host refusals and device clamps.
+ *
+ * Order of every sum below ("the two-level order"): element i of a (group,
+ * species) segment, counted from lo, belongs to chunk i / C and to f64
+ * accumulator i mod 256 of that chunk, in ascending i; a chunk's 256
+ * accumulators are added in ascending index to +0; a segment's chunks in
+ * ascending index to +0; the four species' sums in ascending species to +0;
+ * that sum is added to the output slot.  For the row calls an element is a row
+ * and C = 4096; for the sequence calls an element is a position p - lo of the
+ * segment in `order`, C = 512, and the kept steps of column order[p] are added
+ * in ascending k.
+ *
+ * mbots_policy_ppo_workspace: the bytes of `workspace` for a call over n rows
+ * (or the L * B elements of a sequence batch) and `groups` groups; 8-byte
+ * aligned memory of the call's kind whose content is scratch (the chunks'
+ * partial sums).  A call refuses a smaller one.
+ *
+ * mbots_policy_adv_moments / mbots_policy_seq_adv_moments: moments (f64
+ * [groups][3]) += {1, adv, adv * adv} in exact f64 over the group's kept rows --
+ * those with end[r] != MBOTS_TRAJ_END_RESET (end NULL: all); the kept elements
+ * of the sequence batch -- in the two-level order.  The caller zeroes moments
+ * and passes every table of the update.
+ *
+ * mbots_policy_ppo_loss: logp, value, entropy (the evaluate's outputs),
+ * old_logp, old_value (what act() returned when the rows were recorded), adv,
+ * ret f32 [n].  lo_c = 1 - clip and hi_c = 1 + clip are rounded once on the
+ * host; min(a, b) is b < a ? b : a and max(a, b) is b > a ? b : a, so a NaN in
+ * the first argument stays.  With moments (f64 [groups][3], NULL: A = adv)
+ *     n = moments[g][0], S1 = moments[g][1], S2 = moments[g][2]   (f64)
+ *     mean = (float)(S1 / n)
+ *     var  = (S2 - S1 * (S1 / n)) / (n - 1), 0 unless var > 0
+ *     inv  = 1.0f / ((float)sqrt(var) + 1e-8f)
+ *     and mean = 0, inv = 1 unless n >= 2
+ * For row r of a segment of group g, w as mbots_policy_a2c_loss's:
+ *     A      = (adv - mean) * inv
+ *     lr     = logp - old_logp;  ratio = exp(lr)   (the device actor's exp)
+ *     s1     = ratio * A
+ *     rc     = min(max(ratio, lo_c), hi_c);  s2 = rc * A
+ *     pol    = -min(s1, s2)
+ *     g_logp = (s2 < s1 ? 0 : -s1) * w             a tie takes the unclipped branch
+ *     d      = value - ret;  v1 = d * d
+ *   value_clip > 0 and old_value not NULL:
+ *     dv = value - old_value;  dc = min(max(dv, -value_clip), value_clip)
+ *     d2 = (old_value + dc) - ret;  v2 = d2 * d2
+ *     vl = v2 > v1 ? v2 : v1
+ *     g_value = (value_coef * (v2 > v1 ? (dc == dv ? 2 * d2 : 0) : 2 * d)) * w
+ *   else:
+ *     vl = v1;  g_value = ((2 * value_coef) * d) * w
+ *     g_entropy = (-entropy_coef) * w
+ *     per_row   = ((pol + value_coef * vl) - entropy_coef * entropy) * w
+ *     kl        = ((ratio - 1) - lr) * w
+ *     clipped   = (rc != ratio ? 1 : 0) * w
+ * Rows in no segment receive +0 in g_logp, g_value, g_entropy.  stats (f64
+ * [groups][6]) += the sums, in the two-level order, of the f32 values
+ *     [0] per_row  [1] pol * w  [2] vl * w  [3] entropy * w  [4] kl  [5] clipped
+ * Any of the four outputs may be NULL.  Non-finite inputs propagate into the
+ * sums; a NaN KL closes the gate below, and mbots_policy_adam_clip leaves a
+ * group whose gradient norm is not finite untouched.
+ * mbots_policy_seq_ppo_loss: the same for f32 [L][B] batches at address k * B +
+ * b with w = 1.0f / (float)rows[g] for every kept element; a group with
+ * rows[g] == 0 is passed over, stats included.
+ * Refused: clip outside (0, 1), value_coef < 0, groups outside 1 ..
+ * MBOTS_POLICY_MAX_GROUPS, a workspace smaller than needed.
+ *
+ * mbots_policy_ppo_gate: gate[g] = (gate[g] != 0 and rows[g] != 0 and
+ * stats[g][4] <= target_kl) ? rows[g] : 0, for int64 [groups] gate and rows.
+ * A NaN KL closes the gate; a closed gate stays closed until the caller sets
+ * it again.  Passed as `rows` to mbots_policy_adam or mbots_policy_adam_clip,
+ * the gate leaves a stopped group untouched as it leaves an idle one, so the
+ * KL early stop of a multi-epoch update needs no read by the host. */
+int mbots_policy_ppo_workspace(uint64_t n, uint32_t groups, uint64_t *bytes);
+int mbots_policy_adv_moments(const float *adv, const int32_t *end, uint64_t n, const int32_t *segments,
+                             uint32_t groups, double *moments, void *workspace, uint64_t workspace_bytes,
+                             int32_t device, void *stream);
+int mbots_policy_ppo_loss(const float *logp, const float *value, const float *entropy, const float *old_logp,
+                          const float *old_value, const float *adv, const float *ret, const int32_t *end, uint64_t n,
+                          const int32_t *segments, uint32_t groups, const int64_t *rows, const double *moments,
+                          float clip, float value_clip, float value_coef, float entropy_coef, float *g_logp,
+                          float *g_value, float *g_entropy, double *stats, void *workspace, uint64_t workspace_bytes,
+                          int32_t device, void *stream);
+int mbots_policy_seq_adv_moments(const float *adv, const int32_t *len, const int32_t *t0, const int32_t *end,
+                                 uint32_t L, uint64_t B, const int32_t *order, const int32_t *segments,
+                                 uint32_t groups, int32_t last_table, double *moments, void *workspace,
+                                 uint64_t workspace_bytes, int32_t device, void *stream);
+int mbots_policy_seq_ppo_loss(const float *logp, const float *value, const float *entropy, const float *old_logp,
+                              const float *old_value, const float *adv, const float *ret, const int32_t *len,
+                              const int32_t *t0, const int32_t *end, uint32_t L, uint64_t B, const int32_t *order,
+                              const int32_t *segments, uint32_t groups, int32_t last_table, const int64_t *rows,
+                              const double *moments, float clip, float value_clip, float value_coef,
+                              float entropy_coef, float *g_logp, float *g_value, float *g_entropy, double *stats,
+                              void *workspace, uint64_t workspace_bytes, int32_t device, void *stream);
+int mbots_policy_ppo_gate(const double *stats, const int64_t *rows, uint32_t groups, double target_kl, int64_t *gate,
+                          int32_t device, void *stream);
+
 /* Stream ordering: every call that takes a stream enqueues on it after all
  * work this manager enqueued on the stream of its previous call (an event
  * hop when the two differ; not across a graph capture's boundary).  That

@@ -367,5 +367,15 @@ void policy_adam_clip_counts(const AdamTensor *tensors, uint64_t count, uint64_t
 hipError_t launch_policy_adam_clip(const AdamTensor *tensors, uint64_t count, AdamState *state, uint32_t groups,
                                    const int64_t *rows, const AdamCoef &C, const AdamClipCoef &K, float *grad_norm,
                                    void *workspace, hipStream_t st);
+// PPO on the device (mbots_policy.hpp): one block per (group, species, chunk)
+// leaves the chunk's partials in io.part, a one-block-per-group launch folds
+// them into io.out in the fixed order; the loss follows a fill of the three
+// gradients with +0.  The gate: one block, thread per group
+hipError_t launch_policy_adv_moments(const PolPpoIO &io, uint32_t groups, hipStream_t st);
+hipError_t launch_policy_ppo_loss(const PolPpoIO &io, uint32_t groups, hipStream_t st);
+hipError_t launch_policy_seq_adv_moments(const PolSeqPpoIO &io, uint32_t groups, hipStream_t st);
+hipError_t launch_policy_seq_ppo_loss(const PolSeqPpoIO &io, uint32_t groups, hipStream_t st);
+hipError_t launch_policy_ppo_gate(const double *stats, const int64_t *rows, double target_kl, int64_t *gate,
+                                  uint32_t groups, hipStream_t st);
 
 }  // namespace mbots

@@ -4365,4 +4365,245 @@ int mbots_policy_adam_clip(const struct mbots_policy_adam_tensor *tensors, uint6
     return MBOTS_OK;
 }
 
+// ---- PPO on the device (include/mbots.h "PPO on the device") ----
+namespace {
+int ppo_groups_check(uint32_t groups)
+{
+    if (groups < 1u || groups > MBOTS_POLICY_MAX_GROUPS)
+        return fail(MBOTS_E_INVALID, "groups must be 1.." + std::to_string(MBOTS_POLICY_MAX_GROUPS));
+    return MBOTS_OK;
+}
+
+int ppo_workspace_check(const void *workspace, uint64_t workspace_bytes, uint64_t need)
+{
+    if (need && (!workspace || ((uintptr_t)workspace & 7u) || workspace_bytes < need))
+        return fail(MBOTS_E_INVALID, "8-byte aligned workspace of " + std::to_string(workspace_bytes) + " bytes, " +
+                                         std::to_string(need) + " needed (mbots_policy_ppo_workspace)");
+    return MBOTS_OK;
+}
+
+int ppo_coef(float clip, float value_clip, const float *old_value, float value_coef, float entropy_coef,
+             mbots::PpoCoef &C)
+{
+    if (!(clip > 0.0f && clip < 1.0f)) return fail(MBOTS_E_INVALID, "clip must lie in (0, 1)");
+    if (!(value_coef >= 0.0f)) return fail(MBOTS_E_INVALID, "value_coef must not be negative");
+    C = mbots::PpoCoef{1.0f - clip, 1.0f + clip, value_clip, value_coef, entropy_coef,
+                       value_clip > 0.0f && old_value ? 1u : 0u};
+    return MBOTS_OK;
+}
+
+// The two-level order on the host: out[0 .. kSlots) += group g's sums, elem(s,
+// position, acc) adding an element's shares to its accumulator.
+extern "C++" template <uint32_t kSlots, class Elem>
+void ppo_host_sum(const int32_t *segments, uint32_t g, uint32_t chunk, double *out, Elem &&elem)
+{
+    using namespace mbots;
+    double group[kSlots] = {};
+    std::vector<double> acc((size_t)kLossAcc * kSlots);
+    for (uint32_t s = 0; s < 4u; ++s) {
+        const uint64_t lo = (uint64_t)segments[2u * (4u * g + s)];
+        const uint64_t len = (uint64_t)segments[2u * (4u * g + s) + 1u] - lo;
+        double seg[kSlots] = {};
+        for (uint64_t first = 0; first < len; first += chunk) {
+            std::fill(acc.begin(), acc.end(), 0.0);
+            const uint64_t stop = std::min<uint64_t>(len, first + chunk);
+            for (uint64_t i = first; i < stop; ++i) elem(lo + i, &acc[(i % kLossAcc) * kSlots]);
+            for (uint32_t k = 0; k < kSlots; ++k) {
+                double q = 0.0;
+                for (uint32_t j = 0; j < kLossAcc; ++j) q += acc[(size_t)j * kSlots + k];
+                seg[k] += q;
+            }
+        }
+        for (uint32_t k = 0; k < kSlots; ++k) group[k] += seg[k];
+    }
+    for (uint32_t k = 0; k < kSlots; ++k) out[k] += group[k];
+}
+}  // namespace
+
+int mbots_policy_ppo_workspace(uint64_t n, uint32_t groups, uint64_t *bytes)
+{
+    using namespace mbots;
+    if (!bytes) return fail(MBOTS_E_INVALID, "null argument");
+    if (int rc = ppo_groups_check(groups)) return rc;
+    *bytes = pol_ppo_bytes(std::max(pol_ppo_chunks(n, kPpoChunk), pol_ppo_chunks(n, kPpoSeqChunk)), groups);
+    return MBOTS_OK;
+}
+
+int mbots_policy_adv_moments(const float *adv, const int32_t *end, uint64_t n, const int32_t *segments,
+                             uint32_t groups, double *moments, void *workspace, uint64_t workspace_bytes,
+                             int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (int rc = ppo_groups_check(groups)) return rc;
+    if (!segments || !moments || (n && !adv)) return fail(MBOTS_E_INVALID, "null argument");
+    if (n > (uint64_t)INT32_MAX) return fail(MBOTS_E_INVALID, "more rows than a segment can name");
+    const uint64_t chunks = pol_ppo_chunks(n, kPpoChunk);
+    if (int rc = ppo_workspace_check(workspace, workspace_bytes, pol_ppo_bytes(chunks, groups))) return rc;
+    if (device >= 0) {
+        PolPpoIO io{};
+        io.adv = adv, io.end = end, io.segments = segments, io.out = moments;
+        io.part = static_cast<double *>(workspace), io.n = n, io.chunks = (uint32_t)chunks;
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_adv_moments(io, groups, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    if (int rc = segments_check_host(segments, groups, n, "rows")) return rc;
+    for (uint32_t g = 0; g < groups; ++g)
+        ppo_host_sum<kPpoMoments>(segments, g, kPpoChunk, moments + (size_t)kPpoMoments * g,
+                                  [&](uint64_t r, double *acc) {
+                                      if (!(end && end[r] == kTrajEndReset)) pol_ppo_moment_add(acc, adv[r]);
+                                  });
+    return MBOTS_OK;
+}
+
+int mbots_policy_ppo_loss(const float *logp, const float *value, const float *entropy, const float *old_logp,
+                          const float *old_value, const float *adv, const float *ret, const int32_t *end, uint64_t n,
+                          const int32_t *segments, uint32_t groups, const int64_t *rows, const double *moments,
+                          float clip, float value_clip, float value_coef, float entropy_coef, float *g_logp,
+                          float *g_value, float *g_entropy, double *stats, void *workspace, uint64_t workspace_bytes,
+                          int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (int rc = ppo_groups_check(groups)) return rc;
+    if (!segments || !rows) return fail(MBOTS_E_INVALID, "null segments or rows");
+    if (n && (!logp || !value || !entropy || !old_logp || !adv || !ret)) return fail(MBOTS_E_INVALID, "null argument");
+    if (n > (uint64_t)INT32_MAX) return fail(MBOTS_E_INVALID, "more rows than a segment can name");
+    PpoCoef C;
+    if (int rc = ppo_coef(clip, value_clip, old_value, value_coef, entropy_coef, C)) return rc;
+    const uint64_t chunks = pol_ppo_chunks(n, kPpoChunk);
+    if (int rc = ppo_workspace_check(workspace, workspace_bytes, pol_ppo_bytes(chunks, groups))) return rc;
+    if (device >= 0) {
+        const PolPpoIO io{logp, value, entropy, old_logp, old_value, adv, ret, end, segments, rows, moments, g_logp,
+                          g_value, g_entropy, stats, static_cast<double *>(workspace), n, (uint32_t)chunks, C};
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_ppo_loss(io, groups, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    if (int rc = segments_check_host(segments, groups, n, "rows")) return rc;
+    for (float *o : {g_logp, g_value, g_entropy})
+        if (o) std::fill(o, o + n, 0.0f);
+    for (uint32_t g = 0; g < groups; ++g) {
+        const float scale = pol_loss_scale(rows[g]);
+        const PpoNorm N = pol_ppo_norm(moments ? moments + (size_t)kPpoMoments * g : nullptr);
+        double sums[kPpoStats] = {};
+        ppo_host_sum<kPpoStats>(segments, g, kPpoChunk, sums, [&](uint64_t r, double *acc) {
+            const float w = (end && end[r] == kTrajEndReset ? 0.0f : 1.0f) * scale;
+            float gl, gv, ge, st[kPpoStats];
+            pol_ppo_row(logp[r], value[r], entropy[r], old_logp[r], C.vclip ? old_value[r] : 0.0f, adv[r], ret[r], w,
+                        moments != nullptr, N, C, gl, gv, ge, st);
+            if (g_logp) g_logp[r] = gl;
+            if (g_value) g_value[r] = gv;
+            if (g_entropy) g_entropy[r] = ge;
+            for (uint32_t k = 0; k < kPpoStats; ++k) acc[k] += (double)st[k];
+        });
+        if (stats)
+            for (uint32_t k = 0; k < kPpoStats; ++k) stats[(size_t)kPpoStats * g + k] += sums[k];
+    }
+    return MBOTS_OK;
+}
+
+int mbots_policy_seq_adv_moments(const float *adv, const int32_t *len, const int32_t *t0, const int32_t *end,
+                                 uint32_t L, uint64_t B, const int32_t *order, const int32_t *segments,
+                                 uint32_t groups, int32_t last_table, double *moments, void *workspace,
+                                 uint64_t workspace_bytes, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (!moments) return fail(MBOTS_E_INVALID, "null argument");
+    const int64_t none = 0;
+    if (int rc = seq_loss_args(groups, B, len, t0, end, order, segments, &none)) return rc;
+    if (L && B && !adv) return fail(MBOTS_E_INVALID, "null argument");
+    if (L > (uint32_t)INT32_MAX) return fail(MBOTS_E_INVALID, "L is no int32 length");
+    const uint64_t chunks = pol_ppo_chunks(B, kPpoSeqChunk);
+    if (int rc = ppo_workspace_check(workspace, workspace_bytes, pol_ppo_bytes(chunks, groups))) return rc;
+    if (device >= 0) {
+        PolSeqPpoIO io{};
+        io.adv = adv, io.len = len, io.t0 = t0, io.end = end, io.order = order, io.segments = segments;
+        io.out = moments, io.part = static_cast<double *>(workspace), io.L = L, io.B = B;
+        io.last_table = last_table, io.chunks = (uint32_t)chunks;
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_seq_adv_moments(io, groups, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    if (int rc = seq_loss_check_host(order, segments, groups, len, L ? L : 1u, B)) return rc;
+    if (L == 0) return MBOTS_OK;
+    for (uint32_t g = 0; g < groups; ++g)
+        ppo_host_sum<kPpoMoments>(segments, g, kPpoSeqChunk, moments + (size_t)kPpoMoments * g,
+                                  [&](uint64_t p, double *acc) {
+                                      const int32_t b = order[p];
+                                      const int32_t nk = pol_seq_kept(std::min(len[b], (int32_t)L), t0[b], end[b], last_table);
+                                      for (int32_t k = 0; k < nk; ++k) pol_ppo_moment_add(acc, adv[(uint64_t)k * B + (uint32_t)b]);
+                                  });
+    return MBOTS_OK;
+}
+
+int mbots_policy_seq_ppo_loss(const float *logp, const float *value, const float *entropy, const float *old_logp,
+                              const float *old_value, const float *adv, const float *ret, const int32_t *len,
+                              const int32_t *t0, const int32_t *end, uint32_t L, uint64_t B, const int32_t *order,
+                              const int32_t *segments, uint32_t groups, int32_t last_table, const int64_t *rows,
+                              const double *moments, float clip, float value_clip, float value_coef,
+                              float entropy_coef, float *g_logp, float *g_value, float *g_entropy, double *stats,
+                              void *workspace, uint64_t workspace_bytes, int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (int rc = seq_loss_args(groups, B, len, t0, end, order, segments, rows)) return rc;
+    if (L && B && (!logp || !value || !entropy || !old_logp || !adv || !ret))
+        return fail(MBOTS_E_INVALID, "null argument");
+    if (L > (uint32_t)INT32_MAX) return fail(MBOTS_E_INVALID, "L is no int32 length");
+    PpoCoef C;
+    if (int rc = ppo_coef(clip, value_clip, old_value, value_coef, entropy_coef, C)) return rc;
+    const uint64_t chunks = pol_ppo_chunks(B, kPpoSeqChunk);
+    if (int rc = ppo_workspace_check(workspace, workspace_bytes, pol_ppo_bytes(chunks, groups))) return rc;
+    if (device >= 0) {
+        const PolSeqPpoIO io{logp,  value,   entropy, old_logp, old_value, adv,     ret,       len,
+                             t0,    end,     order,   segments, rows,      moments, g_logp,    g_value,
+                             g_entropy, stats, static_cast<double *>(workspace), L, B, last_table, (uint32_t)chunks, C};
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_seq_ppo_loss(io, groups, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    if (int rc = seq_loss_check_host(order, segments, groups, len, L ? L : 1u, B)) return rc;
+    for (float *o : {g_logp, g_value, g_entropy})
+        if (o) std::fill(o, o + (uint64_t)L * B, 0.0f);
+    if (L == 0) return MBOTS_OK;
+    for (uint32_t g = 0; g < groups; ++g) {
+        if (rows[g] == 0) continue;   // the +0 stay, the statistics are not touched
+        const float w = pol_loss_scale(rows[g]);
+        const PpoNorm N = pol_ppo_norm(moments ? moments + (size_t)kPpoMoments * g : nullptr);
+        double sums[kPpoStats] = {};
+        ppo_host_sum<kPpoStats>(segments, g, kPpoSeqChunk, sums, [&](uint64_t p, double *acc) {
+            const int32_t b = order[p];
+            const int32_t nk = pol_seq_kept(std::min(len[b], (int32_t)L), t0[b], end[b], last_table);
+            for (int32_t k = 0; k < nk; ++k) {
+                const uint64_t r = (uint64_t)k * B + (uint32_t)b;
+                float gl, gv, ge, st[kPpoStats];
+                pol_ppo_row(logp[r], value[r], entropy[r], old_logp[r], C.vclip ? old_value[r] : 0.0f, adv[r], ret[r],
+                            w, moments != nullptr, N, C, gl, gv, ge, st);
+                if (g_logp) g_logp[r] = gl;
+                if (g_value) g_value[r] = gv;
+                if (g_entropy) g_entropy[r] = ge;
+                for (uint32_t q = 0; q < kPpoStats; ++q) acc[q] += (double)st[q];
+            }
+        });
+        if (stats)
+            for (uint32_t k = 0; k < kPpoStats; ++k) stats[(size_t)kPpoStats * g + k] += sums[k];
+    }
+    return MBOTS_OK;
+}
+
+int mbots_policy_ppo_gate(const double *stats, const int64_t *rows, uint32_t groups, double target_kl, int64_t *gate,
+                          int32_t device, void *stream)
+{
+    using namespace mbots;
+    if (int rc = ppo_groups_check(groups)) return rc;
+    if (!stats || !rows || !gate) return fail(MBOTS_E_INVALID, "null argument");
+    if (device >= 0) {
+        HIP_TRY(hipSetDevice(device));
+        HIP_TRY(launch_policy_ppo_gate(stats, rows, target_kl, gate, groups, as_stream(stream)));
+        return MBOTS_OK;
+    }
+    for (uint32_t g = 0; g < groups; ++g)
+        gate[g] = pol_ppo_gate(gate[g], rows[g], stats[(size_t)kPpoStats * g + 4u], target_kl);
+    return MBOTS_OK;
+}
+
 }  // extern "C"

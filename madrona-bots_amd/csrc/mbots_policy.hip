@@ -2388,4 +2388,299 @@ hipError_t launch_policy_adam_clip(const AdamTensor *tensors, uint64_t count, Ad
     return hipGetLastError();
 }
 
+// ---- PPO on the device (mbots_policy.hpp "PPO on the device") ----
+// Block (c, s, g) is chunk c of species s of group g, its 256 threads the
+// chunk's accumulators: thread a takes the elements a, a + 256, ... of the
+// chunk in ascending order.  A block whose chunk lies past the segment's end
+// exits at once, so the grid is sized from n and the group count alone and the
+// order of the sums -- accumulators, chunks, species, each ascending -- is a
+// property of the indices.
+constexpr uint32_t kPpoFlight = 4;
+
+// the block's chunk of segment (g, s): first element and element count; false: past the end
+__device__ __forceinline__ bool ppo_chunk(const int32_t *segments, uint64_t n, uint32_t chunk, uint32_t &lo,
+                                          uint32_t &cnt)
+{
+    uint32_t len;
+    pol_segment(segments, 4u * blockIdx.z + blockIdx.y, n, lo, len);
+    const uint64_t first = (uint64_t)blockIdx.x * chunk;
+    if (first >= len) return false;
+    lo = uniform(lo + (uint32_t)first);
+    cnt = uniform(min(chunk, len - (uint32_t)first));
+    return true;
+}
+
+// the 256 accumulators of kSlots sums meet in LDS; thread k < kSlots adds slot
+// k's in ascending index and leaves the chunk's partial
+template <uint32_t kSlots>
+__device__ __forceinline__ void ppo_chunk_fold(double (*s_acc)[kLossAcc], const double *acc, double *part,
+                                               uint32_t chunks)
+{
+    const uint32_t a = threadIdx.x;
+#pragma unroll
+    for (uint32_t k = 0; k < kSlots; ++k) s_acc[k][a] = acc[k];
+    __syncthreads();
+    if (a < kSlots) {
+        double q = 0.0;
+        for (uint32_t j = 0; j < kLossAcc; ++j) q += s_acc[a][j];
+        part[(((size_t)(4u * blockIdx.z + blockIdx.y)) * chunks + blockIdx.x) * kSlots + a] = q;
+    }
+}
+
+__global__ __launch_bounds__(256) void policy_adv_moments_kernel(PolPpoIO A)
+{
+    __shared__ double s_acc[kPpoMoments][kLossAcc];
+    uint32_t lo, cnt;
+    if (!ppo_chunk(A.segments, A.n, kPpoChunk, lo, cnt)) return;
+    const float *__restrict__ adv = A.adv;
+    const int32_t *__restrict__ end = A.end;
+    double acc[kPpoMoments] = {0.0, 0.0, 0.0};
+    for (uint32_t i0 = threadIdx.x; i0 < cnt; i0 += kPpoFlight * kLossAcc) {
+        float x[kPpoFlight];
+        int32_t e[kPpoFlight];
+#pragma unroll
+        for (uint32_t k = 0; k < kPpoFlight; ++k) {
+            const uint32_t i = i0 + k * kLossAcc;
+            if (i < cnt) {
+                const uint64_t r = (uint64_t)lo + i;
+                x[k] = adv[r];
+                e[k] = end ? end[r] : 0;
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kPpoFlight; ++k)
+            if (i0 + k * kLossAcc < cnt && e[k] != kTrajEndReset) pol_ppo_moment_add(acc, x[k]);
+    }
+    ppo_chunk_fold<kPpoMoments>(s_acc, acc, A.part, A.chunks);
+}
+
+__global__ __launch_bounds__(256) void policy_ppo_loss_kernel(PolPpoIO A)
+{
+    __shared__ double s_acc[kPpoStats][kLossAcc];
+    uint32_t lo, cnt;
+    if (!ppo_chunk(A.segments, A.n, kPpoChunk, lo, cnt)) return;
+    const uint32_t g = blockIdx.z;
+    const float scale = pol_loss_scale(A.rows[g]);
+    const bool normalise = A.moments != nullptr;
+    const PpoNorm N = pol_ppo_norm(normalise ? A.moments + (size_t)kPpoMoments * g : nullptr);
+    const float *__restrict__ logp = A.logp, *__restrict__ value = A.value, *__restrict__ entropy = A.entropy;
+    const float *__restrict__ old_logp = A.old_logp, *__restrict__ old_value = A.old_value;
+    const float *__restrict__ adv = A.adv, *__restrict__ ret = A.ret;
+    const int32_t *__restrict__ end = A.end;
+    double acc[kPpoStats] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t i0 = threadIdx.x; i0 < cnt; i0 += kPpoFlight * kLossAcc) {
+        float x[kPpoFlight][7];
+        int32_t e[kPpoFlight];
+#pragma unroll
+        for (uint32_t k = 0; k < kPpoFlight; ++k) {
+            const uint32_t i = i0 + k * kLossAcc;
+            if (i < cnt) {
+                const uint64_t r = (uint64_t)lo + i;
+                x[k][0] = logp[r], x[k][1] = value[r], x[k][2] = entropy[r], x[k][3] = old_logp[r];
+                x[k][4] = A.C.vclip ? old_value[r] : 0.0f;
+                x[k][5] = adv[r], x[k][6] = ret[r];
+                e[k] = end ? end[r] : 0;
+            }
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < kPpoFlight; ++k) {
+            const uint32_t i = i0 + k * kLossAcc;
+            if (i < cnt) {
+                const uint64_t r = (uint64_t)lo + i;
+                const float w = (e[k] == kTrajEndReset ? 0.0f : 1.0f) * scale;
+                float gl, gv, ge, st[kPpoStats];
+                pol_ppo_row(x[k][0], x[k][1], x[k][2], x[k][3], x[k][4], x[k][5], x[k][6], w, normalise, N, A.C, gl, gv,
+                            ge, st);
+                if (A.g_logp) A.g_logp[r] = gl;
+                if (A.g_value) A.g_value[r] = gv;
+                if (A.g_entropy) A.g_entropy[r] = ge;
+#pragma unroll
+                for (uint32_t j = 0; j < kPpoStats; ++j) acc[j] += (double)st[j];
+            }
+        }
+    }
+    if (A.out == nullptr) return;
+    ppo_chunk_fold<kPpoStats>(s_acc, acc, A.part, A.chunks);
+}
+
+// Block g, thread (s, k) of its first 4 * slots: slot k of segment (g, s)'s
+// chunk partials in ascending chunk; then thread k: the four species ascending,
+// and out[g][k] += that.  skip (may be null): a group with skip[g] == 0 left
+// no partials and is passed over.
+__global__ __launch_bounds__(64) void policy_ppo_fold_kernel(const int32_t *segments, uint64_t n, uint32_t chunk,
+                                                             uint32_t chunks, uint32_t slots, const double *part,
+                                                             const int64_t *skip, double *out)
+{
+    __shared__ double s_sum[4][kPpoStats];
+    const uint32_t g = blockIdx.x, t = threadIdx.x;
+    if (skip && skip[g] == 0) return;
+    if (t < 4u * slots) {
+        const uint32_t s = t / slots, k = t - s * slots;
+        uint32_t lo, len;
+        pol_segment(segments, 4u * g + s, n, lo, len);
+        const uint32_t nch = (uint32_t)(((uint64_t)len + chunk - 1u) / chunk);
+        const double *p = part + ((size_t)(4u * g + s) * chunks) * slots + k;
+        double q = 0.0;
+        for (uint32_t c = 0; c < nch; ++c) q += p[(size_t)c * slots];
+        s_sum[s][k] = q;
+    }
+    __syncthreads();
+    if (t < slots) {
+        double q = 0.0;
+        for (uint32_t s = 0; s < 4u; ++s) q += s_sum[s][t];
+        out[(size_t)g * slots + t] += q;
+    }
+}
+static_assert(4u * kPpoStats <= 64u, "policy_ppo_fold_kernel: one thread per (species, slot)");
+
+// column col's kept elements, its length read as at most L: 0 where the entry
+// names no column
+__device__ __forceinline__ int32_t ppo_seq_kept(const PolSeqPpoIO &A, int32_t col)
+{
+    if ((uint64_t)(uint32_t)col >= A.B) return 0;
+    return pol_seq_kept(min(A.len[col], (int32_t)A.L), A.t0[col], A.end[col], A.last_table);
+}
+
+// the sequence twins: an element is a column position of the segment, its kept
+// steps added in ascending k
+__global__ __launch_bounds__(256) void policy_seq_adv_moments_kernel(PolSeqPpoIO A)
+{
+    __shared__ double s_acc[kPpoMoments][kLossAcc];
+    uint32_t lo, cnt;
+    if (!ppo_chunk(A.segments, A.B, kPpoSeqChunk, lo, cnt)) return;
+    const float *__restrict__ adv = A.adv;
+    const uint64_t B = A.B;
+    double acc[kPpoMoments] = {0.0, 0.0, 0.0};
+    for (uint32_t i = threadIdx.x; i < cnt; i += kLossAcc) {
+        const int32_t col = A.order[lo + i], nk = ppo_seq_kept(A, col);
+        for (int32_t k0 = 0; k0 < nk; k0 += (int32_t)kSeqSteps) {
+            float x[kSeqSteps];
+#pragma unroll
+            for (uint32_t j = 0; j < kSeqSteps; ++j)
+                if (k0 + (int32_t)j < nk) x[j] = adv[(uint64_t)(k0 + (int32_t)j) * B + (uint32_t)col];
+#pragma unroll
+            for (uint32_t j = 0; j < kSeqSteps; ++j)
+                if (k0 + (int32_t)j < nk) pol_ppo_moment_add(acc, x[j]);
+        }
+    }
+    ppo_chunk_fold<kPpoMoments>(s_acc, acc, A.part, A.chunks);
+}
+
+__global__ __launch_bounds__(256) void policy_seq_ppo_loss_kernel(PolSeqPpoIO A)
+{
+    __shared__ double s_acc[kPpoStats][kLossAcc];
+    const uint32_t g = blockIdx.z;
+    const int64_t rows = A.rows[g];
+    if (rows == 0) return;   // the whole block: the fill's +0 stay, the statistics are not touched
+    uint32_t lo, cnt;
+    if (!ppo_chunk(A.segments, A.B, kPpoSeqChunk, lo, cnt)) return;
+    const float w = pol_loss_scale(rows);
+    const bool normalise = A.moments != nullptr;
+    const PpoNorm N = pol_ppo_norm(normalise ? A.moments + (size_t)kPpoMoments * g : nullptr);
+    const float *__restrict__ logp = A.logp, *__restrict__ value = A.value, *__restrict__ entropy = A.entropy;
+    const float *__restrict__ old_logp = A.old_logp, *__restrict__ old_value = A.old_value;
+    const float *__restrict__ adv = A.adv, *__restrict__ ret = A.ret;
+    const uint64_t B = A.B;
+    double acc[kPpoStats] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (uint32_t i = threadIdx.x; i < cnt; i += kLossAcc) {
+        const int32_t col = A.order[lo + i], nk = ppo_seq_kept(A, col);
+        for (int32_t k0 = 0; k0 < nk; k0 += (int32_t)kSeqSteps) {
+            float x[kSeqSteps][7];
+#pragma unroll
+            for (uint32_t j = 0; j < kSeqSteps; ++j)
+                if (k0 + (int32_t)j < nk) {
+                    const uint64_t r = (uint64_t)(k0 + (int32_t)j) * B + (uint32_t)col;
+                    x[j][0] = logp[r], x[j][1] = value[r], x[j][2] = entropy[r], x[j][3] = old_logp[r];
+                    x[j][4] = A.C.vclip ? old_value[r] : 0.0f;
+                    x[j][5] = adv[r], x[j][6] = ret[r];
+                }
+#pragma unroll
+            for (uint32_t j = 0; j < kSeqSteps; ++j)
+                if (k0 + (int32_t)j < nk) {
+                    const uint64_t r = (uint64_t)(k0 + (int32_t)j) * B + (uint32_t)col;
+                    float gl, gv, ge, st[kPpoStats];
+                    pol_ppo_row(x[j][0], x[j][1], x[j][2], x[j][3], x[j][4], x[j][5], x[j][6], w, normalise, N, A.C, gl,
+                                gv, ge, st);
+                    if (A.g_logp) A.g_logp[r] = gl;
+                    if (A.g_value) A.g_value[r] = gv;
+                    if (A.g_entropy) A.g_entropy[r] = ge;
+#pragma unroll
+                    for (uint32_t q = 0; q < kPpoStats; ++q) acc[q] += (double)st[q];
+                }
+        }
+    }
+    if (A.out == nullptr) return;
+    ppo_chunk_fold<kPpoStats>(s_acc, acc, A.part, A.chunks);
+}
+
+// thread g: the gate of group g from its KL sum, stats[g][4]
+__global__ __launch_bounds__(64) void policy_ppo_gate_kernel(const double *stats, const int64_t *rows, double target_kl,
+                                                             int64_t *gate, uint32_t groups)
+{
+    static_assert(kPolMaxGroups <= 64u, "policy_ppo_gate_kernel: one thread per group");
+    const uint32_t g = threadIdx.x;
+    if (g < groups) gate[g] = pol_ppo_gate(gate[g], rows[g], stats[(size_t)kPpoStats * g + 4u], target_kl);
+}
+
+namespace {
+hipError_t ppo_zero(float *a, float *b, float *c, uint64_t n, hipStream_t st)
+{
+    if (n == 0 || !(a || b || c)) return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((n + 255u) / 256u, 2048u);
+    hipLaunchKernelGGL(policy_zero_rows_kernel, dim3(blocks), dim3(256), 0, st, a, b, c, n);
+    return hipGetLastError();
+}
+}  // namespace
+
+hipError_t launch_policy_adv_moments(const PolPpoIO &io, uint32_t groups, hipStream_t st)
+{
+    if (io.chunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(policy_adv_moments_kernel, dim3(io.chunks, 4, groups), dim3(256), 0, st, io);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(policy_ppo_fold_kernel, dim3(groups), dim3(64), 0, st, io.segments, io.n, kPpoChunk, io.chunks,
+                       kPpoMoments, io.part, (const int64_t *)nullptr, io.out);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_ppo_loss(const PolPpoIO &io, uint32_t groups, hipStream_t st)
+{
+    if (hipError_t e = ppo_zero(io.g_logp, io.g_value, io.g_entropy, io.n, st)) return e;
+    if (io.chunks == 0) return hipSuccess;
+    hipLaunchKernelGGL(policy_ppo_loss_kernel, dim3(io.chunks, 4, groups), dim3(256), 0, st, io);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (io.out == nullptr) return hipSuccess;
+    hipLaunchKernelGGL(policy_ppo_fold_kernel, dim3(groups), dim3(64), 0, st, io.segments, io.n, kPpoChunk, io.chunks,
+                       kPpoStats, io.part, (const int64_t *)nullptr, io.out);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_seq_adv_moments(const PolSeqPpoIO &io, uint32_t groups, hipStream_t st)
+{
+    if (io.chunks == 0 || io.L == 0) return hipSuccess;
+    hipLaunchKernelGGL(policy_seq_adv_moments_kernel, dim3(io.chunks, 4, groups), dim3(256), 0, st, io);
+    if (hipError_t e = hipGetLastError()) return e;
+    hipLaunchKernelGGL(policy_ppo_fold_kernel, dim3(groups), dim3(64), 0, st, io.segments, io.B, kPpoSeqChunk, io.chunks,
+                       kPpoMoments, io.part, (const int64_t *)nullptr, io.out);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_seq_ppo_loss(const PolSeqPpoIO &io, uint32_t groups, hipStream_t st)
+{
+    if (hipError_t e = ppo_zero(io.g_logp, io.g_value, io.g_entropy, (uint64_t)io.L * io.B, st)) return e;
+    if (io.chunks == 0 || io.L == 0) return hipSuccess;
+    hipLaunchKernelGGL(policy_seq_ppo_loss_kernel, dim3(io.chunks, 4, groups), dim3(256), 0, st, io);
+    if (hipError_t e = hipGetLastError()) return e;
+    if (io.out == nullptr) return hipSuccess;
+    hipLaunchKernelGGL(policy_ppo_fold_kernel, dim3(groups), dim3(64), 0, st, io.segments, io.B, kPpoSeqChunk, io.chunks,
+                       kPpoStats, io.part, io.rows, io.out);
+    return hipGetLastError();
+}
+
+hipError_t launch_policy_ppo_gate(const double *stats, const int64_t *rows, double target_kl, int64_t *gate,
+                                  uint32_t groups, hipStream_t st)
+{
+    hipLaunchKernelGGL(policy_ppo_gate_kernel, dim3(1), dim3(64), 0, st, stats, rows, target_kl, gate, groups);
+    return hipGetLastError();
+}
+
 }  // namespace mbots

@@ -670,6 +670,144 @@ struct PolSeqLossIO {         // mbots_policy_seq_a2c_loss's (and mbots_policy_s
     float value_coef, entropy_coef;
 };
 
+// ---- PPO on the device (include/mbots.h "PPO on the device"; DESIGN.md "PPO
+// on the device"): the clipped surrogate, the clipped value loss, the advantage
+// moments and the KL gate.  Plain + - * /, pol_exp and comparisons, one
+// rounding each.
+//
+// The two-level order of every sum: element i of a (group, species) segment,
+// counted from lo, belongs to chunk i / chunk and to f64 accumulator i mod 256
+// of that chunk; a chunk's 256 accumulators are added in ascending index to +0,
+// a segment's chunks in ascending index to +0, the four species in ascending
+// order to +0, and that sum is added to the output slot.  An element is a row
+// (kPpoChunk) or a column position of a sequence batch (kPpoSeqChunk), whose
+// kept steps are added in ascending k.  Both chunks are multiples of kLossAcc.
+// (The two chunks were chosen by measurement, profiles/policy_ppo_cost.json;
+// scripts/policy_ppo_cost.py builds the other candidates with these macros.)
+#ifndef MBOTS_PPO_CHUNK
+#define MBOTS_PPO_CHUNK 4096
+#endif
+#ifndef MBOTS_PPO_SEQ_CHUNK
+#define MBOTS_PPO_SEQ_CHUNK 512
+#endif
+constexpr uint32_t kPpoChunk = MBOTS_PPO_CHUNK;          // rows of a chunk
+constexpr uint32_t kPpoSeqChunk = MBOTS_PPO_SEQ_CHUNK;   // column positions of a chunk
+constexpr uint32_t kPpoStats = 6;         // per_row, pol * w, vl * w, entropy * w, kl, clipped
+constexpr uint32_t kPpoMoments = 3;       // count, sum adv, sum adv^2
+static_assert(kPpoChunk % kLossAcc == 0 && kPpoSeqChunk % kLossAcc == 0, "accumulator i mod 256 within a chunk");
+
+// chunk partials of a call: [groups][4][chunks][slots] f64
+MB_HD uint64_t pol_ppo_chunks(uint64_t n, uint32_t chunk) { return (n + chunk - 1u) / chunk; }
+MB_HD uint64_t pol_ppo_bytes(uint64_t chunks, uint32_t groups)
+{
+    return (uint64_t)groups * 4u * chunks * kPpoStats * sizeof(double);
+}
+
+struct PpoCoef {
+    float clip_lo, clip_hi;   // 1 - clip, 1 + clip, rounded once on the host
+    float value_clip;         // read when vclip
+    float value_coef, entropy_coef;
+    uint32_t vclip;           // value_clip > 0 and old_value given
+};
+struct PpoNorm {
+    float mean, inv;
+};
+// a group's normalisation constants from its moments (null: none)
+MB_HD PpoNorm pol_ppo_norm(const double *m)
+{
+    PpoNorm N{0.0f, 1.0f};
+    if (m == nullptr) return N;
+    const double n = m[0], s1 = m[1], s2 = m[2];
+    if (!(n >= 2.0)) return N;
+    const double mu = s1 / n;
+    double var = (s2 - s1 * mu) / (n - 1.0);
+    if (!(var > 0.0)) var = 0.0;
+#ifdef __HIP_DEVICE_COMPILE__
+    const float sd = (float)sqrt(var);
+#else
+    const float sd = (float)std::sqrt(var);
+#endif
+    N.mean = (float)mu;
+    N.inv = 1.0f / (sd + 1e-8f);
+    return N;
+}
+// a kept row's share of the moments: the exact f64 values
+MB_HD void pol_ppo_moment_add(double acc[kPpoMoments], float adv)
+{
+    acc[0] += 1.0;
+    acc[1] += (double)adv;
+    acc[2] += (double)adv * (double)adv;
+}
+// a NaN in the first argument stays: clamps and selections propagate it
+MB_HD float pol_min(float a, float b) { return b < a ? b : a; }
+MB_HD float pol_max(float a, float b) { return b > a ? b : a; }
+
+// a row's three upstream gradients and its six shares of the statistics
+MB_HD void pol_ppo_row(float logp, float value, float entropy, float old_logp, float old_value, float adv, float ret,
+                       float w, bool normalise, const PpoNorm &N, const PpoCoef &C, float &g_logp, float &g_value,
+                       float &g_entropy, float st[kPpoStats])
+{
+    const float A = normalise ? (adv - N.mean) * N.inv : adv;
+    const float lr = logp - old_logp;
+    const float ratio = pol_exp(lr);
+    const float s1 = ratio * A;
+    const float rc = pol_min(pol_max(ratio, C.clip_lo), C.clip_hi);
+    const float s2 = rc * A;
+    const float pol = -pol_min(s1, s2);
+    g_logp = (s2 < s1 ? 0.0f : -s1) * w;   // a tie takes the unclipped branch
+    const float d = value - ret, v1 = d * d;
+    float vl = v1;
+    if (C.vclip) {
+        const float dv = value - old_value;
+        const float dc = pol_min(pol_max(dv, -C.value_clip), C.value_clip);
+        const float d2 = (old_value + dc) - ret, v2 = d2 * d2;
+        vl = v2 > v1 ? v2 : v1;
+        g_value = (C.value_coef * (v2 > v1 ? (dc == dv ? 2.0f * d2 : 0.0f) : 2.0f * d)) * w;
+    } else {
+        g_value = ((2.0f * C.value_coef) * d) * w;
+    }
+    g_entropy = (-C.entropy_coef) * w;
+    st[0] = ((pol + C.value_coef * vl) - C.entropy_coef * entropy) * w;
+    st[1] = pol * w;
+    st[2] = vl * w;
+    st[3] = entropy * w;
+    st[4] = ((ratio - 1.0f) - lr) * w;
+    st[5] = (rc != ratio ? 1.0f : 0.0f) * w;
+}
+
+struct PolPpoIO {             // mbots_policy_ppo_loss's (and mbots_policy_adv_moments') arguments
+    const float *logp, *value, *entropy, *old_logp, *old_value, *adv, *ret;
+    const int32_t *end;       // null: every row kept
+    const int32_t *segments;
+    const int64_t *rows;
+    const double *moments;    // [G][3], null: raw advantages
+    float *g_logp, *g_value, *g_entropy;
+    double *out;              // stats [G][6] (or the moments [G][3] being summed)
+    double *part;             // the workspace: chunk partials
+    uint64_t n;
+    uint32_t chunks;          // per segment: pol_ppo_chunks(n, kPpoChunk)
+    PpoCoef C;
+};
+struct PolSeqPpoIO {          // mbots_policy_seq_ppo_loss's (and mbots_policy_seq_adv_moments') arguments
+    const float *logp, *value, *entropy, *old_logp, *old_value, *adv, *ret;   // [L, B]
+    const int32_t *len, *t0, *end;                                            // [B]
+    const int32_t *order, *segments;
+    const int64_t *rows;
+    const double *moments;
+    float *g_logp, *g_value, *g_entropy;
+    double *out, *part;
+    uint32_t L;
+    uint64_t B;
+    int32_t last_table;
+    uint32_t chunks;          // per segment: pol_ppo_chunks(B, kPpoSeqChunk)
+    PpoCoef C;
+};
+// the gate: the group's rows while it may still step, else 0 (a NaN KL closes it)
+MB_HD int64_t pol_ppo_gate(int64_t gate, int64_t rows, double kl, double target_kl)
+{
+    return gate != 0 && rows != 0 && kl <= target_kl ? rows : 0;
+}
+
 struct AdamTensor {           // struct mbots_policy_adam_tensor
     float *param;
     const float *grad;

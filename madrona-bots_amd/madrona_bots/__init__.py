@@ -31,7 +31,8 @@ __all__ = ["SimManager", "ScriptBotsViewer", "Tensor", "madrona", "ExportID", "E
            "CAPACITY_CLASSES", "TrajectoryWindow", "RENDER_PALETTE", "RENDER_SCALES", "CLS_FLOOR", "CLS_WALL",
            "CLS_FOOD", "CLS_BODY", "CLS_MARK", "PolicyNet", "policy_activation", "ACTIVATIONS", "evaluate_groups",
            "sequence_segments", "evaluate_sequences_groups", "policy_group_rows", "a2c_loss_groups", "PolicyAdam",
-           "sequence_group_rows", "a2c_loss_sequences"]
+           "sequence_group_rows", "a2c_loss_sequences", "advantage_moments_groups", "advantage_moments_sequences",
+           "ppo_loss_groups", "ppo_loss_sequences", "ppo_kl_gate"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "libmbots.so")
@@ -196,6 +197,15 @@ def _load():
         "mbots_policy_adam_clip": [P(_AdamTensor), ctypes.c_uint64, vp, u32, vp, ctypes.c_float, ctypes.c_float,
                                    ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp,
                                    ctypes.c_uint64, i32, vp],
+        "mbots_policy_ppo_workspace": [ctypes.c_uint64, u32, P(ctypes.c_uint64)],
+        "mbots_policy_adv_moments": [vp, vp, ctypes.c_uint64, vp, u32, vp, vp, ctypes.c_uint64, i32, vp],
+        "mbots_policy_ppo_loss": [vp] * 8 + [ctypes.c_uint64, vp, u32, vp, vp] + [ctypes.c_float] * 4 + [vp] * 5 +
+                                 [ctypes.c_uint64, i32, vp],
+        "mbots_policy_seq_adv_moments": [vp, vp, vp, vp, u32, ctypes.c_uint64, vp, vp, u32, i32, vp, vp,
+                                         ctypes.c_uint64, i32, vp],
+        "mbots_policy_seq_ppo_loss": [vp] * 10 + [u32, ctypes.c_uint64, vp, vp, u32, i32, vp, vp] +
+                                     [ctypes.c_float] * 4 + [vp] * 5 + [ctypes.c_uint64, i32, vp],
+        "mbots_policy_ppo_gate": [vp, vp, u32, ctypes.c_double, vp, i32, vp],
     }
     for name, args in sig.items():
         fn = getattr(L, name)
@@ -2206,6 +2216,230 @@ def a2c_loss_sequences(logp, value, entropy, adv, ret, length, t0, end, order, s
         L, B, _ptr(order), _ptr(segments), G, int(last_table), _ptr(rows), value_coef, entropy_coef, _ptr(g[0]),
         _ptr(g[1]), _ptr(g[2]), _ptr(loss), d, st))
     return g[0], g[1], g[2], loss
+
+
+def _ppo_workspace(n, G, dev):
+    """The cached scratch of the PPO calls over n rows (or L * B elements):
+    (uint8 buffer, bytes)."""
+    need = ctypes.c_uint64()
+    _check(_lib.mbots_policy_ppo_workspace(n, G, ctypes.byref(need)))
+    key = (dev, need.value)
+    ws = _workspaces.get(key)
+    if ws is None:
+        ws = _workspaces[key] = torch.empty(max(need.value, 64), dtype=torch.uint8, device=dev)
+    return ws, need.value
+
+
+def _ppo_f64(name, t, shape, dev):
+    """A caller's float64 accumulator of `shape` on dev, or zeros for None."""
+    if t is None:
+        return torch.zeros(shape, dtype=torch.float64, device=dev)
+    if t.dtype != torch.float64 or t.device != dev or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous float64 {list(shape)} on {dev}, not {t.dtype} {list(t.shape)} "
+                         f"on {t.device}")
+    return t
+
+
+def _ppo_segments(segments, dev):
+    G = segments.shape[0] if segments.dim() == 3 else 0
+    if segments.dtype != torch.int32 or segments.device != dev or tuple(segments.shape) != (G, 4, 2) or not 1 <= G <= 64:
+        raise ValueError(f"segments must be int32 [G, 4, 2] of 1..64 groups on {dev}, not {segments.dtype} "
+                         f"{list(segments.shape)} on {segments.device}")
+    return G, segments.detach().contiguous()
+
+
+def _ppo_rows(named, end, dev):
+    """The checked float32 [n] (or [n, 1]) columns and the END column."""
+    n = named[0][1].numel()
+    cols = []
+    for name, t in named:
+        if t is None:
+            cols.append(None)
+            continue
+        if t.dtype != torch.float32 or t.device != dev or t.numel() != n or tuple(t.shape) not in ((n,), (n, 1)):
+            raise ValueError(f"{name} must be float32 [n] or [n, 1] on {dev} with {named[0][0]}'s {n} rows, not "
+                             f"{t.dtype} {list(t.shape)} on {t.device}")
+        cols.append(t.detach().reshape(n).contiguous())
+    if end is not None:
+        if end.dtype != torch.int32 or end.device != dev or tuple(end.shape) not in ((n,), (n, 1)):
+            raise ValueError(f"end must be int32 [n] or [n, 1] on {dev}, not {end.dtype} {list(end.shape)} on "
+                             f"{end.device}")
+        end = end.detach().reshape(n).contiguous()
+    return n, cols, end
+
+
+def _ppo_coefs(clip, value_clip, value_coef):
+    if not 0.0 < clip < 1.0:
+        raise ValueError(f"clip must lie in (0, 1), not {clip}")
+    if not value_coef >= 0.0:
+        raise ValueError(f"value_coef must not be negative, not {value_coef}")
+    return 0.0 if value_clip is None else float(value_clip)
+
+
+def advantage_moments_groups(adv, end, segments, moments=None):
+    """moments[g] += (count, sum adv, sum adv**2) of group g's kept rows of one
+    table, in exact float64 and a fixed order (mbots_policy_adv_moments;
+    DESIGN.md "PPO on the device"): what ppo_loss_groups normalises
+    advantages with.  adv float32 [n] or [n, 1]; end int32 [n] or [n, 1], the
+    window's END column (rows with END_RESET are left out), or None: every row
+    counts; segments int32 [G, 4, 2]; moments float64 [G, 3], accumulated into
+    (None: zeros) and returned -- pass every table of the update once.  CPU and
+    GPU tensors give the same bits.  Nothing waits for the host; capturable."""
+    dev = adv.device
+    G, segments = _ppo_segments(segments, dev)
+    n, (adv,), end = _ppo_rows([("adv", adv)], end, dev)
+    moments = _ppo_f64("moments", moments, (G, 3), dev)
+    ws, nb = _ppo_workspace(n, G, dev)
+    _on_device(dev, lambda d, st: _lib.mbots_policy_adv_moments(
+        _ptr(adv), _ptr(end), n, _ptr(segments), G, _ptr(moments), _ptr(ws), nb, d, st))
+    return moments
+
+
+def advantage_moments_sequences(adv, length, t0, end, order, segments, last_table=-1, moments=None):
+    """advantage_moments_groups for a padded [L, B] sequence batch
+    (mbots_policy_seq_adv_moments): moments[g] += (count, sum, sum of squares)
+    of the kept elements of the columns of group g's segments.  adv float32
+    [L, B]; length, t0, end, order, segments, last_table as
+    sequence_group_rows'.  Returns moments, float64 [G, 3]."""
+    dev = adv.device
+    if adv.dim() != 2 or adv.dtype != torch.float32:
+        raise ValueError(f"adv must be float32 [L, B], not {adv.dtype} {list(adv.shape)}")
+    L, B = adv.shape
+    if length.numel() != B:
+        raise ValueError(f"length must be int32 [{B}] on {dev}, not {length.dtype} {list(length.shape)} on "
+                         f"{length.device}")
+    none = torch.zeros(segments.shape[0] if segments.dim() == 3 else 0, dtype=torch.int64, device=dev)
+    _, G, length, t0, end, order, segments = _sequence_columns(length, t0, end, order, segments, none, dev)
+    moments = _ppo_f64("moments", moments, (G, 3), dev)
+    adv = adv.detach().contiguous()
+    ws, nb = _ppo_workspace(L * B, G, dev)
+    _on_device(dev, lambda d, st: _lib.mbots_policy_seq_adv_moments(
+        _ptr(adv), _ptr(length), _ptr(t0), _ptr(end), L, B, _ptr(order), _ptr(segments), G, int(last_table),
+        _ptr(moments), _ptr(ws), nb, d, st))
+    return moments
+
+
+def ppo_loss_groups(logp, value, entropy, old_logp, old_value, adv, ret, end, segments, rows, clip=0.2,
+                    value_clip=None, value_coef=0.5, entropy_coef=0.01, moments=None, stats=None):
+    """(g_logp, g_value, g_entropy, stats): PPO's clipped loss of a table's
+    recorded rows and its gradients with respect to evaluate's three outputs,
+    in one pass of the library's own arithmetic (mbots_policy_ppo_loss;
+    DESIGN.md "PPO on the device").  logp, value, entropy: float32 [n], what
+    evaluate_groups() returned for the current parameters, read detached;
+    old_logp, old_value: act()'s "logp" and "value" of the table when it was
+    recorded (old_value may be None); adv, ret, end, segments, rows as
+    a2c_loss_groups'.  A row of group g weighs w = (end != END_RESET) / rows[g]:
+
+        A       = (adv - mean_g) / (std_g + 1e-8)  with moments, else adv
+        ratio   = exp(logp - old_logp)
+        pol     = -min(ratio * A, clamp(ratio, 1 - clip, 1 + clip) * A)
+        vl      = (value - ret)**2, or with value_clip > 0 and old_value its maximum with
+                  (old_value + clamp(value - old_value, -value_clip, value_clip) - ret)**2
+        per_row = (pol + value_coef * vl - entropy_coef * entropy) * w
+
+    and g_* are per_row's derivatives (a tie of the two surrogates takes the
+    unclipped one); rows in no segment get +0.  moments: float64 [G, 3] from
+    advantage_moments_groups over the whole update -- the unbiased standard
+    deviation; fewer than two rows: no normalisation -- or None: raw
+    advantages.  stats: float64 [G, 6], accumulated into (None: zeros): the
+    groups' sums of per_row, pol * w, vl * w, entropy * w, the KL estimate
+    ((ratio - 1) - log ratio) * w and the clipped fraction (clamp changed the
+    ratio) * w, in a fixed two-level order that is a property of the row
+    indices alone, so CPU and GPU tensors give the same bits.  Non-finite
+    inputs propagate into stats; a NaN KL closes ppo_kl_gate, and a clipped
+    PolicyAdam leaves a group with a non-finite gradient norm untouched.  Then
+
+        torch.autograd.backward([logp, value, entropy], [g_logp, g_value, g_entropy])
+
+    runs evaluate's backward.  After the first call of a shape nothing
+    allocates but the three outputs; nothing waits for the host; capturable."""
+    dev = logp.device
+    G, segments = _ppo_segments(segments, dev)
+    value_clip = _ppo_coefs(clip, value_clip, value_coef)
+    n, cols, end = _ppo_rows([("logp", logp), ("value", value), ("entropy", entropy), ("old_logp", old_logp),
+                              ("old_value", old_value), ("adv", adv), ("ret", ret)], end, dev)
+    if rows.dtype != torch.int64 or rows.device != dev or tuple(rows.shape) != (G,) or not rows.is_contiguous():
+        raise ValueError(f"rows must be a contiguous int64 [{G}] on {dev}, not {rows.dtype} {list(rows.shape)} on "
+                         f"{rows.device}")
+    if moments is not None:
+        moments = _ppo_f64("moments", moments, (G, 3), dev)
+    stats = _ppo_f64("stats", stats, (G, 6), dev)
+    ws, nb = _ppo_workspace(n, G, dev)
+    g = [torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3)]
+    _on_device(dev, lambda d, st: _lib.mbots_policy_ppo_loss(
+        *[_ptr(c) for c in cols], _ptr(end), n, _ptr(segments), G, _ptr(rows), _ptr(moments), clip, value_clip,
+        value_coef, entropy_coef, _ptr(g[0]), _ptr(g[1]), _ptr(g[2]), _ptr(stats), _ptr(ws), nb, d, st))
+    return g[0], g[1], g[2], stats
+
+
+def ppo_loss_sequences(logp, value, entropy, old_logp, old_value, adv, ret, length, t0, end, order, segments, rows,
+                       last_table=-1, clip=0.2, value_clip=None, value_coef=0.5, entropy_coef=0.01, moments=None,
+                       stats=None):
+    """(g_logp, g_value, g_entropy, stats): ppo_loss_groups for the padded
+    [L, B] sequence batches (mbots_policy_seq_ppo_loss).  logp, value, entropy:
+    float32 [L, B] from evaluate_sequences_groups(); old_logp: the window's
+    gather() of act()'s "logp" tables; old_value: the batch's "value" (or
+    None); adv, ret: the batch's; length, t0, end, order, segments, rows,
+    last_table as a2c_loss_sequences'.  A kept element of a column of group g
+    weighs 1 / rows[g]; every other element gets +0 and takes no part in
+    stats, and so does all of a group with rows[g] == 0.  moments from
+    advantage_moments_sequences.  The sums run over the segments' positions in
+    the same two-level order, a column's kept steps in ascending order."""
+    dev = logp.device
+    if logp.dim() != 2:
+        raise ValueError(f"logp must be float32 [L, B], not {list(logp.shape)}")
+    L, B = logp.shape
+    value_clip = _ppo_coefs(clip, value_clip, value_coef)
+    cols = []
+    for name, t in (("logp", logp), ("value", value), ("entropy", entropy), ("old_logp", old_logp),
+                    ("old_value", old_value), ("adv", adv), ("ret", ret)):
+        if t is None and name == "old_value":
+            cols.append(None)
+            continue
+        if t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (L, B):
+            raise ValueError(f"{name} must be float32 [{L}, {B}] on {dev}, not {t.dtype} {list(t.shape)} on "
+                             f"{t.device}")
+        cols.append(t.detach().contiguous())
+    if length.numel() != B:
+        raise ValueError(f"length must be int32 [{B}] on {dev}, not {length.dtype} {list(length.shape)} on "
+                         f"{length.device}")
+    _, G, length, t0, end, order, segments = _sequence_columns(length, t0, end, order, segments, rows, dev)
+    if moments is not None:
+        moments = _ppo_f64("moments", moments, (G, 3), dev)
+    stats = _ppo_f64("stats", stats, (G, 6), dev)
+    ws, nb = _ppo_workspace(L * B, G, dev)
+    g = [torch.empty((L, B), dtype=torch.float32, device=dev) for _ in range(3)]
+    _on_device(dev, lambda d, st: _lib.mbots_policy_seq_ppo_loss(
+        *[_ptr(c) for c in cols], _ptr(length), _ptr(t0), _ptr(end), L, B, _ptr(order), _ptr(segments), G,
+        int(last_table), _ptr(rows), _ptr(moments), clip, value_clip, value_coef, entropy_coef, _ptr(g[0]), _ptr(g[1]),
+        _ptr(g[2]), _ptr(stats), _ptr(ws), nb, d, st))
+    return g[0], g[1], g[2], stats
+
+
+def ppo_kl_gate(stats, rows, target_kl, gate):
+    """PPO's KL early stop without a read by the host (mbots_policy_ppo_gate):
+
+        gate[g] = rows[g] if gate[g] != 0 and rows[g] != 0 and stats[g, 4] <= target_kl else 0
+
+    stats float64 [G, 6], an epoch's from ppo_loss_groups / ppo_loss_sequences
+    (slot 4: the group's KL estimate); rows, gate int64 [G] on the same device.
+    Start an update with gate = rows.clone() and pass the gate to
+    PolicyAdam.step(gate): a group whose KL passed target_kl -- or is NaN --
+    is left untouched by this and every later step of the update, as an idle
+    group is; a closed gate stays closed until the caller sets it again.
+    Returns gate.  Capturable."""
+    dev = stats.device
+    G = stats.shape[0] if stats.dim() == 2 else 0
+    if not 1 <= G <= 64:
+        raise ValueError(f"stats must be float64 [G, 6] of 1..64 groups, not {list(stats.shape)}")
+    _ppo_f64("stats", stats, (G, 6), dev)
+    for name, t in (("rows", rows), ("gate", gate)):
+        if t.dtype != torch.int64 or t.device != dev or tuple(t.shape) != (G,) or not t.is_contiguous():
+            raise ValueError(f"{name} must be a contiguous int64 [{G}] on {dev}, not {t.dtype} {list(t.shape)} on "
+                             f"{t.device}")
+    _on_device(dev, lambda d, st: _lib.mbots_policy_ppo_gate(_ptr(stats), _ptr(rows), G, float(target_kl), _ptr(gate),
+                                                             d, st))
+    return gate
 
 
 class PolicyAdam:
